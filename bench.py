@@ -10,8 +10,14 @@ over one batch of synthetic (user, item, ripple-set) inputs already resident in 
 Default workload = BASELINE.json's metric config C3: last-fm_50core-shaped tables,
 dim=64, hop=2 (n_mix_hop=1), fan-out=32, fp32.
 
+A plain run sets up, warms up, times exactly --steps steps, writes the last timed step's outputs when
+--dump-outputs DIR is given (fixed seeds: the same arguments give the same inputs on every run) and prints
+the result line.  Everything else below (roofline, batch_sweep, cpu_baseline, other_modes, parity_vs_cpu_sample)
+is measured after the timed steps under --full only.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field):
   value     = pairs scored per second, whole job (all ranks), max-over-ranks time
+  ms_per_step = milliseconds per timed step (wall time of the --steps steps / steps)
   roofline  = the dominant kernel (gather_attn_l2_kernel, mvin_gather_attn_l2_fwd) in its HBM-BOUND
               regime: the same kernel at the same D / K on a 4 GB entity table (16 M rows, uniform
               adjacency, far larger than the 256 MB Infinity Cache), algorithmic bytes per launch
@@ -44,6 +50,9 @@ HBM_LEG_PAIRS = 32768
 # projected-tables form: three tables of 4 M x 64 x 4 B = 1.02 GB each (below the kernel's 1 GiB-per-table limit), 3.07 GB = 12x the
 # Infinity Cache
 HBM_LEG_PRJ_ROWS = 4_000_000
+# --dump-outputs: bytes of array data at most (each .npy header adds ~128 B: the files stay below 64 MB in all)
+DUMP_BYTES = 60_000_000
+DUMP_NAMES = ("scores", "scores_normalized", "user_o", "item_embeddings")
 
 
 def prj_bytes_per_pair(D, K, s=4):
@@ -125,6 +134,14 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: launch / join the --gpus N ranks, all-reduce one number through the process group, "
                          "print {\"launch_check\": ...} on rank 0 and exit before any GPU work (argument plumbing test)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure: roofline / per-kernel timings "
+                         "(repeats of the steps, HBM-bound legs, gather probe), the other modes and feeds, the batch sweep, the training "
+                         "step, the reference's shipped config, the CPU baseline and its parity check (all off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step (scores, sigmoid scores, user_o, item "
+                         "embeddings) as DIR/<name>.npy in float32; above %d MB in all, the same fixed, seeded sample of pairs "
+                         "is written for every array (rank 0's pairs only)" % (DUMP_BYTES // 10 ** 6))
     return ap.parse_args()
 
 
@@ -142,6 +159,30 @@ def self_launch(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.run(cmd, env=env).returncode
+
+
+def dump_outputs(out, dirname, limit=DUMP_BYTES, seed=0):
+    """--dump-outputs: the arrays of the output namespace a caller of the timed path receives (DUMP_NAMES, one row per pair)
+    as DIR/<name>.npy in float32.  When they hold more than ``limit`` bytes, every array keeps the same rows: a sample of
+    pairs drawn with a fixed seed, in ascending pair order.  Returns {name: shape written}."""
+    import torch
+    arrays = {n: getattr(out, n) for n in DUMP_NAMES if isinstance(getattr(out, n, None), torch.Tensor)}
+    rows = arrays["scores"].shape[0]
+    row_bytes = sum(4 * (t.numel() // max(rows, 1)) for t in arrays.values())
+    keep = None
+    if rows * row_bytes > limit:
+        g = torch.Generator().manual_seed(seed)
+        keep = torch.randperm(rows, generator=g)[:limit // row_bytes].sort().values
+    os.makedirs(dirname, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if keep is not None:
+            t = t.index_select(0, keep.to(t.device))
+        arr = t.float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return shapes
 
 
 def cpu_baseline(args, margs, case, params):
@@ -790,15 +831,18 @@ def main():
         out = step_on(i)
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
+    # everything below up to the result line is --full: repeats of the steps in other forms, per-kernel timings, other legs
     single_stream = None
-    if lanes is not None:                              # the same K steps on ONE stream, after the clock stopped (continuity with rounds 1-4)
+    if a.full and lanes is not None:                   # the same K steps on ONE stream, after the clock stopped (continuity with rounds 1-4)
         t1 = time.perf_counter()
         for _ in range(a.steps):
             out = step()
         barrier()
         single_stream = (time.perf_counter() - t1) / a.steps
     faithful = None
-    if scorer is None and not rowshard and model.prj is None and model._prj_for_l2(Bl, Bl * a.fanout ** (a.hop * a.mix - 2)) \
+    if a.full and scorer is None and not rowshard and model.prj is None and model._prj_for_l2(Bl, Bl * a.fanout ** (a.hop * a.mix - 2)) \
             and (model._enc_for_l2(n_parents=Bl * a.fanout ** (a.hop * a.mix - 2)) is not None or model._prj_plain_ok()):
         # the same K steps with the two deepest levels in their round-4 form (W1 / W2 products per distinct child), one stream
         model.prj = False
@@ -814,7 +858,7 @@ def main():
     # ... and with every pair gathering its own rows: the kernels over the projected tables themselves (no per-entity aggregates), on the
     # SAME streams as the timed region.  SURVEY 7.3-c asks for the per-entity route to be a separate, labelled mode: this is the other one.
     gather_mode = None
-    if scorer is None and not rowshard and model.agg is None and model.prj is None:
+    if a.full and scorer is None and not rowshard and model.agg is None and model.prj is None:
         enc_g = model._enc_for_l2(n_parents=Bl * a.fanout ** (a.hop * a.mix - 2))
         if model._prj_for_l2(Bl, Bl * a.fanout ** (a.hop * a.mix - 2)) and (model._fold_for(enc_g) or model._agg_for(enc_g)):
             model.agg = False
@@ -827,7 +871,7 @@ def main():
             barrier()
             gather_mode = ((time.perf_counter() - t1) / a.steps, float((out_g.scores - out.scores).abs().max()))
             model.agg = None
-    if one_call:
+    if a.full and one_call:
         model._profile = []
         model._ka_profile = []
         for _ in range(a.steps):
@@ -849,240 +893,242 @@ def main():
             raise SystemExit(f"bench.py: {ranks_counted} ranks answered the all-reduce, --gpus {a.gpus}")
 
     if rank == 0:
-        # HBM/fabric traffic of the dominant kernel comes from separate rocprofv3 --pmc passes
-        # (FETCH_SIZE, WRITE_SIZE; gfx950 correction applied) archived under profiles/; it is
-        # attached only when that profile was taken on exactly this workload
-        traffic = None
         hoisted = a.hoist != "off" and model.hoist_supported()
         from mvin_amd import ops as _ops
         used_l2 = bool(model.fused and a.hop >= 2 and _ops.gather_attn_l2_supported(a.dim, a.fanout))
-        pmc = pmc_record("pmc_latest.json")
-        try:
-            same = (pmc is not None and a.table_dtype == "f32" and not a.n_entity and pmc.get("bench_args") == {
-                "dataset": a.dataset, "dim": a.dim, "hop": a.hop, "mix": a.mix, "fanout": a.fanout, "adj": a.adj,
-                "items": a.items, "batch": a.batch})
-            if same and used_l2 and world == 1 and not hoisted:
-                traffic = pmc["gather_attn_l2_traffic_bytes_per_launch"] / pmc["gather_attn_l2_pairs_per_launch"] * Bl
-        except (KeyError, ValueError):
-            traffic = None
         L = a.hop * a.mix
         s_ = 2 if a.table_dtype == "bf16" else 4
-        bpp = algorithmic_bytes_per_pair(a.dim, a.fanout, L, s=s_)
-        bpp_faithful = bpp
-        if hoisted:
-            # bytes this mode really needs per pair: K+1 fp32 rows of the hoisted tables + the adjacency row
-            # per level-(L-2) node, + (mode 'step') the table build amortised over the rank's pairs
-            K, D = a.fanout, a.dim
-            bpp = K ** (L - 2) * ((K + 1) * D * 4 + 2 * K * 4) + D * 4 + 4
-            if a.hoist == "step":
-                bpp += case.n_entity * (K * D * s_ + 2 * K * 4 + D * s_ + 4 * D * 4) / Bl
-        kern_ms = [e0.elapsed_time(e1) for e0, e1 in prof]
-        kern_avg_ms = float(np.mean(kern_ms)) if kern_ms else None
-        achieved = (bpp * Bl / (kern_avg_ms * 1e-3) / 1e9) if kern_avg_ms else None
         emulated = a.emulate_world > 1 and world == 1
         # under --emulate-world only rank 0's share was scored: `value` is that MEASURED rate, the W-rank projection is a
         # separate field
         value = (Bl if emulated else a.batch) * a.steps / elapsed
-        table_bytes = case.n_entity * a.dim * s_
-        cache_resident = table_bytes <= 256 * 2 ** 20        # Infinity Cache (MI355X_MICROARCH.md)
         enc = model._enc_for_l2(n_parents=Bl * a.fanout ** (L - 2)) if (used_l2 and not hoisted) else None
         prj_now = (used_l2 and not hoisted and (enc is not None or model._prj_plain_ok())
                    and model._prj_for_l2(Bl, Bl * a.fanout ** (L - 2)))
         fold_now = bool(prj_now and L == 2 and model._fold_for(enc))
         agg_now = bool(fold_now or (prj_now and model._agg_for(enc)))
-        kname = (("gather_mix_kernel (mvin_gather_mix_fwd) + per-entity table build/lookups "
-                  "[entity-table mode: its own bytes per pair, not SURVEY 8(d)'s]") if hoisted
-                 else "linear_mfma_kernel + entity_aggregates_kernel<%d> + score_l2_folded_kernel<%d> (mvin_fold_tables -> mvin_score_l2_folded_fwd: "
-                      "EVERYTHING above key addressing -- four per-entity tables E.W1.A0 | E.W2.A0 | E.W0.A0 | E.W0.Wm0 and the aggregates H0 | G, all "
-                      "rebuilt inside every step from the current parameters, then ONE launch that takes a pair from its item id and query row to "
-                      "its score: six 64 x 64 products on the matrix cores around the gather of its distinct children's G rows; the same sums in "
-                      "another association)" % (a.fanout, a.fanout)
-                 if fold_now
-                 else "entity_aggregates_kernel<%d> + gather_attn_l2_agg_kernel<%d> (mvin_entity_aggregates -> mvin_gather_attn_l2_agg_fwd: per-entity "
-                      "aggregates S0 | G of the projected tables E.W1 | E.W1.A0 | E.W2.A0, all rebuilt inside every step from the current parameters; a "
-                      "pair then gathers its distinct children's G rows and one S0 row -- the same sums in another association)" % (a.fanout, a.fanout)
-                 if agg_now
-                 else "gather_attn_l2_wpp_kernel<%d> (mvin_gather_attn_l2_prj_ordered_fwd: wave-per-parent kernel over the duplicate-slot encoding of the "
-                      "adjacency, rows gathered from the projected tables E.W1 | E.W1.A0 | E.W2.A0 that mvin_project_tables rebuilds every step "
-                      "-- same ids and grandchild rows per pair as mvin_gather_attn_l2_enc_fwd, no product per distinct child; parents taken in "
-                      "item order: %s)" % (a.fanout, bool(model._item_order_for(Bl)))
-                 if (prj_now and enc is not None and _ops.gather_attn_l2_wpp_supported(a.dim, a.fanout))
-                 else "gather_attn_l2_packed_kernel<..., PRJ> (mvin_gather_attn_l2_prj_fwd: duplicate-slot encoding of the adjacency, rows "
-                      "gathered from the projected tables E.W1 | E.W1.A0 | E.W2.A0 that mvin_project_tables rebuilds every step -- same ids "
-                      "and grandchild rows per pair as mvin_gather_attn_l2_enc_fwd, no W1 / W2 / A0 product per distinct child)"
-                 if (prj_now and enc is not None)
-                 else "gather_attn_l2_d32_kernel<..., PRJ> (mvin_gather_attn_l2_prj_fwd over the plain adjacency: rows gathered from the "
-                      "projected tables E.W1 | E.W1.A0 | E.W2.A0 that mvin_project_tables rebuilds every step)"
-                 if prj_now
-                 else "gather_attn_l2_packed_kernel (mvin_gather_attn_l2_enc_fwd: duplicate-slot encoding of the adjacency)"
-                 if enc is not None
-                 else "gather_attn_l2_kernel (mvin_gather_attn_l2_fwd)" if used_l2
-                 else "gather_attn_kernel (mvin_gather_attn_fwd)")
-        peak = L2_PEAK_GBS if cache_resident else HBM_PEAK_GBS
-        # `achieved` / `frac` price the bytes the kernel MUST LOAD (for a plain adjacency that is SURVEY 8(d)'s figure; for the
-        # encoded path it is replaced below by the distinct rows it fetches); the faithful-bytes rate is informational
-        timed = {"bound": "l2" if cache_resident else "hbm", "kernel": kname, "achieved": achieved, "peak": peak,
-                 "unit": "GB/s", "frac": (achieved / peak) if achieved else None,
-                 "bytes_per_pair": bpp, "pairs_per_launch": Bl, "avg_launch_ms": kern_avg_ms,
-                 "faithful_bytes_rate_gbs": achieved,
-                 "table_bytes": table_bytes, "traffic": traffic,
-                 "kernel_timing": ("HIP events around the kernel's launches in a repeat of the same steps after the timed "
-                                   "region (the timed steps are ONE native call each, mvin_score_l2_fwd: no hooks inside)"
-                                   if one_call else "HIP events around the kernel's launches inside the timed steps"),
-                 "hbm_frac_from_traffic": (traffic / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                 if (traffic and kern_avg_ms) else None,
-                 "whole_path_faithful_bytes_rate_gbs": value / world * bpp / 1e9,
-                 "faithful_bytes_per_pair": bpp_faithful,
-                 "note": ("launches inside the timed steps; the %.0f MB entity table is L2 / Infinity-Cache resident, so "
-                          "the algorithmic bytes are served on-chip: priced against the %.1f TB/s L2 aggregate, NOT the HBM "
-                          "peak; `traffic` = bytes per launch beyond L2 from rocprofv3 PMC passes (2*FETCH_SIZE + "
-                          "WRITE_SIZE, profiles/pmc_latest.json)" % (table_bytes / 1e6, L2_PEAK_GBS / 1e3))
-                 if cache_resident else "launches inside the timed steps; the table is far larger than the Infinity Cache"}
-        if enc is not None and L == 2 and kern_avg_ms:
-            # what the encoded path really loads: the DISTINCT slots of the item's row and of its distinct children's rows
-            # (the algorithmic bytes above stay SURVEY 8(d)'s K + K^2 rows per pair: repeated slots are not re-read)
-            enc_e, enc_r, cnt, frac_distinct = enc
-            it = items.long()
-            ch = (enc_e[it] & 0xFFFFFF).long()
-            real = ((enc_r[it] >> 16) & 0xFF) > 0
-            rows_loaded = float((1 + cnt[it].double() + (cnt[ch].double() * real).sum(1)).mean())
-            if prj_now:       # the projected-tables form reads TWO self rows per distinct child (T1[x] and TA1[x])
-                rows_loaded += float(cnt[it].double().mean())
-            K_ = a.fanout
-            # encoded adjacency rows read per pair: the item's and its distinct children's, K words of ids + K of relations each
-            adj_rows = float((1 + cnt[it].double()).mean())
-            if agg_now:
-                # the aggregates form: per pair its S0 row and its distinct children's G rows, its own adjacency row, the query row and
-                # the two output rows; per ENTITY and step (entity_aggregates_kernel) its adjacency row, TA1[e], T1 and TA2 of its
-                # distinct slots, S0[e] and G[e] written -- shared out over the step's pairs
-                rows_loaded = float((1 + cnt[it].double()).mean())
-                adj_rows = 1.0
-                per_entity = float(((2 * cnt.double() + 1) * a.dim * 4 + K_ * 8 + 2 * a.dim * 4).sum()) / Bl
-                loaded_bpp = rows_loaded * a.dim * 4 + K_ * 8 + 3 * a.dim * 4 + per_entity
-                if fold_now:
-                    # folded tail, one launch: per pair H0[x], M0[x] and its distinct children's G rows, its adjacency row, its query and
-                    # user_o rows, the item embedding written, the score; per ENTITY and step E[e] read and four table rows written (table
-                    # build), then the aggregates kernel as above with one more self row (T0A[e])
-                    rows_loaded = float((2 + cnt[it].double()).mean())
-                    per_entity = float(((2 * cnt.double() + 2) * a.dim * 4 + K_ * 8 + 2 * a.dim * 4 + 5 * a.dim * 4).sum()) / Bl
-                    loaded_bpp = rows_loaded * a.dim * 4 + K_ * 8 + 3 * a.dim * 4 + 8 + per_entity
-                timed["aggregates_build_bytes_per_step"] = per_entity * Bl
-            else:
-                loaded_bpp = rows_loaded * a.dim * s_ + adj_rows * K_ * 8 + a.dim * 4 + 4
-            loaded_gbs = loaded_bpp * Bl / (kern_avg_ms * 1e-3) / 1e9
-            timed.update({"achieved": loaded_gbs, "frac": loaded_gbs / peak, "bytes_per_pair": loaded_bpp,
-                          "rows_per_pair_faithful": 1 + K_ + K_ * K_, "rows_per_pair_loaded": rows_loaded,
-                          "adjacency_rows_per_pair_loaded": adj_rows,
-                          "distinct_slots_per_adjacency_row": frac_distinct * K_,
-                          "folded_note": ("folded-tail form: `avg_launch_ms` covers mvin_fold_tables (parameter block, four-table build, aggregates) AND "
-                                          "the scoring launch -- everything above key addressing, mvin_l2_tail_fwd's work included; MVIN_L2_FOLD=0 "
-                                          "times aggregates + tail kernel, MVIN_L2_AGG=0 the kernel over the projected tables") if fold_now else None,
-                          "aggregates_note": ("aggregates form: `avg_launch_ms` covers BOTH launches (aggregates over all %d entities + the per-pair "
-                                              "gather); a pair's rows come from the 27 MB G table, not from its grandchildren's rows of three tables "
-                                              "(rows_per_pair_loaded ~ 1 + its distinct children; the wave-per-parent kernel over the tables loaded "
-                                              "~120); MVIN_L2_AGG=0 times that kernel instead" % case.n_entity) if agg_now else None,
-                          "dedup_note": "the reference's sampler repeats slots whenever deg < K (data_loader_user_set.py:383-384) and the "
-                                        "packed kernel fetches every DISTINCT row once: `achieved` / `frac` / `bytes_per_pair` price what it "
-                                        "loads (distinct entity rows + the encoded adjacency rows + query + score); "
-                                        "`faithful_bytes_rate_gbs` = SURVEY 8(d)'s bytes per pair (every slot's row) over the same time is "
-                                        "informational and can exceed any peak -- it is a rate of work done, not of bytes moved"})
-        if ka_prof and by_user:
-            # the flash form of key addressing + user MLP inside the same (single-stream, instrumented) repeat of the timed steps:
-            # a kernel that IS bound by bytes from beyond the L2 -- every user's ripple rows come from a 245 MB per-call table
-            # (R_KGE[r] . E[e]) and three entity-sized ones, once per user and 32-pair tile
-            prep_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ka_prof]))
-            kern2_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ka_prof]))
-            P_, Nm_, D_ = d["p_hop"], d["n_memory"], a.dim
-            NmP = (Nm_ + 15) // 16 * 16
-            ucount = torch.bincount(users, minlength=case.n_user)
-            n_users_now = int((ucount > 0).sum().item())
-            tiles32 = int(((ucount + 31) // 32).sum().item())
-            slots64 = int(((ucount + 63) // 64).sum().item())
-            row_b = D_ * 4
-            # per 32-pair tile: P NmP rows of R_KGE.E + P NmP rows of E.Wmlp blocks; per 64-pair slot: NmP h-set rows + the record's three
-            # id sections; per pair: the item row, its id, its index in user order, the user_o row written
-            bytes_step = (tiles32 * 2 * P_ * NmP * row_b + slots64 * (NmP * row_b + (NmP + 2 * P_ * NmP) * 4)
-                          + Bl * (row_b + 8 + 4 + row_b))
-            tab_bytes = (case.n_relation + P_ + 1) * case.n_entity * row_b
-            timed["key_addressing_kernel"] = {
-                "kernel": "key_addr_flash_kernel (mvin_key_addressing_flash_fwd: attention reads + user MLP of model.py:161-240 in one barrier-free "
-                          "kernel over per-call tables)",
-                "avg_launch_ms": kern2_ms, "tables_build_ms": prep_ms, "tables_bytes_written_per_step": tab_bytes,
-                "users_in_batch": n_users_now, "tiles_of_32_pairs": tiles32,
-                "bytes_loaded_per_step": bytes_step, "bound": "hbm", "achieved": bytes_step / (kern2_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": bytes_step / (kern2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "note": "bytes the kernel must load per step (every row counted once per tile that needs it; the 245 MB R_KGE.E table and the "
-                        "82 MB of E.Wmlp blocks are far beyond the 8 x 4 MB of L2, the ripple sets are uniform random: SURVEY 8(d)) over its "
-                        "HIP-event time in the instrumented single-stream repeat; rocprofv3 counters of the same kernel under profiles/r6/ "
-                        "(TCC_EA0_RDREQ: ~1.2x these bytes leave the L2)"}
-        if used_l2 and not hoisted and L == 2 and world == 1 and not a.no_probe and kern_avg_ms:
-            gp = gather_probe(model, items, a.fanout, a.dim, s_)
-            rows_gbs = gp["row_bytes_per_pair"] * Bl / (kern_avg_ms * 1e-3) / 1e9     # the fused kernel, rows only
-            gp["fused_kernel_rows_gbs"] = rows_gbs
-            gp["fused_kernel_frac_of_probe"] = rows_gbs / gp["achieved"]
-            gp["note"] = ("mvin_probe_gather_l2: the K + K*K table rows per pair of the timed region's own pairs, read once each with "
-                          "the same 16-byte lane loads by a PLAIN gather-and-sum kernel (one wave per parent, 8 loads in flight, ids "
-                          "from the expanded level lists one round ahead) -- a reference point, not an upper bound; "
-                          "fused_kernel_frac_of_probe = the full kernel's row bytes per second (adjacency chase, softmax, "
-                          "projections, MFMA epilogues on top) over the probe's")
-            timed["gather_only_probe"] = gp
-        roofline = timed
-        if not a.no_hbm_leg and used_l2 and not hoisted and cache_resident and L == 2:
-            # the genuinely HBM-bound measurement of the kernel INSTANCE the timed steps run, live, after the timed region: the
-            # projected-tables instance when that is what they take (its own leg: 4 M-row table, 3 x 1.02 GB of projected tables, its
-            # own bytes per pair), the unprojected instance otherwise; the sibling instances are reported next to it
-            def leg_brief(o):
-                b = {k: o[k] for k in ("kernel", "form", "avg_launch_ms", "achieved", "bytes_per_pair", "pairs_per_launch", "table_rows",
-                                       "table_bytes", "max_abs_err", "verified")}
-                b["frac"] = o["achieved"] / HBM_PEAK_GBS
-                return b
+        roofline = None
+        if a.full:
+            # HBM/fabric traffic of the dominant kernel comes from separate rocprofv3 --pmc passes
+            # (FETCH_SIZE, WRITE_SIZE; gfx950 correction applied) archived under profiles/; it is
+            # attached only when that profile was taken on exactly this workload
+            traffic = None
+            pmc = pmc_record("pmc_latest.json")
+            try:
+                same = (pmc is not None and a.table_dtype == "f32" and not a.n_entity and pmc.get("bench_args") == {
+                    "dataset": a.dataset, "dim": a.dim, "hop": a.hop, "mix": a.mix, "fanout": a.fanout, "adj": a.adj,
+                    "items": a.items, "batch": a.batch})
+                if same and used_l2 and world == 1 and not hoisted:
+                    traffic = pmc["gather_attn_l2_traffic_bytes_per_launch"] / pmc["gather_attn_l2_pairs_per_launch"] * Bl
+            except (KeyError, ValueError):
+                traffic = None
+            bpp = algorithmic_bytes_per_pair(a.dim, a.fanout, L, s=s_)
+            bpp_faithful = bpp
+            if hoisted:
+                # bytes this mode really needs per pair: K+1 fp32 rows of the hoisted tables + the adjacency row
+                # per level-(L-2) node, + (mode 'step') the table build amortised over the rank's pairs
+                K, D = a.fanout, a.dim
+                bpp = K ** (L - 2) * ((K + 1) * D * 4 + 2 * K * 4) + D * 4 + 4
+                if a.hoist == "step":
+                    bpp += case.n_entity * (K * D * s_ + 2 * K * 4 + D * s_ + 4 * D * 4) / Bl
+            kern_ms = [e0.elapsed_time(e1) for e0, e1 in prof]
+            kern_avg_ms = float(np.mean(kern_ms)) if kern_ms else None
+            achieved = (bpp * Bl / (kern_avg_ms * 1e-3) / 1e9) if kern_avg_ms else None
+            table_bytes = case.n_entity * a.dim * s_
+            cache_resident = table_bytes <= 256 * 2 ** 20        # Infinity Cache (MI355X_MICROARCH.md)
+            kname = (("gather_mix_kernel (mvin_gather_mix_fwd) + per-entity table build/lookups "
+                      "[entity-table mode: its own bytes per pair, not SURVEY 8(d)'s]") if hoisted
+                     else "linear_mfma_kernel + entity_aggregates_kernel<%d> + score_l2_folded_kernel<%d> (mvin_fold_tables -> mvin_score_l2_folded_fwd: "
+                          "EVERYTHING above key addressing -- four per-entity tables E.W1.A0 | E.W2.A0 | E.W0.A0 | E.W0.Wm0 and the aggregates H0 | G, all "
+                          "rebuilt inside every step from the current parameters, then ONE launch that takes a pair from its item id and query row to "
+                          "its score: six 64 x 64 products on the matrix cores around the gather of its distinct children's G rows; the same sums in "
+                          "another association)" % (a.fanout, a.fanout)
+                     if fold_now
+                     else "entity_aggregates_kernel<%d> + gather_attn_l2_agg_kernel<%d> (mvin_entity_aggregates -> mvin_gather_attn_l2_agg_fwd: per-entity "
+                          "aggregates S0 | G of the projected tables E.W1 | E.W1.A0 | E.W2.A0, all rebuilt inside every step from the current parameters; a "
+                          "pair then gathers its distinct children's G rows and one S0 row -- the same sums in another association)" % (a.fanout, a.fanout)
+                     if agg_now
+                     else "gather_attn_l2_wpp_kernel<%d> (mvin_gather_attn_l2_prj_ordered_fwd: wave-per-parent kernel over the duplicate-slot encoding of the "
+                          "adjacency, rows gathered from the projected tables E.W1 | E.W1.A0 | E.W2.A0 that mvin_project_tables rebuilds every step "
+                          "-- same ids and grandchild rows per pair as mvin_gather_attn_l2_enc_fwd, no product per distinct child; parents taken in "
+                          "item order: %s)" % (a.fanout, bool(model._item_order_for(Bl)))
+                     if (prj_now and enc is not None and _ops.gather_attn_l2_wpp_supported(a.dim, a.fanout))
+                     else "gather_attn_l2_packed_kernel<..., PRJ> (mvin_gather_attn_l2_prj_fwd: duplicate-slot encoding of the adjacency, rows "
+                          "gathered from the projected tables E.W1 | E.W1.A0 | E.W2.A0 that mvin_project_tables rebuilds every step -- same ids "
+                          "and grandchild rows per pair as mvin_gather_attn_l2_enc_fwd, no W1 / W2 / A0 product per distinct child)"
+                     if (prj_now and enc is not None)
+                     else "gather_attn_l2_d32_kernel<..., PRJ> (mvin_gather_attn_l2_prj_fwd over the plain adjacency: rows gathered from the "
+                          "projected tables E.W1 | E.W1.A0 | E.W2.A0 that mvin_project_tables rebuilds every step)"
+                     if prj_now
+                     else "gather_attn_l2_packed_kernel (mvin_gather_attn_l2_enc_fwd: duplicate-slot encoding of the adjacency)"
+                     if enc is not None
+                     else "gather_attn_l2_kernel (mvin_gather_attn_l2_fwd)" if used_l2
+                     else "gather_attn_kernel (mvin_gather_attn_fwd)")
+            peak = L2_PEAK_GBS if cache_resident else HBM_PEAK_GBS
+            # `achieved` / `frac` price the bytes the kernel MUST LOAD (for a plain adjacency that is SURVEY 8(d)'s figure; for the
+            # encoded path it is replaced below by the distinct rows it fetches); the faithful-bytes rate is informational
+            timed = {"bound": "l2" if cache_resident else "hbm", "kernel": kname, "achieved": achieved, "peak": peak,
+                     "unit": "GB/s", "frac": (achieved / peak) if achieved else None,
+                     "bytes_per_pair": bpp, "pairs_per_launch": Bl, "avg_launch_ms": kern_avg_ms,
+                     "faithful_bytes_rate_gbs": achieved,
+                     "table_bytes": table_bytes, "traffic": traffic,
+                     "kernel_timing": ("HIP events around the kernel's launches in a repeat of the same steps after the timed "
+                                       "region (the timed steps are ONE native call each, mvin_score_l2_fwd: no hooks inside)"
+                                       if one_call else "HIP events around the kernel's launches inside the timed steps"),
+                     "hbm_frac_from_traffic": (traffic / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+                     if (traffic and kern_avg_ms) else None,
+                     "whole_path_faithful_bytes_rate_gbs": value / world * bpp / 1e9,
+                     "faithful_bytes_per_pair": bpp_faithful,
+                     "note": ("launches inside the timed steps; the %.0f MB entity table is L2 / Infinity-Cache resident, so "
+                              "the algorithmic bytes are served on-chip: priced against the %.1f TB/s L2 aggregate, NOT the HBM "
+                              "peak; `traffic` = bytes per launch beyond L2 from rocprofv3 PMC passes (2*FETCH_SIZE + "
+                              "WRITE_SIZE, profiles/pmc_latest.json)" % (table_bytes / 1e6, L2_PEAK_GBS / 1e3))
+                     if cache_resident else "launches inside the timed steps; the table is far larger than the Infinity Cache"}
+            if enc is not None and L == 2 and kern_avg_ms:
+                # what the encoded path really loads: the DISTINCT slots of the item's row and of its distinct children's rows
+                # (the algorithmic bytes above stay SURVEY 8(d)'s K + K^2 rows per pair: repeated slots are not re-read)
+                enc_e, enc_r, cnt, frac_distinct = enc
+                it = items.long()
+                ch = (enc_e[it] & 0xFFFFFF).long()
+                real = ((enc_r[it] >> 16) & 0xFF) > 0
+                rows_loaded = float((1 + cnt[it].double() + (cnt[ch].double() * real).sum(1)).mean())
+                if prj_now:       # the projected-tables form reads TWO self rows per distinct child (T1[x] and TA1[x])
+                    rows_loaded += float(cnt[it].double().mean())
+                K_ = a.fanout
+                # encoded adjacency rows read per pair: the item's and its distinct children's, K words of ids + K of relations each
+                adj_rows = float((1 + cnt[it].double()).mean())
+                if agg_now:
+                    # the aggregates form: per pair its S0 row and its distinct children's G rows, its own adjacency row, the query row and
+                    # the two output rows; per ENTITY and step (entity_aggregates_kernel) its adjacency row, TA1[e], T1 and TA2 of its
+                    # distinct slots, S0[e] and G[e] written -- shared out over the step's pairs
+                    rows_loaded = float((1 + cnt[it].double()).mean())
+                    adj_rows = 1.0
+                    per_entity = float(((2 * cnt.double() + 1) * a.dim * 4 + K_ * 8 + 2 * a.dim * 4).sum()) / Bl
+                    loaded_bpp = rows_loaded * a.dim * 4 + K_ * 8 + 3 * a.dim * 4 + per_entity
+                    if fold_now:
+                        # folded tail, one launch: per pair H0[x], M0[x] and its distinct children's G rows, its adjacency row, its query and
+                        # user_o rows, the item embedding written, the score; per ENTITY and step E[e] read and four table rows written (table
+                        # build), then the aggregates kernel as above with one more self row (T0A[e])
+                        rows_loaded = float((2 + cnt[it].double()).mean())
+                        per_entity = float(((2 * cnt.double() + 2) * a.dim * 4 + K_ * 8 + 2 * a.dim * 4 + 5 * a.dim * 4).sum()) / Bl
+                        loaded_bpp = rows_loaded * a.dim * 4 + K_ * 8 + 3 * a.dim * 4 + 8 + per_entity
+                    timed["aggregates_build_bytes_per_step"] = per_entity * Bl
+                else:
+                    loaded_bpp = rows_loaded * a.dim * s_ + adj_rows * K_ * 8 + a.dim * 4 + 4
+                loaded_gbs = loaded_bpp * Bl / (kern_avg_ms * 1e-3) / 1e9
+                timed.update({"achieved": loaded_gbs, "frac": loaded_gbs / peak, "bytes_per_pair": loaded_bpp,
+                              "rows_per_pair_faithful": 1 + K_ + K_ * K_, "rows_per_pair_loaded": rows_loaded,
+                              "adjacency_rows_per_pair_loaded": adj_rows,
+                              "distinct_slots_per_adjacency_row": frac_distinct * K_,
+                              "folded_note": ("folded-tail form: `avg_launch_ms` covers mvin_fold_tables (parameter block, four-table build, aggregates) AND "
+                                              "the scoring launch -- everything above key addressing, mvin_l2_tail_fwd's work included; MVIN_L2_FOLD=0 "
+                                              "times aggregates + tail kernel, MVIN_L2_AGG=0 the kernel over the projected tables") if fold_now else None,
+                              "aggregates_note": ("aggregates form: `avg_launch_ms` covers BOTH launches (aggregates over all %d entities + the per-pair "
+                                                  "gather); a pair's rows come from the 27 MB G table, not from its grandchildren's rows of three tables "
+                                                  "(rows_per_pair_loaded ~ 1 + its distinct children; the wave-per-parent kernel over the tables loaded "
+                                                  "~120); MVIN_L2_AGG=0 times that kernel instead" % case.n_entity) if agg_now else None,
+                              "dedup_note": "the reference's sampler repeats slots whenever deg < K (data_loader_user_set.py:383-384) and the "
+                                            "packed kernel fetches every DISTINCT row once: `achieved` / `frac` / `bytes_per_pair` price what it "
+                                            "loads (distinct entity rows + the encoded adjacency rows + query + score); "
+                                            "`faithful_bytes_rate_gbs` = SURVEY 8(d)'s bytes per pair (every slot's row) over the same time is "
+                                            "informational and can exceed any peak -- it is a rate of work done, not of bytes moved"})
+            if ka_prof and by_user:
+                # the flash form of key addressing + user MLP inside the same (single-stream, instrumented) repeat of the timed steps:
+                # a kernel that IS bound by bytes from beyond the L2 -- every user's ripple rows come from a 245 MB per-call table
+                # (R_KGE[r] . E[e]) and three entity-sized ones, once per user and 32-pair tile
+                prep_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ka_prof]))
+                kern2_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ka_prof]))
+                P_, Nm_, D_ = d["p_hop"], d["n_memory"], a.dim
+                NmP = (Nm_ + 15) // 16 * 16
+                ucount = torch.bincount(users, minlength=case.n_user)
+                n_users_now = int((ucount > 0).sum().item())
+                tiles32 = int(((ucount + 31) // 32).sum().item())
+                slots64 = int(((ucount + 63) // 64).sum().item())
+                row_b = D_ * 4
+                # per 32-pair tile: P NmP rows of R_KGE.E + P NmP rows of E.Wmlp blocks; per 64-pair slot: NmP h-set rows + the record's three
+                # id sections; per pair: the item row, its id, its index in user order, the user_o row written
+                bytes_step = (tiles32 * 2 * P_ * NmP * row_b + slots64 * (NmP * row_b + (NmP + 2 * P_ * NmP) * 4)
+                              + Bl * (row_b + 8 + 4 + row_b))
+                tab_bytes = (case.n_relation + P_ + 1) * case.n_entity * row_b
+                timed["key_addressing_kernel"] = {
+                    "kernel": "key_addr_flash_kernel (mvin_key_addressing_flash_fwd: attention reads + user MLP of model.py:161-240 in one barrier-free "
+                              "kernel over per-call tables)",
+                    "avg_launch_ms": kern2_ms, "tables_build_ms": prep_ms, "tables_bytes_written_per_step": tab_bytes,
+                    "users_in_batch": n_users_now, "tiles_of_32_pairs": tiles32,
+                    "bytes_loaded_per_step": bytes_step, "bound": "hbm", "achieved": bytes_step / (kern2_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": bytes_step / (kern2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "note": "bytes the kernel must load per step (every row counted once per tile that needs it; the 245 MB R_KGE.E table and the "
+                            "82 MB of E.Wmlp blocks are far beyond the 8 x 4 MB of L2, the ripple sets are uniform random: SURVEY 8(d)) over its "
+                            "HIP-event time in the instrumented single-stream repeat; rocprofv3 counters of the same kernel under profiles/r6/ "
+                            "(TCC_EA0_RDREQ: ~1.2x these bytes leave the L2)"}
+            if used_l2 and not hoisted and L == 2 and world == 1 and not a.no_probe and kern_avg_ms:
+                gp = gather_probe(model, items, a.fanout, a.dim, s_)
+                rows_gbs = gp["row_bytes_per_pair"] * Bl / (kern_avg_ms * 1e-3) / 1e9     # the fused kernel, rows only
+                gp["fused_kernel_rows_gbs"] = rows_gbs
+                gp["fused_kernel_frac_of_probe"] = rows_gbs / gp["achieved"]
+                gp["note"] = ("mvin_probe_gather_l2: the K + K*K table rows per pair of the timed region's own pairs, read once each with "
+                              "the same 16-byte lane loads by a PLAIN gather-and-sum kernel (one wave per parent, 8 loads in flight, ids "
+                              "from the expanded level lists one round ahead) -- a reference point, not an upper bound; "
+                              "fused_kernel_frac_of_probe = the full kernel's row bytes per second (adjacency chase, softmax, "
+                              "projections, MFMA epilogues on top) over the probe's")
+                timed["gather_only_probe"] = gp
+            roofline = timed
+            if not a.no_hbm_leg and used_l2 and not hoisted and cache_resident and L == 2:
+                # the genuinely HBM-bound measurement of the kernel INSTANCE the timed steps run, live, after the timed region: the
+                # projected-tables instance when that is what they take (its own leg: 4 M-row table, 3 x 1.02 GB of projected tables, its
+                # own bytes per pair), the unprojected instance otherwise; the sibling instances are reported next to it
+                def leg_brief(o):
+                    b = {k: o[k] for k in ("kernel", "form", "avg_launch_ms", "achieved", "bytes_per_pair", "pairs_per_launch", "table_rows",
+                                           "table_bytes", "max_abs_err", "verified")}
+                    b["frac"] = o["achieved"] / HBM_PEAK_GBS
+                    return b
 
-            def leg_traffic_of(leg, fname):
-                pl = pmc_record(fname)
-                if pl and all(pl.get(k) == v for k, v in (("dim", a.dim), ("fanout", a.fanout), ("table_rows", leg["table_rows"]),
-                                                          ("pairs_per_launch", leg["pairs_per_launch"]),
-                                                          ("table_dtype", a.table_dtype))) \
-                        and leg["kernel"].split(" ")[0].split("<")[0] in pl.get("kernel", leg["kernel"]):     # the PMC passes timed the same kernel
-                    return pl["traffic_bytes_per_launch"]
-                return None
-            prj_leg = bool(prj_now and a.table_dtype == "f32")
-            leg = hbm_leg(dev, a.dim, a.fanout, a.table_dtype, encoded=enc is not None, prj=prj_leg)
-            leg_traffic = leg_traffic_of(leg, "pmc_hbm_leg_prj.json" if prj_leg else "pmc_hbm_leg.json")
-            siblings = {}
-            if prj_leg and enc is not None:      # the unprojected packed-tile instance on the 16 M-row table (rounds 4-5's roofline leg)
-                o = hbm_leg(dev, a.dim, a.fanout, a.table_dtype, encoded=True)
-                siblings["unprojected_kernel"] = leg_brief(o)
-                siblings["unprojected_kernel"]["traffic"] = leg_traffic_of(o, "pmc_hbm_leg.json")
-            if enc is not None or prj_leg:       # the plain-adjacency kernel on the same 16 M-row table (round 3's roofline kernel)
-                siblings["plain_adjacency_kernel"] = leg_brief(hbm_leg(dev, a.dim, a.fanout, a.table_dtype, encoded=False))
-            roofline = {"bound": "hbm", "kernel": leg["kernel"], "achieved": leg["achieved"], "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": leg["achieved"] / HBM_PEAK_GBS, "traffic": leg_traffic,
-                        "bytes_per_pair": leg["bytes_per_pair"], "bytes_per_pair_formula": leg["bytes_per_pair_formula"],
-                        "pairs_per_launch": leg["pairs_per_launch"],
-                        "avg_launch_ms": leg["avg_launch_ms"], "table_bytes": leg["table_bytes"],
-                        "table_rows": leg["table_rows"], "launches": leg["launches"],
-                        "max_abs_err": leg["max_abs_err"], "verified": leg["verified"], "verified_how": leg["verified_how"],
-                        "instance_is_the_timed_regions": bool(prj_leg == bool(prj_now)) and not agg_now,
-                        "instance_note": ("the timed steps take the per-entity aggregates form (timed_region.kernel): it exists where the batch holds "
-                                          "more parents than ~n_entity / 6 -- on this leg's 4 M-row table the aggregates alone would cost 4 M x 65 "
-                                          "rows per launch, so the gather kernel over the projected tables stays the kernel of this regime (and of "
-                                          "MVIN_L2_AGG=0) and keeps the leg; the aggregates kernels' own bytes and time are under timed_region"
-                                          if agg_now else None),
-                        **siblings,
-                        "workload": ("%s -- %s -- on a %.1f M-row synthetic entity table (%.2f GB of tables: %.0fx the Infinity Cache) with uniform "
-                                     "adjacency (no repeated slots: every row of every slot is loaded), so every gathered row comes from HBM; "
-                                     "measured after the timed region with HIP events around each launch on the launch stream; `traffic` = "
-                                     "2*FETCH_SIZE + WRITE_SIZE per launch from profiles/%s (rocprofv3 --pmc passes over `bench.py "
-                                     "--hbm-leg-only%s`)"
-                                     % (leg["kernel"],
-                                        "the gather kernel over the projected tables (the timed steps' tables; they then read per-entity aggregates of them)"
-                                        if agg_now else
-                                        "the template instance the timed steps launch" if prj_leg == bool(prj_now) else
-                                        "NOT the timed region's instance (that one reads projected tables; see `timed_region.kernel`)",
-                                        leg["table_rows"] / 1e6, leg["table_bytes"] / 1e9, leg["table_bytes"] / (256 * 2 ** 20),
-                                        "pmc_hbm_leg_prj.json" if prj_leg else "pmc_hbm_leg.json",
-                                        " --hbm-leg-form prj" if prj_leg else "")),
-                        "timed_region": timed}
+                def leg_traffic_of(leg, fname):
+                    pl = pmc_record(fname)
+                    if pl and all(pl.get(k) == v for k, v in (("dim", a.dim), ("fanout", a.fanout), ("table_rows", leg["table_rows"]),
+                                                              ("pairs_per_launch", leg["pairs_per_launch"]),
+                                                              ("table_dtype", a.table_dtype))) \
+                            and leg["kernel"].split(" ")[0].split("<")[0] in pl.get("kernel", leg["kernel"]):     # the PMC passes timed the same kernel
+                        return pl["traffic_bytes_per_launch"]
+                    return None
+                prj_leg = bool(prj_now and a.table_dtype == "f32")
+                leg = hbm_leg(dev, a.dim, a.fanout, a.table_dtype, encoded=enc is not None, prj=prj_leg)
+                leg_traffic = leg_traffic_of(leg, "pmc_hbm_leg_prj.json" if prj_leg else "pmc_hbm_leg.json")
+                siblings = {}
+                if prj_leg and enc is not None:      # the unprojected packed-tile instance on the 16 M-row table (rounds 4-5's roofline leg)
+                    o = hbm_leg(dev, a.dim, a.fanout, a.table_dtype, encoded=True)
+                    siblings["unprojected_kernel"] = leg_brief(o)
+                    siblings["unprojected_kernel"]["traffic"] = leg_traffic_of(o, "pmc_hbm_leg.json")
+                if enc is not None or prj_leg:       # the plain-adjacency kernel on the same 16 M-row table (round 3's roofline kernel)
+                    siblings["plain_adjacency_kernel"] = leg_brief(hbm_leg(dev, a.dim, a.fanout, a.table_dtype, encoded=False))
+                roofline = {"bound": "hbm", "kernel": leg["kernel"], "achieved": leg["achieved"], "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": leg["achieved"] / HBM_PEAK_GBS, "traffic": leg_traffic,
+                            "bytes_per_pair": leg["bytes_per_pair"], "bytes_per_pair_formula": leg["bytes_per_pair_formula"],
+                            "pairs_per_launch": leg["pairs_per_launch"],
+                            "avg_launch_ms": leg["avg_launch_ms"], "table_bytes": leg["table_bytes"],
+                            "table_rows": leg["table_rows"], "launches": leg["launches"],
+                            "max_abs_err": leg["max_abs_err"], "verified": leg["verified"], "verified_how": leg["verified_how"],
+                            "instance_is_the_timed_regions": bool(prj_leg == bool(prj_now)) and not agg_now,
+                            "instance_note": ("the timed steps take the per-entity aggregates form (timed_region.kernel): it exists where the batch holds "
+                                              "more parents than ~n_entity / 6 -- on this leg's 4 M-row table the aggregates alone would cost 4 M x 65 "
+                                              "rows per launch, so the gather kernel over the projected tables stays the kernel of this regime (and of "
+                                              "MVIN_L2_AGG=0) and keeps the leg; the aggregates kernels' own bytes and time are under timed_region"
+                                              if agg_now else None),
+                            **siblings,
+                            "workload": ("%s -- %s -- on a %.1f M-row synthetic entity table (%.2f GB of tables: %.0fx the Infinity Cache) with uniform "
+                                         "adjacency (no repeated slots: every row of every slot is loaded), so every gathered row comes from HBM; "
+                                         "measured after the timed region with HIP events around each launch on the launch stream; `traffic` = "
+                                         "2*FETCH_SIZE + WRITE_SIZE per launch from profiles/%s (rocprofv3 --pmc passes over `bench.py "
+                                         "--hbm-leg-only%s`)"
+                                         % (leg["kernel"],
+                                            "the gather kernel over the projected tables (the timed steps' tables; they then read per-entity aggregates of them)"
+                                            if agg_now else
+                                            "the template instance the timed steps launch" if prj_leg == bool(prj_now) else
+                                            "NOT the timed region's instance (that one reads projected tables; see `timed_region.kernel`)",
+                                            leg["table_rows"] / 1e6, leg["table_bytes"] / 1e9, leg["table_bytes"] / (256 * 2 ** 20),
+                                            "pmc_hbm_leg_prj.json" if prj_leg else "pmc_hbm_leg.json",
+                                            " --hbm-leg-form prj" if prj_leg else "")),
+                            "timed_region": timed}
         rec = {
             "metric": "(user,item) pairs scored/sec @ dim=%d hop=%d fan-out=%d; %% HBM roofline"
                       % (a.dim, a.hop, a.fanout),
@@ -1137,7 +1183,7 @@ def main():
                                        if rowshard else
                                        (f"pairs split over {world} ranks; tables replicated" if world > 1
                                         else "single-gpu"))},
-            "roofline": roofline,
+            **({"roofline": roofline} if roofline is not None else {}),
         }
         # what the multi-GPU line rests on, printed so that the first real SCALE run verifies itself
         import torch.distributed as tdist
@@ -1186,12 +1232,12 @@ def main():
                                              "1, two streams); `value` = the MEASURED per-rank rate, `projected_value` = x W is a "
                                              "PROJECTION of the W-GPU line, not a measurement: no fabric is involved; the user-order "
                                              "partition of the global batch is done on the host OUTSIDE the timed steps"}
-        if world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard:
+        if a.full and world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard:
             smh, smr, smt = (mh, mr, mt) if mh is not None else pair_feed()   # per-pair feeds: the reference's own
             uts_sw = uts_d if a.feed == "users" else torch.from_numpy(case.user_triplet_set).to(dev)
             rec["batch_sweep"] = batch_sweep(model, users, items, smh, smr, smt, [int(x) for x in a.sweep.split(",") if x],
                                              uts=uts_sw)
-        if world == 1 and a.hoist == "off" and not rowshard and scorer is None:
+        if a.full and world == 1 and a.hoist == "off" and not rowshard and scorer is None:
             # the same pass with the OTHER feed, after the timed region
             if by_user:
                 pmh, pmr, pmt = pair_feed()
@@ -1216,12 +1262,12 @@ def main():
                 "value": a.batch / dtg, "unit": "pairs/s", "ms_per_step": 1e3 * dtg,
                 "max_abs_diff_vs_timed_feed_scores": (go.scores - out.scores).abs().max().item(), "note": note}
             del go
-        if world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard and a.adj == "kg" and not a.n_entity:
+        if a.full and world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard and a.adj == "kg" and not a.n_entity:
             try:                                                          # informational, after the timed region
                 rec.setdefault("other_modes", {})["uniform_adjacency"] = uniform_adjacency_variant(a, dev)
             except Exception as e:
                 rec.setdefault("other_modes", {})["uniform_adjacency"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_cpu_baseline and a.hoist == "off" and not rowshard and model.hoist_supported():
+        if a.full and world == 1 and not a.no_cpu_baseline and a.hoist == "off" and not rowshard and model.hoist_supported():
             # informational only, measured AFTER the timed region on the same inputs: the entity-table mode
             #  has its own bytes per pair and is never `value`
             hm = MVIN(margs, case.n_user, case.n_entity, case.n_relation, case.adj_entity, case.adj_relation,
@@ -1243,7 +1289,7 @@ def main():
                 "note": "per-entity tables hoist the pair-independent part of the two deepest levels "
                         "(SURVEY 7.3-c route 2b): different algorithmic bytes per pair, reported separately"}
             del hm, ho
-        if world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard and a.table_dtype == "f32":
+        if a.full and world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard and a.table_dtype == "f32":
             # informational, after the timed region: the caller AFTER the path -- forward + loss + backward +
             # Adam on a separate model instance with the same parameters, at the reference's batch sizes
             try:
@@ -1254,12 +1300,12 @@ def main():
                                                                                    items[:nt], tmem)
             except Exception as e:                                        # never lose the scoring line to this leg
                 rec.setdefault("other_modes", {})["training_step"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard and a.dim != 16 and a.table_dtype == "f32":
+        if a.full and world == 1 and not a.no_sweep and a.hoist == "off" and not rowshard and a.dim != 16 and a.table_dtype == "f32":
             try:                                                          # informational, after the timed region
                 rec.setdefault("other_modes", {})["reference_shipped_config"] = shipped_config(a, dev)
             except Exception as e:
                 rec.setdefault("other_modes", {})["reference_shipped_config"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cb, ref, Bc = cpu_baseline(a, margs, case, params)
             rec["cpu_baseline"] = cb
             got = out.scores[:Bc].cpu().numpy()  # rank 0 owns the first pairs of the global batch

@@ -4,7 +4,7 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$root"; mkdir -p gpurun_out; out=gpurun_out/ab_enc.txt; : > $out
 run() {
   for e in 0 1; do
-    line=$(MVIN_L2_ENC=$e python bench.py --no-cpu-baseline --no-hbm-leg --no-sweep --no-probe --steps 10 --warmup 3 "$@" 2>/dev/null | grep '^{' | tail -1)
+    line=$(MVIN_L2_ENC=$e python bench.py --full --no-cpu-baseline --no-hbm-leg --no-sweep --no-probe --steps 10 --warmup 3 "$@" 2>/dev/null | grep '^{' | tail -1)
     python - "$line" "enc=$e $*" >> $out <<'PY'
 import json, sys
 r = json.loads(sys.argv[1]); t = r["roofline"].get("timed_region", r["roofline"])

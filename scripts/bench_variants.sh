@@ -4,7 +4,7 @@
 root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$root"; mkdir -p gpurun_out; out=gpurun_out/bench_variants.jsonl; : > $out
 run() {
-  line=$(python bench.py --no-cpu-baseline --no-hbm-leg --no-sweep --steps 10 --warmup 3 "$@" 2>/dev/null | grep '^{' | tail -1)
+  line=$(python bench.py --full --no-cpu-baseline --no-hbm-leg --no-sweep --steps 10 --warmup 3 "$@" 2>/dev/null | grep '^{' | tail -1)
   [ -n "$line" ] && python - "$line" "$*" >> $out <<'PY'
 import json, sys
 r = json.loads(sys.argv[1]); r["variant_args"] = sys.argv[2]; print(json.dumps(r))

@@ -7,7 +7,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 steps = sys.argv[1] if len(sys.argv) > 1 else "100"
 rows = []
 for W in (1, 2, 4, 8):
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--no-hbm-leg", "--no-sweep", "--no-cpu-baseline", "--steps", steps,
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--no-hbm-leg", "--no-sweep", "--no-cpu-baseline", "--steps", steps,
            "--warmup", "5"] + ([] if W == 1 else ["--emulate-world", str(W)])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])

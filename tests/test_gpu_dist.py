@@ -128,7 +128,7 @@ def test_bench_two_ranks_one_gpu(hip_lib):
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = _run_ranks([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                    "--batch", "4096"], 2)
+                    "--batch", "4096", "--full"], 2)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     rec = json.loads(line)

@@ -99,6 +99,38 @@ def test_bench_algorithmic_bytes_match_survey():
     assert bench.algorithmic_bytes_per_pair(128, 128, 3, s=2) == 558007812
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.py --dump-outputs: the output namespace as float32 .npy files -- whole while it fits the budget, otherwise the
+    same seeded sample of pairs (ascending) for every array, within the budget, identical from run to run."""
+    import types
+    import torch
+    import bench
+    B, D = 1000, 8
+    g = torch.Generator().manual_seed(3)
+    user_o, item_emb = torch.rand((B, D), generator=g), torch.rand((B, D), generator=g)
+    scores = (user_o * item_emb).sum(1)
+    out = types.SimpleNamespace(scores=scores, scores_normalized=torch.sigmoid(scores), user_o=user_o, item_embeddings=item_emb,
+                                importance_list=[])
+    shapes = bench.dump_outputs(out, str(tmp_path / "whole"))
+    assert shapes == {"scores": [B], "scores_normalized": [B], "user_o": [B, D], "item_embeddings": [B, D]}
+    for name in shapes:
+        arr = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert arr.dtype == np.float32
+        np.testing.assert_array_equal(arr, getattr(out, name).numpy())
+    limit = 10_000                                         # 2 + 2 D floats per pair: 138 of the 1 000 pairs fit
+    for run in ("a", "b"):
+        shapes = bench.dump_outputs(out, str(tmp_path / run), limit=limit)
+        assert shapes["scores"] == [138] and shapes["user_o"] == [138, D]
+        assert sum(np.load(tmp_path / run / f"{n}.npy").nbytes for n in shapes) <= limit
+    for name in shapes:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+    # one set of pairs for every array, in ascending order
+    got_s, got_u = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "user_o.npy")
+    rows = [int(np.flatnonzero((user_o.numpy() == u).all(1))[0]) for u in got_u]
+    assert rows == sorted(rows) and len(set(rows)) == len(rows)
+    np.testing.assert_array_equal(got_s, scores.numpy()[rows])
+
+
 def test_algorithmic_bytes_per_pair_matches_survey_table():
     """bench.py's roofline numerator is SURVEY.md 8(d)'s figure: T*D*s + (T-K^L)*K*8 + D*s + 4."""
     import importlib.util
