@@ -724,6 +724,26 @@ MVIN_API int mvin_build_ripple_sets(const int64_t* indptr, const int32_t* dst, c
                            const int64_t* hist_ptr, const int32_t* hist_items, int n_user, int P, int Nm,
                            int n_neighbor, uint64_t seed, int32_t* out, void* stream);
 
+/* ---- top-K recommendation: the ranking step of the reference's top-K evaluation (util.py:178-181) for many users at once --
+ * mvin_topk_rows: row r of `scores` is scores[r*ld .. r*ld+n) (never written).  Column j is candidate item cand_ids[j]
+ * (cand_ids NULL: item col_offset + j, which must fit int32) at global position col_offset + j.  out_ids / out_vals [rows, k]
+ * receive row r's k best ELIGIBLE candidates in order:
+ *  - higher score first; equal scores: lower position first, carry entries before every column of this block, carry entries
+ *    in their own order -- Python's stable sorted(key=score, reverse=True) over the candidates in position order;
+ *  - -0.0 equals +0.0; NaN ranks below -inf (NaNs in position order); the values written are the input bits;
+ *  - a column is eligible unless its item id is in row r's exclusion list: excl_ids[excl_ptr[r] .. excl_ptr[r+1]), ascending
+ *    (excl_ptr [rows+1] int64; both NULL = no exclusions);
+ *  - carry_ids / carry_vals [rows, k] (both or neither): a running top-K from earlier column blocks; id -1 = padding, dropped;
+ *    out_* may alias carry_*, so a loop over column blocks updates its running top-K in place;
+ *  - fewer than k eligible candidates: the tail is id -1, value -inf.
+ * Errors (< 0, nothing launched): null required pointers, k unsupported, rows < 0, n < 0, ld < n.  n == 0 gives each row its
+ * carry entries (or padding).  `ws` may be NULL when mvin_topk_rows_ws_bytes says 0. */
+MVIN_API int mvin_topk_rows_supported(int k);                                  /* 1 for 1 <= k <= 1024 */
+MVIN_API int64_t mvin_topk_rows_ws_bytes(int64_t rows, int64_t n, int k);      /* 0: no workspace needed */
+MVIN_API int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                            const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals,
+                            int k, void* ws, int32_t* out_ids, float* out_vals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

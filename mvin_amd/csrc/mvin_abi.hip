@@ -394,6 +394,33 @@ int mvin_order_by_key(const int64_t* keys_i64, const int32_t* keys_i32, int64_t 
     return hip_result(mvin::launch_order_by_key(keys_i64, keys_i32, B, workspace, order, (hipStream_t)stream), who);
 }
 
+int mvin_topk_rows_supported(int k) { return mvin::topk_rows_supported(k) ? 1 : 0; }
+
+int64_t mvin_topk_rows_ws_bytes(int64_t rows, int64_t n, int k) {
+    (void)rows;
+    (void)n;
+    (void)k;
+    return 0;                                             // one workgroup per row, everything it keeps sits in LDS
+}
+
+int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                   const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals, int k, void* ws,
+                   int32_t* out_ids, float* out_vals, void* stream) {
+    (void)ws;
+    const char* who = "mvin_topk_rows";
+    if (!mvin::topk_rows_supported(k)) return fail(-2, "%s: k=%d (1 <= k <= 1024)", who, k);
+    if (rows < 0 || rows >= (int64_t(1) << 31) || n < 0 || n >= (int64_t(1) << 31) || ld < n)
+        return fail(-2, "%s: rows=%lld n=%lld ld=%lld", who, (long long)rows, (long long)n, (long long)ld);
+    if (!out_ids || !out_vals || (n > 0 && !scores)) return fail(-1, "%s: null scores / out_ids / out_vals", who);
+    if ((carry_ids == nullptr) != (carry_vals == nullptr)) return fail(-1, "%s: carry_ids and carry_vals go together", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together", who);
+    if (!cand_ids && (col_offset < 0 || col_offset + n > (int64_t)0x7FFFFFFF))
+        return fail(-2, "%s: col_offset=%lld: implicit ids col_offset + j must be int32", who, (long long)col_offset);
+    return hip_result(mvin::launch_topk_rows(scores, rows, n, ld, cand_ids, col_offset, excl_ptr, excl_ids, carry_ids, carry_vals, k,
+                                             out_ids, out_vals, (hipStream_t)stream),
+                      who);
+}
+
 int mvin_gather_attn_l2_prj_ordered_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, int adjacency_encoded,
                                         const void* parent_ids, int parent_ids_i64, const int32_t* order, const float* t0, const float* t1,
                                         const float* q, int B, int parents_per_pair, int K, int D, int n_entity, int nR, float* nagg0,

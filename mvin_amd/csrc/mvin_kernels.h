@@ -432,6 +432,10 @@ hipError_t launch_group_pairs(const int64_t* u64, const int32_t* u32, int64_t B,
 hipError_t launch_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, hipStream_t st);   // mvin_bwd.hip
 bool fused_d32_supported(int D, int K);        // wave-per-parent variant for D = 32, K in {8, 16} (mvin_fused_d32.hip)
 bool fused_d32_applies(const FusedL2Args& a, int D);
+bool topk_rows_supported(int k);                               // row-wise top-K selection (mvin_topk.hip)
+hipError_t launch_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                            const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals, int k,
+                            int32_t* out_ids, float* out_vals, hipStream_t st);
 size_t order_ws_elems(int64_t B);                             // pairs in key order (mvin_order.hip)
 hipError_t launch_order_by_key(const int64_t* k64, const int32_t* k32, int64_t B, int32_t* ws, int32_t* order, hipStream_t st);
 bool fused_wpp_supported(int D, int K);                       // wave-per-parent kernel over projected tables, dim 64 (mvin_fused_wpp.hip)

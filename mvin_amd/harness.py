@@ -100,6 +100,100 @@ class DeviceFeeder(object):
                                          [sel[i, 2].contiguous() for i in range(self.P)]).scores_normalized
 
 
+    def score_grid(self, users, candidates, out=None):
+        """sigmoid scores of every (users[i], candidates[j]) pair as a device tensor [U, N] (``out`` if given): the pair list is
+        built on the device and scored by ONE ``forward_users`` call, in whatever form the model's automatic rules pick."""
+        import torch
+        dev = self.model.device
+        u = _dev_ids(users, dev)
+        it = _dev_ids(candidates, dev)
+        U, N = u.shape[0], it.shape[0]
+        if out is None:
+            out = torch.empty((U, N), dtype=torch.float32, device=dev)
+        if U == 0 or N == 0:
+            return out
+        sig = self.model.forward_users(u.repeat_interleave(N), it.repeat(U), self.uts, distinct_users=U).scores_normalized
+        out.copy_(sig.view(U, N))
+        return out
+
+    def exclusion_csr(self, users, record):
+        """Row i = the items of ``record[users[i]]`` (a get_user_record dict; a missing user has an empty row), ascending, as a
+        device CSR pair (ptr int64 [U+1], ids int32) for ops.topk_rows / recommend.  Host plumbing, built once per call."""
+        import torch
+        ptr, ids = _exclusion_csr_host(users, record)
+        dev = self.model.device
+        return torch.from_numpy(ptr).to(dev), torch.from_numpy(ids).to(dev)
+
+    def recommend(self, users, k, candidates, exclude=None, max_pairs=524288):
+        """The ``k`` best candidates of every user: (items int64 [U, k], scores f32 [U, k]) on the device, best first; equal scores
+        keep the order of ``candidates`` (pass them ascending for the reference's tie order); rows with fewer than ``k`` eligible
+        candidates end in item -1, score -inf.  ``exclude``: a get_user_record dict (``users`` then on the host) or an
+        ``exclusion_csr`` pair.  Users are scored in chunks of at most ``max_pairs`` pairs (``score_grid``); a candidate list longer
+        than ``max_pairs`` is also cut into column blocks whose running top-K is carried through ops.topk_rows.  Enqueues only:
+        no synchronisation, no copy to the host."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        k, max_pairs = int(k), int(max_pairs)
+        if max_pairs < 1:
+            raise ValueError(f"max_pairs={max_pairs}")
+        if isinstance(exclude, dict):
+            if torch.is_tensor(users) and users.is_cuda:
+                raise ValueError("recommend: an exclusion record needs host users (or pass feeder.exclusion_csr(users, record))")
+            exclude = self.exclusion_csr(users, exclude)
+        u = _dev_ids(users, dev)
+        U = u.shape[0]
+        contiguous, base = False, 0
+        if torch.is_tensor(candidates):
+            cand = candidates.to(dev).long().reshape(-1)
+            N = cand.shape[0]
+        else:
+            arr = np.asarray(candidates, dtype=np.int64).reshape(-1)
+            N = arr.shape[0]
+            # a contiguous id range (the full catalogue): the kernel derives each column's id from its position
+            contiguous = bool(N and arr[0] >= 0 and arr[-1] < (1 << 31) - 1 and np.array_equal(arr, np.arange(arr[0], arr[0] + N)))
+            base = int(arr[0]) if contiguous else 0
+            cand = torch.from_numpy(arr).to(dev)
+        cand_ids = None if contiguous else cand.to(torch.int32)
+        out_ids = torch.empty((U, k), dtype=torch.int32, device=dev)
+        out_vals = torch.empty((U, k), dtype=torch.float32, device=dev)
+        if U == 0:
+            return out_ids.long(), out_vals
+        cols = max(1, min(N, max_pairs))
+        per = max(1, max_pairs // cols)
+        for u0 in range(0, U, per):
+            u1 = min(U, u0 + per)
+            out = (out_ids[u0:u1], out_vals[u0:u1])
+            excl = None if exclude is None else (exclude[0][u0:u1 + 1], exclude[1])
+            carry = None
+            for c0 in range(0, N, cols) if N else [0]:
+                c1 = min(N, c0 + cols)
+                grid = self.score_grid(u[u0:u1], cand[c0:c1])
+                ops.topk_rows(grid, k, cand_ids=None if cand_ids is None else cand_ids[c0:c1], col_offset=base + c0,
+                              excl=excl, carry=carry, out=out)
+                carry = out
+        return out_ids.long(), out_vals
+
+
+def _dev_ids(x, dev):
+    import torch
+    if torch.is_tensor(x):
+        return x.to(dev).long().reshape(-1)
+    return torch.from_numpy(np.asarray(x, dtype=np.int64).reshape(-1)).to(dev)
+
+
+def _exclusion_csr_host(users, record):
+    import torch
+    if torch.is_tensor(users):
+        users = users.cpu().numpy()
+    users = np.asarray(users).reshape(-1)
+    rows = [np.sort(np.fromiter(record.get(int(u), ()), dtype=np.int64)) for u in users]
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([r.size for r in rows])
+    ids = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, dtype=np.int32)
+    return ptr, ids
+
+
 # --------------------------------------------------------------------------- training loop
 def train_epoch(args, model, train_data, user_triplet_set, sess=None, rng=None):
     """One epoch of train.py:56-64 through ``model.train(sess, feed_dict)``: shuffle, then full
@@ -322,6 +416,27 @@ def topk_eval_device(feeder, user_list, train_record, eval_record, test_record, 
             [float(np.mean(ndcg_list[k])) for k in k_list], None, None)
 
 
+def topk_eval_batched(feeder, user_list, train_record, eval_record, test_record, item_set, k_list, mode="test",
+                      max_pairs=524288):
+    """topk_eval_device's numbers from ONE batched recommendation: the users of ``user_list`` present in the ``mode`` record are
+    scored against ``sorted(item_set)`` and ranked on the device (DeviceFeeder.recommend, mvin_topk_rows), their train items
+    excluded; one copy of the [U, max(k_list)] ids comes back.  The top max(k_list) items are all the metrics read, the stale-k
+    NDCG list included (k_list[-1] <= max(k_list)).  Ties go to the lower item id (topk_eval_device inherits the set's
+    iteration order, which is usually but not always ascending)."""
+    precision_list = {k: [] for k in k_list}
+    recall_list = {k: [] for k in k_list}
+    ndcg_list = {k: [] for k in k_list}
+    ref = eval_record if mode == "eval" else test_record
+    users = [u for u in user_list if u in ref]
+    if users:
+        items, _ = feeder.recommend(users, max(k_list), sorted(item_set), exclude=train_record, max_pairs=max_pairs)
+        items = items.cpu().numpy()
+        for user, row in zip(users, items):
+            _rank_metrics(row[row >= 0].tolist(), ref[user], k_list, precision_list, recall_list, ndcg_list)
+    return ([float(np.mean(precision_list[k])) for k in k_list], [float(np.mean(recall_list[k])) for k in k_list],
+            [float(np.mean(ndcg_list[k])) for k in k_list], None, None)
+
+
 # --------------------------------------------------------------------------- the train.py loop
 class EarlyStop(object):
     """train_util.py:20-61 (Early_stop_info): keep the best evaluation score, save the stage-wise
@@ -349,7 +464,7 @@ class EarlyStop(object):
 
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
-          topk_early_stop=False, graph="auto"):
+          topk_early_stop=False, graph="auto", topk_impl="host"):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -365,6 +480,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     ``graph``: replay every optimisation step as one hipGraph (training.GraphedTrainer; same kernels, losses read back
     once per epoch); "auto" = at batch sizes up to 2 048, where a step is launch- and latency-bound (the reference's
     scripts train at 512 / 1 024).
+    ``topk_impl``: "host" ranks user by user on the host (topk_eval_device); "batched" ranks every user on the device in one
+    call (topk_eval_batched; ties by ascending item id).
     Returns (model, history): one dict per epoch."""
     from .model import MVIN
     n_user, n_item, n_entity, n_relation = data[0], data[1], data[2], data[3]
@@ -374,6 +491,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         model = MVIN(args, n_user, n_entity, n_relation, adj_entity, adj_relation, device=device, hoist=bool(hoist))
         if getattr(args, "load_pretrain_emb", False):
             model.restore_pretrain_emb()                                       # train.py:53-54
+    if topk_impl not in ("host", "batched"):
+        raise ValueError(f"topk_impl={topk_impl!r}: expected 'host' or 'batched'")
     feeder = DeviceFeeder(model, uts)
     stop = EarlyStop(getattr(args, "tolerance", 2), getattr(args, "early_stop", 3),
                      getattr(args, "save_final_model", True))
@@ -390,8 +509,12 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         rec = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else float("nan")}
         if show_topk:
             for mode in ("eval", "test"):
-                p, r, n, _, _ = topk_eval_device(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list,
-                                                 topk_batch, mode=mode)
+                if topk_impl == "batched":
+                    p, r, n, _, _ = topk_eval_batched(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list,
+                                                      mode=mode)
+                else:
+                    p, r, n, _, _ = topk_eval_device(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list,
+                                                     topk_batch, mode=mode)
                 rec[mode] = {"precision": p, "recall": r, "ndcg": n}
             score = rec["eval"]["recall"][2]
         else:

@@ -357,6 +357,65 @@ def order_by_key(keys, ws=None, out=None):
     return out
 
 
+def topk_rows_supported(k):
+    return bool(_lib.load().mvin_topk_rows_supported(int(k)))
+
+
+def topk_rows(scores, k, cand_ids=None, col_offset=0, excl=None, carry=None, out=None):
+    """mvin_topk_rows: the ``k`` best eligible candidates of every row of ``scores`` ([rows, n] f32; rows may be strided, columns
+    must be dense), higher score first, ties by position (carry entries first, then column order) -- the reference's stable
+    ``sorted(..., reverse=True)``.  ``cand_ids`` [n] int32: item id of each column (None: ``col_offset + j``); ``excl``: a
+    ``(ptr int64 [rows+1], ids int32)`` CSR of item ids excluded per row, each row ascending; ``carry``: ``(ids, vals)`` [rows, k],
+    a running top-K of earlier column blocks (id -1 = padding); ``out``: ``(ids, vals)`` to write, may be ``carry`` itself.
+    Returns ``(ids int32 [rows, k], vals f32 [rows, k])``; short rows are padded with id -1, value -inf."""
+    lib = _lib.load()
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise _lib.MvinHipError("scores: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if scores.dtype != F32:
+        raise TypeError(f"scores: expected {F32}, got {scores.dtype}")
+    if scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1) or scores.stride(0) < scores.shape[1]:
+        raise ValueError("scores: expected a [rows, n] tensor with dense rows")
+    k = int(k)
+    if not topk_rows_supported(k):
+        raise ValueError(f"k={k}: mvin_topk_rows takes 1 <= k <= 1024")
+    rows, n = scores.shape
+    dev = scores.device
+    if cand_ids is not None:
+        _chk(cand_ids, I32, "cand_ids")
+        if cand_ids.numel() != n:
+            raise ValueError(f"cand_ids: {cand_ids.numel()} ids for {n} columns")
+    ptr = ids = None
+    if excl is not None:
+        ptr, ids = excl
+        _chk(ptr, torch.int64, "excl ptr")
+        _chk(ids, I32, "excl ids")
+        if ptr.numel() != rows + 1:
+            raise ValueError(f"excl ptr: {ptr.numel()} entries for {rows} rows")
+    cid = cval = None
+    if carry is not None:
+        cid, cval = carry
+        _chk(cid, I32, "carry ids")
+        _chk(cval, F32, "carry vals")
+        if tuple(cid.shape) != (rows, k) or tuple(cval.shape) != (rows, k):
+            raise ValueError(f"carry: expected [{rows}, {k}]")
+    if out is None:
+        out = (torch.empty((rows, k), dtype=I32, device=dev), torch.empty((rows, k), dtype=F32, device=dev))
+    oid, oval = out
+    _chk(oid, I32, "out ids")
+    _chk(oval, F32, "out vals")
+    if tuple(oid.shape) != (rows, k) or tuple(oval.shape) != (rows, k):
+        raise ValueError(f"out: expected [{rows}, {k}]")
+    nws = lib.mvin_topk_rows_ws_bytes(rows, n, k)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    ld = scores.stride(0) if rows > 1 else n
+    ids_p = None if ids is None or ids.numel() == 0 else _p(ids)
+    if ptr is not None and ids_p is None:
+        ids_p = _p(ptr)                         # every row empty: any valid pointer, nothing is read through it
+    _lib.check(lib.mvin_topk_rows(_p(scores) if n > 0 else None, rows, n, ld, _p(cand_ids), int(col_offset), _p(ptr), ids_p,
+                                  _p(cid), _p(cval), k, _p(ws), _p(oid), _p(oval), _stream()), "mvin_topk_rows")
+    return oid, oval
+
+
 def gather_attn_l2_prj(ws, enc_entity, enc_relation, parent_ids, t0, t1, q, B, parents_per_pair, K, D, nR, n_entity, encoded=True, order=None):
     """mvin_gather_attn_l2_prj_fwd: gather_attn_l2_enc over the workspace of ``project_tables`` (built with attention =
     (t0 is not None)).  ``encoded=False``: the two adjacency arrays are the plain adjacency (D = 32, K in {8, 16}).
