@@ -744,6 +744,27 @@ MVIN_API int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_
                             const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals,
                             int k, void* ws, int32_t* out_ids, float* out_vals, void* stream);
 
+/* ---- CTR metrics: exact integer counts behind the reference's CTR evaluation (util.py:44-56: roc_auc_score, accuracy and
+ * f1_score of every batch) for many segments at once --
+ * mvin_ctr_counts: segment s is scores[s*ld .. s*ld+seg_len) (f32) with labels[s*ld .. s*ld+seg_len) (int32, 0 or 1); neither is
+ * written.  out [n_seg, 6] int64 receives per segment:
+ *   n_pos, n_neg   label counts (label 1 / label 0);
+ *   tp, fp         positives / negatives predicted positive, prediction = (score >= 0.5f) compared in f32;
+ *   u2             2 * #{(p, n): s_p > s_n} + #{(p, n): s_p == s_n} over positive p and negative n, i.e. twice the
+ *                  Mann-Whitney U: AUC = u2 / (2 * n_pos * n_neg).  Scores compare as numbers, -0.0 equals +0.0;
+ *   bad            non-finite scores plus labels other than 0 and 1 (such labels count in neither class); the other
+ *                  columns are not meaningful for a segment with bad > 0.
+ * Every count is exact and independent of the launch shape.  seg_len <= MVIN_CTR_SEG_CAP: one workgroup per segment, no
+ * workspace; longer segments (up to 2^31 - 1) take a sequence of launches on `stream` through `ws`
+ * (mvin_ctr_counts_ws_bytes bytes, may be NULL when that is 0).
+ * Errors (< 0, nothing launched): -2 for seg_len < 1, seg_len > 2^31 - 1, n_seg < 0, n_seg * seg_len > 2^40 or
+ * ld < seg_len; -1 for null scores /
+ * labels / out, or a null ws that is needed.  n_seg == 0 launches nothing. */
+#define MVIN_CTR_SEG_CAP 16384
+MVIN_API int64_t mvin_ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);     /* < 0: invalid sizes */
+MVIN_API int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
+                             int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

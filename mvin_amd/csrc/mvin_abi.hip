@@ -421,6 +421,26 @@ int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, con
                       who);
 }
 
+static bool ctr_bad_sizes(int64_t n_seg, int64_t seg_len) {     // also: at most 2^40 pairs in all
+    return seg_len < 1 || seg_len > (int64_t)0x7FFFFFFF || n_seg < 0 || n_seg > ((int64_t)1 << 40) / seg_len;
+}
+
+int64_t mvin_ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len) {
+    if (ctr_bad_sizes(n_seg, seg_len)) return fail(-2, "mvin_ctr_counts_ws_bytes: n_seg=%lld seg_len=%lld", (long long)n_seg, (long long)seg_len);
+    return mvin::ctr_counts_ws_bytes(n_seg, seg_len);
+}
+
+int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws, int64_t* out,
+                    void* stream) {
+    const char* who = "mvin_ctr_counts";
+    if (ctr_bad_sizes(n_seg, seg_len) || ld < seg_len)
+        return fail(-2, "%s: n_seg=%lld seg_len=%lld ld=%lld", who, (long long)n_seg, (long long)seg_len, (long long)ld);
+    if (!scores || !labels || !out) return fail(-1, "%s: null scores / labels / out", who);
+    if (!ws && n_seg > 0 && mvin::ctr_counts_ws_bytes(n_seg, seg_len) > 0)
+        return fail(-1, "%s: null ws (seg_len=%lld needs mvin_ctr_counts_ws_bytes)", who, (long long)seg_len);
+    return hip_result(mvin::launch_ctr_counts(scores, labels, n_seg, seg_len, ld, ws, out, (hipStream_t)stream), who);
+}
+
 int mvin_gather_attn_l2_prj_ordered_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, int adjacency_encoded,
                                         const void* parent_ids, int parent_ids_i64, const int32_t* order, const float* t0, const float* t1,
                                         const float* q, int B, int parents_per_pair, int K, int D, int n_entity, int nR, float* nagg0,

@@ -14,6 +14,7 @@
 //   5. ids and values are fetched from where each survivor came from (the values are the input bits), staged in LDS, then written.
 // The row is never staged in LDS (a last-fm row is 192 KB); what a pass needs per candidate is one coalesced load and one bitmap read.
 #include "mvin_kernels.h"
+#include "mvin_score_image.h"
 
 namespace mvin {
 
@@ -35,13 +36,6 @@ struct TopkArgs {
     int32_t* out_ids;
     float* out_vals;
 };
-
-__device__ __forceinline__ unsigned topk_image(float v) {
-    unsigned u = __float_as_uint(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0u;     // NaN: below -inf (map(-inf) = 0x007FFFFF)
-    if (u == 0x80000000u) u = 0u;                       // -0.0 == +0.0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // is `id` in the ascending list [0, E)?  Branch-free lower bound.
 __device__ __forceinline__ bool topk_in_sorted(const int32_t* list, int E, int32_t id) {
@@ -109,11 +103,11 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(TopkArgs a) {
     auto fetch = [&](int64_t e, unsigned& img) -> bool {
         if (e >= T) return false;
         if (e < kc) {
-            img = topk_image(crow_v[e]);
+            img = score_image(crow_v[e]);
             return crow_i[e] != -1;
         }
         const int64_t j = e - kc;
-        img = topk_image(srow[j]);
+        img = score_image(srow[j]);
         if (a.use_bitmap) return !((sBm[j >> 5] >> (j & 31)) & 1u);
         if (E == 0) return true;
         return !topk_in_sorted(ex, E, a.cand_ids ? a.cand_ids[j] : (int32_t)(a.col_offset + j));

@@ -342,6 +342,60 @@ def ctr_eval_device(feeder, data, batch_size, streams=None, window=16):
     return aucs, accs, f1s, float(np.mean(aucs)), float(np.mean(accs)), float(np.mean(f1s))
 
 
+def _score_split(feeder, data, m, max_pairs):
+    """Device scores and int32 labels of the first ``m`` pairs of ``data`` (columns uploaded once), scored by ``feeder.scores``
+    on consecutive slices of at most ``max_pairs`` pairs into one buffer.  Labels other than 0 / 1 become 2, which
+    mvin_ctr_counts reports as bad."""
+    import torch
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError(f"max_pairs={max_pairs}")
+    dev = feeder.model.device
+    cols = np.asarray(data)[:m]
+    users = torch.from_numpy(np.ascontiguousarray(cols[:, 0], dtype=np.int64)).to(dev)
+    items = torch.from_numpy(np.ascontiguousarray(cols[:, 1], dtype=np.int64)).to(dev)
+    lab = cols[:, 2]
+    labels = torch.from_numpy(np.where((lab == 0) | (lab == 1), lab, 2).astype(np.int32)).to(dev)
+    scores = torch.empty((m,), dtype=torch.float32, device=dev)
+    for s0 in range(0, m, max_pairs):
+        s1 = min(m, s0 + max_pairs)
+        scores[s0:s1] = feeder.scores(users[s0:s1], items[s0:s1])
+    return scores, labels
+
+
+def ctr_eval_batched(feeder, data, batch_size, max_pairs=524288):
+    """ctr_eval_device's numbers (per-batch AUC / ACC / F1 of the full batches, util.py:44-56, and their means) with the
+    metrics computed on the device: the split is scored in slices of at most ``max_pairs`` pairs into one score buffer (the
+    ragged tail dropped, util.py:49), ONE mvin_ctr_counts launch counts every batch exactly (ops.ctr_counts with seg_len =
+    ``batch_size``) and one [batches, 6] copy comes back; ops.ctr_metrics_from_counts turns it into sklearn's numbers.  No
+    per-batch synchronisation.  With ``max_pairs = batch_size`` every forward is the call ctr_eval_device makes, so the scores
+    are the same bits; larger slices may take other kernel forms, whose scores can differ in the last bits."""
+    from . import ops
+    B = int(batch_size)
+    S = np.asarray(data).shape[0] // B
+    if S == 0:
+        return [], [], [], float(np.mean([])), float(np.mean([])), float(np.mean([]))
+    scores, labels = _score_split(feeder, data, S * B, max_pairs)
+    counts = ops.ctr_counts(scores, labels, B).cpu().numpy()
+    auc, acc, f1 = ops.ctr_metrics_from_counts(counts)
+    aucs, accs, f1s = auc.tolist(), acc.tolist(), f1.tolist()
+    return aucs, accs, f1s, float(np.mean(aucs)), float(np.mean(accs)), float(np.mean(f1s))
+
+
+def ctr_eval_split(feeder, data, max_pairs=524288):
+    """Exact ``(auc, acc, f1)`` over ALL pairs of the split as one population (ops.ctr_counts with one segment of the whole
+    split; no pair dropped).  The reference has no such metric -- its CTR numbers are means over batches (ctr_eval) -- so this
+    is a number of its own, not a replacement for the per-batch mean."""
+    from . import ops
+    n = np.asarray(data).shape[0]
+    if n == 0:
+        raise ValueError("ctr_eval_split: empty split")
+    scores, labels = _score_split(feeder, data, n, max_pairs)
+    counts = ops.ctr_counts(scores, labels, n).cpu().numpy()
+    auc, acc, f1 = ops.ctr_metrics_from_counts(counts)
+    return float(auc[0]), float(acc[0]), float(f1[0])
+
+
 def topk_settings(train_data, eval_data, test_data, n_item, user_num=250, k_list=(1, 2, 5, 10, 25, 50, 100)):
     """util.py:14-41 without the pickle round trip: the ``user_num`` users with the most
     positive train interactions among those present in all three splits."""
@@ -464,7 +518,7 @@ class EarlyStop(object):
 
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
-          topk_early_stop=False, graph="auto", topk_impl="host"):
+          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host"):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -482,7 +536,11 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     scripts train at 512 / 1 024).
     ``topk_impl``: "host" ranks user by user on the host (topk_eval_device); "batched" ranks every user on the device in one
     call (topk_eval_batched; ties by ascending item id).
+    ``ctr_impl``: "host" evaluates CTR batch by batch with sklearn on the host (ctr_eval_device); "batched" scores each split
+    into one device buffer and counts every batch's metrics exactly in one launch (ctr_eval_batched).
     Returns (model, history): one dict per epoch."""
+    if ctr_impl not in ("host", "batched"):
+        raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
     from .model import MVIN
     n_user, n_item, n_entity, n_relation = data[0], data[1], data[2], data[3]
     train_data, eval_data, test_data = (np.asarray(d) for d in data[4:7])
@@ -519,7 +577,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
             score = rec["eval"]["recall"][2]
         else:
             for name, d in (("train", train_data), ("eval", eval_data), ("test", test_data)):
-                _, _, _, auc, acc, f1 = ctr_eval_device(feeder, d, args.batch_size)
+                ctr = ctr_eval_batched if ctr_impl == "batched" else ctr_eval_device
+                _, _, _, auc, acc, f1 = ctr(feeder, d, args.batch_size)
                 rec[name] = {"auc": auc, "acc": acc, "f1": f1}
             score = rec["eval"]["auc"]                                          # Eval_score_info.eval_st_score
         history.append(rec)

@@ -416,6 +416,95 @@ def topk_rows(scores, k, cand_ids=None, col_offset=0, excl=None, carry=None, out
     return oid, oval
 
 
+CTR_SEG_CAP = 16384          # MVIN_CTR_SEG_CAP: the longest segment mvin_ctr_counts handles in one workgroup, without workspace
+CTR_COLUMNS = ("n_pos", "n_neg", "tp", "fp", "u2", "bad")
+
+
+class UndefinedMetricWarning(UserWarning):
+    """A metric is undefined for some segments (sklearn's warning of the same name and meaning)."""
+
+
+def _ctr_rows(t, name, dtype):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name}: expected a [segments, seg_len] tensor with dense rows")
+
+
+def ctr_counts(scores, labels, seg_len, out=None):
+    """mvin_ctr_counts: the exact CTR counts of every segment, an int64 [S, 6] device tensor (columns ``CTR_COLUMNS``: label
+    counts, tp / fp of ``score >= 0.5``, twice the Mann-Whitney U, non-finite scores plus labels other than 0 / 1).
+    ``scores`` f32 and ``labels`` int32 are either 1-D of S * seg_len pairs (contiguous) or [S, seg_len] with dense rows and
+    the same row stride.  Enqueues only: no synchronisation, no copy to the host (ctr_metrics_from_counts reads the result)."""
+    lib = _lib.load()
+    seg_len = int(seg_len)
+    if seg_len < 1:
+        raise ValueError(f"seg_len={seg_len}: expected >= 1")
+    if isinstance(scores, torch.Tensor) and scores.dim() == 1:
+        if scores.numel() % seg_len:
+            raise ValueError(f"scores: {scores.numel()} pairs are not whole segments of {seg_len}")
+        _chk(scores, F32, "scores")
+        scores = scores.view(-1, seg_len)
+    if isinstance(labels, torch.Tensor) and labels.dim() == 1:
+        _chk(labels, I32, "labels")
+        labels = labels.view(-1, seg_len) if labels.numel() % seg_len == 0 else labels
+    _ctr_rows(scores, "scores", F32)
+    _ctr_rows(labels, "labels", I32)
+    if tuple(scores.shape) != tuple(labels.shape) or scores.shape[1] != seg_len:
+        raise ValueError(f"scores {tuple(scores.shape)} and labels {tuple(labels.shape)}: expected [S, {seg_len}] both")
+    S = scores.shape[0]
+    ld = scores.stride(0) if S > 1 else seg_len
+    if S > 1 and labels.stride(0) != ld:
+        raise ValueError(f"labels: row stride {labels.stride(0)}, scores: {ld}; the two must share one layout")
+    dev = scores.device
+    if out is None:
+        out = torch.empty((S, 6), dtype=torch.int64, device=dev)
+    _chk(out, torch.int64, "out")
+    if tuple(out.shape) != (S, 6):
+        raise ValueError(f"out: expected [{S}, 6]")
+    if S == 0:
+        return out
+    nws = lib.mvin_ctr_counts_ws_bytes(S, seg_len)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_ctr_counts_ws_bytes")
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    _lib.check(lib.mvin_ctr_counts(_p(scores), _p(labels), S, seg_len, ld, _p(ws), _p(out), _stream()), "mvin_ctr_counts")
+    return out
+
+
+def ctr_metrics_from_counts(counts):
+    """Per-segment ``(auc, acc, f1)`` float64 arrays from ctr_counts rows (a host array, [S, 6] or [6]), by sklearn 1.7's
+    conventions: ``auc = u2 / (2 n_pos n_neg)`` -- NaN for a segment with one class only, with ONE UndefinedMetricWarning per
+    call naming how many segments; ``acc = (tp + n_neg - fp) / n``; ``f1 = 2 tp / (2 tp + fp + fn)``, 0.0 where that
+    denominator is 0.  A segment with ``bad > 0`` (a NaN or infinite score, or a label other than 0 / 1, which sklearn rejects)
+    raises ValueError."""
+    import warnings
+    import numpy as np
+    c = np.asarray(counts)
+    if c.ndim == 1:
+        c = c.reshape(1, -1)
+    if c.ndim != 2 or c.shape[1] != 6:
+        raise ValueError(f"counts: expected [S, 6], got {c.shape}")
+    c = c.astype(np.int64, copy=False)
+    n_pos, n_neg, tp, fp, u2, bad = (c[:, q] for q in range(6))
+    if (bad > 0).any():
+        s = int(np.flatnonzero(bad > 0)[0])
+        raise ValueError(f"segment {s}: {int(bad[s])} non-finite score(s) or label(s) other than 0 / 1")
+    n = (n_pos + n_neg).astype(np.float64)
+    one = (n_pos == 0) | (n_neg == 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        auc = np.where(one, np.nan, u2.astype(np.float64) / (2.0 * n_pos.astype(np.float64) * n_neg.astype(np.float64)))
+        acc = (tp + n_neg - fp).astype(np.float64) / n
+        den = (2 * tp + fp + (n_pos - tp)).astype(np.float64)
+        f1 = np.where(den > 0, (2 * tp).astype(np.float64) / np.where(den > 0, den, 1.0), 0.0)
+    if one.any():
+        warnings.warn(f"Only one class is present in {int(one.sum())} of {c.shape[0]} segment(s): ROC AUC is not defined there "
+                      "(NaN)", UndefinedMetricWarning, stacklevel=2)
+    return auc, acc, f1
+
+
 def gather_attn_l2_prj(ws, enc_entity, enc_relation, parent_ids, t0, t1, q, B, parents_per_pair, K, D, nR, n_entity, encoded=True, order=None):
     """mvin_gather_attn_l2_prj_fwd: gather_attn_l2_enc over the workspace of ``project_tables`` (built with attention =
     (t0 is not None)).  ``encoded=False``: the two adjacency arrays are the plain adjacency (D = 32, K in {8, 16}).

@@ -1,0 +1,166 @@
+"""-m gpu: exact CTR counts on the device (mvin_ctr_counts / ops.ctr_counts) bit for bit against a numpy oracle, the metrics
+derived from them against sklearn, and the batched / whole-split CTR evaluations of the harness against ctr_eval_device."""
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from ctr_oracle import ctr_counts_oracle, families, sklearn_metrics
+from mvin_amd import harness, ops, synth
+from mvin_amd.config import make_args
+from mvin_amd.params import init_params
+
+pytestmark = pytest.mark.gpu
+
+CAP = ops.CTR_SEG_CAP
+SEG_LENS = [1, 2, 3, 63, 64, 65, 511, 512, 513, 4096, CAP - 1, CAP, CAP + 1, 65536, 524288]
+
+
+def _dev(s, y):
+    return torch.from_numpy(s).cuda(), torch.from_numpy(y).cuda()
+
+
+def _metrics(counts):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return ops.ctr_metrics_from_counts(counts)
+
+
+def _check(s, y, counts, n_sklearn=6):
+    ref = ctr_counts_oracle(s, y)
+    assert counts.dtype == np.int64 and counts.shape == ref.shape
+    assert np.array_equal(counts, ref), np.argwhere(counts != ref)[:8]
+    auc, acc, f1 = _metrics(counts)
+    for i in np.linspace(0, s.shape[0] - 1, min(n_sklearn, s.shape[0])).astype(int):
+        ra, rc, rf = sklearn_metrics(s[i], y[i])
+        assert (np.isnan(ra) and np.isnan(auc[i])) or abs(ra - auc[i]) <= 1e-12, (i, ra, auc[i])
+        assert abs(rc - acc[i]) <= 1e-12 and abs(rf - f1[i]) <= 1e-12, (i, rc, acc[i], rf, f1[i])
+
+
+@pytest.mark.parametrize("L", SEG_LENS)
+def test_counts_match_oracle(hip_lib, L):
+    rng = np.random.default_rng(L)
+    S = max(1, min(2000, (1 << 19) // L))
+    for name, (s, y) in families(rng, S, L).items():
+        out = ops.ctr_counts(*_dev(s, y), L).cpu().numpy()
+        _check(s, y, out, n_sklearn=2 if L >= 65536 else 6)
+
+
+def test_thousands_of_batches_in_one_launch(hip_lib):
+    rng = np.random.default_rng(5)
+    s, y = families(rng, 4096, 512)["uniform"]
+    sd, yd = _dev(s, y)
+    out = ops.ctr_counts(sd.view(-1), yd.view(-1), 512).cpu().numpy()
+    _check(s, y, out)
+
+
+@pytest.mark.parametrize("L", [63, 512, CAP + 1, 3 * CAP + 5])
+def test_strided_rows(hip_lib, L):
+    rng = np.random.default_rng(11)
+    S, ld = 5, L + 37
+    for name in ("uniform", "ties4"):
+        s, y = families(rng, S, L)[name]
+        sw = np.full((S, ld), np.nan, np.float32)
+        yw = np.full((S, ld), 7, np.int32)                       # the gap between rows is never read
+        sw[:, :L], yw[:, :L] = s, y
+        sd, yd = _dev(sw, yw)
+        out = ops.ctr_counts(sd[:, :L], yd[:, :L], L).cpu().numpy()
+        _check(s, y, out)
+
+
+def test_whole_split_segment(hip_lib):
+    rng = np.random.default_rng(12)
+    L = (1 << 22) + 7
+    for name in ("uniform", "ulps", "equal"):
+        fam = families(rng, 1, L) if name == "uniform" else {name: families(rng, 1, L)[name]}
+        s, y = fam[name]
+        out = ops.ctr_counts(*_dev(s, y), L).cpu().numpy()
+        _check(s, y, out, n_sklearn=1 if name != "equal" else 0)
+
+
+def test_launched_twice_gives_identical_bits(hip_lib):
+    rng = np.random.default_rng(13)
+    for S, L in ((1000, 512), (3, 70000)):
+        s, y = families(rng, S, L)["ties4"]
+        sd, yd = _dev(s, y)
+        a = ops.ctr_counts(sd, yd, L).cpu().numpy()
+        b = ops.ctr_counts(sd, yd, L).cpu().numpy()
+        assert a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("L", [512, CAP + 1])
+def test_non_finite_scores_raise(hip_lib, L):
+    rng = np.random.default_rng(14)
+    s, y = families(rng, 4, L)["uniform"]
+    s[1, 7] = np.nan
+    s[3, L - 1] = np.inf
+    out = ops.ctr_counts(*_dev(s, y), L).cpu().numpy()
+    torch.cuda.synchronize()
+    assert out[:, 5].tolist() == [0, 1, 0, 1]
+    assert np.array_equal(out, ctr_counts_oracle(s, y))
+    with pytest.raises(ValueError, match="segment 1"):
+        ops.ctr_metrics_from_counts(out)
+
+
+# ---- the harness: the small model of tests/test_gpu_harness.py
+def build():
+    from mvin_amd.model import MVIN
+    args = make_args(dim=16, neighbor_sample_size=4, h_hop=2, n_mix_hop=1, p_hop=2, n_memory=8, batch_size=32)
+    n_user, n_entity, n_relation, n_item = 30, 400, 6, 60
+    rng = np.random.default_rng(7)
+    adj_e, adj_r = synth.uniform_adjacency(n_entity, n_relation, 4, seed=8)
+    uts = synth.ripple_sets(n_user, n_entity, n_relation, 2, 8, seed=9)
+    params = init_params(args, n_user, n_entity, n_relation, seed=10, random_agg_bias=True)
+    model = MVIN(args, n_user, n_entity, n_relation, adj_e, adj_r, params=params, device="cuda:0")
+    data = np.stack([rng.integers(0, n_user, 700), rng.integers(0, n_item, 700), rng.integers(0, 2, 700)], axis=1)
+    return args, model, uts, data, n_item
+
+
+def test_batched_eval_equals_device_eval_per_batch(hip_lib):
+    args, model, uts, data, _ = build()
+    feeder = harness.DeviceFeeder(model, uts)
+    a = harness.ctr_eval_device(feeder, data, 32)
+    b = harness.ctr_eval_batched(feeder, data, 32, max_pairs=32)
+    assert len(b[0]) == len(a[0]) == 700 // 32
+    for x, y in zip(a[:3], b[:3]):
+        np.testing.assert_allclose(y, x, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(b[3:], a[3:], rtol=0, atol=1e-12)
+
+
+def test_batched_eval_default_slices(hip_lib):
+    args, model, uts, data, _ = build()
+    feeder = harness.DeviceFeeder(model, uts)
+    a = harness.ctr_eval_device(feeder, data, 32)
+    b = harness.ctr_eval_batched(feeder, data, 32)
+    assert abs(a[3] - b[3]) <= 1e-5
+    scores, _ = harness._score_split(feeder, data, 700 // 32 * 32, 524288)
+    if not (np.abs(scores.cpu().numpy().astype(np.float64) - 0.5) < 1e-6).any():
+        np.testing.assert_allclose(b[1], a[1], rtol=0, atol=1e-12)
+        np.testing.assert_allclose(b[2], a[2], rtol=0, atol=1e-12)
+
+
+def test_whole_split_metric_matches_sklearn(hip_lib):
+    args, model, uts, data, _ = build()
+    feeder = harness.DeviceFeeder(model, uts)
+    auc, acc, f1 = harness.ctr_eval_split(feeder, data)
+    scores, _ = harness._score_split(feeder, data, data.shape[0], 524288)
+    ra, rc, rf = sklearn_metrics(scores.cpu().numpy(), data[:, 2])
+    assert abs(auc - ra) <= 1e-12 and abs(acc - rc) <= 1e-12 and abs(f1 - rf) <= 1e-12
+
+
+def test_train_ctr_impl_batched_matches_host(hip_lib):
+    args, _, uts, data, n_item = build()
+    split = (30, n_item, 400, 6, data[:450], data[450:570], data[570:])
+    hist = {}
+    for impl in ("host", "batched"):
+        _, model, _, _, _ = build()
+        args.n_epochs, args.tolerance, args.early_stop, args.save_final_model = 3, 2, 5, False
+        full = split + (None, None, uts)                           # the adjacency is read only to build a model
+        _, hist[impl] = harness.train(args, full, model=model, rng=np.random.default_rng(1), ctr_impl=impl)
+    assert len(hist["host"]) == len(hist["batched"]) == 3
+    for h, b in zip(hist["host"], hist["batched"]):
+        assert abs(h["loss"] - b["loss"]) <= 1e-6 * max(1.0, abs(h["loss"]))
+        for name in ("train", "eval", "test"):
+            assert abs(h[name]["auc"] - b[name]["auc"]) <= 1e-5, (name, h, b)
+            assert abs(h[name]["acc"] - b[name]["acc"]) <= 1e-5 and abs(h[name]["f1"] - b[name]["f1"]) <= 1e-5, (name, h, b)
