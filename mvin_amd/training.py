@@ -179,8 +179,11 @@ class Trainer(object):
                                   apply=apply).item())
 
     def lr_t(self, t):
-        """Bias-corrected step size of tf.train.AdamOptimizer at (1-based) step t."""
-        return self.lr * np.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
+        """Bias-corrected step size of tf.train.AdamOptimizer at (1-based) step t.  From beta1 / beta2 as float32, which is
+        what mvin_l2_adam_multi receives for the moments (and what TF's beta powers are): with the decimal 0.999 here
+        and float32(0.999) there, 1 - beta2 differed by 1.3e-5 and the correction left every step 6.4e-6 too long."""
+        b1, b2 = float(np.float32(self.b1)), float(np.float32(self.b2))
+        return self.lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
 
     def enqueue(self, user_indices, item_indices, labels, memories_h, memories_r, memories_t, apply=True,
                 lr_dev=None):

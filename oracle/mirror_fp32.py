@@ -27,9 +27,10 @@ def _t(x, dtype=F32):
     return torch.as_tensor(x).to(dtype)
 
 
-def as_torch_params(params):
-    """numpy/torch dict -> dict of fp32 torch CPU tensors."""
-    return {k: _t(v) for k, v in params.items()}
+def as_torch_params(params, dtype=F32):
+    """numpy/torch dict -> dict of torch CPU tensors of ``dtype`` (fp32: the pinned graph; float64 is asked for
+    explicitly, by oracle/train_ref.py's float64 route -- never inferred from what the caller hands in)."""
+    return {k: _t(v, dtype) for k, v in params.items()}
 
 
 # --------------------------------------------------------------------------- #
@@ -208,9 +209,10 @@ def aggregate(args, p, entities, relations, transfer_o):
 
 
 def forward(args, params, adj_entity, adj_relation, user_indices, item_indices,
-            memories_h, memories_r, memories_t, trace=False):
-    """model.py:137-159 wiring.  Returns a SimpleNamespace with scores etc."""
-    p = as_torch_params(params)
+            memories_h, memories_r, memories_t, trace=False, dtype=F32):
+    """model.py:137-159 wiring.  Returns a SimpleNamespace with scores etc.  ``dtype``: the precision the graph runs in
+    (fp32 unless torch.float64 is asked for)."""
+    p = as_torch_params(params, dtype)
     adj_entity = torch.as_tensor(adj_entity).long()
     adj_relation = torch.as_tensor(adj_relation).long()
     user_indices = torch.as_tensor(user_indices).long()

@@ -30,9 +30,9 @@ def _l2(x):
     return (x * x).sum() / 2
 
 
-def loss_from_params(args, p, adj_entity, adj_relation, users, items, labels, mem_h, mem_r, mem_t):
-    """p: dict of torch tensors (requires_grad as wanted).  Returns (loss, pieces dict, forward out)."""
-    out = mirror_fp32.forward(args, p, adj_entity, adj_relation, users, items, mem_h, mem_r, mem_t)
+def loss_from_params(args, p, adj_entity, adj_relation, users, items, labels, mem_h, mem_r, mem_t, dtype=torch.float32):
+    """p: dict of torch tensors of ``dtype`` (requires_grad as wanted).  Returns (loss, pieces dict, forward out)."""
+    out = mirror_fp32.forward(args, p, adj_entity, adj_relation, users, items, mem_h, mem_r, mem_t, dtype=dtype)
     labels = torch.as_tensor(np.asarray(labels)).to(out.scores.dtype)
     base = torch.nn.functional.binary_cross_entropy_with_logits(out.scores, labels, reduction="mean")
     l2 = torch.zeros((), dtype=out.scores.dtype)
@@ -64,11 +64,14 @@ def loss_and_grads(args, params, adj_entity, adj_relation, users, items, labels,
                    dtype=torch.float32):
     """Returns (loss float, grads dict of numpy arrays for every parameter that receives a
     gradient; parameters without one -- urh_bias, unused tables -- are absent, as TF's
-    minimize() skips variables whose gradient is None)."""
+    minimize() skips variables whose gradient is None).  dtype=torch.float64 runs the same graph in float64
+    (parameters are widened, never re-drawn): the higher-precision reference for tests at sizes where the float32
+    graph's own rounding is a visible share of the tolerance."""
+    if dtype not in (torch.float32, torch.float64):
+        raise NotImplementedError("the mirror runs in float32 (the pinned graph) or float64")
     p = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in params.items()}
-    if dtype != torch.float32:
-        raise NotImplementedError("the mirror is an fp32 graph")
-    loss, pieces, out = loss_from_params(args, p, adj_entity, adj_relation, users, items, labels, mem_h, mem_r, mem_t)
+    loss, pieces, out = loss_from_params(args, p, adj_entity, adj_relation, users, items, labels, mem_h, mem_r, mem_t,
+                                         dtype=dtype)
     loss.backward()
     grads = {k: v.grad.numpy().copy() for k, v in p.items() if v.grad is not None}
     return float(loss.detach()), grads, {k: float(v.detach()) for k, v in pieces.items()}, out
@@ -81,17 +84,20 @@ class AdamRef(object):
     Embedding tables receive IndexedSlices in TF; its _apply_sparse decays m and v of ALL rows and
     then updates all rows, which equals this dense rule with zero gradient on untouched rows."""
 
-    def __init__(self, params, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-        self.lr, self.b1, self.b2, self.eps, self.t = lr, beta1, beta2, eps, 0
-        self.m = {k: np.zeros_like(np.asarray(v, dtype=np.float32)) for k, v in params.items()}
-        self.v = {k: np.zeros_like(np.asarray(v, dtype=np.float32)) for k, v in params.items()}
+    def __init__(self, params, lr, beta1=0.9, beta2=0.999, eps=1e-8, dtype=np.float32):
+        """dtype=np.float64: the same rule with float64 moments, step size and parameters (the reference of the
+        kernel tests); the float32 default is what the trajectories of the suite have always been compared with."""
+        self.lr, self.b1, self.b2, self.eps, self.t, self.dt = lr, beta1, beta2, eps, 0, np.dtype(dtype).type
+        self.m = {k: np.zeros_like(np.asarray(v, dtype=dtype)) for k, v in params.items()}
+        self.v = {k: np.zeros_like(np.asarray(v, dtype=dtype)) for k, v in params.items()}
 
     def step(self, params, grads):
         self.t += 1
-        lr_t = np.float32(self.lr * np.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t))
+        dt = self.dt
+        lr_t = dt(self.lr * np.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t))
         for k, g in grads.items():
-            g = g.astype(np.float32)
-            self.m[k] = np.float32(self.b1) * self.m[k] + np.float32(1 - self.b1) * g
-            self.v[k] = np.float32(self.b2) * self.v[k] + np.float32(1 - self.b2) * g * g
-            params[k] = (params[k] - lr_t * self.m[k] / (np.sqrt(self.v[k]) + np.float32(self.eps))).astype(np.float32)
+            g = g.astype(dt)
+            self.m[k] = dt(self.b1) * self.m[k] + dt(1 - self.b1) * g
+            self.v[k] = dt(self.b2) * self.v[k] + dt(1 - self.b2) * g * g
+            params[k] = (params[k] - lr_t * self.m[k] / (np.sqrt(self.v[k]) + dt(self.eps))).astype(dt)
         return params

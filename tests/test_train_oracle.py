@@ -53,17 +53,7 @@ def test_gradients_match_finite_differences():
     _, grads, _, _ = train_ref.loss_and_grads(args, params, *feed)
 
     def loss64(p64):
-        p = {k: torch.tensor(v, dtype=torch.float64) for k, v in p64.items()}
-        # the mirror casts to fp32; evaluate the same loss in fp64 by hand-calling its pieces
-        from oracle import mirror_fp32
-        old = mirror_fp32.as_torch_params
-        mirror_fp32.as_torch_params = lambda d: d
-        try:
-            l, _, _ = train_ref.loss_from_params(args, p, *[torch.as_tensor(x) if i < 2 else x for i, x in enumerate(feed[:2])],
-                                                 *feed[2:])
-        finally:
-            mirror_fp32.as_torch_params = old
-        return float(l)
+        return train_ref.loss_and_grads(args, p64, *feed, dtype=torch.float64)[0]
 
     p64 = {k: np.asarray(v, dtype=np.float64) for k, v in params.items()}
     rng = np.random.default_rng(0)
@@ -94,3 +84,39 @@ def test_adam_rule():
     w1 = p1["w"].copy()
     p2 = opt.step(dict(p1), {"w": np.zeros(3, np.float32)})  # zero gradient still moves (m decays, not zero)
     assert p2["w"][0] < w1[0] and p2["w"][1] == -2.0
+
+
+def test_float64_route_agrees_with_the_pinned_float32_route():
+    """loss_and_grads(dtype=torch.float64) is the float32 graph widened, nothing else: on a toy case the two agree to
+    float32 round-off (a few hundred float32 operations per output: 1e-5 of each gradient's largest entry), the
+    same parameters receive a gradient, and the float64 route does return float64."""
+    args, case, params, labels = setup()
+    feed = (case.adj_entity, case.adj_relation, case.users, case.items, labels, case.memories_h, case.memories_r,
+            case.memories_t)
+    l32, g32, p32, o32 = train_ref.loss_and_grads(args, params, *feed)
+    l64, g64, p64, o64 = train_ref.loss_and_grads(args, params, *feed, dtype=torch.float64)
+    assert o32.scores.dtype == torch.float32 and o64.scores.dtype == torch.float64
+    assert abs(l32 - l64) <= 2e-6 * abs(l64)
+    for k in p64:
+        assert abs(p32[k] - p64[k]) <= 2e-6 * abs(p64[k]) + 1e-9, k
+    assert set(g32) == set(g64)
+    differs = False
+    for k, g in g64.items():
+        assert g.dtype == np.float64 and g32[k].dtype == np.float32, k
+        err = np.abs(g32[k] - g).max()
+        assert err <= 1e-5 * np.abs(g).max() + 1e-9, (k, err)
+        differs |= bool(err > 0)
+    assert differs                                  # the float64 route is not the float32 one relabelled
+    np.testing.assert_allclose(o32.scores.detach().numpy(), o64.scores.detach().numpy(), rtol=0, atol=1e-5)
+
+
+def test_adam_rule_in_float64_follows_the_float32_rule():
+    rng = np.random.default_rng(3)
+    p0 = {"w": rng.standard_normal(50).astype(np.float32)}
+    a, b = train_ref.AdamRef(p0, lr=0.01), train_ref.AdamRef(p0, lr=0.01, dtype=np.float64)
+    pa, pb = {"w": p0["w"].copy()}, {"w": p0["w"].astype(np.float64)}
+    for _ in range(3):
+        g = rng.standard_normal(50).astype(np.float32)
+        pa, pb = a.step(pa, {"w": g}), b.step(pb, {"w": g})
+    assert pa["w"].dtype == np.float32 and pb["w"].dtype == np.float64 and b.m["w"].dtype == np.float64
+    np.testing.assert_allclose(pa["w"], pb["w"], rtol=0, atol=1e-6)
