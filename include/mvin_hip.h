@@ -765,6 +765,30 @@ MVIN_API int64_t mvin_ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);     /
 MVIN_API int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, void* stream);
 
+/* ---- training negatives: the label-0 rows of convert_rating (KGCN/preprocess.py:60-70: for every user, as many items as the
+ * user has positives, np.random.choice(list(item_set - pos - neg), replace=False)), drawn on the GPU as a pure function of
+ * (seed, round) so that they can be redrawn every epoch --
+ * mvin_sample_negatives: user u gets counts[u] = m[u] slots, out_items[out_ptr[u] .. out_ptr[u+1]).  The rule, per user:
+ *  - X_u = the ids of u's exclusion row excl_ids[excl_ptr[u] .. excl_ptr[u+1]) that lie in [0, n_item); the row may be in any
+ *    order and may repeat ids, ids outside the range are ignored (both arrays NULL = no exclusions);
+ *  - c_u = n_item - |X_u|, m_eff = min(m[u], c_u);
+ *  - the draw sequence is x_j = rnd_below(n_item, seed, 4, u, round, j), j = 0, 1, 2, ... (the draw function of the two samplers
+ *    above, stream 4), cut at j = 64 * n_item draws;
+ *  - the slots receive the first m_eff values of that sequence that are not in X_u and have not occurred earlier in the
+ *    sequence, IN SEQUENCE ORDER: a uniform sample without replacement from the complement of X_u;
+ *  - slots that stay unfilled hold -1: m[u] > c_u, or the cut was reached.  Collecting all c eligible values takes more than
+ *    n_item * (ln c + t) draws with probability below e^-t and ln c < 21.5, so a valid request is cut with probability
+ *    below e^-42 per user: the cut bounds the kernel's loop, nobody will see it;
+ *  - status[0] = users with an unfilled slot, status[1] = slots left at -1 (both written by the call).
+ * The result is a pure function of the arguments: independent of the launch shape, the workgroup size and timing.
+ * Errors (< 0, nothing launched): -1 for null counts / out_ptr / out_items / status or one of excl_ptr / excl_ids NULL without
+ * the other; -2 for n_user < 0; -3 for an unsupported n_item.  n_user == 0 launches nothing. */
+#define MVIN_NEG_MAX_ITEMS (1 << 20)    /* one bit per item in the workgroup's LDS: 128 KB of the 160 KB */
+MVIN_API int mvin_sample_negatives_supported(int n_item);                      /* 1 for 1 <= n_item <= MVIN_NEG_MAX_ITEMS */
+MVIN_API int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
+                                   int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

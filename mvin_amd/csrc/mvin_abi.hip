@@ -1473,6 +1473,21 @@ int mvin_build_ripple_sets(const int64_t* indptr, const int32_t* dst, const int3
     return hip_result(mvin::launch_ripple_build(r, (hipStream_t)stream), "mvin_build_ripple_sets");
 }
 
+int mvin_sample_negatives_supported(int n_item) { return mvin::sample_negatives_supported(n_item) ? 1 : 0; }
+
+int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
+                          int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status,
+                          void* stream) {
+    const char* who = "mvin_sample_negatives";
+    if (!counts || !out_ptr || !out_items || !status) return fail(-1, "%s: null pointer (counts / out_ptr / out_items / status)", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together (both NULL = no exclusions)", who);
+    if (n_user < 0) return fail(-2, "%s: n_user=%d", who, n_user);
+    if (!mvin::sample_negatives_supported(n_item))
+        return fail(-3, "%s: unsupported n_item=%d (1..%d: the catalogue's bitmap lives in LDS)", who, n_item, MVIN_NEG_MAX_ITEMS);
+    return hip_result(mvin::launch_sample_negatives(excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, seed, round, out_items,
+                                                    status, (hipStream_t)stream), who);
+}
+
 // ---------------------------------------------------------------------------- training
 int mvin_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, void* stream) {
     if (n < 0 || nbins < 1 || nbins > 4096) return fail(-2, "mvin_count_ids: n=%lld nbins=%d (1..4096)", (long long)n, nbins);

@@ -439,6 +439,9 @@ hipError_t launch_topk_rows(const float* scores, int64_t rows, int64_t n, int64_
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);
+bool sample_negatives_supported(int n_item);                  // per-user negatives without replacement (mvin_negatives.hip)
+hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
+                                   int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out, int64_t* status, hipStream_t st);
 size_t order_ws_elems(int64_t B);                             // pairs in key order (mvin_order.hip)
 hipError_t launch_order_by_key(const int64_t* k64, const int32_t* k32, int64_t B, int32_t* ws, int32_t* order, hipStream_t st);
 bool fused_wpp_supported(int D, int K);                       // wave-per-parent kernel over projected tables, dim 64 (mvin_fused_wpp.hip)

@@ -9,24 +9,9 @@
 //   without replacement = Floyd's algorithm (uniform over k-subsets)
 //   with replacement    = independent uniform draws
 #include "mvin_kernels.h"
+#include "mvin_rnd.h"     // rnd32 / rnd_below: the draw function, shared with mvin_negatives.hip
 
 namespace mvin {
-
-__device__ __forceinline__ uint32_t rnd32(uint64_t seed, uint64_t stream, uint64_t a, uint64_t b, uint64_t c) {
-    uint64_t z = seed ^ (stream * 0xD1B54A32D192ED03ull) ^ (a * 0x9E3779B97F4A7C15ull) ^
-                 (b * 0xC2B2AE3D27D4EB4Full) ^ (c * 0x165667B19E3779F9ull);
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (uint32_t)(z >> 32);
-}
-
-// uniform integer in [0, n), n < 2^32 (multiply-high; bias < n / 2^32)
-__device__ __forceinline__ uint32_t rnd_below(uint32_t n, uint64_t seed, uint64_t stream, uint64_t a, uint64_t b,
-                                              uint64_t c) {
-    return (uint32_t)(((uint64_t)rnd32(seed, stream, a, b, c) * n) >> 32);
-}
 
 // ---------------------------------------------------------------------------------------
 // contruct_random_adj: K neighbors per entity; without replacement when deg >= K (:383),

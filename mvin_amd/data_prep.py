@@ -5,7 +5,9 @@ construct_kg / contruct_random_adj / get_user_triplet_set
 The reference builds these with pure-Python dict loops (minutes on amazon-book, repeated for
 every stage-wise restart, main.py:16).  Here the KG becomes a CSR on the device (torch sort =
 plumbing), and the two samplers are HIP kernels (mvin_sample_adjacency, mvin_build_ripple_sets)
-whose draws are a pure function of a seed, so adjacency can be re-sampled every epoch.
+whose draws are a pure function of a seed, so adjacency can be re-sampled every epoch.  The training negatives
+(convert_rating, KGCN/preprocess.py:60-70) are drawn the same way by mvin_sample_negatives (sample_negatives,
+NegativeSampler), fresh for every epoch.
 """
 import numpy as np
 import torch
@@ -73,3 +75,137 @@ def get_user_triplet_set(csr, hist, n_user, p_hop, n_memory, seed=1, n_neighbor=
                                           n_memory, n_neighbor, seed, _p(out), _stream()),
                "mvin_build_ripple_sets")
     return out
+
+
+# --------------------------------------------------------------------------- training negatives
+def _interaction_csr_host(rows, n_user, labels=1):
+    """(ptr int64 [nU+1], ids int32) on the host: user u's row = the DISTINCT items u is listed with in any of ``rows``
+    ([n, 3] (user, item, label) arrays) under label ``labels`` (None: under any label), ascending."""
+    if isinstance(rows, np.ndarray) or torch.is_tensor(rows):
+        rows = [rows]
+    parts = []
+    for r in rows:
+        r = np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1, 3)
+        parts.append(r[:, :2] if labels is None else r[r[:, 2] == labels, :2])
+    ui = np.concatenate(parts) if parts else np.zeros((0, 2), dtype=np.int64)
+    if ui.shape[0] and (ui[:, 0].min() < 0 or ui[:, 0].max() >= n_user):
+        raise ValueError(f"interaction_csr: user ids outside [0, {n_user})")
+    if ui.shape[0] and (ui[:, 1].min() < -(1 << 31) or ui[:, 1].max() >= (1 << 31)):
+        raise ValueError("interaction_csr: item ids do not fit int32")
+    ui = np.unique(ui, axis=0)                                   # sorted by (user, item), duplicates dropped
+    ptr = np.zeros(n_user + 1, dtype=np.int64)
+    np.add.at(ptr, ui[:, 0] + 1, 1)
+    np.cumsum(ptr, out=ptr)
+    return ptr, np.ascontiguousarray(ui[:, 1].astype(np.int32))
+
+
+def interaction_csr(rows, n_user, device="cuda", labels=1):
+    """The per-user exclusion list of ``sample_negatives`` as a device CSR pair (ptr int64 [nU+1], ids int32) from any number
+    of [n, 3] (user, item, label) arrays: every item a user has with label 1 in any of them -- or, with ``labels=None``, every
+    item the user is listed with at all, which is convert_rating's ``item_set - pos - neg`` (KGCN/preprocess.py:60-70) for a
+    caller with explicit negatives.  Rows come out ascending and distinct.  Host plumbing, like ``history_csr``."""
+    ptr, ids = _interaction_csr_host(rows, n_user, labels)
+    return torch.from_numpy(ptr).to(device), torch.from_numpy(ids).to(device)
+
+
+def sample_negatives(excl, n_item, counts, seed=1, round=0, check=True, total=None):
+    """mvin_sample_negatives: for every user u, ``counts[u]`` items outside u's exclusion row, uniformly and without
+    replacement, as a pure function of (``seed``, ``round``) -- include/mvin_hip.h states the rule.  ``excl``: an
+    ``interaction_csr`` pair on the device, or None for no exclusions.  ``counts``: int array [nU], device or host.
+    Returns (neg_ptr int64 [nU+1] = the cumulative counts, neg_items int32 [neg_ptr[-1]]) on the device; user u's negatives
+    are neg_items[neg_ptr[u]:neg_ptr[u+1]] in draw order.  A user with fewer eligible items than ``counts[u]`` keeps -1 in
+    the slots that cannot be filled:
+      check=True   reads the two status words back (one synchronisation) and raises ValueError naming how many users fell
+                   short and the first such user's m and c;
+      check=False  returns the status tensor (int64 [2]: users short, slots at -1) as a third value and never synchronises,
+                   provided ``counts`` is a host array or ``total`` = sum(counts) is passed (sizing the output from device
+                   counts is a read-back)."""
+    lib = _lib.load()
+    if torch.is_tensor(counts) and counts.is_cuda:
+        dev = counts.device
+        cnt = counts.to(torch.int32).contiguous()
+    else:
+        host = np.ascontiguousarray(np.asarray(counts.cpu() if torch.is_tensor(counts) else counts, dtype=np.int64))
+        if host.size and (host.min() < 0 or host.max() >= (1 << 31)):
+            raise ValueError("sample_negatives: counts must lie in [0, 2^31)")
+        dev = excl[0].device if excl is not None else torch.device("cuda")
+        cnt = torch.from_numpy(host.astype(np.int32)).to(dev)
+        if total is None:
+            total = int(host.sum())
+    n_user = cnt.shape[0]
+    neg_ptr = torch.zeros(n_user + 1, dtype=torch.int64, device=dev)
+    neg_ptr[1:] = torch.cumsum(cnt, 0)
+    if total is None:
+        total = int(neg_ptr[-1])
+    items = torch.empty(int(total), dtype=torch.int32, device=dev)
+    status = torch.zeros(2, dtype=torch.int64, device=dev)
+    if total > 0:
+        ep, ei = (None, None) if excl is None else (excl[0].contiguous(), excl[1].contiguous())
+        if ep is not None and (ep.dtype != torch.int64 or ei.dtype != torch.int32 or ep.shape[0] != n_user + 1):
+            raise ValueError("sample_negatives: excl = (ptr int64 [nU+1], ids int32)")
+        if ei is not None and ei.numel() == 0:      # nobody excludes anything: an empty tensor has no address to pass
+            ep, ei = None, None
+        _lib.check(lib.mvin_sample_negatives(_p(ep), _p(ei), _p(cnt), _p(neg_ptr), n_user, int(n_item),
+                                             int(seed) & ((1 << 64) - 1), int(round) & ((1 << 64) - 1), _p(items), _p(status),
+                                             _stream()), "mvin_sample_negatives")
+    if not check:
+        return neg_ptr, items, status
+    short_users, short_slots = status.cpu().tolist()
+    if short_users:
+        u = int(torch.searchsorted(neg_ptr, torch.nonzero(items < 0)[0], right=True)[0]) - 1
+        row = np.zeros(0, dtype=np.int64) if excl is None else excl[1][int(excl[0][u]):int(excl[0][u + 1])].cpu().numpy()
+        c = int(n_item) - np.unique(row[(row >= 0) & (row < n_item)]).size
+        raise ValueError(f"sample_negatives: {short_users} users fell short ({short_slots} slots left at -1); the first is user "
+                         f"{u} with m={int(cnt[u])} requested and c={c} eligible items of {int(n_item)}")
+    return neg_ptr, items
+
+
+class NegativeSampler(object):
+    """Fresh training negatives for every epoch: convert_rating's rule (KGCN/preprocess.py:60-70 -- per user, as many unwatched
+    items as positives, without replacement) with the draws made on the device by ``sample_negatives``.
+
+    Holds on ``device``: the positive rows of ``train_data`` (label 1, in ``train_data`` order), the exclusion CSR over the
+    label-1 items of ``train_data`` and of every array in ``exclude`` (pass the eval and test splits: no held-out positive is
+    then taught as a negative), and the counts m[u] = floor(ratio * p_u + 0.5) with p_u = positives of u in ``train_data``
+    (round half up, computed in float64; ``ratio=1.0`` is the reference's ``size=len(pos_item_set)``).  A user with fewer
+    eligible items c_u = n_item - |distinct in-range exclusions| than m[u] gets m[u] = c_u; that is said once through
+    ``warnings.warn``.  ``epoch(round)`` is a pure function of (seed, round)."""
+
+    def __init__(self, train_data, n_user, n_item, exclude=(), ratio=1.0, seed=1, device="cuda"):
+        d = np.asarray(train_data, dtype=np.int64).reshape(-1, 3)
+        pos = d[d[:, 2] == 1]
+        self.n_user, self.n_item, self.seed, self.ratio = int(n_user), int(n_item), int(seed), float(ratio)
+        self.device = torch.device(device)
+        self.pos_rows = torch.from_numpy(np.ascontiguousarray(pos)).to(self.device)
+        ptr, ids = _interaction_csr_host([d] + [np.asarray(e) for e in exclude], self.n_user, labels=1)
+        self.excl = (torch.from_numpy(ptr).to(self.device), torch.from_numpy(ids).to(self.device))
+        n_pos_of = np.bincount(pos[:, 0], minlength=self.n_user).astype(np.int64)
+        want = np.floor(self.ratio * n_pos_of.astype(np.float64) + 0.5).astype(np.int64)
+        in_range = (ids >= 0) & (ids < self.n_item)
+        row_of = np.repeat(np.arange(self.n_user), np.diff(ptr))
+        eligible = self.n_item - np.bincount(row_of[in_range], minlength=self.n_user).astype(np.int64)
+        m = np.minimum(want, eligible)
+        self.clipped_users = int(np.count_nonzero(want > eligible))
+        if self.clipped_users:
+            import warnings
+            warnings.warn(f"NegativeSampler: {self.clipped_users} users have fewer eligible items than requested negatives; "
+                          f"they get every eligible item ({int((want - m).sum())} negatives fewer in all)")
+        self.counts_host = m
+        self.n_pos, self.n_neg = int(pos.shape[0]), int(m.sum())
+        self.counts = torch.from_numpy(m.astype(np.int32)).to(self.device)
+        self.neg_users = torch.from_numpy(np.repeat(np.arange(self.n_user, dtype=np.int64), m)).to(self.device)
+        self.last_status = None
+
+    def epoch(self, round):
+        """int64 [n_pos + n_neg, 3] (user, item, label) on the device: the positives first, in ``train_data`` order, then the
+        negatives of ``round`` (label 0), user-major, each user's in draw order.  Nothing goes back to the host;
+        ``last_status`` keeps the call's status tensor."""
+        _, items, self.last_status = sample_negatives(self.excl, self.n_item, self.counts, seed=self.seed, round=round,
+                                                      check=False, total=self.n_neg)
+        rows = torch.empty((self.n_pos + self.n_neg, 3), dtype=torch.int64, device=self.device)
+        rows[:self.n_pos] = self.pos_rows
+        neg = rows[self.n_pos:]
+        neg[:, 0] = self.neg_users
+        neg[:, 1] = items
+        neg[:, 2] = 0
+        return rows

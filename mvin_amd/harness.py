@@ -208,11 +208,9 @@ def train_epoch(args, model, train_data, user_triplet_set, sess=None, rng=None):
     return losses
 
 
-def train_epoch_device(feeder, train_data, batch_size, rng=None, graph=False):
-    """Same epoch with device-side feeds (ripple sets gathered on the GPU).  ``graph=True``: every step is one
-    hipGraph replay (training.GraphedTrainer, captured once per batch size) and the losses are read back once,
-    at the end of the epoch, instead of once per step."""
-    import torch
+def _epoch_trainer(feeder, batch_size, graph):
+    """The model's Trainer (made on first use) and, for ``graph=True`` on one rank, its GraphedTrainer captured at
+    ``batch_size`` (None: eager steps)."""
     from .training import GraphedTrainer, Trainer
     model = feeder.model
     if model.trainer is None:
@@ -228,9 +226,14 @@ def train_epoch_device(feeder, train_data, batch_size, rng=None, graph=False):
                 import warnings
                 warnings.warn(f"hipGraph capture of the training step failed ({e}); running the epoch eagerly")
                 gt = model._graphed_trainer = None
-    (rng or np.random).shuffle(train_data)
-    dev = model.device
-    data = torch.from_numpy(np.ascontiguousarray(train_data)).to(dev)
+    return gt
+
+
+def _run_epoch_on_device(feeder, data, batch_size, gt):
+    """One epoch over ``data``, an int64 [n, 3] (user, item, label) tensor on the model's device, in row order: full
+    minibatches only, the ragged tail dropped.  ``gt``: the GraphedTrainer of ``_epoch_trainer`` or None.  Returns the losses."""
+    import torch
+    model = feeder.model
     losses, start = [], 0
     while start + batch_size <= data.shape[0]:
         blk = data[start:start + batch_size]
@@ -244,6 +247,41 @@ def train_epoch_device(feeder, train_data, batch_size, rng=None, graph=False):
     if gt is not None and losses:
         losses = torch.cat(losses).cpu().tolist()
     return losses
+
+
+def train_epoch_device(feeder, train_data, batch_size, rng=None, graph=False):
+    """Same epoch with device-side feeds (ripple sets gathered on the GPU).  ``graph=True``: every step is one
+    hipGraph replay (training.GraphedTrainer, captured once per batch size) and the losses are read back once,
+    at the end of the epoch, instead of once per step."""
+    import torch
+    gt = _epoch_trainer(feeder, batch_size, graph)
+    (rng or np.random).shuffle(train_data)
+    data = torch.from_numpy(np.ascontiguousarray(train_data)).to(feeder.model.device)
+    return _run_epoch_on_device(feeder, data, batch_size, gt)
+
+
+def resampled_epoch_rows(sampler, round, device, perm_seed=None):
+    """The rows ``train_epoch_resampled`` trains on: ``sampler.epoch(round)`` permuted on the device by a
+    ``torch.Generator`` seeded with ``perm_seed`` (None: derived from the sampler's seed and ``round``), so the same
+    (sampler, round, perm_seed) gives the same rows in the same order.  int64 [n, 3] on ``device``; nothing goes to the host."""
+    import torch
+    rows = sampler.epoch(round)
+    if perm_seed is None:
+        perm_seed = (int(sampler.seed) * 0x9E3779B97F4A7C15 + int(round) * 0xC2B2AE3D27D4EB4F + 1) & ((1 << 63) - 1)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(perm_seed))
+    return rows[torch.randperm(rows.shape[0], generator=gen, device=device)]
+
+
+def train_epoch_resampled(feeder, sampler, batch_size, round, graph=False, perm_seed=None):
+    """One epoch whose label-0 rows are drawn for this epoch: the positives of ``sampler`` (data_prep.NegativeSampler) plus
+    ``sampler.epoch(round)``'s fresh negatives, permuted on the device (``resampled_epoch_rows``), then full minibatches
+    only through the same Trainer / GraphedTrainer steps as ``train_epoch_device``.  Returns the losses like it.
+    The rows are a pure function of (sampler, round, perm_seed): every rank of a data-parallel run computes the same epoch
+    tensor without communication, exactly as every rank holds the same ``train_data`` in ``train_epoch_device``."""
+    gt = _epoch_trainer(feeder, batch_size, graph)
+    data = resampled_epoch_rows(sampler, round, feeder.model.device, perm_seed)
+    return _run_epoch_on_device(feeder, data, batch_size, gt)
 
 
 # --------------------------------------------------------------------------- ranking metrics
@@ -518,7 +556,7 @@ class EarlyStop(object):
 
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
-          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host"):
+          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed"):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -538,9 +576,16 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     call (topk_eval_batched; ties by ascending item id).
     ``ctr_impl``: "host" evaluates CTR batch by batch with sklearn on the host (ctr_eval_device); "batched" scores each split
     into one device buffer and counts every batch's metrics exactly in one launch (ctr_eval_batched).
+    ``negatives``: "fixed" trains on the label-0 rows ``train_data`` came with, every epoch; "resample" keeps the positives
+    of ``train_data`` and draws one fresh negative per positive for every epoch on the device (data_prep.NegativeSampler with
+    ``round`` = the epoch, seed ``args.neg_seed`` or 1; train_epoch_resampled), never an item the user has with label 1 in
+    train, eval or test.  The per-epoch CTR evaluation of the train split still evaluates the fixed ``train_data``, which keeps
+    the history comparable.  The draws depend on (seed, epoch) only: every rank of a multi-rank run builds the same epoch.
     Returns (model, history): one dict per epoch."""
     if ctr_impl not in ("host", "batched"):
         raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
+    if negatives not in ("fixed", "resample"):
+        raise ValueError(f"negatives={negatives!r}: expected 'fixed' or 'resample'")
     from .model import MVIN
     n_user, n_item, n_entity, n_relation = data[0], data[1], data[2], data[3]
     train_data, eval_data, test_data = (np.asarray(d) for d in data[4:7])
@@ -561,9 +606,17 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
             item_set = set(int(i) for i in data[12])                            # item_set_most_pop, train.py:70,75
     history = []
     train_data = train_data.copy()
+    sampler = None
+    if negatives == "resample":
+        from .data_prep import NegativeSampler
+        sampler = NegativeSampler(train_data, n_user, n_item, exclude=(eval_data, test_data), ratio=1.0,
+                                  seed=getattr(args, "neg_seed", 1), device=model.device)
     for epoch in range(getattr(args, "n_epochs", 20)):
-        losses = train_epoch_device(feeder, train_data, args.batch_size, rng=rng,
-                                    graph=(args.batch_size <= 2048) if graph == "auto" else bool(graph))
+        use_graph = (args.batch_size <= 2048) if graph == "auto" else bool(graph)
+        if sampler is not None:
+            losses = train_epoch_resampled(feeder, sampler, args.batch_size, epoch, graph=use_graph)
+        else:
+            losses = train_epoch_device(feeder, train_data, args.batch_size, rng=rng, graph=use_graph)
         rec = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else float("nan")}
         if show_topk:
             for mode in ("eval", "test"):
