@@ -744,6 +744,30 @@ MVIN_API int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_
                             const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals,
                             int k, void* ws, int32_t* out_ids, float* out_vals, void* stream);
 
+/* ---- full-ranking evaluation: where named items land in the ranking of a row, without ranking the row --
+ * mvin_rank_positives: rows, columns and eligibility mean what they mean for mvin_topk_rows: row r of `scores` is
+ * scores[r*ld .. r*ld+n) (never written); column j is candidate item cand_ids[j] (cand_ids NULL: item col_offset + j, which must
+ * fit int32); a column is eligible unless its item id is in row r's exclusion list excl_ids[excl_ptr[r] .. excl_ptr[r+1]),
+ * ascending (both NULL = no exclusions); candidates are expected to be distinct.  Row r names the items
+ * pos_ids[pos_ptr[r] .. pos_ptr[r+1]), ascending and distinct (pos_ptr [rows+1] int64, offsets into pos_ids AND into the
+ * outputs; T = pos_ptr[rows] entries in all).  Entry t, with j_t the eligible column that carries its id:
+ *  - out_counts[t] = (greater, equal_before, equal_after): the row's eligible columns whose score is above the entry's, equal
+ *    to it with j < j_t, equal to it with j > j_t.  Scores compare as mvin_topk_rows orders them: -0.0 equals +0.0, every NaN
+ *    ranks below -inf and all NaNs are equal.  greater + equal_before is the index the item has in mvin_topk_rows's output;
+ *  - out_vals[t] = the input bits of the entry's score;
+ *  - no eligible column carries the id (absent, or excluded): counts (-1, -1, -1), value quiet NaN (0x7FC00000).
+ * out_eligible[r] = the number of eligible columns of row r.  Every number is exact and independent of the launch shape; a row
+ * may name any number of entries (none, or thousands: they are taken in pieces).  A row whose entries are not ascending and
+ * distinct gets unspecified numbers, never an access out of range.
+ * Errors (< 0, nothing launched): -2 for rows < 0, n < 0, ld < n, n > 2^31 - 1 or implicit ids beyond int32; -1 for null
+ * pos_ptr / pos_ids / out_*, null scores with n > 0, or exactly one of excl_ptr / excl_ids null.  rows == 0 launches nothing;
+ * n == 0 marks every entry missing and every eligible count 0.  `ws`: mvin_rank_positives_ws_bytes bytes, NULL when that is 0. */
+MVIN_API int64_t mvin_rank_positives_ws_bytes(int64_t rows, int64_t n, int64_t n_pos);   /* 0: no workspace needed; < 0: invalid sizes */
+MVIN_API int mvin_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                                 const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* pos_ptr, const int32_t* pos_ids,
+                                 void* ws, int32_t* out_counts /* [T,3] */, float* out_vals /* [T] */,
+                                 int32_t* out_eligible /* [rows] */, void* stream);
+
 /* ---- CTR metrics: exact integer counts behind the reference's CTR evaluation (util.py:44-56: roc_auc_score, accuracy and
  * f1_score of every batch) for many segments at once --
  * mvin_ctr_counts: segment s is scores[s*ld .. s*ld+seg_len) (f32) with labels[s*ld .. s*ld+seg_len) (int32, 0 or 1); neither is

@@ -93,6 +93,8 @@ SIGNATURES = {
     "mvin_topk_rows_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     "mvin_topk_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
                        + [C.c_int] + [C.c_void_p] * 4),
+    "mvin_rank_positives_ws_bytes": (C.c_int64, [C.c_int64] * 3),
+    "mvin_rank_positives": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 9),
     "mvin_ctr_counts_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_ctr_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvin_order_by_key_ws_elems": (C.c_size_t, [C.c_int64]),

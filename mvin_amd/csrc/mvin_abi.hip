@@ -421,6 +421,33 @@ int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, con
                       who);
 }
 
+static bool rank_bad_sizes(int64_t rows, int64_t n) {
+    return rows < 0 || rows >= (int64_t(1) << 31) || n < 0 || n > (int64_t)0x7FFFFFFF;
+}
+
+int64_t mvin_rank_positives_ws_bytes(int64_t rows, int64_t n, int64_t n_pos) {
+    if (rank_bad_sizes(rows, n) || n_pos < 0)
+        return fail(-2, "mvin_rank_positives_ws_bytes: rows=%lld n=%lld n_pos=%lld", (long long)rows, (long long)n, (long long)n_pos);
+    return 0;                                             // one workgroup per row, everything it keeps sits in LDS
+}
+
+int mvin_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                        const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* pos_ptr, const int32_t* pos_ids, void* ws,
+                        int32_t* out_counts, float* out_vals, int32_t* out_eligible, void* stream) {
+    (void)ws;                                             // mvin_rank_positives_ws_bytes is 0 for every valid shape
+    const char* who = "mvin_rank_positives";
+    if (rank_bad_sizes(rows, n) || ld < n)
+        return fail(-2, "%s: rows=%lld n=%lld ld=%lld", who, (long long)rows, (long long)n, (long long)ld);
+    if (!pos_ptr || !pos_ids || !out_counts || !out_vals || !out_eligible || (n > 0 && !scores))
+        return fail(-1, "%s: null scores / pos_ptr / pos_ids / out_counts / out_vals / out_eligible", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: null one of excl_ptr / excl_ids (they go together)", who);
+    if (!cand_ids && (col_offset < 0 || col_offset + n > (int64_t)0x7FFFFFFF))
+        return fail(-2, "%s: col_offset=%lld: implicit ids col_offset + j must be int32", who, (long long)col_offset);
+    return hip_result(mvin::launch_rank_positives(scores, rows, n, ld, cand_ids, col_offset, excl_ptr, excl_ids, pos_ptr, pos_ids,
+                                                  out_counts, out_vals, out_eligible, (hipStream_t)stream),
+                      who);
+}
+
 static bool ctr_bad_sizes(int64_t n_seg, int64_t seg_len) {     // also: at most 2^40 pairs in all
     return seg_len < 1 || seg_len > (int64_t)0x7FFFFFFF || n_seg < 0 || n_seg > ((int64_t)1 << 40) / seg_len;
 }

@@ -436,6 +436,9 @@ bool topk_rows_supported(int k);                               // row-wise top-K
 hipError_t launch_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
                             const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals, int k,
                             int32_t* out_ids, float* out_vals, hipStream_t st);
+hipError_t launch_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                                 const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* pos_ptr, const int32_t* pos_ids,
+                                 int32_t* out_counts, float* out_vals, int32_t* out_eligible, hipStream_t st);   // exact ranks of named items (mvin_rank.hip)
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);

@@ -15,12 +15,11 @@
 // The row is never staged in LDS (a last-fm row is 192 KB); what a pass needs per candidate is one coalesced load and one bitmap read.
 #include "mvin_kernels.h"
 #include "mvin_score_image.h"
+#include "mvin_row_select.h"   // kTopkBitmapMaxN, kTopkExclLds, topk_in_sorted
 
 namespace mvin {
 
 constexpr int kTopkMaxK = 1024;
-constexpr int kTopkBitmapMaxN = 131072;   // columns covered by the LDS exclusion bitmap (16 KB); beyond: binary search every pass
-constexpr int kTopkExclLds = 2048;        // exclusion ids staged in LDS per row (8 KB); a longer list is searched in global memory
 constexpr int kTopkUnroll = 4;
 
 struct TopkArgs {
@@ -36,18 +35,6 @@ struct TopkArgs {
     int32_t* out_ids;
     float* out_vals;
 };
-
-// is `id` in the ascending list [0, E)?  Branch-free lower bound.
-__device__ __forceinline__ bool topk_in_sorted(const int32_t* list, int E, int32_t id) {
-    int lo = 0, len = E;
-    while (len > 0) {
-        const int half = len >> 1;
-        const bool right = list[lo + half] < id;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
-    return lo < E && list[lo] == id;
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void topk_rows_kernel(TopkArgs a) {

@@ -174,6 +174,68 @@ class DeviceFeeder(object):
                 carry = out
         return out_ids.long(), out_vals
 
+    def rank_positives(self, users, positives, candidates, exclude=None, max_pairs=524288):
+        """Where every user's ``positives`` land in the user's ranking of ``candidates``, without ranking them: the device
+        tensors ``(pos_ptr int64 [U+1], pos_ids int32 [T], counts int32 [T, 3], vals f32 [T], eligible int32 [U])`` of
+        ops.rank_positives -- per positive (greater, equal_before, equal_after) among the user's eligible candidates and its
+        score, (-1, -1, -1) / NaN when it is no candidate or excluded; equal scores rank in the order of ``candidates``, as in
+        ``recommend``.  ``positives`` and ``exclude``: a get_user_record dict (``users`` then on the host) or an
+        ``exclusion_csr`` pair.  Users are taken in chunks of max(1, max_pairs // N) rows; a chunk's scores fill one [rows, N]
+        buffer through ``score_grid`` calls of at most ``max_pairs`` pairs each (column blocks when N > max_pairs), then ONE
+        mvin_rank_positives call ranks the chunk.  Enqueues only: no synchronisation, no copy to the host."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        max_pairs = int(max_pairs)
+        if max_pairs < 1:
+            raise ValueError(f"max_pairs={max_pairs}")
+        for rec in (positives, exclude):
+            if isinstance(rec, dict) and torch.is_tensor(users) and users.is_cuda:
+                raise ValueError("rank_positives: a record needs host users (or pass feeder.exclusion_csr(users, record))")
+        if isinstance(positives, dict):
+            positives = self.exclusion_csr(users, positives)
+        if isinstance(exclude, dict):
+            exclude = self.exclusion_csr(users, exclude)
+        pos_ptr, pos_ids = positives
+        u = _dev_ids(users, dev)
+        U = u.shape[0]
+        cand, cand_ids, base = _candidate_ids(candidates, dev)
+        N = cand.shape[0]
+        T = pos_ids.numel()
+        counts = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        vals = torch.empty((T,), dtype=torch.float32, device=dev)
+        eligible = torch.empty((U,), dtype=torch.int32, device=dev)
+        per = max(1, max_pairs // max(1, N))
+        buf = torch.empty((min(per, U), N), dtype=torch.float32, device=dev)
+        for u0 in range(0, U, per):
+            u1 = min(U, u0 + per)
+            grid = buf[:u1 - u0]
+            cols = max(1, max_pairs // (u1 - u0))
+            if cols >= N:
+                self.score_grid(u[u0:u1], cand, out=grid)
+            else:
+                for c0 in range(0, N, cols):
+                    c1 = min(N, c0 + cols)
+                    self.score_grid(u[u0:u1], cand[c0:c1], out=grid[:, c0:c1])
+            ops.rank_positives(grid, (pos_ptr[u0:u1 + 1], pos_ids), cand_ids=cand_ids, col_offset=base,
+                               excl=None if exclude is None else (exclude[0][u0:u1 + 1], exclude[1]),
+                               out=(counts, vals, eligible[u0:u1]))
+        return pos_ptr, pos_ids, counts, vals, eligible
+
+
+def _candidate_ids(candidates, dev):
+    """(ids int64 [N] on the device, int32 ids per column or None, first id): a host list that is a contiguous id range (the full
+    catalogue) needs no id per column, the kernels derive it from the position."""
+    import torch
+    if torch.is_tensor(candidates):
+        cand = candidates.to(dev).long().reshape(-1)
+        return cand, cand.to(torch.int32), 0
+    arr = np.asarray(candidates, dtype=np.int64).reshape(-1)
+    N = arr.shape[0]
+    contiguous = bool(N and arr[0] >= 0 and arr[-1] < (1 << 31) - 1 and np.array_equal(arr, np.arange(arr[0], arr[0] + N)))
+    cand = torch.from_numpy(arr).to(dev)
+    return cand, None if contiguous else cand.to(torch.int32), int(arr[0]) if contiguous else 0
+
 
 def _dev_ids(x, dev):
     import torch
@@ -529,6 +591,71 @@ def topk_eval_batched(feeder, user_list, train_record, eval_record, test_record,
             [float(np.mean(ndcg_list[k])) for k in k_list], None, None)
 
 
+def _ranked_metrics(feeder, users, positives, exclude, candidates, k_list, ndcg_window, max_pairs, auc=True):
+    """rank_positives for ``users`` and ONE copy back (counts, value bits and eligible counts packed into one int32 tensor):
+    the per-user arrays of ops.rank_metrics_from_counts."""
+    import torch
+    from . import ops
+    ptr, ids = _exclusion_csr_host(users, positives)
+    dev = feeder.model.device
+    pos = (torch.from_numpy(ptr).to(dev), torch.from_numpy(ids).to(dev))
+    _, _, counts, vals, eligible = feeder.rank_positives(users, pos, candidates, exclude=exclude, max_pairs=max_pairs)
+    T, U = ids.size, len(users)
+    packed = torch.cat([counts.reshape(-1), vals.view(torch.int32), eligible]).cpu().numpy()
+    return ops.rank_metrics_from_counts(ptr, packed[:3 * T].reshape(T, 3), packed[4 * T:4 * T + U], k_list,
+                                        vals=packed[3 * T:4 * T].view(np.float32) if auc else None, ndcg_window=ndcg_window)
+
+
+def rank_eval(feeder, users, train_record, truth_record, item_set, k_list, max_pairs=524288, ndcg_window=None):
+    """Ranking metrics of the ``users`` present in ``truth_record`` from the exact ranks of their truth items among
+    ``sorted(item_set)``, their ``train_record`` items excluded (DeviceFeeder.rank_positives, mvin_rank_positives): no top-K
+    selection, so no bound on k, and one copy of a few ints per truth item comes back.  Returns a dict of means over those
+    users: a list per k of ``k_list`` for precision, recall, hit_ratio, mrr, map, ndcg (window ``ndcg_window``, default
+    max(k_list)) and ndcg_ideal as ops.rank_metrics_from_counts defines them, ``auc`` (the mean of the per-user AUC of truth
+    items against the other eligible candidates, over the users where it is defined) and ``n_users``."""
+    import warnings
+    from . import ops
+    users = [u for u in users if u in truth_record]
+    out = {m: [float("nan")] * len(k_list) for m in ops.RANK_METRICS}
+    out.update(auc=float("nan"), n_users=len(users))
+    if not users:
+        return out
+    per = _ranked_metrics(feeder, users, truth_record, train_record, sorted(item_set), k_list, ndcg_window, max_pairs)
+    for m in ops.RANK_METRICS:
+        out[m] = [float(np.mean(per[m][:, q].tolist())) for q in range(len(k_list))]
+    defined = per["auc"][~np.isnan(per["auc"])]
+    out["auc"] = float(np.mean(defined)) if defined.size else float("nan")
+    return out
+
+
+def topk_eval_ranked(feeder, user_list, train_record, eval_record, test_record, item_set, k_list, mode="test",
+                     max_pairs=524288):
+    """topk_eval_batched's numbers, equal to the last bit, from ranks instead of a selection: the same users are scored against
+    ``sorted(item_set)`` by the same calls, mvin_rank_positives finds the place of every truth item among the user's eligible
+    candidates, and precision / recall / the stale-k NDCG follow from those places (ops.rank_metrics_from_counts with the
+    window k_list[-1]).  No k is too large for it, and what comes back is a few ints per truth item."""
+    ref = eval_record if mode == "eval" else test_record
+    users = [u for u in user_list if u in ref]
+    p, r, n = ([[] for _ in k_list] for _ in range(3))
+    if users:
+        per = _ranked_metrics(feeder, users, ref, train_record, sorted(item_set), k_list, k_list[-1], max_pairs, auc=False)
+        p, r, n = ([per[m][:, q].tolist() for q in range(len(k_list))] for m in ("precision", "recall", "ndcg"))
+    return ([float(np.mean(x)) for x in p], [float(np.mean(x)) for x in r], [float(np.mean(x)) for x in n], None, None)
+
+
+def full_ranking_eval(feeder, train_data, split_data, n_item, k_list=(20, 40, 60, 80, 100), max_pairs=524288):
+    """The all-ranking protocol of the KG-recommender papers (the reference's KGAT/utility/batch_test.py:test): EVERY user
+    with a label-1 row in ``split_data`` against the whole catalogue ``range(n_item)``, the user's label-1 items of
+    ``train_data`` masked, each metric averaged over those users.  Returns rank_eval's dict (ndcg over the window max(k_list),
+    as that protocol computes it, and the per-user AUC)."""
+    train_record = get_user_record(np.asarray(train_data), True)
+    truth = get_user_record(np.asarray(split_data), False)
+    users = sorted(int(u) for u in truth)
+    truth = {int(u): v for u, v in truth.items()}
+    return rank_eval(feeder, users, {int(u): v for u, v in train_record.items()}, truth, range(int(n_item)), list(k_list),
+                     max_pairs=max_pairs)
+
+
 # --------------------------------------------------------------------------- the train.py loop
 class EarlyStop(object):
     """train_util.py:20-61 (Early_stop_info): keep the best evaluation score, save the stage-wise
@@ -573,7 +700,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     once per epoch); "auto" = at batch sizes up to 2 048, where a step is launch- and latency-bound (the reference's
     scripts train at 512 / 1 024).
     ``topk_impl``: "host" ranks user by user on the host (topk_eval_device); "batched" ranks every user on the device in one
-    call (topk_eval_batched; ties by ascending item id).
+    call (topk_eval_batched; ties by ascending item id); "ranked" computes the same numbers as "batched", to the last bit, from
+    the exact ranks of the truth items (topk_eval_ranked, mvin_rank_positives: no selection, no bound on k).
     ``ctr_impl``: "host" evaluates CTR batch by batch with sklearn on the host (ctr_eval_device); "batched" scores each split
     into one device buffer and counts every batch's metrics exactly in one launch (ctr_eval_batched).
     ``negatives``: "fixed" trains on the label-0 rows ``train_data`` came with, every epoch; "resample" keeps the positives
@@ -594,8 +722,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         model = MVIN(args, n_user, n_entity, n_relation, adj_entity, adj_relation, device=device, hoist=bool(hoist))
         if getattr(args, "load_pretrain_emb", False):
             model.restore_pretrain_emb()                                       # train.py:53-54
-    if topk_impl not in ("host", "batched"):
-        raise ValueError(f"topk_impl={topk_impl!r}: expected 'host' or 'batched'")
+    if topk_impl not in ("host", "batched", "ranked"):
+        raise ValueError(f"topk_impl={topk_impl!r}: expected 'host', 'batched' or 'ranked'")
     feeder = DeviceFeeder(model, uts)
     stop = EarlyStop(getattr(args, "tolerance", 2), getattr(args, "early_stop", 3),
                      getattr(args, "save_final_model", True))
@@ -620,9 +748,9 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         rec = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else float("nan")}
         if show_topk:
             for mode in ("eval", "test"):
-                if topk_impl == "batched":
-                    p, r, n, _, _ = topk_eval_batched(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list,
-                                                      mode=mode)
+                if topk_impl in ("batched", "ranked"):
+                    topk = topk_eval_ranked if topk_impl == "ranked" else topk_eval_batched
+                    p, r, n, _, _ = topk(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list, mode=mode)
                 else:
                     p, r, n, _, _ = topk_eval_device(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list,
                                                      topk_batch, mode=mode)

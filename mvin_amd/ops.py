@@ -505,6 +505,193 @@ def ctr_metrics_from_counts(counts):
     return auc, acc, f1
 
 
+RANK_METRICS = ("precision", "recall", "hit_ratio", "mrr", "map", "ndcg", "ndcg_ideal")
+RANK_MISSING = 0x7FC00000    # the bits mvin_rank_positives writes as the value of an entry that no eligible column carries
+
+
+def _rank_csr(pair, rows, name):
+    ptr, ids = pair
+    _chk(ptr, torch.int64, f"{name} ptr")
+    _chk(ids, I32, f"{name} ids")
+    if ptr.dim() != 1 or ptr.numel() != rows + 1:
+        raise ValueError(f"{name} ptr: {ptr.numel()} entries for {rows} rows")
+    if ids.dim() != 1:
+        raise ValueError(f"{name} ids: expected a 1-D tensor")
+    return ptr, ids
+
+
+def rank_positives(scores, pos, cand_ids=None, col_offset=0, excl=None, out=None):
+    """mvin_rank_positives: where the named items of every row land in the row's ranking, without ranking it.  ``scores``,
+    ``cand_ids``, ``col_offset`` and ``excl`` are topk_rows's ([rows, n] f32 with dense rows, rows may be strided; item id per
+    column; ``(ptr, ids)`` CSR of excluded ids per row, ascending).  ``pos``: a ``(ptr int64 [rows+1], ids int32 [T])`` CSR of the
+    items to rank per row, each row ascending and distinct; ``ptr`` holds offsets into ``ids`` AND into the outputs, so a slice
+    ``ptr[r0:r1+1]`` with the whole ``ids`` ranks rows r0 .. r1 into their places of whole-size outputs.  Returns
+    ``(counts int32 [T, 3], vals f32 [T], eligible int32 [rows])`` (``out``: the same triple to write into): per entry
+    (greater, equal_before, equal_after) among the row's eligible columns and the input bits of its score -- (-1, -1, -1) and a
+    quiet NaN when no eligible column carries the id -- and per row the number of eligible columns.  greater + equal_before is the
+    item's index in topk_rows's output.  Enqueues only: no synchronisation, no copy to the host."""
+    lib = _lib.load()
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise _lib.MvinHipError("scores: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if scores.dtype != F32:
+        raise TypeError(f"scores: expected {F32}, got {scores.dtype}")
+    if scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1) or scores.stride(0) < scores.shape[1]:
+        raise ValueError("scores: expected a [rows, n] tensor with dense rows")
+    rows, n = scores.shape
+    dev = scores.device
+    if cand_ids is not None:
+        _chk(cand_ids, I32, "cand_ids")
+        if cand_ids.numel() != n:
+            raise ValueError(f"cand_ids: {cand_ids.numel()} ids for {n} columns")
+    if pos is None or len(pos) != 2:
+        raise ValueError("pos: expected a (ptr, ids) pair")
+    pptr, pids = _rank_csr(pos, rows, "pos")
+    T = pids.numel()
+    eptr = eids = None
+    if excl is not None:
+        eptr, eids = _rank_csr(excl, rows, "excl")
+    if out is None:
+        out = (torch.empty((T, 3), dtype=I32, device=dev), torch.empty((T,), dtype=F32, device=dev),
+               torch.empty((rows,), dtype=I32, device=dev))
+    counts, vals, eligible = out
+    _chk(counts, I32, "out counts")
+    _chk(vals, F32, "out vals")
+    _chk(eligible, I32, "out eligible")
+    if tuple(counts.shape) != (T, 3) or tuple(vals.shape) != (T,) or tuple(eligible.shape) != (rows,):
+        raise ValueError(f"out: expected counts [{T}, 3], vals [{T}] and eligible [{rows}]")
+    if rows == 0:
+        return counts, vals, eligible
+    nws = lib.mvin_rank_positives_ws_bytes(rows, n, T)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_rank_positives_ws_bytes")
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    ld = scores.stride(0) if rows > 1 else n
+    anyp = _p(pptr)                             # an empty id array: any valid pointer, nothing is read or written through it
+    _lib.check(lib.mvin_rank_positives(_p(scores) if n > 0 else None, rows, n, ld, _p(cand_ids), int(col_offset), _p(eptr),
+                                       None if eptr is None else (_p(eids) if eids.numel() else _p(eptr)),
+                                       _p(pptr), _p(pids) if T else anyp, _p(ws), _p(counts) if T else anyp,
+                                       _p(vals) if T else anyp, _p(eligible), _stream()), "mvin_rank_positives")
+    return counts, vals, eligible
+
+
+def _score_image_host(vals):
+    """mvin_score_image.h on the host: uint32 images of f32 scores (-0.0 = +0.0, every NaN = 0, below image(-inf))."""
+    import numpy as np
+    u = np.ascontiguousarray(vals, dtype=np.float32).view(np.uint32).astype(np.int64)
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    u = np.where(u == 0x80000000, 0, u)
+    img = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
+    return np.where(nan, 0, img).astype(np.int64)
+
+
+def _dcg_sum(r):
+    """dcg of a 0 / 1 relevance vector, with the operations of harness.dcg_at_k (so that sums agree to the last bit)."""
+    import numpy as np
+    return float(np.sum(r / np.log2(np.arange(2, r.size + 2)))) if r.size else 0.0
+
+
+def rank_metrics_from_counts(pos_ptr, counts, eligible, k_list, vals=None, ndcg_window=None):
+    """Per-row ranking metrics (float64, on the host) from rank_positives's integers.  ``pos_ptr`` [rows+1], ``counts`` [T, 3],
+    ``eligible`` [rows], ``vals`` [T] are host arrays.  Per row: P = its entries (found or not), rho = greater + equal_before of a
+    found entry (its 0-based place in the ranking), h_k = #{rho < k}.  Returns a dict of [rows, len(k_list)] arrays:
+      precision = h_k / k;  recall = h_k / P (NaN for a row without entries);  hit_ratio = 1.0 if h_k > 0 else 0.0;
+      mrr = 1 / (1 + min rho) if min rho < k else 0;  map = (1/k) sum_{i=1..k} h_i / i (the reference's ap_at_k, metrics.py:67-80,
+      not the textbook average precision);
+      ndcg = the reference's (metrics.py:21-31) over the hit list of the first w = ``ndcg_window`` places (default max(k_list)):
+      dcg = sum_{rho < min(k, w)} 1 / log2(rho + 2) over the dcg of min(k, h_w) leading hits, 0 where that is 0 -- with
+      w = k_list[-1] what harness._rank_metrics computes, to the last bit;
+      ndcg_ideal = the same dcg over the dcg of min(k, P) leading hits (not a number of the reference);
+    and, when ``vals`` is given, ``auc`` [rows]: the AUC of the row's found entries against its other eligible columns, ties
+    counted half -- NaN where a row has no found entry or no other eligible column, with ONE UndefinedMetricWarning per call."""
+    import warnings
+    import numpy as np
+    ptr = np.asarray(pos_ptr, dtype=np.int64).reshape(-1)
+    c = np.asarray(counts).astype(np.int64, copy=False)
+    rows = ptr.size - 1
+    if rows < 0 or c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError(f"pos_ptr [rows+1] and counts [T, 3] expected, got {ptr.shape} and {c.shape}")
+    elig = np.asarray(eligible).astype(np.int64, copy=False).reshape(-1)
+    if elig.size != rows:
+        raise ValueError(f"eligible: {elig.size} entries for {rows} rows")
+    ks = [int(k) for k in k_list]
+    if not ks or min(ks) < 1:
+        raise ValueError(f"k_list={list(k_list)}: expected at least one k >= 1")
+    w = max(ks) if ndcg_window is None else int(ndcg_window)
+    if w < 1:
+        raise ValueError(f"ndcg_window={ndcg_window}")
+    P = np.diff(ptr)
+    if rows and (P.min() < 0 or ptr[-1] > c.shape[0] or ptr[0] < 0):
+        raise ValueError("pos_ptr: not the offsets of counts")
+    sel = np.arange(ptr[0], ptr[-1]) if rows else np.zeros(0, np.int64)
+    row_of = np.repeat(np.arange(rows), P)
+    c = c[sel]
+    found = c[:, 0] >= 0
+    rho = np.where(found, c[:, 0] + c[:, 1], np.iinfo(np.int64).max)
+    kmax = max(max(ks), w)
+    hist = np.zeros((rows, kmax), dtype=np.int64)
+    top = rho < kmax
+    np.add.at(hist, (row_of[top], rho[top]), 1)
+    h = np.cumsum(hist, axis=1)                                    # h[:, i-1] = h_i
+    first = np.full(rows, np.iinfo(np.int64).max, dtype=np.int64)
+    np.minimum.at(first, row_of, rho)
+    out = {m: np.zeros((rows, len(ks)), dtype=np.float64) for m in RANK_METRICS}
+    ap_terms = h[:, :max(ks)].astype(np.float64) / np.arange(1, max(ks) + 1, dtype=np.float64)
+    ap_sum = np.cumsum(ap_terms, axis=1)                           # sequential, like the reference's loop
+    disc = 1.0 / np.log2(np.arange(2, kmax + 2))
+    ideal = np.concatenate([[0.0], np.cumsum(disc)])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for q, k in enumerate(ks):
+            hk = h[:, k - 1]
+            out["precision"][:, q] = hk / k
+            out["recall"][:, q] = hk / P.astype(np.float64)
+            out["hit_ratio"][:, q] = (hk > 0).astype(np.float64)
+            out["mrr"][:, q] = np.where(first < k, 1.0 / (1.0 + np.where(first < k, first, 0)), 0.0)
+            out["map"][:, q] = ap_sum[:, k - 1] / k
+    # ndcg row by row through _dcg_sum: the hit list has min(w, eligible) places, as the ranked list it stands for
+    hw = h[:, w - 1] if rows else np.zeros(0, np.int64)
+    order = np.argsort(row_of[top], kind="stable")
+    rr, pp = row_of[top][order], rho[top][order]
+    starts = np.searchsorted(rr, np.arange(rows + 1))
+    for r in np.flatnonzero(hw > 0):
+        L = int(min(w, elig[r]))
+        hits = pp[starts[r]:starts[r + 1]]
+        rel = np.zeros(L, dtype=np.float64)
+        rel[hits[hits < L]] = 1.0
+        for q, k in enumerate(ks):
+            cut = rel[:k]
+            dcg = _dcg_sum(cut)
+            best = np.zeros(cut.size, dtype=np.float64)
+            best[:min(k, int(hw[r]))] = 1.0
+            idcg = _dcg_sum(best)
+            out["ndcg"][r, q] = dcg / idcg if idcg else 0.0
+            out["ndcg_ideal"][r, q] = dcg / ideal[min(k, int(P[r]), kmax)]
+    if vals is not None:
+        v = np.asarray(vals, dtype=np.float32).reshape(-1)[sel]
+        img = _score_image_host(v)
+        f_row, f_img, f_c = row_of[found], img[found], c[found]
+        n_found = np.bincount(f_row, minlength=rows).astype(np.int64)
+        n_neg = elig - n_found
+        # found entries of the same row above / equal to each found entry, from one sort by (row, image)
+        key = f_row * (1 << 32) + f_img
+        uniq, inv, cnt_u = np.unique(key, return_inverse=True, return_counts=True)
+        end_u = np.cumsum(cnt_u)                                  # entries with key <= uniq[i]
+        row_end = np.cumsum(n_found)                              # entries of rows <= r
+        pos_above = row_end[f_row] - end_u[inv]
+        pos_equal = cnt_u[inv] - 1
+        neg_above = f_c[:, 0] - pos_above
+        neg_equal = f_c[:, 1] + f_c[:, 2] - pos_equal
+        u2 = np.zeros(rows, dtype=np.int64)
+        np.add.at(u2, f_row, 2 * (n_neg[f_row] - neg_above) - neg_equal)
+        undefined = (n_found == 0) | (n_neg <= 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            auc = np.where(undefined, np.nan, u2.astype(np.float64) / (2.0 * n_found.astype(np.float64) * n_neg.astype(np.float64)))
+        out["auc"] = auc
+        if undefined.any():
+            warnings.warn(f"No found positive or no negative in {int(undefined.sum())} of {rows} row(s): the row's AUC is not "
+                          "defined there (NaN)", UndefinedMetricWarning, stacklevel=2)
+    return out
+
+
 def gather_attn_l2_prj(ws, enc_entity, enc_relation, parent_ids, t0, t1, q, B, parents_per_pair, K, D, nR, n_entity, encoded=True, order=None):
     """mvin_gather_attn_l2_prj_fwd: gather_attn_l2_enc over the workspace of ``project_tables`` (built with attention =
     (t0 is not None)).  ``encoded=False``: the two adjacency arrays are the plain adjacency (D = 32, K in {8, 16}).
