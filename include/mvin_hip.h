@@ -813,6 +813,37 @@ MVIN_API int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_
                                    int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status,
                                    void* stream);
 
+/* ---- KG exploration: which distinct KG edges lie within the model's receptive field of a seed set, and which of them the
+ * sampled adjacencies have reached so far (the reference sketches the number in data_loader_user_set.py:208-239,
+ * get_all_user_entity_count -> args.use_neighbor_rate, and leaves it commented out) --
+ * The KG comes as an EDGE INDEX (data_prep.kg_edge_index): eptr [n_entity+1] int64, edst / erel [M] int32; row h lists the
+ * DISTINCT (tail, relation) pairs of entity h, ascending by (tail, relation), so slot e is the edge (h, edst[e], erel[e]) and
+ * bit e (word e / 32, bit e % 32) of a bitmap of ceil(M / 32) uint32 words stands for it.  `seeds` [n_seed] int32 may repeat;
+ * seeds outside [0, n_entity) are ignored.
+ * mvin_kg_field: F_0 = seeds; for i < hops every edge whose head is in F_i belongs to the field and F_{i+1} = the tails of
+ * those edges (it replaces F_i).  field_bits is written in full; out_counts [hops+1] int64 = |F_1| .. |F_hops|, then the number
+ * of field edges.
+ * mvin_kg_explore: G_0 = seeds; for i < hops, for h in G_i and k < K: when (h, adj_entity[h,k], adj_relation[h,k]) is an edge
+ * of the index it is explored and its tail is in G_{i+1}; a slot that is no edge (the zero row of an entity without edges, an
+ * id out of range) is ignored and its tail is NOT followed, so G_i is a subset of F_i and explored a subset of the field.
+ * adj_entity / adj_relation [n_entity, K] int32.  explored_bits is read and OR-updated (a loop over adjacencies accumulates
+ * in place; start from zeros); out_counts [3] int64 = edges this adjacency explores, edges newly set by this call, edges set
+ * after it.
+ * Every bit and count is exact and independent of the launch shape and of timing.  `ws`: mvin_kg_explore_ws_bytes(n_entity, M)
+ * = 4 * (2 * ceil(n_entity / 32) + M + ceil(M / 32)) bytes, 8-byte aligned (two entity bitmaps, a row id per slot, one edge
+ * bitmap); NULL is accepted when M == 0.
+ * Errors (< 0, nothing launched): -1 for a null eptr / out_counts, a null edst / erel / ws / bitmap with M > 0, null seeds with
+ * n_seed > 0 or a null adjacency; -2 for hops outside 1..8, K < 1, n_entity < 0, M < 0, n_seed < 0 or n_entity / M beyond
+ * int32.  M == 0 gives all-zero counts; n_seed == 0 sets nothing (mvin_kg_field: zero bitmap and counts; mvin_kg_explore:
+ * counts 0, 0 and the unchanged total). */
+MVIN_API int64_t mvin_kg_explore_ws_bytes(int64_t n_entity, int64_t M);        /* < 0: invalid sizes */
+MVIN_API int mvin_kg_field(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int64_t n_entity, int64_t M,
+                           const int32_t* seeds, int64_t n_seed, int hops, void* ws, uint32_t* field_bits,
+                           int64_t* out_counts /* [hops+1] */, void* stream);
+MVIN_API int mvin_kg_explore(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int64_t n_entity, int64_t M,
+                             const int32_t* adj_entity, const int32_t* adj_relation, int K, const int32_t* seeds, int64_t n_seed,
+                             int hops, void* ws, uint32_t* explored_bits, int64_t* out_counts /* [3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,10 @@ SIGNATURES = {
                        + [C.c_int] + [C.c_void_p] * 4),
     "mvin_rank_positives_ws_bytes": (C.c_int64, [C.c_int64] * 3),
     "mvin_rank_positives": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 9),
+    "mvin_kg_explore_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mvin_kg_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
+    "mvin_kg_explore": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                  C.c_int] + [C.c_void_p] * 4),
     "mvin_ctr_counts_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_ctr_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvin_order_by_key_ws_elems": (C.c_size_t, [C.c_int64]),

@@ -448,6 +448,42 @@ int mvin_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld
                       who);
 }
 
+static bool kg_bad_sizes(int64_t n_entity, int64_t M) {
+    return n_entity < 0 || n_entity > (int64_t)0x7FFFFFFF || M < 0 || M > (int64_t)0x7FFFFFFF;
+}
+
+int64_t mvin_kg_explore_ws_bytes(int64_t n_entity, int64_t M) {
+    if (kg_bad_sizes(n_entity, M)) return fail(-2, "mvin_kg_explore_ws_bytes: n_entity=%lld M=%lld", (long long)n_entity, (long long)M);
+    return mvin::kg_explore_ws_bytes((int)n_entity, M);
+}
+
+int mvin_kg_field(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int64_t n_entity, int64_t M, const int32_t* seeds,
+                  int64_t n_seed, int hops, void* ws, uint32_t* field_bits, int64_t* out_counts, void* stream) {
+    const char* who = "mvin_kg_field";
+    if (kg_bad_sizes(n_entity, M) || n_seed < 0 || hops < 1 || hops > 8)
+        return fail(-2, "%s: n_entity=%lld M=%lld n_seed=%lld hops=%d (hops in 1..8, sizes within int32)", who, (long long)n_entity,
+                    (long long)M, (long long)n_seed, hops);
+    if (!eptr || !out_counts || (n_seed > 0 && !seeds)) return fail(-1, "%s: null eptr / seeds / out_counts", who);
+    if (M > 0 && (!edst || !erel || !ws || !field_bits)) return fail(-1, "%s: null edst / erel / ws / field_bits with M=%lld", who, (long long)M);
+    return hip_result(mvin::launch_kg_field(eptr, edst, erel, (int)n_entity, M, seeds, n_seed, hops, ws, field_bits, out_counts,
+                                            (hipStream_t)stream), who);
+}
+
+int mvin_kg_explore(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int64_t n_entity, int64_t M,
+                    const int32_t* adj_entity, const int32_t* adj_relation, int K, const int32_t* seeds, int64_t n_seed, int hops,
+                    void* ws, uint32_t* explored_bits, int64_t* out_counts, void* stream) {
+    const char* who = "mvin_kg_explore";
+    if (kg_bad_sizes(n_entity, M) || n_seed < 0 || hops < 1 || hops > 8 || K < 1)
+        return fail(-2, "%s: n_entity=%lld M=%lld n_seed=%lld hops=%d K=%d (hops in 1..8, K >= 1, sizes within int32)", who,
+                    (long long)n_entity, (long long)M, (long long)n_seed, hops, K);
+    if (!eptr || !out_counts || (n_seed > 0 && !seeds) || !adj_entity || !adj_relation)
+        return fail(-1, "%s: null eptr / seeds / adj_entity / adj_relation / out_counts", who);
+    if (M > 0 && (!edst || !erel || !ws || !explored_bits))
+        return fail(-1, "%s: null edst / erel / ws / explored_bits with M=%lld", who, (long long)M);
+    return hip_result(mvin::launch_kg_explore(eptr, edst, erel, (int)n_entity, M, adj_entity, adj_relation, K, seeds, n_seed, hops, ws,
+                                              explored_bits, out_counts, (hipStream_t)stream), who);
+}
+
 static bool ctr_bad_sizes(int64_t n_seg, int64_t seg_len) {     // also: at most 2^40 pairs in all
     return seg_len < 1 || seg_len > (int64_t)0x7FFFFFFF || n_seg < 0 || n_seg > ((int64_t)1 << 40) / seg_len;
 }

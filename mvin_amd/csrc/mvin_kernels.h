@@ -445,6 +445,13 @@ hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t
 bool sample_negatives_supported(int n_item);                  // per-user negatives without replacement (mvin_negatives.hip)
 hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
                                    int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out, int64_t* status, hipStream_t st);
+int64_t kg_explore_ws_bytes(int n_entity, int64_t M);        // exact KG exploration counts (mvin_explore.hip)
+hipError_t launch_kg_field(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int n_entity, int64_t M,
+                           const int32_t* seeds, int64_t n_seed, int hops, void* ws, uint32_t* field_bits, int64_t* out_counts,
+                           hipStream_t st);
+hipError_t launch_kg_explore(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int n_entity, int64_t M,
+                             const int32_t* adj_entity, const int32_t* adj_relation, int K, const int32_t* seeds, int64_t n_seed,
+                             int hops, void* ws, uint32_t* explored_bits, int64_t* out_counts, hipStream_t st);
 size_t order_ws_elems(int64_t B);                             // pairs in key order (mvin_order.hip)
 hipError_t launch_order_by_key(const int64_t* k64, const int32_t* k32, int64_t B, int32_t* ws, int32_t* order, hipStream_t st);
 bool fused_wpp_supported(int D, int K);                       // wave-per-parent kernel over projected tables, dim 64 (mvin_fused_wpp.hip)

@@ -7,7 +7,9 @@ every stage-wise restart, main.py:16).  Here the KG becomes a CSR on the device 
 plumbing), and the two samplers are HIP kernels (mvin_sample_adjacency, mvin_build_ripple_sets)
 whose draws are a pure function of a seed, so adjacency can be re-sampled every epoch.  The training negatives
 (convert_rating, KGCN/preprocess.py:60-70) are drawn the same way by mvin_sample_negatives (sample_negatives,
-NegativeSampler), fresh for every epoch.
+NegativeSampler), fresh for every epoch.  KGExploration counts, exactly and on the device, how much of the KG within the
+model's receptive field the sampled adjacencies have covered (mvin_kg_field / mvin_kg_explore): the number that says whether
+another stage-wise restart, with its fresh adjacency, can show the model anything new.
 """
 import numpy as np
 import torch
@@ -209,3 +211,70 @@ class NegativeSampler(object):
         neg[:, 1] = items
         neg[:, 2] = 0
         return rows
+
+
+# --------------------------------------------------------------------------- KG exploration
+def kg_edge_index(csr):
+    """The DISTINCT edges of a ``build_csr`` KG as (eptr int64 [nE+1], edst int32 [M], erel int32 [M]) on its device: row h =
+    the distinct (tail, relation) pairs listed under h, ascending by (tail, relation).  Duplicate CSR slots of one row count
+    once, as in the reference's ``set`` of (h, t, r) tuples (data_loader_user_set.py:208-239).  Host plumbing (torch unique),
+    like ``build_csr``."""
+    indptr, dst, rel = csr
+    n_entity = indptr.shape[0] - 1
+    dev = indptr.device
+    if dst.numel() == 0:
+        z = torch.zeros(0, dtype=torch.int32, device=dev)
+        return torch.zeros(n_entity + 1, dtype=torch.int64, device=dev), z, z.clone()
+    src = torch.repeat_interleave(torch.arange(n_entity, device=dev), indptr[1:] - indptr[:-1])
+    rows = torch.unique(torch.stack([src, dst.long(), rel.long()], dim=1), dim=0)          # lexicographic, distinct
+    eptr = torch.zeros(n_entity + 1, dtype=torch.int64, device=dev)
+    eptr[1:] = torch.cumsum(torch.bincount(rows[:, 0], minlength=n_entity), 0)
+    return eptr.contiguous(), rows[:, 1].to(torch.int32).contiguous(), rows[:, 2].to(torch.int32).contiguous()
+
+
+class KGExploration(object):
+    """How much of the KG within the model's reach the sampled adjacencies have covered so far (the reference's
+    get_all_user_entity_count -> args.use_neighbor_rate = [all, used, rate], data_loader_user_set.py:208-239, which it leaves
+    commented out and returns [0, 0, 0] for).
+
+    ``seeds``: the items of train_data[:, 1] under any label (the reference's item_pool); repeats are fine.  ``hops``: pass
+    ``config.tree_depth(args)`` = n_mix_hop * h_hop, the depth the model actually reads -- the reference passes ``h_hop``,
+    which is the same thing at n_mix_hop = 1.  The FIELD is every distinct edge (h, t, r) whose head lies in F_i for some
+    i < hops, with F_0 = seeds and F_{i+1} = the tails of the edges leaving F_i (it replaces F_i, as in the reference).
+    ``update`` walks one adjacency the same way from the seeds, but follows a slot (h, adj_entity[h,k], adj_relation[h,k]) only
+    when it is an edge of the KG (the all-zero row of an entity without edges is not), so explored is a subset of the field and
+    ``rate`` never exceeds 1.  Everything is an exact integer count made on the device (ops.kg_field / ops.kg_explore)."""
+
+    def __init__(self, csr, seeds, hops):
+        from . import ops
+        self.index = kg_edge_index(csr)
+        dev = self.index[0].device
+        self.n_entity, self.n_edges, self.hops = self.index[0].shape[0] - 1, self.index[1].numel(), int(hops)
+        s = seeds if torch.is_tensor(seeds) else torch.from_numpy(np.unique(np.asarray(seeds, dtype=np.int64)))
+        s = s.to(dev).reshape(-1)
+        s = s[(s >= 0) & (s < self.n_entity)]       # ids beyond int32 cannot be entities; the kernels ignore the rest themselves
+        self.seeds = s.to(torch.int32).contiguous()
+        self.field_bits, counts = ops.kg_field(self.index, self.seeds, self.hops)
+        counts = counts.cpu().tolist()
+        self.frontier_sizes, self.field_edges = counts[:-1], int(counts[-1])
+        self.explored_bits = torch.zeros_like(self.field_bits)
+        self.explored_total, self.n_updates = 0, 0
+
+    def update(self, adj_entity, adj_relation):
+        """Add one sampled adjacency (device tensors, or numpy arrays as MVIN.set_adjacency takes them).  Returns
+        (explored_now, new, explored_total): edges this adjacency reaches, those no earlier one had reached, all so far."""
+        from . import ops
+        dev = self.index[0].device
+
+        def conv(a):
+            if torch.is_tensor(a):
+                return a.to(dev).to(torch.int32).contiguous()
+            return torch.from_numpy(np.asarray(a).astype(np.int32)).to(dev).contiguous()
+        now, new, total = ops.kg_explore(self.index, conv(adj_entity), conv(adj_relation), self.seeds, self.hops,
+                                         self.explored_bits).cpu().tolist()
+        self.explored_total, self.n_updates = int(total), self.n_updates + 1
+        return int(now), int(new), int(total)
+
+    @property
+    def rate(self):
+        return self.explored_total / self.field_edges if self.field_edges else 0.0

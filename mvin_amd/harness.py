@@ -666,10 +666,13 @@ class EarlyStop(object):
         self.best, self.best_saved = -float("inf"), -float("inf")
         self.counter, self.tolerance, self.early_stop = 0, tolerance, early_stop
         self.save_final_model = save_final_model
+        self.on_best = None          # called as on_best(epoch, score, model) wherever the best-epoch save happens (train's ``on_best``)
 
     def update(self, epoch, score, model):
         if score > self.best_saved:
             self.best_saved = score
+            if self.on_best is not None:
+                self.on_best(epoch, score, model)
             if self.save_final_model and model.path is not None and getattr(model.path, "emb", None):
                 model.save_pretrain_emb_fuc(None, None)
         if epoch + 1 > self.tolerance:
@@ -683,7 +686,7 @@ class EarlyStop(object):
 
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
-          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed"):
+          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -709,6 +712,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     ``round`` = the epoch, seed ``args.neg_seed`` or 1; train_epoch_resampled), never an item the user has with label 1 in
     train, eval or test.  The per-epoch CTR evaluation of the train split still evaluates the fixed ``train_data``, which keeps
     the history comparable.  The draws depend on (seed, epoch) only: every rank of a multi-rank run builds the same epoch.
+    ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
+    one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
     if ctr_impl not in ("host", "batched"):
         raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
@@ -727,6 +732,7 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     feeder = DeviceFeeder(model, uts)
     stop = EarlyStop(getattr(args, "tolerance", 2), getattr(args, "early_stop", 3),
                      getattr(args, "save_final_model", True))
+    stop.on_best = on_best
     if show_topk:
         user_list, train_rec, eval_rec, test_rec, item_set, k_list = topk_settings(train_data, eval_data, test_data,
                                                                                    n_item)
@@ -768,6 +774,179 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         if stop.update(epoch, score, model) and (topk_early_stop or not show_topk):
             break
     return model, history
+
+
+# --------------------------------------------------------------------------- stage-wise training (main.py:24-45)
+def stage_seeds(sampling_seed, stage):
+    """(adjacency seed, ripple-set seed) of stage ``stage``: sampling_seed + 1 + 2 * stage and sampling_seed + 2 + 2 * stage.
+    At stage 0 these are the seeds data_io.load_data(seed=sampling_seed) draws with."""
+    return int(sampling_seed) + 1 + 2 * int(stage), int(sampling_seed) + 2 + 2 * int(stage)
+
+
+class StageTracker(object):
+    """The book-keeping of the reference's stage-wise loop (main.py:24-45 with train_util.py's Train_info_record_sw_emb /
+    Train_info_record_emb_sw_ndcg), without its log files.  Pure Python.
+
+    Within a stage the epoch with the highest evaluation score counts -- eval AUC, or with ``show_topk`` eval recall at
+    k_list[2]; strict ``>``, starting from 0 (update_score) -- and its test metrics are the stage's.  Across stages
+    (train_over) a stage whose score is strictly above the best so far becomes the best and resets the miss counter; any other
+    stage, one that only EQUALS the best included, counts as a miss.  ``end_stage`` says stop once ``patience`` misses have
+    accumulated -- looked at after a restart only, as main.py:42 does, so stage 1 always runs -- or after ``max_stages``
+    restarts.  Feed it ``start_stage()``, ``epoch(rec)`` with every record of harness.train's history, ``end_stage()``."""
+
+    def __init__(self, max_stages=5, patience=3, show_topk=False):
+        self.max_stages, self.patience, self.show_topk = int(max_stages), int(patience), bool(show_topk)
+        self.stage = -1
+        self.misses = 0
+        self.best_stage, self.best_score, self.best_eval, self.best_test = None, 0, None, None
+        self.records = []
+        self._cur = None
+
+    def score_of(self, rec):
+        return rec["eval"]["recall"][2] if self.show_topk else rec["eval"]["auc"]
+
+    def start_stage(self):
+        self.stage += 1
+        self._cur = {"stage": self.stage, "score": 0, "best_epoch": None, "eval": None, "test": None}
+        return self.stage
+
+    def epoch(self, rec):
+        """True when ``rec`` is the stage's best epoch so far."""
+        score = self.score_of(rec)
+        if score > self._cur["score"]:
+            self._cur.update(score=score, best_epoch=rec.get("epoch"), eval=rec["eval"], test=rec["test"])
+            return True
+        return False
+
+    def end_stage(self):
+        """Close the stage; True when the loop stops here."""
+        cur = self._cur
+        if cur["score"] > self.best_score:
+            self.best_stage, self.best_score, self.best_eval, self.best_test = cur["stage"], cur["score"], cur["eval"], cur["test"]
+            self.misses = 0
+        else:
+            self.misses += 1
+        cur["misses"] = self.misses
+        self.records.append(cur)
+        return (self.stage >= 1 and self.misses >= self.patience) or self.stage >= self.max_stages
+
+
+class StagewiseResult(object):
+    """What train_stagewise returns beside the model and the feeder: ``stages`` (one dict per stage run), ``best_stage`` (the
+    index of the stage whose best epoch the model holds), ``best_eval`` / ``best_test`` (that epoch's metrics: the numbers the
+    reference publishes) and ``use_neighbor_rate`` ([field_edges, explored_total, rate] or None)."""
+
+    def __init__(self, stages, tracker, use_neighbor_rate):
+        self.stages, self.tracker = stages, tracker
+        self.best_stage, self.best_eval, self.best_test = tracker.best_stage, tracker.best_eval, tracker.best_test
+        self.use_neighbor_rate = use_neighbor_rate
+
+
+def train_stagewise(args, data, kg, *, max_stages=5, patience=3, show_topk=False, sampling_seed=1, init_seed=0,
+                    resample_first=False, explore=True, on_stage=None, device="cuda", log=None, **train_kw):
+    """Stage-wise training, the procedure of main.py:24-45: train stage 0, then restart up to ``max_stages`` times.  Every
+    restart draws a fresh sampled adjacency and fresh ripple sets on the device, builds a new model, copies the four ``_STWS``
+    embedding tables in from the best epoch of the stage before, and trains again; the loop stops after ``patience`` stages
+    without a better evaluation score (StageTracker).  The published number is the test score of the best stage's best epoch.
+
+    ``data``: harness.train's tuple; ``kg``: the [n, 3] (h, r, t) triples or a data_prep.build_csr triple.  For stage s:
+      * inputs: stage 0 trains on data[7:10] as given unless ``resample_first``; every other stage draws
+        construct_adj(seed = sampling_seed + 1 + 2 s) and get_user_triplet_set(seed = sampling_seed + 2 + 2 s) (``stage_seeds``;
+        at s = 0 that is what data_io.load_data(seed=sampling_seed) draws).  The train / eval / test split stays FIXED: the
+        reference re-splits with an unseeded generator on every restart, which leaks test rows into training;
+      * model: a fresh MVIN(seed = init_seed + s) -- every other parameter and the Adam state start over, as the reference's
+        new graph and global initialiser do -- with, for s > 0, the STWS tables of the PREVIOUS stage's best epoch (not the
+        best stage's: the reference's checkpoint file is overwritten by the first epoch of every stage).  args.SW_stage = s;
+      * training: one harness.train(args, stage_data, model=model, show_topk=..., **train_kw) call; its ``on_best`` hook keeps
+        device clones of all parameters at the stage's best epoch.  The file checkpoint works as before when args.path.emb is set;
+      * exploration (``explore``): a data_prep.KGExploration over the items of the train split and hops = tree_depth(args),
+        updated with every stage's adjacency; the stage record carries field_edges, explored_now, new_edges, explored_total,
+        rate, and args.use_neighbor_rate = [field_edges, explored_total, round(rate, 6)].
+    ``on_stage(stage, model, feeder, record)`` is called before a stage trains; ``log`` receives every epoch record
+    (harness.train) and, after each stage, the stage record without its history.  Returns (model, feeder, result): the model as
+    it was at the best epoch of the best stage, with that stage's adjacency re-installed (redrawn from its seed) and a
+    DeviceFeeder over that stage's ripple sets; ``result``: a StagewiseResult."""
+    import torch
+    from . import data_prep
+    from .config import tree_depth
+    from .model import MVIN
+    n_user, n_item, n_entity, n_relation = data[0], data[1], data[2], data[3]
+    train_data = np.asarray(data[4])
+    K, P, Nm = args.neighbor_sample_size, args.p_hop, args.n_memory
+    if isinstance(kg, (tuple, list)) and len(kg) == 3 and all(torch.is_tensor(t) for t in kg):
+        csr = tuple(kg)
+    else:
+        csr = data_prep.build_csr(kg, n_entity, device=device)
+    hist = data_prep.history_csr(train_data, n_user, device=device)
+    hoist = bool(train_kw.pop("hoist", True))
+
+    def draw(stage):
+        seed_adj, seed_uts = stage_seeds(sampling_seed, stage)
+        return (data_prep.construct_adj(csr, n_entity, K, seed=seed_adj),
+                data_prep.get_user_triplet_set(csr, hist, n_user, P, Nm, seed=seed_uts))
+
+    expl = data_prep.KGExploration(csr, train_data[:, 1], tree_depth(args)) if explore else None
+    tracker = StageTracker(max_stages, patience, show_topk)
+    stages, snaps, prev = [], {}, None
+    while True:
+        s = tracker.start_stage()
+        given = s == 0 and not resample_first
+        if given:
+            adj_e, adj_r, uts = data[7], data[8], data[9]
+        else:
+            (adj_e, adj_r), uts = draw(s)
+        args.SW_stage = s
+        model = MVIN(args, n_user, n_entity, n_relation, adj_e, adj_r, device=device, seed=init_seed + s, hoist=hoist)
+        if prev is not None:
+            model.load_stws(prev)
+        record = {"stage": s, "seed_adj": None if given else stage_seeds(sampling_seed, s)[0],
+                  "seed_uts": None if given else stage_seeds(sampling_seed, s)[1], "init_seed": init_seed + s}
+        if expl is not None:
+            now, new, total = expl.update(model.adj_entity, model.adj_relation)
+            record.update(field_edges=expl.field_edges, explored_now=now, new_edges=new, explored_total=total, rate=expl.rate)
+            args.use_neighbor_rate = [expl.field_edges, total, round(expl.rate, 6)]
+        feeder = DeviceFeeder(model, uts)
+        if on_stage is not None:
+            on_stage(s, model, feeder, record)
+        best = {}
+
+        def keep(epoch, score, m, best=best):
+            best.update(epoch=epoch, score=score, state=m.state())
+
+        stage_data = tuple(data[:7]) + (model.adj_entity, model.adj_relation, feeder.uts) + tuple(data[10:])
+        _, history = train(args, stage_data, show_topk=show_topk, model=model, device=device, log=log, hoist=hoist,
+                           on_best=keep, **train_kw)
+        for rec in history:
+            tracker.epoch(rec)
+        stop = tracker.end_stage()
+        cur = tracker.records[-1]
+        record.update(history=history, best_epoch=cur["best_epoch"], score=cur["score"], eval=cur["eval"], test=cur["test"],
+                      misses=cur["misses"])
+        stages.append(record)
+        prev = best.get("state")
+        snaps[s] = (prev, (model.adj_entity, model.adj_relation, feeder.uts) if given else None)
+        for old in list(snaps):                    # only the best stage's snapshot is needed again
+            if old != s and old != tracker.best_stage:
+                del snaps[old]
+        if log:
+            log({k: v for k, v in record.items() if k != "history"})
+        if stop:
+            break
+    b = tracker.best_stage if tracker.best_stage is not None else s       # no stage ever scored above 0: the last one
+    state, inputs = snaps[b]
+    if b != s:                                     # the last model object carries on, as the best stage's model
+        if inputs is None:
+            (adj_e, adj_r), uts = draw(b)
+        else:
+            adj_e, adj_r, uts = inputs
+        model.set_adjacency(adj_e, adj_r)
+        feeder = DeviceFeeder(model, uts)
+    if state is not None:
+        model.load_state(state)
+    model.trainer = None                           # its moments belong to the last stage's run, not to these parameters
+    model._graphed_trainer = None
+    args.SW_stage = b
+    return model, feeder, StagewiseResult(stages, tracker, getattr(args, "use_neighbor_rate", None) if explore else None)
 
 
 # --------------------------------------------------------------------------- case study (f-4)

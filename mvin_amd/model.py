@@ -401,6 +401,34 @@ class MVIN(object):
                 getattr(self, k).copy_(torch.from_numpy(z[k]).to(self.device))   # casts to the table dtype
         self.invalidate()
 
+    def _state_tensors(self):
+        """Every parameter tensor by name (the STWS tables, the stacked projections, the MLPs, the aggregators' weights)."""
+        p = {k: getattr(self, k) for k in self._STWS + ("user_mlp_matrix", "user_mlp_bias", "_transfer_W", "_transfer_b",
+                                                        "h_emb_item_mlp_matrix", "h_emb_item_mlp_bias")}
+        for n in range(self.n_mix_hop):
+            p[f"enti_transfer_matrix_{n}"] = self.enti_transfer_matrix_list[n]
+            p[f"enti_transfer_bias_{n}"] = self.enti_transfer_bias_list[n]
+        for (i, n), agg in self._agg.items():
+            for nm in ("weights", "bias", "urh_weights", "urh_bias"):
+                p[f"agg_{i}_{n}_{nm}"] = getattr(agg, nm)
+        return p
+
+    def state(self):
+        """Device clones of all parameters, by name: a snapshot ``load_state`` puts back (nothing goes to the host)."""
+        return {k: t.clone() for k, t in self._state_tensors().items()}
+
+    def load_state(self, state, names=None):
+        """Copy a ``state()`` snapshot (or its ``names`` subset) into the parameters IN PLACE -- a Trainer or captured graph
+        that holds their addresses stays valid -- then drop every derived table."""
+        mine = self._state_tensors()
+        for k in (mine if names is None else names):
+            mine[k].copy_(state[k])              # casts to the table dtype
+        self.invalidate()
+
+    def load_stws(self, state):
+        """The four stage-wise tables of a ``state()`` snapshot (restore_pretrain_emb without the file)."""
+        self.load_state(state, self._STWS)
+
     def invalidate(self):
         """Call after changing parameters in place through raw pointers (the optimizer does):
         drops every derived table (relation logits, hoisted entity tables)."""

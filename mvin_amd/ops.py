@@ -505,6 +505,73 @@ def ctr_metrics_from_counts(counts):
     return auc, acc, f1
 
 
+def _kg_index(index, seeds):
+    eptr, edst, erel = index
+    _chk(eptr, torch.int64, "eptr")
+    _chk(edst, I32, "edst")
+    _chk(erel, I32, "erel")
+    _chk(seeds, I32, "seeds")
+    if eptr.dim() != 1 or eptr.numel() < 1 or edst.dim() != 1 or tuple(erel.shape) != tuple(edst.shape) or seeds.dim() != 1:
+        raise ValueError("edge index: expected (eptr int64 [nE+1], edst int32 [M], erel int32 [M]) and seeds int32 [n]")
+    return eptr, edst, erel, eptr.numel() - 1, edst.numel()
+
+
+def _kg_ws(lib, n_entity, M, dev):
+    nws = lib.mvin_kg_explore_ws_bytes(n_entity, M)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_kg_explore_ws_bytes")
+    return torch.empty(((nws + 7) // 8,), dtype=torch.int64, device=dev) if nws > 0 else None
+
+
+def kg_field(index, seeds, hops):
+    """mvin_kg_field: the KG edges within ``hops`` levels of ``seeds`` (int32 ids on the device; repeats and ids out of range
+    are fine).  ``index``: a data_prep.kg_edge_index triple.  Returns ``(field_bits int32 [ceil(M/32)], counts int64 [hops+1])``
+    on the device: bit e of the bitmap (word e // 32, bit e % 32) is edge slot e; counts = |F_1| .. |F_hops|, then the number of
+    field edges.  Enqueues only: no synchronisation, no copy to the host."""
+    lib = _lib.load()
+    eptr, edst, erel, nE, M = _kg_index(index, seeds)
+    dev = eptr.device
+    bits = torch.empty(((M + 31) // 32,), dtype=I32, device=dev)
+    counts = torch.empty((int(hops) + 1 if 1 <= int(hops) <= 8 else 1,), dtype=torch.int64, device=dev)
+    ws = _kg_ws(lib, nE, M, dev) if M else None
+    _lib.check(lib.mvin_kg_field(_p(eptr), _p(edst) if M else None, _p(erel) if M else None, nE, M,
+                                 _p(seeds) if seeds.numel() else None, seeds.numel(), int(hops), _p(ws),
+                                 _p(bits) if M else None, _p(counts), _stream()), "mvin_kg_field")
+    return bits, counts
+
+
+def kg_explore(index, adj_entity, adj_relation, seeds, hops, explored_bits, out=None):
+    """mvin_kg_explore: the KG edges the adjacency ``(adj_entity, adj_relation)`` (int32 [nE, K] on the device) reaches within
+    ``hops`` levels of ``seeds``; a slot that is no edge of ``index`` is ignored and not followed.  ``explored_bits`` (int32
+    [ceil(M/32)], zeros to begin with) is OR-updated in place, so feeding one adjacency after another accumulates.  Returns
+    counts int64 [3] on the device (``out`` if given): edges this adjacency explores, edges newly set, edges set now.
+    Enqueues only."""
+    lib = _lib.load()
+    eptr, edst, erel, nE, M = _kg_index(index, seeds)
+    dev = eptr.device
+    _chk(adj_entity, I32, "adj_entity")
+    _chk(adj_relation, I32, "adj_relation")
+    if adj_entity.dim() != 2 or adj_entity.shape[0] != nE or tuple(adj_relation.shape) != tuple(adj_entity.shape):
+        raise ValueError(f"adj_entity / adj_relation: expected [{nE}, K] both")
+    K = adj_entity.shape[1]
+    _chk(explored_bits, I32, "explored_bits")
+    if tuple(explored_bits.shape) != ((M + 31) // 32,):
+        raise ValueError(f"explored_bits: expected [{(M + 31) // 32}]")
+    if out is None:
+        out = torch.empty((3,), dtype=torch.int64, device=dev)
+    _chk(out, torch.int64, "out")
+    if tuple(out.shape) != (3,):
+        raise ValueError("out: expected [3]")
+    if nE == 0:
+        out.zero_()
+        return out
+    ws = _kg_ws(lib, nE, M, dev) if M else None
+    _lib.check(lib.mvin_kg_explore(_p(eptr), _p(edst) if M else None, _p(erel) if M else None, nE, M, _p(adj_entity),
+                                   _p(adj_relation), K, _p(seeds) if seeds.numel() else None, seeds.numel(), int(hops), _p(ws),
+                                   _p(explored_bits) if M else None, _p(out), _stream()), "mvin_kg_explore")
+    return out
+
+
 RANK_METRICS = ("precision", "recall", "hit_ratio", "mrr", "map", "ndcg", "ndcg_ideal")
 RANK_MISSING = 0x7FC00000    # the bits mvin_rank_positives writes as the value of an entry that no eligible column carries
 
