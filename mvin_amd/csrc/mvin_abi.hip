@@ -39,6 +39,41 @@ size_t geom_sum(int B, int K, int from, int to) {  // B * sum_{e=from..to} K^e
     return s * (size_t)B;
 }
 
+// ---- the per-call entity tables of dim 64 (mvin_entity_tables.hip): one job list, one launch ----
+// ER[r] = R_KGE[r] . E (mvin_project_relations), TW[j] = E . Wmlp[64 j : 64 j + 64] (mvin_key_addressing_flash_prepare) and
+// TA1 | TA2 | T0A | M0 = E . Wstack[i] (mvin_fold_tables): each entry point lists its own, mvin_score_l2_fwd all of them.
+struct EntityTableList {
+    const float* E;
+    int n_entity;
+    hipStream_t st;
+    hipError_t err = hipSuccess;
+    int n = 0;
+    mvin::EntityTableJob jobs[mvin::kEtMaxJobs];
+    void add(const float* W, int w_nk, float* out) {
+        if (n == mvin::kEtMaxJobs) flush();
+        jobs[n++] = mvin::EntityTableJob{W, out, w_nk};
+    }
+    void flush() {
+        if (n > 0 && err == hipSuccess) err = mvin::launch_entity_tables(E, n_entity, jobs, n, st);
+        n = 0;
+    }
+};
+
+// any of the three groups (a null destination: not asked for); dim 64
+int build_entity_tables(const char* who, const float* E, int n_entity, const float* relation_kge, int nR, float* er, const float* user_mlp_W,
+                        int n_o, float* tw, const float* fold_blk, float* fold_tabs, void* stream) {
+    const size_t tab = (size_t)n_entity * 64, DD = (size_t)64 * 64;
+    EntityTableList l{E, n_entity, (hipStream_t)stream};
+    if (er)
+        for (int r = 0; r < nR; ++r) l.add(relation_kge + r * DD, 1, er + r * tab);        // R_KGE[r] is [n][k]: read in place
+    if (tw)
+        for (int j = 0; j < n_o; ++j) l.add(user_mlp_W + j * DD, 0, tw + j * tab);
+    if (fold_tabs)
+        for (int i = 0; i < 4; ++i) l.add(fold_blk + i * DD, 0, fold_tabs + i * tab);      // W1.A0 | W2.A0 | W0.A0 | W0.Wm0
+    l.flush();
+    return hip_result(l.err, who);
+}
+
 }  // namespace
 
 extern "C" {
@@ -608,34 +643,29 @@ int mvin_fold_tables(const float* entity_emb, const int32_t* enc_entity, const i
                                stream);
 }
 
-int mvin_fold_tables_ex(const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, const float* W0,
-                        const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0, const float* a0,
-                        const float* Wmix, const float* bmix, const float* A1, int aggregates, int K, int D, int n_entity, int nR, float* ws,
-                        void* stream) {
-    const char* who = "mvin_fold_tables";
+static int fold_tables_check(const char* who, const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* W0,
+                             const float* W1, const float* W2, const float* A0, const float* Wmix, const float* A1, int aggregates, int K, int D,
+                             int n_entity, int nR, const float* ws) {
     if (!entity_emb || !enc_entity || !enc_relation || !W0 || !W1 || !W2 || !A0 || !Wmix || !A1 || !ws) return fail(-1, "%s: null pointer", who);
     if (!(aggregates ? fold_applies(D, K, n_entity, nR, 1) : fold_gather_applies(D, K, n_entity, nR, 1)))
         return fail(-3, "%s: D = 64 with K in {16, 32, 64} or D = 32 with K in {16, 32}; n_entity <= 2^24, tables < 1 GiB, adjacency < 2 GiB, nR <= 4096 "
                         "(D=%d K=%d n_entity=%d nR=%d)", who, D, K, n_entity, nR);
-    const size_t tab = (size_t)n_entity * D;
-    float* blk = ws + 6 * tab;
+    return 0;
+}
+
+// the parameter block behind the six tables (Wstack, the query terms, the regrouped copies)
+static int fold_tables_block(const char* who, const float* t0, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
+                             const float* b2, const float* A0, const float* a0, const float* Wmix, const float* bmix, const float* A1, int K, int D,
+                             int n_entity, float* ws, void* stream) {
     const float c = t0 ? 1.f / (float)K : 1.f;            // sum of a row's slot weights over K  (aggregators.py:139-152)
-    if (int rc = hip_result(mvin::launch_fold_prepare(W0, b0, W1, b1, W2, b2, A0, a0, Wmix, bmix, A1, c, D, blk, (hipStream_t)stream), who)) return rc;
-    mvin_linear_args l{};
-    l.src[0] = entity_emb;
-    l.nsrc = 1;
-    l.Dsrc = D;
-    l.Dout = D;
-    l.rows = n_entity;
-    l.rows_per_group = 1;
-    l.W = blk;                                // W1.A0 | W2.A0 | W0.A0 | W0.Wm0
-    l.w_zstride = (int64_t)D * D;
-    l.out = ws;                               // TA1 | TA2 | T0A | M0
-    l.ldo = D;
-    l.nz = 4;
-    l.out_zstride = (int64_t)n_entity * D;
-    if (int rc = mvin_linear_fwd(&l, stream)) return rc;
-    if (!aggregates) return 0;                // (the gather form: per-row tables only, every pair walks its own children)
+    return hip_result(mvin::launch_fold_prepare(W0, b0, W1, b1, W2, b2, A0, a0, Wmix, bmix, A1, c, D, ws + (size_t)6 * n_entity * D,
+                                                (hipStream_t)stream), who);
+}
+
+// H0 | G from the four tables
+static int fold_tables_aggregates(const char* who, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, int K, int D,
+                                  int n_entity, int nR, float* ws, void* stream) {
+    const size_t tab = (size_t)n_entity * D;
     mvin::EntityAggArgs f{};
     f.tabS = ws;                              // H0[e] = T0A[e] + sum_k w_k TA1[y_k]
     f.selfS = ws + 2 * tab;
@@ -653,6 +683,36 @@ int mvin_fold_tables_ex(const float* entity_emb, const int32_t* enc_entity, cons
     f.table_bytes = (uint64_t)tab * 4;
     f.adj_bytes = (uint64_t)n_entity * (uint64_t)K * 4;
     return hip_result(mvin::launch_entity_aggregates(f, (hipStream_t)stream), who);
+}
+
+int mvin_fold_tables_ex(const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, const float* W0,
+                        const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0, const float* a0,
+                        const float* Wmix, const float* bmix, const float* A1, int aggregates, int K, int D, int n_entity, int nR, float* ws,
+                        void* stream) {
+    const char* who = "mvin_fold_tables";
+    if (int rc = fold_tables_check(who, entity_emb, enc_entity, enc_relation, W0, W1, W2, A0, Wmix, A1, aggregates, K, D, n_entity, nR, ws)) return rc;
+    if (int rc = fold_tables_block(who, t0, W0, b0, W1, b1, W2, b2, A0, a0, Wmix, bmix, A1, K, D, n_entity, ws, stream)) return rc;
+    float* blk = ws + (size_t)6 * n_entity * D;
+    if (D == 64) {                            // TA1 | TA2 | T0A | M0 = E . Wstack[i]: the table kernel of dim 64
+        if (int rc = build_entity_tables(who, entity_emb, n_entity, nullptr, 0, nullptr, nullptr, 0, nullptr, blk, ws, stream)) return rc;
+    } else {
+        mvin_linear_args l{};
+        l.src[0] = entity_emb;
+        l.nsrc = 1;
+        l.Dsrc = D;
+        l.Dout = D;
+        l.rows = n_entity;
+        l.rows_per_group = 1;
+        l.W = blk;                                // W1.A0 | W2.A0 | W0.A0 | W0.Wm0
+        l.w_zstride = (int64_t)D * D;
+        l.out = ws;                               // TA1 | TA2 | T0A | M0
+        l.ldo = D;
+        l.nz = 4;
+        l.out_zstride = (int64_t)n_entity * D;
+        if (int rc = mvin_linear_fwd(&l, stream)) return rc;
+    }
+    if (!aggregates) return 0;                // (the gather form: per-row tables only, every pair walks its own children)
+    return fold_tables_aggregates(who, enc_entity, enc_relation, t0, K, D, n_entity, nR, ws, stream);
 }
 
 int mvin_score_l2_folded_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, const int64_t* items_i64,
@@ -985,6 +1045,9 @@ int mvin_l2_tail_fwd(const void* entity_emb, const int64_t* items_i64, const int
     return hip_result(mvin::launch_l2_tail(t, D, (hipStream_t)stream), who);
 }
 
+static int flash_prepare_impl(const char* who, const float* entity_emb, const float* relation_kge, const float* w, const float* user_mlp_W,
+                              int n_entity, int nR, int D, int P, float* ws, float* fold_ws, void* stream);
+
 int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
     const char* who = "mvin_score_l2_fwd";
     if (!a) return fail(-1, "%s: null args", who);
@@ -1016,6 +1079,11 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
     l.out_zstride = D;
     int rc = 0;
     bool flash = false;
+    // the folded tail this call will take further down (0: none, 1: over the aggregates H0 | G, 2: every pair gathers its own rows)
+    const bool fold_ok = a->fold_ws && a->enc_entity && a->enc_relation && a->W0 && a->W1 && a->W2 && !a->table_bf16;
+    const int fold_form = !fold_ok ? 0 : a->fold_gather ? (fold_gather_applies(D, a->K, a->n_entity, nR, a->B) ? 2 : 0)
+                                                        : (fold_applies(D, a->K, a->n_entity, nR, a->B) ? 1 : 0);
+    bool fold_built = false;                  // its four tables left the flash form's table launch
     if (grouped) {
         // the batch in user order (device-side counting sort, no host sync), then a user's rows staged once per segment
         int32_t* ws = a->group_ws;
@@ -1029,8 +1097,20 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
             // flash form: per-call tables (R_KGE[r] . E[e], E . Wmlp blocks) from the CURRENT parameters, then ONE barrier-free kernel
             // for the attention reads and the user MLP.  Its scheduling scratch: the counters / offsets / ranks of the counting sort
             // (2 n_user + B words at the head of group_ws), dead once the batch is grouped
-            rc = mvin_key_addressing_flash_prepare(reinterpret_cast<const float*>(a->entity_emb), a->relation_kge, a->h_set_w, a->user_mlp_W,
-                                                   a->n_entity, nR, D, a->P, a->ka_flash, stream);
+            // A step that also takes the folded tail builds ALL its tables in the one launch: the folded form's parameter block
+            // first, then ER | TW | TA1 | TA2 | T0A | M0.  Both workspaces belong to this stream and nothing reads the folded
+            // tables before the aggregates below, so building them ahead of key addressing changes no result
+            if (fold_form) {
+                rc = fold_tables_check("mvin_fold_tables", reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->W0, a->W1,
+                                       a->W2, a->A0, a->Wmix, a->A1, fold_form == 1, a->K, D, a->n_entity, nR, a->fold_ws);
+                if (rc) return rc;
+                rc = fold_tables_block("mvin_fold_tables", a->t0, a->W0, a->b0, a->W1, a->b1, a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1,
+                                       a->K, D, a->n_entity, a->fold_ws, stream);
+                if (rc) return rc;
+                fold_built = true;
+            }
+            rc = flash_prepare_impl("mvin_key_addressing_flash_prepare", reinterpret_cast<const float*>(a->entity_emb), a->relation_kge, a->h_set_w,
+                                    a->user_mlp_W, a->n_entity, nR, D, a->P, a->ka_flash, fold_built ? a->fold_ws : nullptr, stream);
             if (rc) return rc;
             if (mvin_key_addressing_flash_ws_elems(a->B, a->n_user) > (size_t)2 * a->n_user + (size_t)a->B)
                 return fail(-2, "%s: group_ws too small for the flash form's scheduling scratch", who);
@@ -1080,11 +1160,11 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
     if (rc) return rc;
     }
     // the parents of a depth-2 tree are the items themselves: the kernel reads the int64 ids in place (no expand launch)
-    if (a->fold_ws && a->fold_gather && a->enc_entity && a->enc_relation && a->W0 && a->W1 && a->W2 && !a->table_bf16 &&
-        fold_gather_applies(D, a->K, a->n_entity, nR, a->B)) {
+    if (fold_form == 2) {
         // folded tail, every pair gathering its own rows: the four per-row tables (no aggregates), parents in item order, one launch
-        rc = mvin_fold_tables_ex(reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->t0, a->W0, a->b0, a->W1, a->b1,
-                                 a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1, 0, a->K, D, a->n_entity, nR, a->fold_ws, stream);
+        if (!fold_built)
+            rc = mvin_fold_tables_ex(reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->t0, a->W0, a->b0, a->W1, a->b1,
+                                     a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1, 0, a->K, D, a->n_entity, nR, a->fold_ws, stream);
         if (rc) return rc;
         const int32_t* order = nullptr;
         if (a->item_order_ws) {
@@ -1097,10 +1177,13 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
                                                a->user_o, a->A1, a->a1, a->Wmix, a->B, a->K, D, a->n_entity, nR, a->item_emb, a->scores, a->sig,
                                                stream);
     }
-    if (a->fold_ws && !a->fold_gather && a->enc_entity && a->enc_relation && a->W0 && a->W1 && a->W2 && !a->table_bf16 && fold_applies(D, a->K, a->n_entity, nR, a->B)) {
+    if (fold_form == 1) {
         // folded-tail form: four per-entity tables + the aggregates H0 | G from the CURRENT parameters, then two launches per batch
-        rc = mvin_fold_tables(reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->t0, a->W0, a->b0, a->W1, a->b1,
-                              a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1, a->K, D, a->n_entity, nR, a->fold_ws, stream);
+        if (fold_built)
+            rc = fold_tables_aggregates("mvin_fold_tables", a->enc_entity, a->enc_relation, a->t0, a->K, D, a->n_entity, nR, a->fold_ws, stream);
+        else
+            rc = mvin_fold_tables(reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->t0, a->W0, a->b0, a->W1, a->b1,
+                                  a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1, a->K, D, a->n_entity, nR, a->fold_ws, stream);
         if (rc) return rc;
         return mvin_score_l2_folded_fwd(a->fold_ws, a->enc_entity, a->enc_relation, a->items, nullptr, a->t0, a->t1, a->user_o, a->user_o, a->A1,
                                         a->a1, a->Wmix, a->B, a->K, D, a->n_entity, nR, a->nagg0, a->nagg1, a->item_emb, a->scores, a->sig,
@@ -1285,22 +1368,26 @@ int mvin_project_relations(const float* entity_emb, const float* relation_kge, c
     if (!entity_emb || !relation_kge || !ws) return fail(-1, "%s: null pointer", who);
     if (n_entity <= 0 || nR <= 0 || (D != 16 && D != 32 && D != 64 && D != 128)) return fail(-2, "%s: n_entity=%d nR=%d D=%d", who, n_entity, nR, D);
     float* hs = ws + (size_t)nR * n_entity * D;
-    float* RT = hs + (size_t)((n_entity + 3) & ~3);
-    if (int rc = hip_result(mvin::launch_transpose_blocks(relation_kge, nR, D, RT, (hipStream_t)stream), who)) return rc;
-    mvin_linear_args l{};                     // ER[r][e][n] = sum_k E[e][k] R_KGE[r][n][k]  (= R_KGE[r] . E[e], model.py:214-220)
-    l.src[0] = entity_emb;
-    l.nsrc = 1;
-    l.Dsrc = D;
-    l.Dout = D;
-    l.rows = n_entity;
-    l.rows_per_group = 1;
-    l.W = RT;
-    l.w_zstride = (int64_t)D * D;
-    l.out = ws;
-    l.ldo = D;
-    l.nz = nR;
-    l.out_zstride = (int64_t)n_entity * D;
-    if (int rc = mvin_linear_fwd(&l, stream)) return rc;
+    if (D == 64) {                            // the table kernel of dim 64 reads R_KGE[r] in place (the scratch behind hs stays unused)
+        if (int rc = build_entity_tables(who, entity_emb, n_entity, relation_kge, nR, ws, nullptr, 0, nullptr, nullptr, nullptr, stream)) return rc;
+    } else {
+        float* RT = hs + (size_t)((n_entity + 3) & ~3);
+        if (int rc = hip_result(mvin::launch_transpose_blocks(relation_kge, nR, D, RT, (hipStream_t)stream), who)) return rc;
+        mvin_linear_args l{};                     // ER[r][e][n] = sum_k E[e][k] R_KGE[r][n][k]  (= R_KGE[r] . E[e], model.py:214-220)
+        l.src[0] = entity_emb;
+        l.nsrc = 1;
+        l.Dsrc = D;
+        l.Dout = D;
+        l.rows = n_entity;
+        l.rows_per_group = 1;
+        l.W = RT;
+        l.w_zstride = (int64_t)D * D;
+        l.out = ws;
+        l.ldo = D;
+        l.nz = nR;
+        l.out_zstride = (int64_t)n_entity * D;
+        if (int rc = mvin_linear_fwd(&l, stream)) return rc;
+    }
     if (w) return hip_result(mvin::launch_entity_dot(entity_emb, w, n_entity, D, hs, (hipStream_t)stream), who);
     return 0;
 }
@@ -1328,26 +1415,25 @@ size_t mvin_key_addressing_flash_tables_elems(int n_entity, int nR, int D, int P
     return mvin_project_relations_elems(n_entity, nR, D) + (size_t)(P + (has_set ? 1 : 0)) * n_entity * D;
 }
 
-int mvin_key_addressing_flash_prepare(const float* entity_emb, const float* relation_kge, const float* w, const float* user_mlp_W,
-                                      int n_entity, int nR, int D, int P, float* ws, void* stream) {
-    const char* who = "mvin_key_addressing_flash_prepare";
+// ER | hs | TW of the flash form -- and, for a step that also takes the folded tail (fold_ws given: its parameter block already
+// written on this stream), the four folded tables in the same launch
+static int flash_prepare_impl(const char* who, const float* entity_emb, const float* relation_kge, const float* w, const float* user_mlp_W,
+                              int n_entity, int nR, int D, int P, float* ws, float* fold_ws, void* stream) {
     if (!entity_emb || !relation_kge || !user_mlp_W || !ws) return fail(-1, "%s: null pointer", who);
     if (n_entity <= 0 || nR <= 0 || D != 64 || P < 1 || P > 8) return fail(-2, "%s: n_entity=%d nR=%d D=%d P=%d", who, n_entity, nR, D, P);
-    if (int rc = mvin_project_relations(entity_emb, relation_kge, w, n_entity, nR, D, ws, stream)) return rc;
-    mvin_linear_args l{};                     // TW[j][e][n] = sum_k E[e][k] Wmlp[D j + k][n]  (model.py:232-236 taken per entity)
-    l.src[0] = entity_emb;
-    l.nsrc = 1;
-    l.Dsrc = D;
-    l.Dout = D;
-    l.rows = n_entity;
-    l.rows_per_group = 1;
-    l.W = user_mlp_W;
-    l.w_zstride = (int64_t)D * D;
-    l.out = ws + mvin_project_relations_elems(n_entity, nR, D);
-    l.ldo = D;
-    l.nz = P + (w ? 1 : 0);
-    l.out_zstride = (int64_t)n_entity * D;
-    return mvin_linear_fwd(&l, stream);
+    // ER[r][e][n] = sum_k E[e][k] R_KGE[r][n][k], TW[j][e][n] = sum_k E[e][k] Wmlp[D j + k][n]  (model.py:214-220, :232-236 taken per entity)
+    if (int rc = build_entity_tables(who, entity_emb, n_entity, relation_kge, nR, ws, user_mlp_W, P + (w ? 1 : 0),
+                                     ws + mvin_project_relations_elems(n_entity, nR, D), fold_ws ? fold_ws + (size_t)6 * n_entity * D : nullptr,
+                                     fold_ws, stream))
+        return rc;
+    if (w) return hip_result(mvin::launch_entity_dot(entity_emb, w, n_entity, D, ws + (size_t)nR * n_entity * D, (hipStream_t)stream), who);
+    return 0;
+}
+
+int mvin_key_addressing_flash_prepare(const float* entity_emb, const float* relation_kge, const float* w, const float* user_mlp_W,
+                                      int n_entity, int nR, int D, int P, float* ws, void* stream) {
+    return flash_prepare_impl("mvin_key_addressing_flash_prepare", entity_emb, relation_kge, w, user_mlp_W, n_entity, nR, D, P, ws, nullptr,
+                              stream);
 }
 
 int mvin_key_addressing_flash_fwd(const float* entity_emb, const float* ws, const int32_t* user_records, const int32_t* seg_user,

@@ -612,7 +612,8 @@ hipError_t launch_entity_aggregates(const EntityAggArgs& a, hipStream_t st) {
 }
 
 // ---- folded-tail form: the per-call parameter block behind its four tables and two aggregates (mvin_fold_tables) ----
-//   Wstack [4][D][D] = W1.A0 | W2.A0 | W0.A0 | W0.Wm0     (the B operands of the table build: TA1 | TA2 | T0A | M0)
+//   Wstack [4][D][D] = W1.A0 | W2.A0 | W0.A0 | W0.Wm0     (the weights of the table build: TA1 | TA2 | T0A | M0 -- dim 64: entity_tables_kernel,
+//                                                           mvin_entity_tables.hip; dim 32: linear_mfma_kernel)
 //   Wv [D][D] = (W1 + c W2).A0      bv [D] = (b1 + c b2).A0 + a0        (the children's query term, as in the projected-tables form)
 //   Wq [D][D] = (W0 + c W1).A0      bq [D] = (b0 + c b1).A0 + a0        ((ev0 + nagg0) A0 + a0 = H0[x] + q Wq + bq)
 //   bm [D]    = bmix + b0.Wm0                                           (ev0 Wm0 = M0[x] + q W0.Wm0 + b0.Wm0)

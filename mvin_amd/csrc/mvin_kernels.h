@@ -481,6 +481,14 @@ hipError_t split_read_trace(long long* host_dst, size_t n);
 bool fused_packed_supported(int D, int K);
 bool key_addr_static_er_ok(int P, int Nm, int nR, int n_entity, bool has_set);
 hipError_t launch_transpose_blocks(const float* R, int nR, int D, float* RT, hipStream_t st);
+// the per-call entity tables of dim 64 in one launch (mvin_entity_tables.hip): out[e][:] = E[e][:] . W for every job
+constexpr int kEtMaxJobs = 24;     // jobs per launch
+struct EntityTableJob {
+    const float* W;            // [64, 64]
+    float* out;                // [nE, 64]
+    int w_nk;                  // 0: W stored [k][n] (a weight matrix rows multiply); 1: stored [n][k] (R_KGE[r], read in place)
+};
+hipError_t launch_entity_tables(const float* E, int n_entity, const EntityTableJob* jobs, int njobs, hipStream_t st);
 hipError_t launch_entity_dot(const float* E, const float* w, int n, int D, float* out, hipStream_t st);
 hipError_t launch_prj_prepare(const float* W1, const float* W2, const float* b1, const float* b2, const float* A0, const float* a0,
                               float c, int D, float* blk, hipStream_t st);     // packed-tile variant over the duplicate-slot encoding (mvin_fused_packed.hip)

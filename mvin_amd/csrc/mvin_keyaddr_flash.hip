@@ -6,7 +6,8 @@
 //     o[pair, :]      = sum_m softmax_m(logits)[pair, m] E[t_m]                        (:223-230)
 // followed by user_o = concat(o_list) . user_mlp_matrix + bias (:232-236).  U_m depends on the (relation, entity) pair alone and
 // the MLP is linear in the tail rows, so both move from the gathered rows to per-call TABLES built from the current parameters
-// (mvin_key_addressing_flash_prepare; an exact re-association like the projected tables of the two deepest levels):
+// (mvin_key_addressing_flash_prepare: entity_tables_kernel, mvin_entity_tables.hip, all tables in one launch; an exact re-association like the
+// projected tables of the two deepest levels):
 //     ER[r][e] = R_KGE[r] . E[e]  ([nR, nE, D]);   TW_j[e] = E[e] . Wmlp[64 j : 64 j + 64, :]  (one [nE, D] table per block j of o_list)
 //     user_o[pair] = bias + sum_m p_hset[m] TW_0[h_m] + sum_hop sum_m p_hop[pair, m] TW_{1 + hop}[t_m]
 // The static per-user records (mvin_build_user_records) hold the row numbers.  Both products of a hop run TRANSPOSED on
