@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Stage timeline of one wave of the flash key-addressing kernel (development aid): MVIN_KAF_TRACE=1, GPU box."""
+"""Stage timeline of one wave of the flash key-addressing kernel (development aid): MVIN_KAF_TRACE=1, GPU box.
+MVIN_KAF_PREFETCH=0 traces the per-slot order; the default form has fetched a slot's descriptors, record ids, pair indices and item
+ids during the slot before, so its "descriptors" stamp only marks the wait for the record ids' DMA (requested most of a slot ago)."""
 import ctypes as C, os, sys
 import numpy as np, torch
 os.environ["MVIN_KAF_TRACE"] = "1"
@@ -27,7 +29,9 @@ assert _lib.load().mvin_debug_read_trace(buf.ctypes.data_as(C.c_void_p), buf.siz
 f = buf.reshape(64, 16).astype(np.float64)
 ok = (f[:, 0] > 0) & (f[:, 15] > f[:, 0])
 f = f[ok][2:50]
-names = {0: "slot top", 1: "descriptors", 2: "h-set done, U requested", 3: "hop0 top", 4: "hop0 logits", 5: "hop0 softmax", 6: "hop0 reads",
+pf = os.environ.get("MVIN_KAF_PREFETCH", "1") != "0"
+print("form: %s" % ("slot k + 1 fetched during slot k" if pf else "per-slot order (MVIN_KAF_PREFETCH=0)"))
+names = {0: "slot top", 1: "record ids in LDS" if pf else "descriptors", 2: "h-set done, U requested", 3: "hop0 top", 4: "hop0 logits", 5: "hop0 softmax", 6: "hop0 reads",
          7: "hop1 top", 8: "hop1 logits", 9: "hop1 softmax", 10: "hop1 reads", 15: "slot end"}
 print("slots traced: %d ; cycles per slot %.0f (s_memtime ticks; 100 MHz counter x ~21-24 = shader cycles if constant-rate)" % (len(f), np.mean(f[:, 15] - f[:, 0])))
 names.update({11: "h-set rows requested", 12: "hs values requested", 13: "h-set softmax", 14: "h-set reads + U requested"})
