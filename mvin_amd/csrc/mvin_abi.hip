@@ -86,6 +86,7 @@ int mvin_debug_read_trace(long long* host_dst, size_t n) {
     static const bool pk = getenv("MVIN_PACK_TRACE") != nullptr;
     if (getenv("MVIN_SMALL_TRACE")) return (int)mvin::small_read_trace(host_dst, n);
     if (getenv("MVIN_KAF_TRACE")) return (int)mvin::kaf_read_trace(host_dst, n);
+    if (getenv("MVIN_FOLD_TRACE")) return (int)mvin::fold_read_trace(host_dst, n);
     if (pk) return (int)mvin::pack_read_prof(host_dst, n);
     if (ka && getenv("MVIN_KA_TRACE")[0] == '2') return (int)mvin::kas_read_trace(host_dst, n);     // the kernel over static records
     return (int)(ka ? mvin::ka_read_trace(host_dst, n) : mvin::split_read_trace(host_dst, n));

@@ -18,6 +18,7 @@ constexpr int kAggPad = 4;            // list entries of padding behind a group'
 constexpr unsigned kAggOob = 0xFFFFFFF0u;       // a byte offset beyond every buffer: the load returns zeros, no memory access
 constexpr unsigned kAggPadRow = 0xFFFFFE00u;    // ... that stays beyond them (and below 2^32) with a lane's column offset added
 constexpr int agg_list_words(int K) { return 4 * 2 * (K + kAggPad); }      // per wave: 4 groups x (K + padding) x (offset, weight)
+constexpr size_t fused_agg_lds_words(int nR, int K) { return (size_t)((nR + 3) & ~3) + (size_t)kAggWaves * (16 * kAggUvLd + agg_list_words(K)); }
 size_t fused_agg_lds_bytes(int nR, int K);
 
 __device__ __forceinline__ int agg_xor16_imax(int v) {
@@ -53,15 +54,16 @@ __device__ __forceinline__ bool agg_logit_table(const float* t, int nR, float* s
 }
 
 // weights of a row's slots (SPL per lane of the 2^LG-lane group that holds it; cr = relation | multiplicity << 16 | ...): multiplicity x
-// softmax over the distinct slots, over K (aggregators.py:118-146); a padding slot (multiplicity 0) weighs 0
+// softmax over the distinct slots, over K (aggregators.py:118-146); a padding slot (multiplicity 0) weighs 0.  rmax = nR - 1: a relation id
+// beyond the table (a corrupt adjacency word) reads its last entry, not whatever lies behind it in LDS
 template <int SPL, bool FAST, int LG = 4>
-__device__ __forceinline__ void agg_row_weights(const unsigned (&cr)[SPL], bool att, const float* sT, float invK, float (&wk)[SPL]) {
+__device__ __forceinline__ void agg_row_weights(const unsigned (&cr)[SPL], bool att, const float* sT, unsigned rmax, float invK, float (&wk)[SPL]) {
     float lg[SPL];
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < SPL; ++i) {
         const float mu = (float)((cr[i] >> 16) & 0xFFu);
-        const float l = att ? sT[cr[i] & 0xFFFFu] : (FAST ? 1.f : 0.f);
+        const float l = att ? sT[min(cr[i] & 0xFFFFu, rmax)] : (FAST ? 1.f : 0.f);
         if constexpr (FAST) {
             wk[i] = mu * l;                              // l = exp(logit - global max)
         } else {

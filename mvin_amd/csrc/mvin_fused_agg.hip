@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kAggWaves * 64) void entity_aggregates_kernel(Entit
             const float4 sg = agg_row4(selfG, so);
             const float4 ss = agg_row4(selfS, so);       // (no selfS: an empty buffer, zeros)
             float wk[SPL];
-            agg_row_weights<SPL, FAST>(cr, att, sT, invK, wk);
+            agg_row_weights<SPL, FAST>(cr, att, sT, (unsigned)(a.nR - 1), invK, wk);
             int cc = (int)(cr[0] >> 24);                 // the row's distinct-slot count (in every slot word)
             cc = valid ? (cc < 1 ? 1 : (cc > K ? K : cc)) : 0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the previous step's reads of the lists are done)
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(kAggWaves * 64, K == 64 ? 3 : 4) void gather_attn_l
                 const float4 u1 = *reinterpret_cast<const float4*>(sUV + j * kAggUvLd + 4 * c);
                 const float4 vv = *reinterpret_cast<const float4*>(sUV + j * kAggUvLd + D + 4 * c);
                 float wk[SPL];
-                agg_row_weights<SPL, FAST>(cr, att1, sT, invK, wk);
+                agg_row_weights<SPL, FAST>(cr, att1, sT, (unsigned)(a.nR - 1), invK, wk);
                 int cc = (int)(cr[0] >> 24);
                 cc = pvalid ? (cc < 1 ? 1 : (cc > K ? K : cc)) : 0;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the previous step's reads of the lists are done)
@@ -307,20 +307,41 @@ __global__ __launch_bounds__(kAggWaves * 64, K == 64 ? 3 : 4) void gather_attn_l
 //        t = q Wq + bq ; v = q Wv + bv ; m = q Wqm                                        (matrix cores; t, v -> LDS, m stays in registers)
 //        out0 = relu(H0[x] + t) ; Z2 = out0 + sum_c (p1_c / K) relu(G[x_c] + v)           (four pairs at a time, one per 16-lane group)
 //        out2 = relu(Z2 A1 + a1) ; item = M0[x] + m + out0 Wm1 + out2 Wm2 + bm ; score = <user_o, item>       (matrix cores)
-template <int K>
+// PIPE (the default; MVIN_FOLD_PIPE=0 gives the per-batch order from the same binary) takes a batch's dependent global round trips off
+// its critical path -- none of their addresses depends on a computed value, only on the item ids and the adjacency words:
+//   * behind the last weight request of the second chain, as its operands and ring buffers die: this batch's M0 rows, the NEXT batch's
+//     item ids and query rows (carried into the next batch as its x0 / qb), this batch's user_o rows (the query rows are not kept
+//     through the batch for the default wiring user_o = q: the gather phase has those 16 registers in flight as G rows);
+//   * behind the last weight request of the first chain (t's and v's accumulators are dead there): the adjacency + H0 rows of the
+//     first TWO quads; quad it + 1's (it > 0) go out in FRONT of quad it's G rows -- loads return in order, so the next quad's lists
+//     wait for them alone;
+//   * a quad's first 12 G rows are in flight at once (three half-round buffers, refilled as they are summed; a fourth does not fit the
+//     168 registers of three waves per SIMD), and with the (offset, weight) lists double-buffered (MODE 2: where the LDS allows it)
+//     quad it + 1's softmax weights and lists are computed UNDER quad it's row requests instead of between two quads' requests.
+// The arithmetic and the order of every sum are those of the per-batch order: a pair's G rows enter a01 / a23 in list order, in the same
+// rounds of four (up to the batch's longest list rounded up to eight) -- results are bit-identical.
+// TRACE: wave 0 of workgroup 0 stamps its first batches' stage boundaries (MVIN_FOLD_TRACE=1, scripts/trace_fold.py); the "... there"
+// stamps drain the wave's loads first, so the build's shares are meaningful, not its run time.
+constexpr int kFoldTraceBatches = 16, kFoldTraceSlots = 20;
+__device__ long long g_fold_trace[kFoldTraceBatches * kFoldTraceSlots];
+
+template <int K, int MODE, bool TRACE = false>      // MODE 0: the per-batch order; 1: PIPE; 2: PIPE with two list buffers per wave
 __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(FoldArgs a) {
     constexpr int D = 64, SPL = K / 16;
+    constexpr bool PIPE = MODE > 0, db = MODE == 2;
+    constexpr int lb = db ? agg_list_words(K) : 0;       // words from a list buffer to the other one (by quad parity)
     static_assert(K == 16 || K == 32 || K == 64, "K");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int nRp = (a.nR + 3) & ~3;
     float* sT = smem;                                    // [nRp] relation logits of aggregator (1,.), or exp(logit - max) of them
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform: the batch loop's counters are scalars)
     const int g = lane >> 4, c = lane & 15;
-    float* sUV = sT + nRp + wave * (16 * kAggUvLd + agg_list_words(K));      // this wave's [16 pairs][t -> out0 (64) | v -> Z2 (64) | pad]
+    float* sUV = sT + nRp + wave * (16 * kAggUvLd + agg_list_words(K) + lb);      // this wave's [16 pairs][t -> out0 (64) | v -> Z2 (64) | pad]
     unsigned* sLo = reinterpret_cast<unsigned*>(sUV + 16 * kAggUvLd) + g * (K + kAggPad);
     float* sLw = reinterpret_cast<float*>(reinterpret_cast<unsigned*>(sUV + 16 * kAggUvLd) + 4 * (K + kAggPad)) + g * (K + kAggPad);
     const bool att1 = a.t1 != nullptr;
     const float invK = 1.f / (float)K;
+    const unsigned rmax = (unsigned)(a.nR - 1);
     const bool fast = agg_logit_table(a.t1, a.nR, sT, tid, lane);
     __syncthreads();                                     // the only workgroup barrier
 
@@ -331,36 +352,70 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
     const __amdgpu_buffer_rsrc_t adjR = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.adj_r), 0, (int)a.adj_bytes, 0x00020000);
     const unsigned c16 = (unsigned)c * 16u;
     if (c < kAggPad) {                                   // the padding behind a group's K slots: beyond the buffer, no weight
-        sLo[K + c] = kAggPadRow;
-        sLw[K + c] = 0.f;
+        sLo[K + c] = kAggPadRow, sLo[lb + K + c] = kAggPadRow;
+        sLw[K + c] = 0.f, sLw[lb + K + c] = 0.f;
     }
 
     const int64_t nbatch = (a.B + 15) >> 4;
     const int64_t nwaves = (int64_t)gridDim.x * kAggWaves;
+    int traced = 0;                                      // (TRACE) batches this wave has stamped
+    auto stamp = [&](int slot, bool drain) {
+        if constexpr (TRACE) {
+            if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (blockIdx.x == 0 && tid == 0 && traced < kFoldTraceBatches) g_fold_trace[traced * kFoldTraceSlots + slot] = __builtin_readcyclecounter();
+        }
+    };
     auto run = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
+        // (the lane's coordinates and list pointers once more, from the lane counter: nothing of the prologue's stays alive across the
+        //  two instances of this body)
+        const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), g = lane >> 4, c = lane & 15;
+        unsigned* sLo = reinterpret_cast<unsigned*>(sUV + 16 * kAggUvLd) + g * (K + kAggPad);
+        float* sLw = reinterpret_cast<float*>(reinterpret_cast<unsigned*>(sUV + 16 * kAggUvLd) + 4 * (K + kAggPad)) + g * (K + kAggPad);
+        const unsigned c16 = (unsigned)c * 16u;
+        // (PIPE) the raw item ids and the query rows of the wave's next batch, requested a batch ahead.  A wave's last batch asks for the
+        // launch's last batch again: the loads are clamped, not branched around.
+        unsigned xn = 0;
+        f32x4 qn[4];
+        auto fetch_batch = [&](int64_t b) {
+            const int64_t prn = min((min(b, nbatch - 1) << 4) + c, a.B - 1);
+            xn = (unsigned)a.items[prn * a.pid_stride];
+            const char* qrow = reinterpret_cast<const char*>(a.q) + (size_t)((unsigned)prn * (unsigned)(D * 4) + (unsigned)g * 16u);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) qn[nt] = *reinterpret_cast<const f32x4*>(qrow + 64 * nt);
+        };
+        if constexpr (PIPE) fetch_batch((int64_t)blockIdx.x * kAggWaves + wave);
         for (int64_t batch = (int64_t)blockIdx.x * kAggWaves + wave; batch < nbatch; batch += nwaves) {
             const int64_t p_base = batch << 4;
+            stamp(0, false);
             // pair c of the batch in every group: its row of the launch and its entity id
             const int64_t pr = min(p_base + c, a.B - 1);
             const bool cvalid = p_base + c < a.B;
-            unsigned x0u = (unsigned)a.items[pr * a.pid_stride];
+            unsigned x0u;
+            if constexpr (PIPE) x0u = xn;
+            else x0u = (unsigned)a.items[pr * a.pid_stride];
             x0u = x0u < a.max_id ? x0u : a.max_id;
             const int x0c = (int)x0u;
             unsigned woff = ((unsigned)(4 * g) * (unsigned)D + (unsigned)c * 4u) * 4u;      // Wperm[4 g][c][0]
             unsigned boff = (unsigned)g * 16u;
             unsigned roff = (unsigned)pr * (unsigned)(D * 4) + (unsigned)g * 16u;     // floats [4 g, 4 g + 4) of row `pr` of a [B][64] array
             asm volatile("" : "+v"(woff), "+v"(boff));   // (loop-invariant loads are not to be hoisted out of the batch loop)
-            // THREE products as one chain of 12 k tiles, acc_j[ntp] += sum over k of W_j[k][16 ntp + c] b_j[nt] (64 MFMAs each).  A from the
+            // NP products as one chain of 4 NP k tiles, acc_j[ntp] += sum over k of W_j[k][16 ntp + c] b_j[nt] (64 MFMAs each).  A from the
             // regrouped copies of the blocks (Wperm: the four column tiles' values of a lane's k in one 16-byte load -- buffer loads, so that
             // they are known not to alias the LDS traffic around them) through a ring of three register buffers: the loads of k tiles
-            // s + 1 and s + 2 are in flight under the MFMAs of tile s, across the products' boundaries.  `between(j)` runs behind product j.
-            auto chain3 = [&](const float* W0p, const float* W1p, const float* W2p, const f32x4 (&b0)[4], const f32x4 (&b1)[4], const f32x4 (&b2)[4],
-                              f32x4 (&acc0)[4], f32x4 (&acc1)[4], f32x4 (&acc2)[4], auto&& between) {
-                asm volatile("" : "+s"(W0p), "+s"(W1p), "+s"(W2p));      // (descriptors and k-tile bases are not to live in SGPRs across the batch loop: 1 100 spills)
-                const __amdgpu_buffer_rsrc_t wr[3] = {__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W0p), 0, D * D * 4, 0x00020000),
-                                                      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1p), 0, D * D * 4, 0x00020000),
-                                                      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2p), 0, D * D * 4, 0x00020000)};
+            // s + 1 and s + 2 are in flight under the MFMAs of tile s, across the products' boundaries.  `wsel(j)` is product j's block,
+            // `bsel(j)` / `asel(j)` its B operand and accumulators; `between(j)` runs behind product j; `late(i)`, i = 0, 1, 2, in front of
+            // the MFMAs of the last three tiles, behind the chain's LAST weight request: loads issued there are not in the way of any later
+            // wait for a weight tile -- the counter is in order --, have the remaining tiles' MFMAs to arrive under, and from i = 1 on a
+            // ring buffer is free for them.
+            auto chain = [&](auto np_, auto&& wsel, auto&& bsel, auto&& asel, auto&& between, auto&& late) {
+                constexpr int NP = decltype(np_)::value, T = 4 * NP;
+                __amdgpu_buffer_rsrc_t wr[NP];
+                static_for<NP>([&](auto j_) {
+                    const float* Wp = wsel(j_);
+                    asm volatile("" : "+s"(Wp));         // (descriptors and k-tile bases are not to live in SGPRs across the batch loop: 1 100 spills)
+                    wr[decltype(j_)::value] = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wp), 0, D * D * 4, 0x00020000);
+                });
                 f32x4 ring[3][4];
                 auto load = [&](auto s_) {
                     constexpr int s = decltype(s_)::value, j = s / 4, nt = s % 4;
@@ -372,12 +427,13 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                 };
                 load(std::integral_constant<int, 0>{});
                 load(std::integral_constant<int, 1>{});
-                static_for<12>([&](auto s_) {
+                static_for<T>([&](auto s_) {
                     constexpr int s = decltype(s_)::value, j = s / 4, nt = s % 4;
-                    if constexpr (s + 2 < 12) load(std::integral_constant<int, s + 2>{});
+                    if constexpr (s + 2 < T) load(std::integral_constant<int, s + 2>{});
+                    if constexpr (s >= T - 3) late(std::integral_constant<int, s - (T - 3)>{});
                     __builtin_amdgcn_sched_barrier(0);
-                    const f32x4 (&b)[4] = j == 0 ? b0 : j == 1 ? b1 : b2;
-                    f32x4 (&acc)[4] = j == 0 ? acc0 : j == 1 ? acc1 : acc2;
+                    const f32x4 (&b)[4] = bsel(std::integral_constant<int, j>{});
+                    f32x4 (&acc)[4] = asel(std::integral_constant<int, j>{});
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -393,30 +449,6 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                 for (int ntp = 0; ntp < 4; ++ntp)
                     acc[ntp] = bias ? *reinterpret_cast<const f32x4*>(bias + 64 * ntp + (size_t)boff) : f32x4{0.f, 0.f, 0.f, 0.f};
             };
-            f32x4 qm[4], qb[4];
-            {
-                const char* qbase = reinterpret_cast<const char*>(a.q);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) qb[nt] = *reinterpret_cast<const f32x4*>(qbase + 64 * nt + (size_t)roff);
-                f32x4 at[4], av[4];
-                bias4(a.bq, at);
-                bias4(a.bv, av);
-                bias4(a.bm, qm);
-                if (!(a.dbg & 4))
-                    chain3(a.Wq, a.Wv, a.Wqm, qb, qb, qb, at, av, qm, [&](auto j_) {
-                        constexpr int j = decltype(j_)::value;
-                        if constexpr (j < 2) {           // t, then v: into the pairs' LDS rows
-                            const f32x4 (&acc)[4] = j == 0 ? at : av;
-#pragma unroll
-                            for (int ntp = 0; ntp < 4; ++ntp) *reinterpret_cast<f32x4*>(sUV + c * kAggUvLd + j * D + 16 * ntp + 4 * g) = acc[ntp];
-                        }
-                    });
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-            const int nquad = (a.dbg & 8) ? 0 : (int)((min((int64_t)16, a.B - p_base) + 3) >> 2);
             struct Quad {
                 unsigned ce[SPL], cr[SPL];
                 float4 s0;
@@ -428,96 +460,252 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                 qd.s0 = agg_row4(aggS, x0 * (unsigned)(D * 4) + c16);
                 return qd;
             };
-            Quad nx = quad_load(0);
-            for (int it = 0; it < nquad; ++it) {
-                const int j = 4 * it + g;                // this group's pair of the batch
-                const bool pvalid = p_base + j < a.B;
-                const Quad qd = nx;
-                if (it + 1 < nquad) nx = quad_load(it + 1);
-                const unsigned (&ce)[SPL] = qd.ce;
-                const unsigned (&cr)[SPL] = qd.cr;
-                float* rowT = sUV + j * kAggUvLd + 4 * c;
-                const float4 tt = *reinterpret_cast<const float4*>(rowT);
-                const float4 vv = *reinterpret_cast<const float4*>(rowT + D);
+            Quad q0, q1;                                 // (PIPE) the adjacency + H0 rows of the current quad and the one behind it
+            auto late1 = [&](auto s_) {                  // (every id of the batch is a real one -- `pr` is clamped --, so neither load needs a test)
+                if constexpr (PIPE && decltype(s_)::value == 0) q0 = quad_load(0), q1 = quad_load(1);
+            };
+            f32x4 qm[4], qb[4];
+            {
+                const char* qbase = reinterpret_cast<const char*>(a.q);
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    if constexpr (PIPE) qb[nt] = qn[nt];
+                    else qb[nt] = *reinterpret_cast<const f32x4*>(qbase + 64 * nt + (size_t)roff);
+                }
+                stamp(1, true);
+                f32x4 at[4], av[4];
+                bias4(a.bq, at);
+                bias4(a.bv, av);
+                auto store_tv = [&](auto j_) {           // t, then v: into the pairs' LDS rows
+                    constexpr int j = decltype(j_)::value;
+                    if constexpr (j < 2) {
+                        const f32x4 (&acc)[4] = j == 0 ? at : av;
+#pragma unroll
+                        for (int ntp = 0; ntp < 4; ++ntp) *reinterpret_cast<f32x4*>(sUV + c * kAggUvLd + j * D + 16 * ntp + 4 * g) = acc[ntp];
+                    }
+                };
+                bias4(a.bm, qm);
+                if (a.dbg & 4) late1(std::integral_constant<int, 0>{});
+                else
+                    chain(std::integral_constant<int, 3>{}, [&](auto j_) { return decltype(j_)::value == 0 ? a.Wq : decltype(j_)::value == 1 ? a.Wv : a.Wqm; },
+                          [&](auto) -> const f32x4 (&)[4] { return qb; },
+                          [&](auto j_) -> f32x4 (&)[4] {
+                              if constexpr (decltype(j_)::value == 0) return at;
+                              else if constexpr (decltype(j_)::value == 1) return av;
+                              else return qm;
+                          }, store_tv, late1);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            stamp(2, false);
+
+            const int nquad = (a.dbg & 8) ? 0 : (int)((min((int64_t)16, a.B - p_base) + 3) >> 2);
+            auto issue = [&](const unsigned* lo, int k, float4 (&r)[4]) {
+                const uint4 o4 = *reinterpret_cast<const uint4*>(lo + k);
+                r[0] = agg_row4(aggG, o4.x + c16), r[1] = agg_row4(aggG, o4.y + c16);
+                r[2] = agg_row4(aggG, o4.z + c16), r[3] = agg_row4(aggG, o4.w + c16);
+            };
+            auto sum4 = [&](const float4 (&r)[4], const float4& w, const f32x2 v01, const f32x2 v23, f32x2& a01, f32x2& a23) {
+                const float ws_[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const f32x2 o01 = f32x2{r[t].x, r[t].y} + v01, o23 = f32x2{r[t].z, r[t].w} + v23;
+                    const f32x2 w2 = {ws_[t], ws_[t]};
+                    a01 = __builtin_elementwise_fma(w2, f32x2{fmaxf(o01[0], 0.f), fmaxf(o01[1], 0.f)}, a01);
+                    a23 = __builtin_elementwise_fma(w2, f32x2{fmaxf(o23[0], 0.f), fmaxf(o23[1], 0.f)}, a23);
+                }
+            };
+            // a quad's (offset, weight) lists from its adjacency row, into the list buffer `ob` words behind the first; returns the
+            // batch's longest list of this quad (wave-uniform)
+            auto lists = [&](const Quad& qd, int it, int ob) -> int {
+                const bool pvalid = p_base + 4 * it + g < a.B;
                 float wk[SPL];
-                agg_row_weights<SPL, FAST>(cr, att1, sT, invK, wk);
-                int cc = (int)(cr[0] >> 24);
+                agg_row_weights<SPL, FAST>(qd.cr, att1, sT, rmax, invK, wk);
+                int cc = (int)(qd.cr[0] >> 24);
                 cc = pvalid ? (cc < 1 ? 1 : (cc > K ? K : cc)) : 0;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the previous step's reads of the lists are done)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the reads of this buffer's previous lists are done)
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int i = 0; i < SPL; ++i) {
-                    sLo[SPL * c + i] = ((cr[i] >> 16) & 0xFFu) ? (ce[i] & 0xFFFFFFu) * (unsigned)(D * 4) : kAggPadRow;
-                    sLw[SPL * c + i] = wk[i];
+                    sLo[ob + SPL * c + i] = ((qd.cr[i] >> 16) & 0xFFu) ? (qd.ce[i] & 0xFFFFFFu) * (unsigned)(D * 4) : kAggPadRow;
+                    sLw[ob + SPL * c + i] = wk[i];
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const int kmax = (a.dbg & 1) ? 0 : __builtin_amdgcn_readfirstlane(agg_xor32_imax(agg_xor16_imax(cc)));
-                const f32x2 v01 = {vv.x, vv.y}, v23 = {vv.z, vv.w};
-                f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-                float4 ra[4], rb[4];
-                float4 wa, wb;
-                auto issue = [&](int k, float4 (&r)[4], float4& w) {
-                    const uint4 o4 = *reinterpret_cast<const uint4*>(sLo + k);
-                    w = *reinterpret_cast<const float4*>(sLw + k);
-                    r[0] = agg_row4(aggG, o4.x + c16), r[1] = agg_row4(aggG, o4.y + c16);
-                    r[2] = agg_row4(aggG, o4.z + c16), r[3] = agg_row4(aggG, o4.w + c16);
-                };
-                auto sum4 = [&](const float4 (&r)[4], const float4& w) {
-                    const float ws_[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const f32x2 o01 = f32x2{r[t].x, r[t].y} + v01, o23 = f32x2{r[t].z, r[t].w} + v23;
-                        const f32x2 w2 = {ws_[t], ws_[t]};
-                        a01 = __builtin_elementwise_fma(w2, f32x2{fmaxf(o01[0], 0.f), fmaxf(o01[1], 0.f)}, a01);
-                        a23 = __builtin_elementwise_fma(w2, f32x2{fmaxf(o23[0], 0.f), fmaxf(o23[1], 0.f)}, a23);
+                return (a.dbg & 1) ? 0 : __builtin_amdgcn_readfirstlane(agg_xor32_imax(agg_xor16_imax(cc)));
+            };
+            if constexpr (PIPE) {
+                int kmax = lists(q0, 0, 0);
+                for (int it = 0; it < nquad; ++it) {
+                    stamp(3 + 3 * it, false);
+                    const int cur = (it & 1) ? lb : 0;
+                    float* rowT = sUV + (4 * it + g) * kAggUvLd + 4 * c;
+                    const float4 vv = *reinterpret_cast<const float4*>(rowT + D);
+                    const f32x2 v01 = {vv.x, vv.y}, v23 = {vv.z, vv.w};
+                    f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
+                    // the rounds of four children that are summed: list entries below the longest list rounded up to eight, as in the
+                    // per-batch order; the first three rounds are in flight at once
+                    const int kr = (kmax + 7) & ~7;
+                    float4 r0[4], r1[4], r2[4];
+                    auto wts = [&](int k) { return *reinterpret_cast<const float4*>(sLw + cur + k); };      // (read where they are used: 16 registers less)
+                    // the next quad's adjacency + H0 rows IN FRONT of this quad's G rows: loads return in order, so the lists below wait
+                    // for these alone (quad 1's came with quad 0's)
+                    const float4 s0 = q0.s0;
+                    if (it > 0 && it + 1 < nquad) q1 = quad_load(it + 1);
+                    issue(sLo + cur, 0, r0);
+                    issue(sLo + cur, 4, r1);
+                    if (kr > 8) issue(sLo + cur, 8, r2);
+                    stamp(4 + 3 * it, true);
+                    __builtin_amdgcn_sched_barrier(0);
+                    int kmax_n = 0;
+                    if (db && it + 1 < nquad) kmax_n = lists(q1, it + 1, lb - cur);      // under the row requests
+                    __builtin_amdgcn_sched_barrier(0);
+                    for (int k0 = 0; k0 < kr; k0 += 24) {      // rounds k0 .. k0 + 20 through the three buffers; kr is a multiple of 8
+                        sum4(r0, wts(k0), v01, v23, a01, a23);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (k0 + 12 < kr) issue(sLo + cur, k0 + 12, r0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        sum4(r1, wts(k0 + 4), v01, v23, a01, a23);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (k0 + 8 < kr) {
+                            if (k0 + 16 < kr) issue(sLo + cur, k0 + 16, r1);
+                            __builtin_amdgcn_sched_barrier(0);
+                            sum4(r2, wts(k0 + 8), v01, v23, a01, a23);
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (k0 + 16 < kr) issue(sLo + cur, k0 + 20, r2);
+                            __builtin_amdgcn_sched_barrier(0);
+                            sum4(r0, wts(k0 + 12), v01, v23, a01, a23);
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (k0 + 16 < kr) {
+                                if (k0 + 24 < kr) issue(sLo + cur, k0 + 24, r0);
+                                __builtin_amdgcn_sched_barrier(0);
+                                sum4(r1, wts(k0 + 16), v01, v23, a01, a23);
+                                __builtin_amdgcn_sched_barrier(0);
+                                if (k0 + 24 < kr) issue(sLo + cur, k0 + 28, r1);
+                                __builtin_amdgcn_sched_barrier(0);
+                                sum4(r2, wts(k0 + 20), v01, v23, a01, a23);
+                                __builtin_amdgcn_sched_barrier(0);
+                                if (k0 + 32 < kr) issue(sLo + cur, k0 + 32, r2);
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
                     }
-                };
-                issue(0, ra, wa);
-                for (int k0 = 0; k0 < kmax; k0 += 8) {
-                    issue(k0 + 4, rb, wb);
-                    __builtin_amdgcn_sched_barrier(0);
-                    sum4(ra, wa);
-                    __builtin_amdgcn_sched_barrier(0);
-                    issue(k0 + 8, ra, wa);
-                    __builtin_amdgcn_sched_barrier(0);
-                    sum4(rb, wb);
-                    __builtin_amdgcn_sched_barrier(0);
+                    // out0 = relu(H0[x] + t) ; Z2 = out0 + nagg1: this pair's two rows of the block, in place of t and v
+                    const float4 tt = *reinterpret_cast<const float4*>(rowT);
+                    const float4 o0 = make_float4(fmaxf(s0.x + tt.x, 0.f), fmaxf(s0.y + tt.y, 0.f), fmaxf(s0.z + tt.z, 0.f), fmaxf(s0.w + tt.w, 0.f));
+                    *reinterpret_cast<float4*>(rowT) = o0;
+                    *reinterpret_cast<float4*>(rowT + D) = make_float4(a01[0] + o0.x, a01[1] + o0.y, a23[0] + o0.z, a23[1] + o0.w);
+                    if (!db && it + 1 < nquad) kmax_n = lists(q1, it + 1, 0);            // (one list buffer: behind this quad's last read of it)
+                    kmax = kmax_n;
+                    q0 = q1;
+                    stamp(5 + 3 * it, false);
                 }
-                // out0 = relu(H0[x] + t) ; Z2 = out0 + nagg1: this pair's two rows of the block, in place of t and v
-                const float4 o0 = make_float4(fmaxf(qd.s0.x + tt.x, 0.f), fmaxf(qd.s0.y + tt.y, 0.f), fmaxf(qd.s0.z + tt.z, 0.f),
-                                              fmaxf(qd.s0.w + tt.w, 0.f));
-                *reinterpret_cast<float4*>(rowT) = o0;
-                *reinterpret_cast<float4*>(rowT + D) = make_float4(a01[0] + o0.x, a01[1] + o0.y, a23[0] + o0.z, a23[1] + o0.w);
+            } else {
+                Quad nx = quad_load(0);
+                for (int it = 0; it < nquad; ++it) {
+                    stamp(3 + 3 * it, false);
+                    const Quad qd = nx;
+                    if (it + 1 < nquad) nx = quad_load(it + 1);
+                    float* rowT = sUV + (4 * it + g) * kAggUvLd + 4 * c;
+                    const float4 tt = *reinterpret_cast<const float4*>(rowT);
+                    const float4 vv = *reinterpret_cast<const float4*>(rowT + D);
+                    const int kmax = lists(qd, it, 0);
+                    const f32x2 v01 = {vv.x, vv.y}, v23 = {vv.z, vv.w};
+                    f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
+                    float4 ra[4], rb[4];
+                    float4 wa, wb;
+                    auto wts = [&](int k) { return *reinterpret_cast<const float4*>(sLw + k); };
+                    // (half rounds of four children, one in flight while the other is summed; both are issued unconditionally: slots
+                    //  behind a pair's distinct count -- and the four list entries behind the K-th -- point beyond the buffer)
+                    issue(sLo, 0, ra), wa = wts(0);
+                    if constexpr (TRACE) {
+                        issue(sLo, 4, rb), wb = wts(4);
+                        stamp(4 + 3 * it, true);
+                    }
+                    for (int k0 = 0; k0 < kmax; k0 += 8) {
+                        if (!TRACE || k0 > 0) issue(sLo, k0 + 4, rb), wb = wts(k0 + 4);
+                        __builtin_amdgcn_sched_barrier(0);
+                        sum4(ra, wa, v01, v23, a01, a23);
+                        __builtin_amdgcn_sched_barrier(0);
+                        issue(sLo, k0 + 8, ra), wa = wts(k0 + 8);
+                        __builtin_amdgcn_sched_barrier(0);
+                        sum4(rb, wb, v01, v23, a01, a23);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    // out0 = relu(H0[x] + t) ; Z2 = out0 + nagg1: this pair's two rows of the block, in place of t and v
+                    const float4 o0 = make_float4(fmaxf(qd.s0.x + tt.x, 0.f), fmaxf(qd.s0.y + tt.y, 0.f), fmaxf(qd.s0.z + tt.z, 0.f),
+                                                  fmaxf(qd.s0.w + tt.w, 0.f));
+                    *reinterpret_cast<float4*>(rowT) = o0;
+                    *reinterpret_cast<float4*>(rowT + D) = make_float4(a01[0] + o0.x, a01[1] + o0.y, a23[0] + o0.z, a23[1] + o0.w);
+                    stamp(5 + 3 * it, false);
+                }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             // ---- out2 = relu(Z2 A1 + a1) ; item = M0[x] + m + out0 Wm1 + out2 Wm2 (+ bm, in m) ; score ----
             {
-                f32x4 zb[4], ob[4], o2[4];
+                f32x4 zb[4], ob[4], o2[4], m0r[4], uor[4];
+                auto m0_load = [&]() {
+#pragma unroll
+                    for (int ntp = 0; ntp < 4; ++ntp)
+                        m0r[ntp] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.M0) + (size_t)x0u * (D * 4) + 64 * ntp + (size_t)boff);
+                };
+                auto uo_load = [&]() {
+#pragma unroll
+                    for (int ntp = 0; ntp < 4; ++ntp)
+                        uor[ntp] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.user_o) + 64 * ntp + (size_t)roff);
+                };
+                // behind the chain's last weight request: this batch's M0 rows, a tile later (a ring buffer is free by then) the wave's next
+                // batch, another tile later this batch's user_o rows -- also where user_o IS the query: a copy kept since the batch's top
+                // would hold 16 registers through the gather phase, which has them in flight as G rows instead
+                auto late2 = [&](auto s_) {
+                    if constexpr (PIPE && decltype(s_)::value == 0) m0_load();
+                    if constexpr (PIPE && decltype(s_)::value == 1) fetch_batch(batch + nwaves);
+                    if constexpr (PIPE && decltype(s_)::value == 2) uo_load();
+                };
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) zb[nt] = *reinterpret_cast<const f32x4*>(sUV + c * kAggUvLd + D + 16 * nt + 4 * g);
                 bias4(a.a1, o2);
-                // Z2 A1 -> out2 (its accumulators, through the ReLU, are the third product's B operand); out0 Wm1 and out2 Wm2 into the item row
-                if (!(a.dbg & 2))
-                    chain3(a.A1, a.Wm1, a.Wm2, zb, ob, o2, o2, qm, qm, [&](auto j_) {
-                        if constexpr (decltype(j_)::value == 0) {
+                auto relu_o2 = [&]() {
 #pragma unroll
-                            for (int nt = 0; nt < 4; ++nt) {
-                                o2[nt] = f32x4{fmaxf(o2[nt][0], 0.f), fmaxf(o2[nt][1], 0.f), fmaxf(o2[nt][2], 0.f), fmaxf(o2[nt][3], 0.f)};
-                                ob[nt] = *reinterpret_cast<const f32x4*>(sUV + c * kAggUvLd + 16 * nt + 4 * g);      // out0: the second product's B operand
-                            }
-                        }
-                    });
-                const bool uo_is_q = a.user_o == a.q;     // (default wiring: the query IS user_o -- its rows are in registers since the batch's top)
+                    for (int nt = 0; nt < 4; ++nt) o2[nt] = f32x4{fmaxf(o2[nt][0], 0.f), fmaxf(o2[nt][1], 0.f), fmaxf(o2[nt][2], 0.f), fmaxf(o2[nt][3], 0.f)};
+                };
+                auto read_ob = [&]() {                   // out0: the B operand of out0 Wm1
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) ob[nt] = *reinterpret_cast<const f32x4*>(sUV + c * kAggUvLd + 16 * nt + 4 * g);
+                };
+                // Z2 A1 -> out2 (its accumulators, through the ReLU, are the third product's B operand); out0 Wm1 and out2 Wm2 into the item row
+                if (a.dbg & 2) late2(std::integral_constant<int, 0>{}), late2(std::integral_constant<int, 1>{}), late2(std::integral_constant<int, 2>{});
+                else
+                    chain(std::integral_constant<int, 3>{}, [&](auto j_) { constexpr int j = decltype(j_)::value; return j == 0 ? a.A1 : j == 1 ? a.Wm1 : a.Wm2; },
+                          [&](auto j_) -> const f32x4 (&)[4] {
+                              constexpr int j = decltype(j_)::value;
+                              if constexpr (j == 0) return zb;
+                              else if constexpr (j == 1) return ob;
+                              else return o2;
+                          },
+                          [&](auto j_) -> f32x4 (&)[4] { if constexpr (decltype(j_)::value == 0) return o2; else return qm; },
+                          [&](auto j_) {
+                              if constexpr (decltype(j_)::value == 0) relu_o2(), read_ob();
+                          }, late2);
+                stamp(15, false);
+                if constexpr (!PIPE) m0_load();
+                stamp(16, true);
+                // (per-batch order, default wiring: the query IS user_o -- its rows are in registers since the batch's top)
+                if constexpr (!PIPE) {
+                    if (a.user_o != a.q) uo_load();
+                    else
+#pragma unroll
+                        for (int ntp = 0; ntp < 4; ++ntp) uor[ntp] = qb[ntp];
+                }
                 float part = 0.f;
 #pragma unroll
                 for (int ntp = 0; ntp < 4; ++ntp) {
-                    const f32x4 m0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.M0) + (size_t)x0u * (D * 4) + 64 * ntp + (size_t)boff);
-                    const f32x4 uo = uo_is_q ? qb[ntp] : *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.user_o) + 64 * ntp + (size_t)roff);
-                    const f32x4 it4 = qm[ntp] + m0;
+                    const f32x4 uo = uor[ntp];
+                    const f32x4 it4 = qm[ntp] + m0r[ntp];
                     if (a.item_emb && cvalid) *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(a.item_emb) + 64 * ntp + (size_t)roff) = it4;
                     part += it4[0] * uo[0] + it4[1] * uo[1] + it4[2] * uo[2] + it4[3] * uo[3];
                 }
@@ -526,31 +714,80 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                     a.scores[pr] = part;
                     if (a.sig) a.sig[pr] = 1.f / (1.f + expf(-part));
                 }
+                stamp(17, false);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the next batch's block waits for this batch's reads
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if constexpr (TRACE) ++traced;
         }
     };
     if (fast) run(std::true_type{});
     else run(std::false_type{});
 }
 
+hipError_t fold_read_trace(long long* host_dst, size_t n) {
+    const size_t have = sizeof(g_fold_trace) / sizeof(long long);
+    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_fold_trace), (n < have ? n : have) * sizeof(long long));
+}
+
+// The switches are read once per process: MVIN_FOLD_PIPE=0 the per-batch order, MVIN_FOLD_GRID=n at most n workgroups (tests: a wave
+// walks several batches at a tiny B), MVIN_FOLD_TRACE=1 the stamped build, MVIN_FOLD_WGS=n workgroups per CU (measurement).
 template <int K>
 static hipError_t launch_fold_k(const FoldArgs& a, hipStream_t st) {
-    const size_t lds = fused_agg_lds_bytes(a.nR, K);
-    static thread_local int per_cu = 0;
-    if (per_cu == 0) {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(score_l2_folded_kernel<K>), kAggWaves * 64, lds) != hipSuccess || v < 1)
-            v = 4;
-        per_cu = v > 8 ? 8 : v;
-        if (const char* e = getenv("MVIN_FOLD_WGS")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;      // (measurement: workgroups per CU)
+    static const bool pipe = !(getenv("MVIN_FOLD_PIPE") && atoi(getenv("MVIN_FOLD_PIPE")) == 0);
+    static const bool trace = getenv("MVIN_FOLD_TRACE") != nullptr;
+    static const int grid_cap = getenv("MVIN_FOLD_GRID") ? atoi(getenv("MVIN_FOLD_GRID")) : 0;
+    static const int wgs = getenv("MVIN_FOLD_WGS") ? atoi(getenv("MVIN_FOLD_WGS")) : 0;
+    using Kern = void (*)(FoldArgs);
+    constexpr size_t kLdsNoOptIn = 48 * 1024;            // dynamic LDS above it needs a function attribute
+    constexpr bool kTwoLists = fused_agg_lds_words(0, K) * sizeof(float) + (size_t)kAggWaves * agg_list_words(K) * sizeof(float) <= kLdsNoOptIn;
+    auto kernel_of = [&](int mode) -> Kern {
+        if (trace) {
+            if constexpr (kTwoLists) {
+                if (mode == 2) return score_l2_folded_kernel<K, 2, true>;
+            }
+            return mode ? (Kern)score_l2_folded_kernel<K, 1, true> : (Kern)score_l2_folded_kernel<K, 0, true>;
+        }
+        if constexpr (kTwoLists) {
+            if (mode == 2) return score_l2_folded_kernel<K, 2, false>;
+        }
+        return mode ? (Kern)score_l2_folded_kernel<K, 1, false> : (Kern)score_l2_folded_kernel<K, 0, false>;
+    };
+    // the form, its LDS and its workgroups per CU, per (device, relation count): the second list buffer is taken where it keeps the
+    // launch under the LDS size that needs no opt-in and costs no workgroup per CU
+    struct Plan {
+        int dev, nR, per_cu;
+        size_t lds;
+        Kern kern;
+    };
+    static thread_local Plan plan{-1, -1, 0, 0, nullptr};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
+    if (plan.dev != dev || plan.nR != a.nR) {
+        auto occupancy = [&](Kern k, size_t lds) {
+            int v = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(k), kAggWaves * 64, lds) != hipSuccess || v < 1) v = 0;
+            return v > 8 ? 8 : v;
+        };
+        const size_t lds1 = fused_agg_lds_bytes(a.nR, K), lds2 = lds1 + (size_t)kAggWaves * agg_list_words(K) * sizeof(float);
+        const int mode1 = pipe ? 1 : 0;
+        const int occ1 = occupancy(kernel_of(mode1), lds1);
+        const int occ2 = pipe && kTwoLists && lds2 <= kLdsNoOptIn ? occupancy(kernel_of(2), lds2) : 0;
+        const bool two = occ2 > 0 && occ2 >= occ1;
+        plan.kern = kernel_of(two ? 2 : mode1);
+        plan.lds = two ? lds2 : lds1;
+        plan.per_cu = two ? occ2 : occ1 > 0 ? occ1 : 4;
+        if (wgs > 0) plan.per_cu = wgs;
+        plan.dev = dev, plan.nR = a.nR;
+        if (getenv("MVIN_FOLD_REPORT"))
+            fprintf(stderr, "score_l2_folded_kernel<%d>: mode %d, LDS %zu bytes per workgroup, %d workgroups per CU\n", K, two ? 2 : mode1, plan.lds, plan.per_cu);
     }
     const int64_t nbatch = (a.B + 15) >> 4;
     const int64_t want = (nbatch + kAggWaves - 1) / kAggWaves;
-    const int64_t cap = 256 * (int64_t)per_cu;           // persistent grid
-    score_l2_folded_kernel<K><<<(int)(want < cap ? want : cap), kAggWaves * 64, lds, st>>>(a);
+    int64_t cap = 256 * (int64_t)plan.per_cu;            // persistent grid
+    if (grid_cap > 0 && grid_cap < cap) cap = grid_cap;
+    plan.kern<<<(int)(want < cap ? want : cap), kAggWaves * 64, plan.lds, st>>>(a);
     return hipGetLastError();
 }
 
@@ -580,9 +817,7 @@ bool fused_fold_supported(int D, int K) { return fused_agg_supported(D, K) || (D
 size_t fused_fold_d32_lds_bytes(int nR, int K);
 size_t fused_fold_lds_bytes(int D, int nR, int K) { return D == 32 ? fused_fold_d32_lds_bytes(nR, K) : fused_agg_lds_bytes(nR, K); }
 
-size_t fused_agg_lds_bytes(int nR, int K) {
-    return ((size_t)((nR + 3) & ~3) + (size_t)kAggWaves * (16 * kAggUvLd + agg_list_words(K))) * sizeof(float);
-}
+size_t fused_agg_lds_bytes(int nR, int K) { return fused_agg_lds_words(nR, K) * sizeof(float); }
 
 // the projected-tables form over the ENCODED adjacency with every buffer addressable by 32-bit byte offsets, aggregates given
 bool fused_agg_applies(const FusedL2Args& a, int D) {

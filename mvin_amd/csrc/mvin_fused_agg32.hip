@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kAggWaves * 64) void entity_aggregates_d32_kernel(E
             const float4 sg = agg_row4(selfG, so);
             const float4 ss = agg_row4(selfS, so);       // (no selfS: an empty buffer, zeros)
             float wk[SPL];
-            agg_row_weights<SPL, FAST, 3>(cr, att, sT, invK, wk);
+            agg_row_weights<SPL, FAST, 3>(cr, att, sT, (unsigned)(a.nR - 1), invK, wk);
             int cc = (int)(cr[0] >> 24);                 // the row's distinct-slot count (in every slot word)
             cc = valid ? (cc < 1 ? 1 : (cc > K ? K : cc)) : 0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the previous step's reads of the lists are done)
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_d32_kernel(
                 const float4 tt = *reinterpret_cast<const float4*>(rowT);
                 const float4 vv = *reinterpret_cast<const float4*>(rowT + D);
                 float wk[SPL];
-                agg_row_weights<SPL, FAST, 3>(cr, att1, sT, invK, wk);
+                agg_row_weights<SPL, FAST, 3>(cr, att1, sT, (unsigned)(a.nR - 1), invK, wk);
                 int cc = (int)(cr[0] >> 24);
                 cc = pvalid ? (cc < 1 ? 1 : (cc > K ? K : cc)) : 0;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the previous step's reads of the lists are done)

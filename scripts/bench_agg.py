@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """The per-entity aggregates form of the two deepest levels on the C3 bench batch (Zipf items): table build + aggregates + launch against
-the wave-per-parent kernel over the projected tables.  Development aid, GPU box."""
+the wave-per-parent kernel over the projected tables.  Development aid, GPU box.
+
+    python scripts/bench_agg.py [pairs [fan-out]]      (524 288 pairs, fan-out 32; the wave-per-parent kernel is skipped where it has no instance)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvin_amd import ops, synth
-D, K = 64, 32
+D = 64
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 524288
+K = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 case = synth.dataset_case("last-fm_50core", K=K, B=B, seed=0, zipf=True, uniform_adj=False)
 dev = torch.device("cuda:0")
 g = torch.Generator(device=dev); g.manual_seed(0)
@@ -41,12 +44,17 @@ us, _ = timed(lambda: ops.project_tables(E, W[0], W[1], b[0], b[1], W[2], b[2], 
 print(f"project_tables:                   {us:8.1f} us")
 us, _ = timed(lambda: ops.entity_aggregates(ws, enc_e, enc_r, t0, K, D, nR, nE, out=agg))
 print(f"entity_aggregates:                {us:8.1f} us")
-us, ref = timed(lambda: ops.gather_attn_l2_prj(ws, enc_e, enc_r, items, t0, t1, q, B, 1, K, D, nR, nE, order=order))
-print(f"wave-per-parent, item order:      {us:8.1f} us")
+try:
+    us, ref = timed(lambda: ops.gather_attn_l2_prj(ws, enc_e, enc_r, items, t0, t1, q, B, 1, K, D, nR, nE, order=order))
+    print(f"wave-per-parent, item order:      {us:8.1f} us")
+except Exception as e:      # (no instance at this fan-out)
+    ref = None
+    print(f"wave-per-parent, item order:      skipped ({type(e).__name__})")
+diff = lambda a: "" if ref is None else f"   max |diff| {float((a[0] - ref[0]).abs().max()):.2e} {float((a[1] - ref[1]).abs().max()):.2e}"      # noqa: E731
 us, a = timed(lambda: ops.gather_attn_l2_agg(ws, agg, enc_e, enc_r, items, t0, t1, q, B, 1, K, D, nR, nE))
-print(f"aggregates form, as given:        {us:8.1f} us   max |diff| {float((a[0] - ref[0]).abs().max()):.2e} {float((a[1] - ref[1]).abs().max()):.2e}")
+print(f"aggregates form, as given:        {us:8.1f} us{diff(a)}")
 us, a = timed(lambda: ops.gather_attn_l2_agg(ws, agg, enc_e, enc_r, items, t0, t1, q, B, 1, K, D, nR, nE, order=order))
-print(f"aggregates form, item order:      {us:8.1f} us   max |diff| {float((a[0] - ref[0]).abs().max()):.2e} {float((a[1] - ref[1]).abs().max()):.2e}")
+print(f"aggregates form, item order:      {us:8.1f} us{diff(a)}")
 
 # ---- folded-tail form against aggregates + tail kernel (everything above key addressing) ----
 W0 = (torch.rand((D, D), device=dev, generator=g) - 0.5) / 8
