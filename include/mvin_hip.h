@@ -206,8 +206,9 @@ MVIN_API int mvin_order_by_key(const int64_t* keys_i64, const int32_t* keys_i32,
 /* The same launch with its parents taken in the order `order` (int32 [B], a permutation of the launch's parents; NULL = as given):
  * slot i works on parent order[i] -- its id, its query row, its rows of nagg0 / nagg1 -- so the results do not depend on it.
  * Pairs that share an item gather the same rows; next to each other (mvin_order_by_key over the item ids) their loads are cache
- * hits instead of trips past the L2.  Taken by the wave-per-parent kernel only: encoded adjacency, D = 64, K <= 32,
- * parents_per_pair = 1 (-3 otherwise). */
+ * hits instead of trips past the L2.  Needs projected tables over an encoded adjacency and parents_per_pair = 1 (-3 otherwise);
+ * honoured by the wave-per-parent kernel (D = 64, K <= 32, its LDS and offset limits) and ignored where the launch takes another
+ * kernel, as in mvin_score_l2_fwd. */
 MVIN_API int mvin_gather_attn_l2_prj_ordered_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, int adjacency_encoded,
                                 const void* parent_ids, int parent_ids_i64, const int32_t* order, const float* t0, const float* t1,
                                 const float* q, int B, int parents_per_pair, int K, int D, int n_entity, int nR, float* nagg0,

@@ -286,10 +286,11 @@ static int gather_attn_l2_impl(const void* table, const int32_t* adj_entity, con
         return hip_result(mvin::launch_gather_attn_l2_agg(f, (hipStream_t)stream), "mvin_gather_attn_l2_agg_fwd");
     }
     if (order) {
-        f.order = order;
-        if (!(prj && encoded && parents_per_pair == 1 && mvin::fused_wpp_applies(f, D)))
-            return fail(-3, "%s: a parent order is taken by the wave-per-parent kernel only (projected tables, encoded adjacency, D = 64, K <= 32, "
-                            "one parent per pair)", who);
+        if (!(prj && encoded && parents_per_pair == 1))
+            return fail(-3, "%s: a parent order goes with projected tables, an encoded adjacency and one parent per pair", who);
+        // only the wave-per-parent kernel takes it; where that kernel does not apply the order is not passed on, as in mvin_score_l2_fwd
+        // (results do not depend on it)
+        if (mvin::fused_wpp_applies(f, D)) f.order = order;
     }
     while ((4 << l) < K) ++l;
     f.lpn_log2 = l;

@@ -33,7 +33,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import ops
+from . import l2_plan, ops
 from .aggregators import SumAggregator_urh_matrix
 from .params import aggregator_keys, init_params
 
@@ -100,6 +100,7 @@ class MVIN(object):
             raise ValueError("hoist must be False, True or 'step'")
         self.hoist = hoist
         self.dedup = None            # None: MVIN_L2_ENC / auto; True / False: force the encoded / the plain adjacency
+        self._l2_static, self._l2_memo = None, {}             # see _l2_shape_caps, _l2_plan
         self._hoisted = None
         self._table_token = None     # see _hoist_key
         self._parse_args(args, adj_entity, adj_relation)
@@ -154,11 +155,6 @@ class MVIN(object):
         if getattr(self, "_built", False):
             self.prepare()           # the encoding of the NEW adjacency, eagerly (never inside a later forward / capture)
 
-    # a sampled adjacency repeats slots whenever deg < K (data_loader_user_set.py:383-384); the packed-tile fused kernel
-    # walks the distinct slots only.  It pays when rows repeat: below this mean fraction of distinct slots per row it is
-    # taken ("auto"); MVIN_L2_ENC=0 / 1 (or MVIN.dedup = False / True) force the plain / the encoded path.
-    ENC_AUTO_MAX_DISTINCT_FRACTION = 0.75
-
     def encoded_adjacency(self):
         """(enc_entity, enc_relation, cnt, mean distinct fraction) of the current adjacency (mvin_encode_adjacency),
         built once per set_adjacency; None when the shape has no packed-tile kernel."""
@@ -167,42 +163,103 @@ class MVIN(object):
                 # two launches, an allocation and a host sync (.item()): none of that belongs in a captured graph
                 raise RuntimeError("the duplicate-slot encoding of the adjacency is not built yet: call model.prepare() "
                                    "(or run one eager forward) before capturing a graph")
-            K = self.n_neighbor
-            if (K > 128 or int(self.n_relation) > 4096 or int(self.n_entity) > (1 << 24)
-                    or not ops.encode_adjacency_supported(self.dim, K)):
+            if not self._l2_shape_caps()[1].enc:
                 self._enc = False
             else:
                 enc_e, enc_r, cnt = ops.encode_adjacency(self.adj_entity, self.adj_relation)
-                frac = float(cnt.float().mean().item()) / K       # one host sync per adjacency
+                frac = float(cnt.float().mean().item()) / self.n_neighbor      # one host sync per adjacency
                 self._enc = (enc_e, enc_r, cnt, frac)
         return self._enc or None
 
-    ENC_AUTO_MIN_PARENTS = 2048      # below: a few tiles per workgroup, the pipeline's fill / drain dominates (B = 512: 68 vs 58 us)
+    # ------------------------------------------------------------------ form of the two deepest levels (mvin_amd/l2_plan.py)
+    # thresholds: l2_plan.THRESHOLDS, each with its measurement; these three stay settable (class or model), read through the table
+    ENC_AUTO_MAX_DISTINCT_FRACTION = l2_plan.THRESHOLDS.enc_auto_max_distinct_fraction
+    ENC_AUTO_MIN_PARENTS = l2_plan.THRESHOLDS.enc_auto_min_parents
+    ITEM_ORDER_MIN_BATCH = l2_plan.THRESHOLDS.item_order_min_batch
 
+    def _enc_mode(self):         # "0" / "1": the plain / the encoded adjacency forced; else automatic
+        return os.environ.get("MVIN_L2_ENC", "auto") if self.dedup is None else ("1" if self.dedup else "0")
+
+    def _l2_shape_caps(self):
+        """(L2Shape, L2Caps): the shape and the library's capability answers, gathered once per (n_entity, n_relation, dim, K, table dtype)."""
+        E = self.entity_emb_matrix
+        key = (self.n_entity, self.n_relation, E.dtype, E.numel(), self.fused, self.args.User_orient)
+        c = self._l2_static
+        if c is None or c[0] != key:
+            D, K, nE, nR = self.dim, self.n_neighbor, int(self.n_entity), int(self.n_relation)
+            sh = l2_plan.L2Shape(D, K, self.n_mix_hop * self.h_hop, nE, nR, E.dtype == torch.float32, E.numel() * E.element_size(),
+                                 bool(self.args.User_orient), self.fused)
+            caps = l2_plan.L2Caps(enc=K <= 128 and nR <= 4096 and nE <= (1 << 24) and ops.encode_adjacency_supported(D, K),
+                                  prj_plain=ops.gather_attn_l2_prj_supported(D, K, False, nE, nR),
+                                  agg=ops.gather_attn_l2_agg_supported(D, K, nE, nR), fold=ops.score_l2_folded_supported(D, K, nE, nR),
+                                  fold_gather=ops.score_l2_folded_gather_supported(D, K, nE, nR))
+            c = self._l2_static = (key, sh, caps)
+        return c[1], c[2]
+
+    def _l2_inputs(self, want_probs=False):
+        """(shape, overrides, capabilities, thresholds, distinct fraction) as l2_plan takes them; the mean fraction of distinct slots per
+        adjacency row is None without an encoding (which is not built where no call can take it)."""
+        sh, caps = self._l2_shape_caps()
+        th = l2_plan.THRESHOLDS._replace(enc_auto_max_distinct_fraction=self.ENC_AUTO_MAX_DISTINCT_FRACTION,
+                                         enc_auto_min_parents=self.ENC_AUTO_MIN_PARENTS, item_order_min_batch=self.ITEM_ORDER_MIN_BATCH)
+        mode = self._enc_mode()
+        ov = l2_plan.L2Overrides(self.prj, self.agg, self.fold, mode, self.item_order, os.environ.get("MVIN_L2_WPP", "1") != "0")
+        enc = None if (want_probs or self.fused is False or mode == "0") else self.encoded_adjacency()
+        return sh, ov, caps, th, None if enc is None else enc[3]
+
+    def _l2_plan(self, B, n_parents, want_probs=False, use_tail=True, gather_form=True):
+        # remembered per everything it reads, as raw attributes: ~2 us against ~6.5 for gathering the inputs and deciding (the native
+        # call at a few thousand pairs is host-bound)
+        E = self.entity_emb_matrix
+        key = (B, n_parents, want_probs, use_tail, gather_form, self.prj, self.agg, self.fold, self._enc_mode(), self.item_order, self.fused,
+               self._generation, E.dtype, E.numel(), self.n_entity, self.n_relation, self.args.User_orient, os.environ.get("MVIN_L2_WPP"),
+               self.ENC_AUTO_MAX_DISTINCT_FRACTION, self.ENC_AUTO_MIN_PARENTS, self.ITEM_ORDER_MIN_BATCH)
+        plan = self._l2_memo.get(key)
+        if plan is None:
+            if len(self._l2_memo) >= 64:
+                self._l2_memo.clear()
+            plan = self._l2_memo[key] = l2_plan.plan(*self._l2_inputs(want_probs), B, n_parents, want_probs, use_tail, gather_form)
+        return plan
+
+    # the plan's rules one by one, as bench.py and the tests read them
     def _enc_for_l2(self, want_probs=False, n_parents=None):
         """The encoded adjacency when the two deepest levels should take the packed-tile kernel for this call."""
-        mode = os.environ.get("MVIN_L2_ENC", "auto") if self.dedup is None else ("1" if self.dedup else "0")
-        if mode == "0" or want_probs or self.fused is False:
-            return None
-        if mode != "1":
-            # measured (scripts/ab_enc.sh): the wave-per-parent kernel keeps D = 32, K <= 16 (BASELINE C2: 1.53 vs 1.88 ms)
-            # ... unless the call takes the folded tail over per-entity aggregates, which reads the encoding (C2 at bench size)
-            if self.dim == 32 and self.n_neighbor <= 16 and not (
-                    n_parents is not None and self.n_mix_hop * self.h_hop == 2 and self.args.User_orient and self.fold is not False
-                    and self.agg is not False and self.prj is not False and self.entity_emb_matrix.dtype == torch.float32
-                    and n_parents * self.n_neighbor >= 10 * self.n_entity and self._fold_shape_ok()):
-                return None
-            if n_parents is not None and n_parents < self.ENC_AUTO_MIN_PARENTS:
-                return None
-        if self.entity_emb_matrix.numel() * self.entity_emb_matrix.element_size() >= (1 << 32):
-            return None
-        # the packed-tile kernel addresses the adjacency and its output rows with 32-bit offsets (fused_packed_applies)
-        if self.adj_entity.numel() * 4 >= (1 << 31) or (n_parents is not None and n_parents * self.dim * 4 >= (1 << 31)):
-            return None
-        enc = self.encoded_adjacency()
-        if enc is None or (mode != "1" and enc[3] > self.ENC_AUTO_MAX_DISTINCT_FRACTION):
-            return None
-        return enc
+        return self.encoded_adjacency() if l2_plan.encoded(*self._l2_inputs(want_probs), n_parents, want_probs) else None
+
+    def _prj_for_l2(self, B, n_parents=None):
+        return l2_plan.projected(*self._l2_inputs()[:4], B, n_parents)
+
+    def _prj_plain_ok(self):
+        return l2_plan.projected_plain(*self._l2_shape_caps())
+
+    def _agg_for(self, enc):
+        _, ov, caps, _, _ = self._l2_inputs()
+        return l2_plan.aggregates(ov, caps, enc is not None)
+
+    def _fold_for(self, enc):
+        sh, ov, caps, _, _ = self._l2_inputs()
+        return l2_plan.folded(sh, ov, caps, enc is not None)
+
+    def _agg_shape_ok(self):
+        return bool(self._l2_shape_caps()[1].agg)
+
+    def _fold_shape_ok(self):
+        return bool(self._l2_shape_caps()[1].fold)
+
+    def _fold_gather_ok(self):
+        return bool(self._l2_shape_caps()[1].fold_gather)
+
+    def _item_order_for(self, B):
+        sh, ov, _, th, _ = self._l2_inputs()
+        return l2_plan.item_order(sh, ov, th, B)
+
+    def _stream_ws(self, cache, n_ws, dtype=torch.float32, stream=None):
+        """The current stream's workspace of ``n_ws`` elements in ``cache`` (a dict per kind, keyed by stream handle); reallocated when n_ws changes."""
+        cs = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        ws = cache.get(cs)
+        if ws is None or ws.numel() != n_ws:
+            ws = cache[cs] = torch.empty((n_ws,), dtype=dtype, device=self.device)
+        return ws
 
     def _build_inputs(self):
         """model.py:49-64."""
@@ -345,8 +402,7 @@ class MVIN(object):
         aggregators and -- given a device-resident ``user_triplet_set`` -- its one-time id check and static per-user records
         (an allocation of up to USER_RECORDS_MAX_BYTES + a kernel).  Called by __init__ and set_adjacency for the encoding;
         call it yourself before capturing a forward in a hipGraph or running it on a side stream."""
-        mode = os.environ.get("MVIN_L2_ENC", "auto") if self.dedup is None else ("1" if self.dedup else "0")
-        if self.fused is not False and mode != "0":      # (forbidden encoding: nothing to build -- 2 launches, a sync, 2 n_entity K words)
+        if self.fused is not False and self._enc_mode() != "0":      # (forbidden encoding: nothing to build -- 2 launches, a sync, 2 n_entity K words)
             self.encoded_adjacency()
         for agg in self.aggregators:
             if agg.User_orient_rela:
@@ -538,6 +594,19 @@ class MVIN(object):
                           rows_per_group=K ** e).view(B, -1, D) for e in range(1, top)]
         return ev, c
 
+    def _prof_start(self):
+        """``self._profile`` a list (bench.py): HIP events around the launches of the deepest levels."""
+        if self._profile is None:
+            return None
+        e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        e[0].record()
+        return e
+
+    def _prof_stop(self, e):
+        if e is not None:
+            e[1].record()
+            self._profile.append(e)
+
     def _apply(self, agg, ev, ents, rels, hop, c, fused_level, want_probs):
         """One aggregator application at one hop (model.py:296-305)."""
         a, D, K = self.args, self.dim, self.n_neighbor
@@ -548,15 +617,11 @@ class MVIN(object):
         if fused_level is not None:
             Wc = self.transfer_matrix_list[fused_level] if a.User_orient else None
             cc = c[fused_level] if a.User_orient else None
-            if self._profile is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
+            prof = self._prof_start()
             res = ops.gather_attn(self.entity_emb_matrix, self.adj_entity, self.adj_relation,
                                   ents[hop].view(-1), t, ev[hop].view(B * N, D), Wc, cc, agg.weights,
                                   agg.bias, B, N, K, D, want_probs=wp)
-            if self._profile is not None:
-                ev1.record()
-                self._profile.append((ev0, ev1))
+            self._prof_stop(prof)
             return res
         return ops.agg(ev[hop].view(B * N, D), ev[hop + 1].view(B * N * K, D), rels[hop].view(-1), t,
                        agg.weights, agg.bias, B, N, K, D, want_probs=wp)
@@ -670,97 +735,52 @@ class MVIN(object):
         ev, c = (None, {}) if use_tail else self._project_levels(ents, q, top, need_c=() if use_l2 else (L,))
         nagg = pp = pc = None
         if use_hoist:
-            if self._profile is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+            prof = self._prof_start()
             nagg = self._hoisted_naggs(ents[L - 2].view(-1), q, B)
-            if self._profile is not None:
-                e1.record()
-                self._profile.append((e0, e1))
+            self._prof_stop(prof)
         elif use_l2:
             a0, a1 = self._agg[(0, 0)], self._agg[(1, 0)]
-            uo = self.args.User_orient
-            enc = self._enc_for_l2(want_probs, n_parents=B * K ** (L - 2))
-            tabs = None
-            prj_now = not want_probs and (enc is not None or self._prj_plain_ok()) and self._prj_for_l2(B, B * K ** (L - 2))
-            if prj_now and use_tail and self._fold_for(enc) and self.entity_emb_matrix.dtype == torch.float32:
-                # folded-tail form (mvin_fold_tables -> mvin_score_l2_folded_fwd): tables and aggregates from the current parameters,
-                # then everything above key addressing in one launch -- what mvin_score_l2_fwd runs for this call
-                Wp, bp = self.transfer_matrix_list, self.transfer_matrix_bias
-                cs = torch.cuda.current_stream().cuda_stream
-                n_ws = ops._lib.load().mvin_fold_tables_elems(self.n_entity, D)
-                fw = self._fold_ws.get(cs)
-                if fw is None or fw.numel() != n_ws:
-                    fw = self._fold_ws[cs] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-                t0 = a0.relation_scores() if a0.User_orient_rela else None
-                t1 = a1.relation_scores() if a1.User_orient_rela else None
-                if self._profile is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                ops.fold_tables(self.entity_emb_matrix, enc[0], enc[1], t0, Wp[0], bp[0], Wp[1], bp[1], Wp[2], bp[2], a0.weights, a0.bias,
-                                self.enti_transfer_matrix_list[0], self.enti_transfer_bias_list[0], a1.weights, K, self.n_relation, out=fw)
-                item_emb, scores, sig = ops.score_l2_folded(fw, enc[0], enc[1], item32, t0, t1, q, user_o, a1.weights, a1.bias,
-                                                            self.enti_transfer_matrix_list[0], K, D, self.n_relation, self.n_entity)
-                if self._profile is not None:
-                    e1.record()
-                    self._profile.append((e0, e1))
+            uo, E, nE, nR = self.args.User_orient, self.entity_emb_matrix, self.n_entity, self.n_relation
+            Wp, bp, Wmix = self.transfer_matrix_list, self.transfer_matrix_bias, self.enti_transfer_matrix_list[0]
+            # (this schedule has no gather form of the folded tail; its parents are the level-(L-2) nodes)
+            plan = self._l2_plan(B, B * K ** (L - 2), want_probs, use_tail, gather_form=False)
+            enc = self.encoded_adjacency() if plan.adjacency == "encoded" else None
+            ae, ar = (enc[0], enc[1]) if enc is not None else (self.adj_entity, self.adj_relation)
+            parents, ppp = ents[L - 2].view(-1), K ** (L - 2)
+            t0, t1 = a0.relation_scores() if a0.User_orient_rela else None, a1.relation_scores() if a1.User_orient_rela else None
+            if plan.form == "folded":
+                # tables and aggregates from the current parameters, then everything above key addressing in one launch (as mvin_score_l2_fwd)
+                fw = self._stream_ws(self._fold_ws, ops._lib.load().mvin_fold_tables_elems(nE, D))
+                prof = self._prof_start()
+                ops.fold_tables(E, ae, ar, t0, Wp[0], bp[0], Wp[1], bp[1], Wp[2], bp[2], a0.weights, a0.bias, Wmix,
+                                self.enti_transfer_bias_list[0], a1.weights, K, nR, out=fw)
+                item_emb, scores, sig = ops.score_l2_folded(fw, ae, ar, item32, t0, t1, q, user_o, a1.weights, a1.bias, Wmix, K, D, nR, nE)
+                self._prof_stop(prof)
                 return item_emb, scores, sig, []
-            # (the projected-tables kernels write no attention outputs: a want_probs pass keeps the form that does)
-            if prj_now:
-                # projected-tables form (mvin_gather_attn_l2_prj_fwd): E.W1 | E.W1.A0 | E.W2.A0 from the current parameters, per call
-                Wp, bp = self.transfer_matrix_list, self.transfer_matrix_bias
-                tabs = ops.project_tables(self.entity_emb_matrix, Wp[L - 1], Wp[L], bp[L - 1], bp[L], a0.weights, a0.bias, K,
-                                          a0.User_orient_rela)
-            if self._profile is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            l2_args = (a0.relation_scores() if a0.User_orient_rela else None,
-                       a1.relation_scores() if a1.User_orient_rela else None,
-                       self.transfer_matrix_list[L - 1] if uo else None, self.transfer_matrix_list[L] if uo else None,
-                       self.transfer_matrix_bias[L - 1] if uo else None, self.transfer_matrix_bias[L] if uo else None,
-                       q if uo else None, a0.weights, a0.bias, B, K ** (L - 2), K, D, self.n_relation)
-            if tabs is not None:
-                ae, ar = (enc[0], enc[1]) if enc is not None else (self.adj_entity, self.adj_relation)
-                order = None
-                if self._agg_for(enc):
-                    # per-entity aggregates S0 | G of the tables just built: ~cnt rows per parent instead of ~cnt^2
-                    cs = torch.cuda.current_stream().cuda_stream
-                    n_ws = ops._lib.load().mvin_entity_aggregates_elems(self.n_entity, D)
-                    at = self._agg_tables.get(cs)
-                    if at is None or at.numel() != n_ws:
-                        at = self._agg_tables[cs] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-                    ops.entity_aggregates(tabs, ae, ar, l2_args[0], K, D, self.n_relation, self.n_entity, out=at)
-                    n0, n1 = ops.gather_attn_l2_agg(tabs, at, ae, ar, ents[L - 2].view(-1), l2_args[0], l2_args[1], q, B,
-                                                    K ** (L - 2), K, D, self.n_relation, self.n_entity)
-                else:
-                    if enc is not None and L == 2 and self._item_order_for(B) and ops.gather_attn_l2_wpp_supported(D, K):
-                        order = ops.order_by_key(ents[0].view(-1))
-                    n0, n1 = ops.gather_attn_l2_prj(tabs, ae, ar, ents[L - 2].view(-1), l2_args[0], l2_args[1], q, B,
-                                                    K ** (L - 2), K, D, self.n_relation, self.n_entity, encoded=enc is not None, order=order)
-                pp = pc = None
-            elif enc is not None:
-                n0, n1 = ops.gather_attn_l2_enc(self.entity_emb_matrix, enc[0], enc[1], ents[L - 2].view(-1), *l2_args)
-                pp = pc = None
+            if plan.form in ("tables", "aggregates"):        # E.W1 | E.W1.A0 | E.W2.A0 from the current parameters, per call
+                tabs = ops.project_tables(E, Wp[L - 1], Wp[L], bp[L - 1], bp[L], a0.weights, a0.bias, K, a0.User_orient_rela)
+            prof = self._prof_start()
+            if plan.form == "aggregates":
+                # per-entity aggregates S0 | G of the tables just built: ~cnt rows per parent instead of ~cnt^2
+                at = self._stream_ws(self._agg_tables, ops._lib.load().mvin_entity_aggregates_elems(nE, D))
+                ops.entity_aggregates(tabs, ae, ar, t0, K, D, nR, nE, out=at)
+                n0, n1 = ops.gather_attn_l2_agg(tabs, at, ae, ar, parents, t0, t1, q, B, ppp, K, D, nR, nE)
+            elif plan.form == "tables":
+                order = ops.order_by_key(ents[0].view(-1)) if plan.item_order else None      # (dropped by the library where no kernel takes it)
+                n0, n1 = ops.gather_attn_l2_prj(tabs, ae, ar, parents, t0, t1, q, B, ppp, K, D, nR, nE, encoded=enc is not None, order=order)
             else:
-                n0, n1, pp, pc = ops.gather_attn_l2(
-                    self.entity_emb_matrix, self.adj_entity, self.adj_relation, ents[L - 2].view(-1), *l2_args,
-                    want_probs=want_probs and a0.User_orient_rela)
-            if self._profile is not None:
-                e1.record()
-                self._profile.append((e0, e1))
+                l2_args = (t0, t1, Wp[L - 1] if uo else None, Wp[L] if uo else None, bp[L - 1] if uo else None, bp[L] if uo else None,
+                           q if uo else None, a0.weights, a0.bias, B, ppp, K, D, nR)
+                if enc is not None:
+                    n0, n1 = ops.gather_attn_l2_enc(E, ae, ar, parents, *l2_args)
+                else:
+                    n0, n1, pp, pc = ops.gather_attn_l2(E, ae, ar, parents, *l2_args, want_probs=want_probs and a0.User_orient_rela)
+            self._prof_stop(prof)
             nagg = (n0, n1)
             if use_tail:
-                item_emb, scores, sig = ops.l2_tail(
-                    self.entity_emb_matrix, item32, q if uo else None, user_o, n0, n1,
-                    self.transfer_matrix_list[0] if uo else None, self.transfer_matrix_bias[0] if uo else None,
-                    a0.weights, a0.bias, a1.weights, a1.bias, self.enti_transfer_matrix_list[0],
-                    self.enti_transfer_bias_list[0])
-                importance = []
-                if want_probs and a0.User_orient_rela:
-                    importance = [pp.view(B, 1, K) if pp is not None else None,
-                                  pc.view(B, K, K) if pc is not None else None]
-                elif want_probs:
-                    importance = [None, None]
+                item_emb, scores, sig = ops.l2_tail(E, item32, q if uo else None, user_o, n0, n1, Wp[0] if uo else None, bp[0] if uo else None,
+                                                    a0.weights, a0.bias, a1.weights, a1.bias, Wmix, self.enti_transfer_bias_list[0])
+                importance = [pp.view(B, 1, K) if pp is not None else None, pc.view(B, K, K) if pc is not None else None] if want_probs else []
                 return item_emb, scores, sig, importance
         importance = []
         out = None
@@ -867,6 +887,35 @@ class MVIN(object):
         return (item.shape[0] <= self.small_max_batch and not want_probs and self._profile is None
                 and item.dtype == torch.int64 and (memories_h is None or memories_h[0].dim() == 2) and self._small_static_ok())
 
+    def _score_args_static(self, depth=None):
+        """The static half of ScoreL2Args -- adjacency, KGE, MLPs, projections, aggregators, mix, shape words -- and the tensors whose
+        addresses it holds (kept alive with the block; rebinding a parameter attribute needs invalidate(), as for the cached relation
+        logits).  ``depth``: the single-launch pass takes trees of depth 1 or 2, passes the depth and has W_e / b_e for e <= depth only
+        (a one-hop tree has aggregator (0,0) only); None: mvin_score_l2_fwd, depth-2 trees."""
+        from . import _lib
+        a, L = self.args, 2 if depth is None else depth
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        a0, a1 = self._agg[(0, 0)], self._agg.get((1, 0))
+        s = _lib.ScoreL2Args()
+        s.adj_entity, s.adj_relation = ptr(self.adj_entity), ptr(self.adj_relation)
+        s.relation_kge = ptr(self.relation_emb_KGE_matrix)
+        s.h_set_w = ptr(self.h_emb_item_mlp_matrix) if a.PS_O_ft else None
+        s.user_mlp_W, s.user_mlp_b = ptr(self.user_mlp_matrix), ptr(self.user_mlp_bias)
+        for e in range(3):
+            setattr(s, f"W{e}", ptr(self.transfer_matrix_list[e]) if (a.User_orient and e <= L) else None)
+            setattr(s, f"b{e}", ptr(self.transfer_matrix_bias[e]) if (a.User_orient and e <= L) else None)
+        s.A0, s.a0 = ptr(a0.weights), ptr(a0.bias)
+        s.A1, s.a1 = (ptr(a1.weights), ptr(a1.bias)) if a1 is not None else (None, None)
+        s.Wmix, s.bmix = ptr(self.enti_transfer_matrix_list[0]), ptr(self.enti_transfer_bias_list[0])
+        s.D, s.K, s.P, s.Nm = self.dim, self.n_neighbor, self.p_hop, self.n_memory
+        s.n_entity, s.n_relation = self.n_entity, self.n_relation
+        s.depth = depth or 0
+        keep = (self.adj_entity, self.adj_relation, self.relation_emb_KGE_matrix, self.h_emb_item_mlp_matrix,
+                self.user_mlp_matrix, self.user_mlp_bias, list(self.transfer_matrix_list), list(self.transfer_matrix_bias),
+                a0.weights, a0.bias, a1.weights if a1 is not None else None, a1.bias if a1 is not None else None,
+                self.enti_transfer_matrix_list[0], self.enti_transfer_bias_list[0])
+        return s, keep
+
     def _score_small_native(self, item, mem_h, mem_r, mem_t, uts=None, users=None):
         """model.py:125-159 as ONE kernel launch (mvin_score_small_fwd).  The argument block is built once per parameter
         generation; per call only the table / logit-table / feed / output pointers are refreshed and ONE output buffer is
@@ -880,32 +929,13 @@ class MVIN(object):
         t1 = a1.relation_scores() if (a1 is not None and a1.User_orient_rela) else None
         st = self._small_state
         if st is None or st["key"] != self._generation or st["dedup"] != self.dedup:
-            a = self.args
-            ptr = lambda t: t.data_ptr() if t is not None else None
-            uo = a.User_orient
-            s = _lib.ScoreL2Args()
-            s.adj_entity, s.adj_relation = ptr(self.adj_entity), ptr(self.adj_relation)
-            s.relation_kge = ptr(self.relation_emb_KGE_matrix)
-            s.h_set_w = ptr(self.h_emb_item_mlp_matrix) if a.PS_O_ft else None
-            s.user_mlp_W, s.user_mlp_b = ptr(self.user_mlp_matrix), ptr(self.user_mlp_bias)
-            L = self.h_hop
-            for e in range(3):
-                setattr(s, f"W{e}", ptr(self.transfer_matrix_list[e]) if (uo and e <= L) else None)
-                setattr(s, f"b{e}", ptr(self.transfer_matrix_bias[e]) if (uo and e <= L) else None)
-            s.A0, s.a0 = ptr(a0.weights), ptr(a0.bias)
-            s.A1, s.a1 = (ptr(a1.weights), ptr(a1.bias)) if a1 is not None else (None, None)
-            s.Wmix, s.bmix = ptr(self.enti_transfer_matrix_list[0]), ptr(self.enti_transfer_bias_list[0])
-            s.D, s.K, s.P, s.Nm, s.depth = D, self.n_neighbor, P, self.n_memory, L
-            s.n_entity, s.n_relation, s.table_bf16 = self.n_entity, self.n_relation, 0
+            s, keep = self._score_args_static(depth=self.h_hop)
+            s.table_bf16 = 0
             # the duplicate-slot encoding whenever the adjacency has one (distinct rows only; a row without repeats costs the
             # same either way) unless the plain adjacency is forced (MVIN.dedup = False / MVIN_L2_ENC=0)
-            mode = os.environ.get("MVIN_L2_ENC", "auto") if self.dedup is None else ("1" if self.dedup else "0")
-            enc = self.encoded_adjacency() if mode != "0" else None
-            s.enc_entity, s.enc_relation = (ptr(enc[0]), ptr(enc[1])) if enc is not None else (None, None)
-            keep = (self.adj_entity, self.adj_relation, self.relation_emb_KGE_matrix, self.h_emb_item_mlp_matrix,
-                    self.user_mlp_matrix, self.user_mlp_bias, list(self.transfer_matrix_list), list(self.transfer_matrix_bias),
-                    a0.weights, a0.bias, a1.weights if a1 is not None else None, a1.bias if a1 is not None else None,
-                    self.enti_transfer_matrix_list[0], self.enti_transfer_bias_list[0], enc)
+            enc = self.encoded_adjacency() if self._enc_mode() != "0" else None
+            s.enc_entity, s.enc_relation = (enc[0].data_ptr(), enc[1].data_ptr()) if enc is not None else (None, None)
+            keep += (enc,)
             st = self._small_state = {"key": self._generation, "args": s, "ref": C.byref(s), "keep": keep, "arr": (C.c_void_p * P),
                                       "dedup": self.dedup, "fn": _lib.load().mvin_score_small_fwd, "live": None}
         s = st["args"]
@@ -938,11 +968,10 @@ class MVIN(object):
         measured at C3 the kernel over the records goes 0.94 -> 0.74 ms, the table R_KGE[r] . E[e] (245 MB, rebuilt per call) costs
         0.11 ms, and with two scoring streams its writes compete with the other stream's kernels -- 2.74 -> 2.67 ms per step on
         one stream, 197.0 -> 197.6 M pairs/s on two."""
-        a = self.args
         if not self.ka_er or records is None or self.entity_emb_matrix.dtype != torch.float32 or self.p_hop < 1:
             return False
         return bool(ops.key_addressing_grouped_er_supported(self.dim, self.p_hop, self.n_memory, self.n_relation, self.n_entity,
-                                                            bool(a.PS_O_ft)))
+                                                            bool(self.args.PS_O_ft)))
 
     def _ka_flash_for(self, uts, records, B):
         """Flash form of the grouped key addressing + user MLP (mvin_key_addressing_flash_fwd) for a batch of B pairs?  Its per-call
@@ -962,104 +991,6 @@ class MVIN(object):
             return False
         return users * self.p_hop * self.n_memory >= self.n_relation * self.n_entity
 
-    def _ka_flash_tables(self, stream):
-        n_ws = _lib_flash_elems(self)
-        ws = self._ka_flash_ws.get(stream)
-        if ws is None or ws.numel() != n_ws:
-            ws = self._ka_flash_ws[stream] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-        return ws
-
-    ITEM_ORDER_MIN_BATCH = 32768
-
-    def _item_order_for(self, B):
-        """Parents of the projected-tables launch in ITEM order (mvin_order_by_key, ~36 us per 524 288 pairs)?  Pairs of the same item
-        gather the same rows; back to back they are cache hits -- the launch's requests past the L2 halve at BASELINE C3 (7.5 -> 3.6 GB),
-        and those bytes are what bounds the step.  For the wave-per-parent kernel (dim 64, fan-out <= 32, depth-2 trees: the parents
-        are the pairs) and batches large enough to hold repeated items; ``self.item_order`` True / False (MVIN_ITEM_ORDER=1 / 0) forces it."""
-        if self.dim != 64 or self.n_neighbor > 32 or self.n_mix_hop * self.h_hop != 2 or os.environ.get("MVIN_L2_WPP", "1") == "0":
-            return False
-        want = self.item_order
-        if want is None:
-            want = B >= self.ITEM_ORDER_MIN_BATCH
-        return bool(want)
-
-    def _agg_for(self, enc):
-        """Per-entity aggregates form of the two deepest levels (mvin_project_tables -> mvin_entity_aggregates ->
-        mvin_gather_attn_l2_agg_fwd) for a call that takes the projected-tables form?  The aggregates cost ~17 gathered rows per
-        entity and save a parent ~100 of its ~120 (C3): whenever the tables themselves pay (_prj_for_l2's rule is the stricter one),
-        on the shapes the kernels take (D = 64, K in {16, 32, 64}, encoded adjacency).  ``self.agg`` False (MVIN_L2_AGG=0) keeps the kernels
-        over the tables."""
-        if enc is None or self.agg is False:
-            return False
-        return self._agg_shape_ok()
-
-    def _agg_shape_ok(self):
-        """mvin_gather_attn_l2_agg_supported for this model's tables (D = 64, K in {16, 32, 64}, sizes within 32-bit offsets)."""
-        key = (self.n_entity, self.n_relation, self.dim, self.n_neighbor)
-        c = getattr(self, "_agg_ok_cache", None)
-        if c is None or c[0] != key:
-            c = self._agg_ok_cache = (key, ops.gather_attn_l2_agg_supported(self.dim, self.n_neighbor, self.n_entity, self.n_relation))
-        return c[1]
-
-    def _fold_for(self, enc):
-        """Folded-tail form of the native call (mvin_fold_tables -> mvin_score_l2_folded_fwd: the aggregates form with nagg0 and ev0
-        folded into per-entity tables too -- six products per pair instead of eight) wherever the aggregates form is taken by
-        mvin_score_l2_fwd (depth-2 trees, User_orient on).  ``self.fold`` False (MVIN_L2_FOLD=0) keeps aggregates + mvin_l2_tail_fwd."""
-        if enc is None or self.fold is False or self.agg is False or not self.args.User_orient:
-            return False
-        return self._fold_shape_ok()
-
-    def _fold_gather_ok(self):
-        """mvin_score_l2_folded_gather_supported for this model's tables (dim 64, K in {16, 32}; MVIN_L2_FOLD_GATHER=0 says no)."""
-        key = (self.n_entity, self.n_relation, self.dim, self.n_neighbor)
-        c = getattr(self, "_fold_gather_cache", None)
-        if c is None or c[0] != key:
-            c = self._fold_gather_cache = (key, ops.score_l2_folded_gather_supported(self.dim, self.n_neighbor, self.n_entity, self.n_relation))
-        return c[1]
-
-    def _fold_shape_ok(self):
-        """mvin_score_l2_folded_supported for this model's tables (dim 64 with K in {16, 32, 64} like the aggregates form, dim 32 with K in {16, 32})."""
-        key = (self.n_entity, self.n_relation, self.dim, self.n_neighbor)
-        c = getattr(self, "_fold_ok_cache", None)
-        if c is None or c[0] != key:
-            c = self._fold_ok_cache = (key, ops.score_l2_folded_supported(self.dim, self.n_neighbor, self.n_entity, self.n_relation))
-        return c[1]
-
-    def _prj_plain_ok(self):
-        """The projected-tables form over the PLAIN adjacency: the wave-per-parent kernel of D = 32, K in {8, 16} (BASELINE C2) --
-        where the library takes THAT kernel for this model's tables (mvin_gather_attn_l2_prj_supported: its LDS copy of the
-        relation logits fits, the adjacency is below 2 GiB, MVIN_L2_D32 does not forbid it); otherwise the unprojected form stays."""
-        if not (self.dim == 32 and self.n_neighbor in (8, 16) and self.fused is not False):
-            return False
-        key = (self.n_entity, self.n_relation, self.entity_emb_matrix.dtype)
-        c = getattr(self, "_prj_plain_cache", None)
-        if c is None or c[0] != key:
-            ok = (self.entity_emb_matrix.dtype == torch.float32
-                  and ops.gather_attn_l2_prj_supported(self.dim, self.n_neighbor, False, self.n_entity, self.n_relation))
-            c = self._prj_plain_cache = (key, ok)
-        return c[1]
-
-    def _prj_for_l2(self, B, n_parents=None):
-        """Projected-tables form of the fused two-level pass for a batch of B pairs (``n_parents`` level-(L-2) nodes)?
-        ``self.prj``: None = automatic (MVIN_PRJ=0 / 1 overrides), True / False."""
-        if not (self.args.User_orient and self.entity_emb_matrix.dtype == torch.float32
-                and self.entity_emb_matrix.numel() * 4 < (1 << 30) and B * self.dim * 4 < (1 << 30)):
-            return False
-        want = self.prj
-        if want is None:
-            # D <= 64, K <= 32: the other instances of the kernel are at their register budget already (K = 64: the second self row
-            # costs 18 spilled registers in the front role's id pipeline) and measured no faster (C4) -- on request only
-            # (K = 64 takes it where the per-entity aggregates exist, D = 64: there the tables are only the aggregates' input)
-            # With the aggregates / the folded tail behind the tables the form pays earlier -- measured break-even (pairs per step, one GPU):
-            # C3 (K = 32) ~32 768 = 10 n_entity / K, C4 (K = 64) ~8 192 = 4.6 n_entity / K; the kernels over the tables themselves: 16
-            aggs = self.agg is not False and ((self.dim == 64 and self._agg_shape_ok())
-                                              or (self.dim == 32 and self.n_mix_hop * self.h_hop == 2 and self.fold is not False
-                                                  and self._fold_shape_ok()))
-            k_ok = self.n_neighbor <= 32 or (self.n_neighbor == 64 and aggs)
-            factor = (5 if self.n_neighbor == 64 else 10) if aggs else 16
-            want = self.dim <= 64 and k_ok and (n_parents or B) * self.n_neighbor >= factor * self.n_entity
-        return bool(want)
-
     def _score_l2_native(self, item, mem_h, mem_r, mem_t, uts=None, users=None, grouped=False):
         """model.py:125-159 through mvin_score_l2_fwd.  The argument block (every weight pointer) is built once and
         kept until a parameter tensor is replaced; per call only the batch pointers change."""
@@ -1067,89 +998,47 @@ class MVIN(object):
         import ctypes as C
         a, D, P, B = self.args, self.dim, self.p_hop, item.shape[0]
         a0, a1 = self._agg[(0, 0)], self._agg[(1, 0)]
-        t0 = a0.relation_scores() if a0.User_orient_rela else None
-        t1 = a1.relation_scores() if a1.User_orient_rela else None
-        uo = a.User_orient
+        t0, t1 = a0.relation_scores() if a0.User_orient_rela else None, a1.relation_scores() if a1.User_orient_rela else None
         # The block is rebuilt when a parameter tensor may have been REPLACED (generation); what legitimately changes
         # from call to call -- the entity table (ShardedMVIN alternates two working tables), the relation-logit tables
         # (rebuilt after every optimizer step) and the batch -- is refreshed per call, and the workspaces live outside
         # the block, per (batch size, stream): no allocation churn on the small-batch path this call exists for, and
         # two streams scoring the same batch size never share V / o_cat / nagg.
-        key = self._generation
         ptr = lambda t: t.data_ptr() if t is not None else None
         st = self._native_l2_state
-        if st is None or st["key"] != key:
-            s = _lib.ScoreL2Args()
-            s.adj_entity, s.adj_relation = ptr(self.adj_entity), ptr(self.adj_relation)
-            s.relation_kge = ptr(self.relation_emb_KGE_matrix)
-            s.h_set_w = ptr(self.h_emb_item_mlp_matrix) if a.PS_O_ft else None
-            s.user_mlp_W, s.user_mlp_b = ptr(self.user_mlp_matrix), ptr(self.user_mlp_bias)
-            for e in range(3):
-                setattr(s, f"W{e}", ptr(self.transfer_matrix_list[e]) if uo else None)
-                setattr(s, f"b{e}", ptr(self.transfer_matrix_bias[e]) if uo else None)
-            s.A0, s.a0, s.A1, s.a1 = ptr(a0.weights), ptr(a0.bias), ptr(a1.weights), ptr(a1.bias)
-            s.Wmix, s.bmix = ptr(self.enti_transfer_matrix_list[0]), ptr(self.enti_transfer_bias_list[0])
-            s.D, s.K, s.P, s.Nm = D, self.n_neighbor, P, self.n_memory
-            s.n_entity, s.n_relation = self.n_entity, self.n_relation
-            # every tensor whose address sits in the block is kept alive with it; rebinding a parameter attribute
-            # needs invalidate(), exactly as for the cached relation logits
-            keep = (self.adj_entity, self.adj_relation, self.relation_emb_KGE_matrix,
-                    self.h_emb_item_mlp_matrix, self.user_mlp_matrix, self.user_mlp_bias, list(self.transfer_matrix_list),
-                    list(self.transfer_matrix_bias), a0.weights, a0.bias, a1.weights, a1.bias,
-                    self.enti_transfer_matrix_list[0], self.enti_transfer_bias_list[0])
-            st = self._native_l2_state = {"key": key, "args": s, "keep": keep, "arr": (C.c_void_p * P)}
+        if st is None or st["key"] != self._generation:
+            s, keep = self._score_args_static()
+            st = self._native_l2_state = {"key": self._generation, "args": s, "keep": keep, "arr": (C.c_void_p * P)}
         s = st["args"]
         s.entity_emb, s.t0, s.t1 = ptr(self.entity_emb_matrix), ptr(t0), ptr(t1)
         s.table_bf16 = 1 if self.entity_emb_matrix.dtype == torch.bfloat16 else 0
-        enc = self._enc_for_l2(n_parents=B)
+        # (depth-2 trees: the parents are the pairs; this call has the one-launch tail and the gather form of the folded tail)
+        plan = self._l2_plan(B, B)
+        form = plan.form
+        enc = self.encoded_adjacency() if plan.adjacency == "encoded" else None
         s.enc_entity, s.enc_relation = (ptr(enc[0]), ptr(enc[1])) if enc is not None else (None, None)
         rec = self.user_records(uts) if grouped else None
         s.user_records = ptr(rec)
         st["live"] = (self.entity_emb_matrix, t0, t1, enc, rec)
         s.ka_er = s.ka_flash = None
-        if grouped and self._ka_flash_for(uts, rec, B):    # flash form: its tables are rebuilt by every call
-            s.ka_flash = self._ka_flash_tables(torch.cuda.current_stream().cuda_stream).data_ptr()
-        elif grouped and self._ka_er_for(uts, rec):        # gathered U rows: the table is rebuilt by every call
-            cs = torch.cuda.current_stream().cuda_stream
-            n_ws = _lib.load().mvin_project_relations_elems(self.n_entity, self.n_relation, D)
-            ew = self._ka_er_ws.get(cs)
-            if ew is None or ew.numel() != n_ws:
-                ew = self._ka_er_ws[cs] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-            s.ka_er = ew.data_ptr()
-        n_o = P + (1 if a.PS_O_ft else 0)
         stream = torch.cuda.current_stream()
-        # projected-tables form of the two deepest levels (mvin_gather_attn_l2_prj_fwd): E.W1 | E.W1.A0 | E.W2.A0 is rebuilt by every call
-        # from the current parameters -- worth it when the batch's distinct children outnumber the entities (the per-entity
-        # products cost ~n_entity rows of work, the per-child products they replace ~B K / 4)
-        prj = (enc is not None or self._prj_plain_ok()) and self._prj_for_l2(B)
-        fold = bool(prj and self._fold_for(enc))           # (its own workspace holds its own tables)
-        # MVIN.agg = False ("every pair gathers its own rows"): the folded tail still applies, in its gather form -- per-row tables only
-        gfold = bool(prj and not fold and enc is not None and self.agg is False and self.fold is not False and self.args.User_orient
-                     and self.n_mix_hop * self.h_hop == 2 and self._fold_gather_ok())
-        if prj and not fold and not gfold:
-            pt = self._prj_tables.get(stream.cuda_stream)
-            n_ws = _lib.load().mvin_project_tables_elems(self.n_entity, D)
-            if pt is None or pt.numel() != n_ws:
-                pt = self._prj_tables[stream.cuda_stream] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-            s.prj_tables = pt.data_ptr()
-        else:
-            s.prj_tables = None
-        s.agg_tables = s.fold_ws = None
-        s.fold_gather = 0
-        if fold or gfold:
-            fw = self._fold_ws.get(stream.cuda_stream)
-            n_ws = _lib.load().mvin_fold_tables_elems(self.n_entity, D)
-            if fw is None or fw.numel() != n_ws:
-                fw = self._fold_ws[stream.cuda_stream] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-            s.fold_ws = fw.data_ptr()
-            s.fold_gather = 1 if gfold else 0
-        elif prj and self._agg_for(enc):
-            at = self._agg_tables.get(stream.cuda_stream)
-            n_ws = _lib.load().mvin_entity_aggregates_elems(self.n_entity, D)
-            if at is None or at.numel() != n_ws:
-                at = self._agg_tables[stream.cuda_stream] = torch.empty((n_ws,), dtype=torch.float32, device=self.device)
-            s.agg_tables = at.data_ptr()
-        wkey = (B, n_o, stream.cuda_stream, bool(grouped), uts.shape[0] if grouped else 0)
+        cs, lib = stream.cuda_stream, _lib.load()
+        if grouped and self._ka_flash_for(uts, rec, B):    # flash form: its tables are rebuilt by every call
+            s.ka_flash = self._stream_ws(self._ka_flash_ws, _lib_flash_elems(self), stream=cs).data_ptr()
+        elif grouped and self._ka_er_for(uts, rec):        # gathered U rows: the table is rebuilt by every call
+            s.ka_er = self._stream_ws(self._ka_er_ws, lib.mvin_project_relations_elems(self.n_entity, self.n_relation, D), stream=cs).data_ptr()
+        n_o = P + (1 if a.PS_O_ft else 0)
+        # projected tables: E.W1 | E.W1.A0 | E.W2.A0 is rebuilt by every call from the current parameters (~n_entity rows of work against
+        # ~B K / 4); the aggregates are built from those tables, the folded forms hold their own tables in their own workspace
+        s.prj_tables = s.agg_tables = s.fold_ws = None
+        if form in ("tables", "aggregates"):
+            s.prj_tables = self._stream_ws(self._prj_tables, lib.mvin_project_tables_elems(self.n_entity, D), stream=cs).data_ptr()
+        if form == "aggregates":
+            s.agg_tables = self._stream_ws(self._agg_tables, lib.mvin_entity_aggregates_elems(self.n_entity, D), stream=cs).data_ptr()
+        elif form in ("folded", "folded_gather"):
+            s.fold_ws = self._stream_ws(self._fold_ws, lib.mvin_fold_tables_elems(self.n_entity, D), stream=cs).data_ptr()
+        s.fold_gather = 1 if form == "folded_gather" else 0
+        wkey = (B, n_o, cs, bool(grouped), uts.shape[0] if grouped else 0)
         ws = self._native_l2_ws.get(wkey)
         if ws is None:        # reused across calls of the same batch size ON THE SAME STREAM (which orders the reuse)
             f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -1160,10 +1049,8 @@ class MVIN(object):
                                              torch.empty(B, dtype=torch.int32, device=self.device), f(B, D), f(B, D), gws, ows)
             if len(self._native_l2_ws) > 8:
                 self._native_l2_ws.pop(next(iter(self._native_l2_ws)))
-        user_o = torch.empty((B, D), dtype=torch.float32, device=self.device)
-        item_emb = torch.empty((B, D), dtype=torch.float32, device=self.device)
-        scores = torch.empty((B,), dtype=torch.float32, device=self.device)
-        sig = torch.empty((B,), dtype=torch.float32, device=self.device)
+        user_o, item_emb = torch.empty((B, D), dtype=torch.float32, device=self.device), torch.empty((B, D), dtype=torch.float32, device=self.device)
+        scores, sig = torch.empty((B,), dtype=torch.float32, device=self.device), torch.empty((B,), dtype=torch.float32, device=self.device)
         s.items = item.data_ptr()
         if uts is not None:       # users feed: the kernel reads the lists of users[b] out of user_triplet_set
             s.uts, s.users, s.n_user = uts.data_ptr(), users.data_ptr(), uts.shape[0]
@@ -1174,15 +1061,13 @@ class MVIN(object):
             s.mem_h, s.mem_r, s.mem_t = C.addressof(ph), C.addressof(pr), C.addressof(pt)
         s.V, s.o_cat, s.parents, s.nagg0, s.nagg1, s.group_ws = (w.data_ptr() if w is not None else None for w in ws[:6])
         s.item_order_ws = None
-        # (the aggregates form gathers ~12 rows of a 27 MB table per pair: item order buys it nothing -- measured 235 vs 252 us at C3)
-        if prj and enc is not None and s.agg_tables is None and (s.fold_ws is None or gfold) and self._item_order_for(B):
+        if plan.item_order:
             if ws[6] is None:
-                ws = self._native_l2_ws[wkey] = ws[:6] + (torch.empty(_lib.load().mvin_order_by_key_ws_elems(B) + B, dtype=torch.int32,
-                                                                      device=self.device),)
+                ws = self._native_l2_ws[wkey] = ws[:6] + (torch.empty(lib.mvin_order_by_key_ws_elems(B) + B, dtype=torch.int32, device=self.device),)
             s.item_order_ws = ws[6].data_ptr()
         s.user_o, s.item_emb, s.scores, s.sig = user_o.data_ptr(), item_emb.data_ptr(), scores.data_ptr(), sig.data_ptr()
         s.B = B
-        _lib.check(_lib.load().mvin_score_l2_fwd(C.byref(s), C.c_void_p(stream.cuda_stream)), "mvin_score_l2_fwd")
+        _lib.check(lib.mvin_score_l2_fwd(C.byref(s), C.c_void_p(cs)), "mvin_score_l2_fwd")
         return SimpleNamespace(scores=scores, scores_normalized=sig, user_o=user_o, item_embeddings=item_emb,
                                importance_list=[])
 
@@ -1200,7 +1085,7 @@ class MVIN(object):
                 evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 evs[0].record()
             tabs = ops.key_addressing_flash_prepare(self.entity_emb_matrix, self.relation_emb_KGE_matrix, w_h, self.user_mlp_matrix, P,
-                                                    out=self._ka_flash_tables(torch.cuda.current_stream().cuda_stream))
+                                                    out=self._stream_ws(self._ka_flash_ws, _lib_flash_elems(self)))
             if kp is not None:
                 evs[1].record()
             uo = ops.key_addressing_flash(self.entity_emb_matrix, tabs, rec, groups, item, P, self.n_memory, self.n_relation,

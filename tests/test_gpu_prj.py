@@ -342,6 +342,52 @@ def test_forced_projection_falls_back_where_no_kernel_takes_it(hip_lib):
         assert_close(out.scores.cpu().numpy(), m.scores.numpy(), f"scores vs fp32 mirror (native_l2_max_batch={native})", rtol=1e-5, atol=1e-6)
 
 
+def _first_n_relation_past_the_wave_per_parent_lds(K):
+    """mvin_fused_wpp.hip: a workgroup of the wave-per-parent kernel holds fused_wpp_lds_bytes(nR, K) = (2 round_up(nR, 4) + kWppWaves
+    (16 kWppUvLd + wpp_list_words(K))) floats of LDS -- the two relation-logit tables and, per wave, sixteen u1 | v rows and the four
+    groups' (offset, weight) lists -- with kWppWaves = 4, kWppUvLd = 132, wpp_list_words(K) = 4 * 2 * (K + 4); fused_wpp_applies
+    takes at most 48 KiB (dynamic LDS beyond it would need a function attribute)."""
+    per_workgroup = 4 * (16 * 132 + 4 * 2 * (K + 4))
+    nR = 1
+    while (2 * ((nR + 3) & ~3) + per_workgroup) * 4 <= 48 * 1024:
+        nR += 1
+    return nR
+
+
+def test_item_order_falls_back_where_the_wave_per_parent_kernel_does_not_apply(hip_lib, monkeypatch):
+    """dim 64, K 16 and enough relations that the wave-per-parent kernel's LDS bound says no: the Python schedule asks for item order
+    like the native one, and the library -- not a Python-side shape test -- decides.  mvin_gather_attn_l2_prj_ordered_fwd drops the
+    order and runs the packed-tile kernel, as mvin_score_l2_fwd does (before, this model raised MvinHipError -3 above
+    native_l2_max_batch); what is not an ordered launch at all (several parents per pair) is still refused."""
+    from mvin_amd._lib import MvinHipError
+    nR = _first_n_relation_past_the_wave_per_parent_lds(16)
+    assert nR == 1601
+    args = make_args(**_shape(64, 16, B=64))
+    case = synth.small_case(args, n_user=8, n_entity=96, n_relation=nR, seed=7, zero_rows=2, repeats=True)
+    params = init_params(args, case.n_user, case.n_entity, case.n_relation, seed=8, random_agg_bias=True)
+    model = _model(args, case, params, True)                 # dedup = True, prj = True
+    model.agg = model.fold = False
+    model._profile = []                                      # the Python schedule
+    orders = []
+    real = ops.gather_attn_l2_prj
+    monkeypatch.setattr(ops, "gather_attn_l2_prj", lambda *a, **kw: (orders.append(kw.get("order") is not None), real(*a, **kw))[1])
+    model.item_order = True
+    out = _pairs(model, case)
+    model.item_order = False
+    ref = _pairs(model, case)
+    assert orders == [True, False]
+    assert torch.equal(out.scores, ref.scores)
+    m, _ = run_oracles(args, case, params)
+    assert_close(out.scores.cpu().numpy(), m.scores.numpy(), "scores vs fp32 mirror", rtol=1e-5, atol=1e-6)
+    assert_close(out.item_embeddings.cpu().numpy(), m.item_embeddings.numpy(), "item_embeddings", rtol=1e-5, atol=1e-6)
+    a0, enc, W, b = model._agg[(0, 0)], model.encoded_adjacency(), model.transfer_matrix_list, model.transfer_matrix_bias
+    ws = ops.project_tables(model.entity_emb_matrix, W[1], W[2], b[1], b[2], a0.weights, a0.bias, 16, True)
+    ids = torch.zeros(8, dtype=torch.int32, device="cuda:0")
+    with pytest.raises(MvinHipError):                        # two parents per pair: no ordered launch
+        real(ws, enc[0], enc[1], ids, None, None, torch.zeros(4, 64, device="cuda:0"), 4, 2, 16, 64, nR, 96,
+             order=torch.arange(8, dtype=torch.int32, device="cuda:0"))
+
+
 @pytest.mark.parametrize("K", [16, 32])
 def test_wave_per_parent_kernel_every_distinct_count(K, hip_lib):
     """The wave-per-parent kernel of dim 64 (mvin_fused_wpp.hip) walks a parent's distinct children four at a time, one per 16-lane group:
