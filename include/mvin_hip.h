@@ -845,6 +845,34 @@ MVIN_API int mvin_kg_explore(const int64_t* eptr, const int32_t* edst, const int
                              const int32_t* adj_entity, const int32_t* adj_relation, int K, const int32_t* seeds, int64_t n_seed,
                              int hops, void* ws, uint32_t* explored_bits, int64_t* out_counts /* [3] */, void* stream);
 
+/* ---- training with a ranking objective: the grouped head of the step (an opt-in extension; the reference trains every model
+ * with sigmoid cross-entropy and leaves its BPR lines commented out, KGAT/BPRMF.py:91-97) --
+ * mvin_rank_head: a batch of B = n_groups * G rows, group-major: row g*G + j is slot j of group g.  Slot 0 is a positive
+ * (user, item), slots 1 .. G-1 are negatives of the same user.  valid [B] (f32 0 / 1, NULL = all valid) masks slots; slot 0 is
+ * valid whatever valid says.  V_g = the valid slots of group g, N_g = V_g without slot 0.  With s[g,j] = <user_o[row],
+ * item_emb[row]> (model.py:158), one launch
+ *   - writes scores [B] = s and dscore [B] = scale * dl_g/ds[g,j] (exactly 0 on masked slots);
+ *   - writes du[row,:] = dscore[row] * item_emb[row,:] and di[row,:] = dscore[row] * user_o[row,:];
+ *   - adds scale * sum_g l_g to loss_accum[0];
+ *   - adds to counts (int64 [2], may be NULL) counts[0] += sum_g sum_{j in N_g} (2 * [s[g,j] < s[g,0]] + [s[g,j] == s[g,0]])
+ *     and counts[1] += sum_g |N_g|: counts[0] / (2 * counts[1]) is the batch's sampled pairwise accuracy, exact integers.
+ * mode MVIN_RANK_SOFTMAX (sampled softmax over one positive and the negatives):
+ *     l_g = log sum_{j in V_g} exp(s[g,j]) - s[g,0];   dl_g/ds[g,j] = p[g,j] - [j == 0] on V_g, p = softmax over V_g;
+ * mode MVIN_RANK_BPR (pairwise):
+ *     l_g = (1 / |N_g|) sum_{j in N_g} softplus(s[g,j] - s[g,0]), 0 when N_g is empty;
+ *     dl_g/ds[g,j] = sigmoid(s[g,j] - s[g,0]) / |N_g| for j in N_g, dl_g/ds[g,0] = minus their sum.
+ * At G = 2 the two are the same function, -log sigmoid(s_pos - s_neg).  Both are evaluated overflow-safe (the maximum is
+ * subtracted; softplus(x) = max(x, 0) + log1p(exp(-|x|))).
+ * scores, dscore, du and di of a group are a pure function of that group's rows: their bits depend neither on n_groups nor
+ * on the other groups nor on the launch shape.  loss_accum is summed with float atomics (one per workgroup).
+ * Errors (< 0, nothing launched): -1 for a null user_o / item_emb / scores / dscore / du / di / loss_accum; -2 for G outside
+ * [2, 64], D not a multiple of 4 or outside [4, 128], an unknown mode or n_groups < 0.  n_groups == 0 launches nothing. */
+#define MVIN_RANK_SOFTMAX 0
+#define MVIN_RANK_BPR 1
+MVIN_API int mvin_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
+                            float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum,
+                            int64_t* counts /* [2] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

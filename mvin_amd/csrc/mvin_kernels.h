@@ -446,6 +446,9 @@ hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t
 bool sample_negatives_supported(int n_item);                  // per-user negatives without replacement (mvin_negatives.hip)
 hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
                                    int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out, int64_t* status, hipStream_t st);
+hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
+                            float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
+                            hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip)
 int64_t kg_explore_ws_bytes(int n_entity, int64_t M);        // exact KG exploration counts (mvin_explore.hip)
 hipError_t launch_kg_field(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int n_entity, int64_t M,
                            const int32_t* seeds, int64_t n_seed, int hops, void* ws, uint32_t* field_bits, int64_t* out_counts,

@@ -196,6 +196,13 @@ class NegativeSampler(object):
         self.n_pos, self.n_neg = int(pos.shape[0]), int(m.sum())
         self.counts = torch.from_numpy(m.astype(np.int32)).to(self.device)
         self.neg_users = torch.from_numpy(np.repeat(np.arange(self.n_user, dtype=np.int64), m)).to(self.device)
+        # pos_index[i]: the place of positive i among its user's positives, in train_data order (rank_groups hands positive
+        # number j of a user the j-th block of the user's negatives)
+        order = np.argsort(pos[:, 0], kind="stable")
+        first = np.concatenate([[0], np.cumsum(n_pos_of)[:-1]]) if self.n_user else np.zeros(0, dtype=np.int64)
+        idx = np.empty(pos.shape[0], dtype=np.int64)
+        idx[order] = np.arange(pos.shape[0], dtype=np.int64) - first[pos[order, 0]]
+        self.pos_index = torch.from_numpy(idx).to(self.device)
         self.last_status = None
 
     def epoch(self, round):
@@ -211,6 +218,39 @@ class NegativeSampler(object):
         neg[:, 1] = items
         neg[:, 2] = 0
         return rows
+
+
+def rank_groups(sampler, round):
+    """The groups a ranking objective trains on (training.Trainer.set_objective): one group per positive of ``sampler``, a
+    ``NegativeSampler`` built with ``ratio`` = n_neg (an integer, 1..63), G = 1 + n_neg slots each.  Returns
+    (users int64 [n_pos], items int64 [n_pos, G], valid float32 [n_pos, G]) on the sampler's device, in ``train_data`` order;
+    nothing goes to the host.
+      slot 0         the positive item;
+      slots 1..n_neg positive number j of user u (``sampler.pos_index``) takes entries j*n_neg .. j*n_neg + n_neg - 1 of u's
+                     negative row of ``round`` (``sample_negatives``: distinct items, none in the exclusion row), so no two
+                     positives of a user share a negative;
+      invalid slot   one that lies beyond the user's m[u] (the sampler clipped the row) or holds -1: ``valid`` is 0 there and
+                     the slot carries the group's POSITIVE item id -- a valid id for every gather; a masked slot receives no
+                     gradient.
+    A pure function of (sampler.seed, round)."""
+    n_neg = int(sampler.ratio)
+    if n_neg != sampler.ratio or not 1 <= n_neg <= 63:
+        raise ValueError(f"rank_groups: the sampler's ratio={sampler.ratio!r} must be an integer n_neg in [1, 63]")
+    neg_ptr, neg_items, sampler.last_status = sample_negatives(sampler.excl, sampler.n_item, sampler.counts, seed=sampler.seed,
+                                                               round=round, check=False, total=sampler.n_neg)
+    dev = sampler.device
+    users, pos_item = sampler.pos_rows[:, 0].contiguous(), sampler.pos_rows[:, 1:2]
+    k = sampler.pos_index[:, None] * n_neg + torch.arange(n_neg, dtype=torch.int64, device=dev)[None, :]
+    ok = k < sampler.counts.to(torch.int64)[users][:, None]                     # inside the user's (possibly clipped) row
+    if sampler.n_neg > 0:
+        neg = neg_items.to(torch.int64)[(neg_ptr[users][:, None] + k).clamp_(max=sampler.n_neg - 1)]
+        ok &= neg >= 0
+        neg = torch.where(ok, neg, pos_item.expand(-1, n_neg))
+    else:
+        neg = pos_item.expand(-1, n_neg)
+    items = torch.cat([pos_item, neg], dim=1).contiguous()
+    valid = torch.cat([torch.ones_like(pos_item, dtype=torch.float32), ok.to(torch.float32)], dim=1).contiguous()
+    return users, items, valid
 
 
 # --------------------------------------------------------------------------- KG exploration

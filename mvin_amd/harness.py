@@ -281,7 +281,8 @@ def _epoch_trainer(feeder, batch_size, graph):
     if graph and model.trainer.world == 1:     # a data-parallel step keeps its all-reduce eager (GraphedTrainer refuses)
         gt = getattr(model, "_graphed_trainer", None)
         if (gt is None or gt.tr is not model.trainer or gt.users.shape[0] != batch_size
-                or gt._storage_key() != gt._captured):      # set_adjacency / a rebound parameter: capture again
+                or gt._storage_key() != gt._captured        # set_adjacency / a rebound parameter: capture again
+                or gt.objective != (model.trainer.objective, model.trainer.group_size)):     # ... or another head
             try:
                 gt = model._graphed_trainer = GraphedTrainer(model.trainer, batch_size)
             except RuntimeError as e:                       # capture failed: the same kernels, launched eagerly
@@ -344,6 +345,60 @@ def train_epoch_resampled(feeder, sampler, batch_size, round, graph=False, perm_
     gt = _epoch_trainer(feeder, batch_size, graph)
     data = resampled_epoch_rows(sampler, round, feeder.model.device, perm_seed)
     return _run_epoch_on_device(feeder, data, batch_size, gt)
+
+
+def ranked_epoch_groups(sampler, round, device, perm_seed=None):
+    """The groups ``train_epoch_ranked`` trains on: ``data_prep.rank_groups(sampler, round)`` with the GROUPS permuted on the
+    device, seeded exactly like ``resampled_epoch_rows``.  (users [n], items [n, G], valid [n, G]); nothing goes to the host."""
+    import torch
+    from .data_prep import rank_groups
+    users, items, valid = rank_groups(sampler, round)
+    if perm_seed is None:
+        perm_seed = (int(sampler.seed) * 0x9E3779B97F4A7C15 + int(round) * 0xC2B2AE3D27D4EB4F + 1) & ((1 << 63) - 1)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(perm_seed))
+    perm = torch.randperm(users.shape[0], generator=gen, device=device)
+    return users[perm], items[perm], valid[perm]
+
+
+def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=False, perm_seed=None):
+    """One epoch under a ranking objective ("bpr" / "softmax", training.Trainer.set_objective): every positive of ``sampler``
+    (a data_prep.NegativeSampler built with ``ratio`` = n_neg) against its n_neg fresh negatives of ``round``, as groups of
+    G = 1 + n_neg rows.  The groups are permuted on the device (``ranked_epoch_groups``) and a step takes
+    ``batch_size // G`` whole groups -- full steps only, the ragged tail dropped.  Returns the losses like the other epoch
+    functions.  ``Trainer.rank_counts`` is zeroed at the start and read back ONCE at the end: the epoch's sampled pairwise
+    accuracy (negatives scored below their positive, ties half) is left in ``model.trainer.last_pairwise_acc`` (nan for an
+    epoch without a valid negative).  A pure function of (sampler, round, perm_seed), like ``train_epoch_resampled``."""
+    import torch
+    from .training import Trainer
+    model = feeder.model
+    G = 1 + int(sampler.ratio)
+    n_g = int(batch_size) // G
+    if n_g < 1:
+        raise ValueError(f"batch_size={batch_size} holds no group of {G} rows")
+    if model.trainer is None:
+        model.trainer = Trainer(model)
+    tr = model.trainer
+    tr.set_objective(objective, G)
+    gt = _epoch_trainer(feeder, n_g * G, graph)
+    users, items, valid = ranked_epoch_groups(sampler, round, model.device, perm_seed)
+    tr.rank_counts.zero_()
+    losses, start = [], 0
+    while start + n_g <= users.shape[0]:
+        u = users[start:start + n_g].repeat_interleave(G)
+        it = items[start:start + n_g].reshape(-1)
+        v = valid[start:start + n_g].reshape(-1)
+        mh, mr, mt = feeder.memories(u)
+        if gt is not None:
+            losses.append(gt.step(u, it, v, mh, mr, mt).clone())
+        else:
+            losses.append(tr.step(u, it, v, mh, mr, mt))
+        start += n_g
+    if gt is not None and losses:
+        losses = torch.cat(losses).cpu().tolist()
+    c0, c1 = tr.rank_counts.cpu().tolist()
+    tr.last_pairwise_acc = c0 / (2.0 * c1) if c1 else float("nan")
+    return losses
 
 
 # --------------------------------------------------------------------------- ranking metrics
@@ -686,7 +741,8 @@ class EarlyStop(object):
 
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
-          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None):
+          topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
+          objective="bce", n_neg=1):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -712,6 +768,12 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     ``round`` = the epoch, seed ``args.neg_seed`` or 1; train_epoch_resampled), never an item the user has with label 1 in
     train, eval or test.  The per-epoch CTR evaluation of the train split still evaluates the fixed ``train_data``, which keeps
     the history comparable.  The draws depend on (seed, epoch) only: every rank of a multi-rank run builds the same epoch.
+    ``objective``: "bce" trains on independent (user, item, label) rows with sigmoid cross-entropy, the reference's loss;
+    "bpr" / "softmax" train every positive against ``n_neg`` (1..63) fresh negatives of the same user per epoch
+    (train_epoch_ranked: groups of 1 + n_neg rows, ``args.batch_size // (1 + n_neg)`` groups per step) and need
+    ``negatives="resample"``.  An opt-in extension (the reference trains with cross-entropy only); the epoch record gains
+    "pairwise_acc", the sampled pairwise accuracy of the epoch's training steps.  Evaluation, early stopping and
+    ``topk_impl`` are the same under every objective.
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
@@ -719,6 +781,16 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
     if negatives not in ("fixed", "resample"):
         raise ValueError(f"negatives={negatives!r}: expected 'fixed' or 'resample'")
+    if objective not in ("bce", "bpr", "softmax"):
+        raise ValueError(f"objective={objective!r}: expected 'bce', 'bpr' or 'softmax'")
+    ranked = objective != "bce"
+    if ranked:
+        if negatives != "resample":
+            raise ValueError(f"objective={objective!r} draws its negatives per epoch: it needs negatives='resample'")
+        if int(n_neg) != n_neg or not 1 <= int(n_neg) <= 63:
+            raise ValueError(f"n_neg={n_neg!r}: expected an integer in [1, 63]")
+        if args.batch_size < 1 + int(n_neg):
+            raise ValueError(f"batch_size={args.batch_size} holds no group of 1 + n_neg = {1 + int(n_neg)} rows")
     from .model import MVIN
     n_user, n_item, n_entity, n_relation = data[0], data[1], data[2], data[3]
     train_data, eval_data, test_data = (np.asarray(d) for d in data[4:7])
@@ -743,15 +815,22 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     sampler = None
     if negatives == "resample":
         from .data_prep import NegativeSampler
-        sampler = NegativeSampler(train_data, n_user, n_item, exclude=(eval_data, test_data), ratio=1.0,
-                                  seed=getattr(args, "neg_seed", 1), device=model.device)
+        sampler = NegativeSampler(train_data, n_user, n_item, exclude=(eval_data, test_data),
+                                  ratio=float(int(n_neg)) if ranked else 1.0, seed=getattr(args, "neg_seed", 1),
+                                  device=model.device)
+    if not ranked and model.trainer is not None:
+        model.trainer.set_objective("bce")
     for epoch in range(getattr(args, "n_epochs", 20)):
         use_graph = (args.batch_size <= 2048) if graph == "auto" else bool(graph)
-        if sampler is not None:
+        if ranked:
+            losses = train_epoch_ranked(feeder, sampler, args.batch_size, epoch, objective, graph=use_graph)
+        elif sampler is not None:
             losses = train_epoch_resampled(feeder, sampler, args.batch_size, epoch, graph=use_graph)
         else:
             losses = train_epoch_device(feeder, train_data, args.batch_size, rng=rng, graph=use_graph)
         rec = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else float("nan")}
+        if ranked:
+            rec["pairwise_acc"] = model.trainer.last_pairwise_acc
         if show_topk:
             for mode in ("eval", "test"):
                 if topk_impl in ("batched", "ranked"):

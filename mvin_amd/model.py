@@ -1294,8 +1294,9 @@ class MVIN(object):
             g = self._train_graphs.get(B)
             if g is False:
                 g = None
-            elif g is not None and g._storage_key() != g._captured:
-                g = None                                   # adjacency / a parameter tensor replaced: capture again
+            elif g is not None and (g._storage_key() != g._captured
+                                    or g.objective != (self.trainer.objective, self.trainer.group_size)):
+                g = None                                   # adjacency / a parameter tensor replaced, another objective: capture again
             if g is None and self._train_seen == B and self._train_graphs.get(B) is not False:
                 try:
                     g = self._train_graphs[B] = GraphedTrainer(self.trainer, B, ids_dtype=item.dtype, warmup=0)

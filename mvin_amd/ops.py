@@ -1292,6 +1292,47 @@ def eltwise(mode, n, x, y=None, z=None, w=None, accum=None, alpha=1.0, beta=0.0,
                                 _stream()), "mvin_eltwise")
 
 
+RANK_MODES = {"softmax": 0, "bpr": 1}      # MVIN_RANK_SOFTMAX / MVIN_RANK_BPR
+
+
+def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None, counts=None, out=None):
+    """mvin_rank_head: the grouped ranking head of the training step in one launch.  ``user_o`` / ``item_emb`` f32 [B, D],
+    B = n_groups * ``group_size`` rows group-major (slot 0 of a group the positive, the others negatives of the same user);
+    ``valid`` f32 [B] of 0 / 1 (None: every slot counts); ``mode`` "softmax" or "bpr" (include/mvin_hip.h states both).
+    Adds ``scale`` * sum of the group losses to ``loss_accum`` (f32 [1]) and, when given, the pairwise-accuracy integers to
+    ``counts`` (int64 [2]).  Returns (scores [B], dscore [B], du [B, D], di [B, D]); ``out`` may pass those four buffers in.
+    Enqueues only."""
+    if mode not in RANK_MODES:
+        raise ValueError(f"mode={mode!r}: expected 'softmax' or 'bpr'")
+    _chk(user_o, F32, "user_o"), _chk(item_emb, F32, "item_emb"), _chk(loss_accum, F32, "loss_accum")
+    _chk(valid, F32, "valid"), _chk(counts, torch.int64, "counts")
+    G = int(group_size)
+    if user_o.dim() != 2 or tuple(item_emb.shape) != tuple(user_o.shape):
+        raise ValueError(f"user_o {tuple(user_o.shape)} and item_emb {tuple(item_emb.shape)}: expected [B, D] both")
+    B, D = user_o.shape
+    if G < 1 or B % G:
+        raise ValueError(f"{B} rows are not whole groups of {G}")
+    if valid is not None and valid.numel() != B:
+        raise ValueError(f"valid: {valid.numel()} flags for {B} rows")
+    if counts is not None and counts.numel() != 2:
+        raise ValueError("counts: expected int64 [2]")
+    if out is None:
+        dev = user_o.device
+        out = (torch.empty(B, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev),
+               torch.empty((B, D), dtype=F32, device=dev), torch.empty((B, D), dtype=F32, device=dev))
+    scores, dscore, du, di = out
+    for t, nm, n in ((scores, "scores", B), (dscore, "dscore", B), (du, "du", B * D), (di, "di", B * D)):
+        _chk(t, F32, nm)
+        if t.numel() != n:
+            raise ValueError(f"{nm}: {t.numel()} elements, expected {n}")
+    if B == 0:                                  # an empty tensor has no address to pass
+        return scores, dscore, du, di
+    _lib.check(_lib.load().mvin_rank_head(_p(user_o), _p(item_emb), _p(valid), B // G, G, D, RANK_MODES[mode], float(scale),
+                                          _p(scores), _p(dscore), _p(du), _p(di), _p(loss_accum), _p(counts), _stream()),
+               "mvin_rank_head")
+    return scores, dscore, du, di
+
+
 def count_ids(ids, nbins, out=None):
     """mvin_count_ids: float occurrence counts [nbins] of an int32 id list (no host sync); added to ``out``."""
     _chk(ids, I32, "ids")

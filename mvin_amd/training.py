@@ -58,12 +58,18 @@ class _Grads(object):
 class Trainer(object):
     """Owns the Adam state of an mvin_amd.model.MVIN and runs training steps on it."""
 
-    def __init__(self, model, lr=None, beta1=0.9, beta2=0.999, eps=1e-8, group=None, world=1):
+    OBJECTIVES = ("bce", "bpr", "softmax")
+
+    def __init__(self, model, lr=None, beta1=0.9, beta2=0.999, eps=1e-8, group=None, world=1, objective="bce",
+                 group_size=None):
         """``world`` > 1: data-parallel training, one process per GPU.  Every rank steps on its own
         1/world of the batch; the data-dependent gradients (and loss terms) of all ranks are summed
         with ONE all-reduce of the flat gradient buffer (RCCL: torch.distributed backend "nccl") before
         the per-parameter L2 terms and the Adam update, which every rank then applies identically --
-        parameters stay bit-identical across ranks."""
+        parameters stay bit-identical across ranks.
+
+        ``objective``: "bce" (the reference's sigmoid cross-entropy over independent rows, model.py:379-380) or a ranking
+        objective over groups of ``group_size`` = 1 + n_neg rows, "bpr" / "softmax" (``set_objective``)."""
         a = model.args
         self.group, self.world = group, int(world)
         if not a.wide_deep:
@@ -81,6 +87,32 @@ class Trainer(object):
         self.params = self._named_params()
         self._build_flat_state()
         self.last_grads = None
+        # pairwise-accuracy integers of the ranked objectives (mvin_rank_head's counts): allocated ONCE, so a captured step
+        # keeps accumulating into it across replays; the caller zeroes and reads it
+        self.rank_counts = torch.zeros(2, dtype=torch.int64, device=model.device)
+        self.last_pairwise_acc = None        # harness.train_epoch_ranked: rank_counts[0] / (2 rank_counts[1]) of its last epoch
+        self.set_objective(objective, group_size)
+
+    def set_objective(self, objective, group_size=None):
+        """Choose the head of the step; parameters, Adam moments and the step counter are kept.
+          "bce"      sigmoid cross-entropy of every row against its label -- the reference's loss and the default;
+          "softmax"  sampled softmax over groups of ``group_size`` consecutive rows: slot 0 of a group is a positive
+                     (user, item), the other slots are negatives of the same user;
+          "bpr"      pairwise BPR over the same groups, the mean over the group's negatives.
+        With a ranking objective the ``labels`` argument of ``step`` / ``enqueue`` carries the slot VALIDITY (1.0 / 0.0; slot 0
+        always counts): a masked slot enters neither the loss nor any data gradient.  The data term is the mean of the group
+        losses over the global batch's groups, 1 / (n_groups * world) each (include/mvin_hip.h: mvin_rank_head states both
+        forms).  The regularisers of model.py:382-412 stay exactly as they are: over EVERY fed row, masked rows included --
+        a masked slot's ripple-set rows are still in the gathered-row L2 term."""
+        if objective not in self.OBJECTIVES:
+            raise ValueError(f"objective={objective!r}: expected one of {self.OBJECTIVES}")
+        if objective == "bce":
+            if group_size is not None:
+                raise ValueError("group_size belongs to the ranking objectives ('bpr' / 'softmax')")
+        elif group_size is None or int(group_size) != group_size or not 2 <= int(group_size) <= 64:
+            raise ValueError(f"group_size={group_size!r}: objective {objective!r} needs 1 + n_neg rows per group, 2..64")
+        self.objective = objective
+        self.group_size = None if objective == "bce" else int(group_size)
 
     def _l2_coefficients(self):
         """Coefficient c of the (c/2) sum(x^2) term of every parameter (slice), model.py:387-412."""
@@ -190,12 +222,15 @@ class Trainer(object):
         """Enqueue one training step on the current stream without any host synchronisation; returns the
         1-element device tensor the loss is accumulated in.  ``lr_dev`` (1-element fp32 device tensor): the
         Adam step size is read from it when the optimizer kernel runs and the step counter is left to the
-        caller -- the form GraphedTrainer captures."""
+        caller -- the form GraphedTrainer captures.  Under a ranking objective (``set_objective``) the rows are whole
+        groups, group-major, and ``labels`` carries the slot validity."""
         m, a = self.m, self.m.args
         dev = m.device
         D, K, H, M, P, nR = m.dim, m.n_neighbor, m.h_hop, m.n_mix_hop, m.p_hop, m.n_relation
         L = M * H
         B = item_indices.shape[0]
+        if self.objective != "bce" and (B == 0 or B % self.group_size):
+            raise ValueError(f"objective {self.objective!r}: a batch of {B} rows is not whole groups of {self.group_size}")
         E, U, R = m.entity_emb_matrix, m.user_emb_matrix, m.relation_emb_KGE_matrix
         user = user_indices.contiguous()
         item = item_indices.contiguous()
@@ -484,15 +519,22 @@ class Trainer(object):
                 ev = new
 
         # scores = sum_d user_o * item_emb (model.py:158) ; loss (model.py:379-380)
-        _, scores, _ = ops.linear([item_emb.view(B, D)], None, D, score_u=user_o)
-        dscore = torch.empty(B, dtype=F32, device=dev)
-        # reduce_mean over the GLOBAL batch (model.py:379): with data parallelism the ranks' sums add up
-        inv_b = 1.0 / (B * self.world)
-        ops.eltwise(1, B, scores, dscore, z=labels, accum=loss_acc, alpha=inv_b, beta=inv_b)
-        du = torch.empty((B, D), dtype=F32, device=dev)
-        di = torch.empty((B, D), dtype=F32, device=dev)
-        ops.eltwise(5, B * D, item_emb.view(B, D), du, z=dscore, alpha=1.0, beta=0.0, D=D)
-        ops.eltwise(5, B * D, user_o, di, z=dscore, alpha=1.0, beta=0.0, D=D)
+        if self.objective == "bce":
+            _, scores, _ = ops.linear([item_emb.view(B, D)], None, D, score_u=user_o)
+            dscore = torch.empty(B, dtype=F32, device=dev)
+            # reduce_mean over the GLOBAL batch (model.py:379): with data parallelism the ranks' sums add up
+            inv_b = 1.0 / (B * self.world)
+            ops.eltwise(1, B, scores, dscore, z=labels, accum=loss_acc, alpha=inv_b, beta=inv_b)
+            du = torch.empty((B, D), dtype=F32, device=dev)
+            di = torch.empty((B, D), dtype=F32, device=dev)
+            ops.eltwise(5, B * D, item_emb.view(B, D), du, z=dscore, alpha=1.0, beta=0.0, D=D)
+            ops.eltwise(5, B * D, user_o, di, z=dscore, alpha=1.0, beta=0.0, D=D)
+        else:
+            # grouped head (set_objective): ``labels`` is the slot validity; score, loss, dscore, du and di in ONE launch,
+            # the mean over the GLOBAL batch's groups
+            n_groups = B // self.group_size
+            _, _, du, di = ops.rank_head(user_o, item_emb.view(B, D), self.group_size, self.objective,
+                                         1.0 / (n_groups * self.world), loss_acc, valid=labels, counts=self.rank_counts)
         G.add(user_o, du)
         G.add(item_emb, di.view_as(item_emb))
 
@@ -592,6 +634,7 @@ class GraphedTrainer(object):
             self.loss = trainer.enqueue(*feed, apply=True, lr_dev=self.lr_dev)
         m.invalidate()                           # nothing ran during capture: no derived table is valid yet
         self._captured = self._storage_key()
+        self.objective = (trainer.objective, trainer.group_size)     # the head the captured launches are
 
     def _storage_key(self):
         """Addresses the captured launches read: a graph outlives neither ``set_adjacency`` nor a parameter tensor
@@ -617,6 +660,9 @@ class GraphedTrainer(object):
         if self._storage_key() != self._captured:
             raise RuntimeError("the model's adjacency or a parameter tensor was replaced since this step was captured: "
                                "build a new GraphedTrainer")
+        if (tr.objective, tr.group_size) != self.objective:
+            raise RuntimeError(f"the trainer's objective changed to {(tr.objective, tr.group_size)} since this step was "
+                               f"captured with {self.objective}: build a new GraphedTrainer")
         tr.t += 1
         self.lr_dev.fill_(float(tr.lr_t(tr.t)))
         self.graph.replay()
