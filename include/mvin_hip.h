@@ -873,6 +873,36 @@ MVIN_API int mvin_rank_head(const float* user_o, const float* item_emb, const fl
                             float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum,
                             int64_t* counts /* [2] or NULL */, void* stream);
 
+/* ---- hard negatives for the ranking objectives: pick the negatives a step trains on out of a scored pool (dynamic negative
+ * sampling; an opt-in extension, the reference trains on the fixed negatives of its ratings file) --
+ * mvin_select_negatives: n_groups pool groups of Gp slots, row-major.  Slot 0 of a group is the positive, slots 1 .. Gp-1 are
+ * candidate negatives of the same user; scores [n_groups, Gp] are the current model's scores of the slots, items their ids,
+ * valid (f32, NULL = every slot) masks slots.  For group g, with key_g = group_key[g] (NULL: g):
+ *   candidates  the slots j in 1 .. Gp-1 with valid[g,j] != 0; C_g of them;
+ *   order A     higher score first, ties to the lower slot.  Scores compare as mvin_topk_rows compares them: -0.0 equals +0.0,
+ *               every NaN ranks below -inf and all NaNs are equal (csrc/mvin_score_image.h, the one comparator of both);
+ *   shortlist   the first min(shortlist, C_g) candidates in order A;
+ *   order B     over the shortlist: ascending r_j = rnd32(seed, 5, key_g, round, j) (csrc/mvin_rnd.h, stream 5;
+ *               oracle/prep_ref.py:rnd32 on the host), ties to the lower slot;
+ *   chosen      the first min(n_neg, |shortlist|) of the shortlist in order B.
+ * Output row g (1 + n_neg slots, the layout of data_prep.rank_groups): slot 0 = items[g,0] with out_valid 1; slots 1 .. hold the
+ * chosen candidates in order A (hardest first) with out_valid 1; the remaining slots hold items[g,0] with out_valid 0.
+ * out_scores (may be NULL) carries the input bits of each written slot's score and the quiet NaN 0x7FC00000 in unfilled slots.
+ * shortlist == n_neg is "the n_neg hardest"; shortlist == Gp - 1 is a uniform n_neg-subset of the candidates whatever the
+ * scores; in between, "uniform among the `shortlist` hardest".
+ * counts (int64 [4], may be NULL; integer atomics, ACCUMULATED): with s_0 the positive's score and every comparison under the
+ * order above, counts[0] += sum over the chosen of (2 * [s_j > s_0] + [s_j == s_0]), counts[1] += the number chosen;
+ * counts[2], counts[3]: the same two sums over all candidates.  counts[0] / (2 * counts[1]) is the share of trained negatives
+ * the model ranks above their positive, counts[2] / (2 * counts[3]) that share of the whole pool.
+ * Every output row is a pure function of its own group's scores / items / valid and (seed, round, key_g): it depends neither on
+ * n_groups nor on the other groups, the launch shape or timing.
+ * Errors (< 0, nothing launched): -1 for a null scores / items / out_items / out_valid; -2 for Gp outside [2, 64], n_neg outside
+ * [1, Gp-1], shortlist outside [n_neg, Gp-1] or n_groups < 0.  n_groups == 0 launches nothing. */
+MVIN_API int mvin_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key,
+                                   int64_t n_groups, int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round,
+                                   int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts /* [4] or NULL */,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1639,6 +1639,21 @@ int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, cons
                                                     status, (hipStream_t)stream), who);
 }
 
+int mvin_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key, int64_t n_groups,
+                          int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round, int64_t* out_items, float* out_valid,
+                          float* out_scores, int64_t* counts, void* stream) {
+    const char* who = "mvin_select_negatives";
+    if (!scores || !items || !out_items || !out_valid)
+        return fail(-1, "%s: null pointer (scores / items / out_items / out_valid)", who);
+    if (Gp < 2 || Gp > 64) return fail(-2, "%s: Gp=%d (2..64)", who, Gp);
+    if (n_neg < 1 || n_neg > Gp - 1) return fail(-2, "%s: n_neg=%d (1..Gp-1 = %d)", who, n_neg, Gp - 1);
+    if (shortlist < n_neg || shortlist > Gp - 1)
+        return fail(-2, "%s: shortlist=%d (n_neg..Gp-1 = %d..%d)", who, shortlist, n_neg, Gp - 1);
+    if (n_groups < 0) return fail(-2, "%s: n_groups=%lld", who, (long long)n_groups);
+    return hip_result(mvin::launch_select_negatives(scores, items, valid, group_key, n_groups, Gp, n_neg, shortlist, seed, round,
+                                                    out_items, out_valid, out_scores, counts, (hipStream_t)stream), who);
+}
+
 // ---------------------------------------------------------------------------- training
 int mvin_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode, float scale,
                    float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts, void* stream) {

@@ -449,6 +449,10 @@ hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_
 hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
                             float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
                             hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip)
+hipError_t launch_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key,
+                                   int64_t n_groups, int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round,
+                                   int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts,
+                                   hipStream_t st);           // hard negatives out of a scored pool (mvin_select_negatives.hip)
 int64_t kg_explore_ws_bytes(int n_entity, int64_t M);        // exact KG exploration counts (mvin_explore.hip)
 hipError_t launch_kg_field(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int n_entity, int64_t M,
                            const int32_t* seeds, int64_t n_seed, int hops, void* ws, uint32_t* field_bits, int64_t* out_counts,

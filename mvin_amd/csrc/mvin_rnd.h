@@ -1,6 +1,6 @@
-// The draw function of the GPU samplers (mvin_prep.hip, mvin_negatives.hip): every draw is a pure function of
+// The draw function of the GPU samplers (mvin_prep.hip, mvin_negatives.hip, mvin_select_negatives.hip): every draw is a pure function of
 // (seed, stream, a, b, c) through a splitmix64 finaliser.  oracle/prep_ref.py restates it in Python integers.
-// Streams in use: 1 adjacency, 2 / 3 ripple sets, 4 negatives.
+// Streams in use: 1 adjacency, 2 / 3 ripple sets, 4 negatives, 5 hard-negative selection (mvin_select_negatives.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -253,6 +253,40 @@ def rank_groups(sampler, round):
     return users, items, valid
 
 
+def select_negatives(*args, **kwargs):
+    """ops.select_negatives (mvin_select_negatives), bound late: ``hard_groups`` reaches the kernel through this name."""
+    from . import ops
+    return ops.select_negatives(*args, **kwargs)
+
+
+def hard_groups(sampler, round, scores, n_neg, shortlist, group_key=None, counts=None, pool=None):
+    """The groups a ranking objective trains on under ``negatives="hard"``: out of the POOL groups of ``sampler`` -- a
+    ``NegativeSampler`` built with ``ratio`` = M, the pool size, ``rank_groups(sampler, round)``: one positive and up to M
+    distinct unwatched items of its user -- and the current model's ``scores`` of every pool slot (f32 [n, 1 + M]), the
+    ``n_neg`` negatives per positive that mvin_select_negatives picks: uniform among the ``shortlist`` highest-scored valid
+    candidates (include/mvin_hip.h states the rule; ``shortlist == n_neg``: the hardest, ``shortlist == M``: uniform whatever
+    the scores).  ``pool``: the (users, items, valid) of ``rank_groups(sampler, round)`` or a row subset of it, when the caller
+    holds it already (None: drawn here); ``group_key`` int64 [n]: each row's index in ``train_data`` order (None: row g is
+    positive g), the key of the row's random draw, so that a row's result does not depend on where it stands.
+    Returns (users int64 [n], items int64 [n, 1 + n_neg], valid f32 [n, 1 + n_neg]) in the layout of ``rank_groups``, the chosen
+    negatives hardest first; ``counts`` (int64 [4]) accumulates the integers of "hard_rate" / "pool_rate".  A pure function of
+    (sampler.seed, round, scores); nothing goes to the host."""
+    M = int(sampler.ratio)
+    n_neg, shortlist = int(n_neg), int(shortlist)
+    if M != sampler.ratio or not 1 <= M <= 63:
+        raise ValueError(f"hard_groups: the sampler's ratio={sampler.ratio!r} must be an integer pool size in [1, 63]")
+    if not 1 <= n_neg <= M:
+        raise ValueError(f"hard_groups: n_neg={n_neg} must lie in [1, pool = {M}]")
+    if not n_neg <= shortlist <= M:
+        raise ValueError(f"hard_groups: shortlist={shortlist} must lie in [n_neg = {n_neg}, pool = {M}]")
+    users, items, valid = rank_groups(sampler, round) if pool is None else pool
+    if tuple(scores.shape) != tuple(items.shape):
+        raise ValueError(f"hard_groups: scores {tuple(scores.shape)} for pool groups {tuple(items.shape)}")
+    out_items, out_valid = select_negatives(scores, items, valid, n_neg, shortlist, sampler.seed, round, group_key=group_key,
+                                            counts=counts)
+    return users, out_items, out_valid
+
+
 # --------------------------------------------------------------------------- KG exploration
 def kg_edge_index(csr):
     """The DISTINCT edges of a ``build_csr`` KG as (eptr int64 [nE+1], edst int32 [M], erel int32 [M]) on its device: row h =

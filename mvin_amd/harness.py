@@ -323,17 +323,23 @@ def train_epoch_device(feeder, train_data, batch_size, rng=None, graph=False):
     return _run_epoch_on_device(feeder, data, batch_size, gt)
 
 
-def resampled_epoch_rows(sampler, round, device, perm_seed=None):
-    """The rows ``train_epoch_resampled`` trains on: ``sampler.epoch(round)`` permuted on the device by a
-    ``torch.Generator`` seeded with ``perm_seed`` (None: derived from the sampler's seed and ``round``), so the same
-    (sampler, round, perm_seed) gives the same rows in the same order.  int64 [n, 3] on ``device``; nothing goes to the host."""
+def _epoch_perm(sampler, round, n, device, perm_seed=None):
+    """The permutation of an epoch's ``n`` rows or groups, on the device: a ``torch.Generator`` seeded with ``perm_seed``
+    (None: derived from the sampler's seed and ``round``)."""
     import torch
-    rows = sampler.epoch(round)
     if perm_seed is None:
         perm_seed = (int(sampler.seed) * 0x9E3779B97F4A7C15 + int(round) * 0xC2B2AE3D27D4EB4F + 1) & ((1 << 63) - 1)
     gen = torch.Generator(device=device)
     gen.manual_seed(int(perm_seed))
-    return rows[torch.randperm(rows.shape[0], generator=gen, device=device)]
+    return torch.randperm(n, generator=gen, device=device)
+
+
+def resampled_epoch_rows(sampler, round, device, perm_seed=None):
+    """The rows ``train_epoch_resampled`` trains on: ``sampler.epoch(round)`` permuted on the device by a
+    ``torch.Generator`` seeded with ``perm_seed`` (None: derived from the sampler's seed and ``round``), so the same
+    (sampler, round, perm_seed) gives the same rows in the same order.  int64 [n, 3] on ``device``; nothing goes to the host."""
+    rows = sampler.epoch(round)
+    return rows[_epoch_perm(sampler, round, rows.shape[0], device, perm_seed)]
 
 
 def train_epoch_resampled(feeder, sampler, batch_size, round, graph=False, perm_seed=None):
@@ -350,14 +356,9 @@ def train_epoch_resampled(feeder, sampler, batch_size, round, graph=False, perm_
 def ranked_epoch_groups(sampler, round, device, perm_seed=None):
     """The groups ``train_epoch_ranked`` trains on: ``data_prep.rank_groups(sampler, round)`` with the GROUPS permuted on the
     device, seeded exactly like ``resampled_epoch_rows``.  (users [n], items [n, G], valid [n, G]); nothing goes to the host."""
-    import torch
     from .data_prep import rank_groups
     users, items, valid = rank_groups(sampler, round)
-    if perm_seed is None:
-        perm_seed = (int(sampler.seed) * 0x9E3779B97F4A7C15 + int(round) * 0xC2B2AE3D27D4EB4F + 1) & ((1 << 63) - 1)
-    gen = torch.Generator(device=device)
-    gen.manual_seed(int(perm_seed))
-    perm = torch.randperm(users.shape[0], generator=gen, device=device)
+    perm = _epoch_perm(sampler, round, users.shape[0], device, perm_seed)
     return users[perm], items[perm], valid[perm]
 
 
@@ -383,6 +384,19 @@ def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=Fals
     gt = _epoch_trainer(feeder, n_g * G, graph)
     users, items, valid = ranked_epoch_groups(sampler, round, model.device, perm_seed)
     tr.rank_counts.zero_()
+    losses = _ranked_steps(feeder, tr, gt, users, items, valid, n_g)
+    if gt is not None and losses:
+        losses = torch.cat(losses).cpu().tolist()
+    c0, c1 = tr.rank_counts.cpu().tolist()
+    tr.last_pairwise_acc = c0 / (2.0 * c1) if c1 else float("nan")
+    return losses
+
+
+def _ranked_steps(feeder, tr, gt, users, items, valid, n_g):
+    """The step loop of a ranked epoch (train_epoch_ranked, train_epoch_hard): ``n_g`` whole groups of ``users`` [n] /
+    ``items`` / ``valid`` [n, G] per step, full steps only.  Returns the step losses: floats of the eager step (``gt`` None),
+    device tensors of the replayed one (the caller reads them back once)."""
+    G = items.shape[1]
     losses, start = [], 0
     while start + n_g <= users.shape[0]:
         u = users[start:start + n_g].repeat_interleave(G)
@@ -394,10 +408,97 @@ def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=Fals
         else:
             losses.append(tr.step(u, it, v, mh, mr, mt))
         start += n_g
+    return losses
+
+
+def score_pool(feeder, users, items, max_pairs=524288, out=None):
+    """The current model's sigmoid scores of every slot of the pool groups ``users`` [n] / ``items`` [n, Gp] as one f32
+    [n, Gp] device buffer (``out`` if given): ``DeviceFeeder.scores`` -- no gradient, no tape -- over chunks of whole groups of
+    at most ``max_pairs`` pairs.  Enqueues only."""
+    import torch
+    n, Gp = items.shape
+    per = max(1, int(max_pairs) // Gp)
+    if out is None:
+        out = torch.empty((n, Gp), dtype=torch.float32, device=items.device)
+    for g0 in range(0, n, per):
+        g1 = min(n, g0 + per)
+        out[g0:g1].view(-1).copy_(feeder.scores(users[g0:g1].repeat_interleave(Gp), items[g0:g1].reshape(-1)))
+    return out
+
+
+def hard_epoch_groups(feeder, sampler, round, n_neg, shortlist, pool=None, index=None, counts=None, max_pairs=524288,
+                      return_pool=False):
+    """The groups ``train_epoch_hard`` trains on, for the weights the model has NOW: draw the pool
+    (``data_prep.rank_groups(sampler, round)``, ``sampler`` built with ``ratio`` = the pool size M; or take ``pool``, that
+    triple, from the caller), score every pool slot (``score_pool``), and let mvin_select_negatives pick ``n_neg`` of the
+    ``shortlist`` highest-scored candidates of every group (``data_prep.hard_groups``).  ``index`` int64 [m]: the rows (in
+    ``train_data`` order) to do this for, in that order -- a part of a permuted epoch; it is also each row's selection key, so
+    a row's draw depends neither on the permutation nor on how the epoch is cut into parts.  None: every row.
+    Returns (users [m], items [m, 1 + n_neg], valid [m, 1 + n_neg]); with ``return_pool`` also (pool items [m, 1 + M],
+    pool valid, scores f32 [m, 1 + M]) of the same rows.  ``counts`` int64 [4] accumulates.  Nothing goes to the host."""
+    from .data_prep import hard_groups, rank_groups
+    users, items, valid = rank_groups(sampler, round) if pool is None else pool
+    if index is not None:
+        users, items, valid = users[index], items[index].contiguous(), valid[index].contiguous()
+    scores = score_pool(feeder, users, items, max_pairs)
+    out = hard_groups(sampler, round, scores, n_neg, shortlist, group_key=index, counts=counts, pool=(users, items, valid))
+    return out + (items, valid, scores) if return_pool else out
+
+
+def train_epoch_hard(feeder, sampler, batch_size, round, objective, n_neg, shortlist=None, rescore=1, graph=False,
+                     perm_seed=None, max_pairs=524288):
+    """One epoch under a ranking objective on HARD negatives (dynamic negative sampling): ``sampler`` is a
+    data_prep.NegativeSampler built with ``ratio`` = the pool size M (n_neg <= M <= 63).  Every positive gets a pool of M
+    distinct unwatched items of its user for ``round``; the pool is scored with the current weights and ``n_neg`` of the
+    ``shortlist`` (None: n_neg, "the hardest") highest-scored candidates are trained on (``hard_epoch_groups``).  The groups are
+    permuted and stepped through exactly as in ``train_epoch_ranked`` (same ``perm_seed`` rule, ``batch_size // (1 + n_neg)``
+    whole groups per step, full steps only).  ``rescore`` = k cuts the permuted epoch into k consecutive parts and scores and
+    selects each part immediately before training on it, so later parts see newer weights.  Single rank only: the ranks of a
+    data-parallel run would have to reproduce the same scores bit for bit.
+    Leaves in ``model.trainer``: ``last_pairwise_acc`` as ``train_epoch_ranked`` does, and ``last_hard_rate`` /
+    ``last_pool_rate``, the share of the trained negatives / of all pool candidates that the model scored above their positive
+    (ties half; nan without a candidate), exact integers read back once together with ``rank_counts``."""
+    import torch
+    from .data_prep import rank_groups
+    from .training import Trainer
+    model = feeder.model
+    n_neg = int(n_neg)
+    shortlist = n_neg if shortlist is None else int(shortlist)
+    rescore = int(rescore)
+    if rescore < 1:
+        raise ValueError(f"rescore={rescore}: expected >= 1")
+    G = 1 + n_neg
+    n_g = int(batch_size) // G
+    if n_g < 1:
+        raise ValueError(f"batch_size={batch_size} holds no group of {G} rows")
+    if model.trainer is None:
+        model.trainer = Trainer(model)
+    tr = model.trainer
+    if tr.world > 1:
+        raise ValueError(f"train_epoch_hard: single rank only (world={tr.world})")
+    tr.set_objective(objective, G)
+    gt = _epoch_trainer(feeder, n_g * G, graph)
+    dev = model.device
+    pool = rank_groups(sampler, round)
+    n = pool[0].shape[0]
+    perm = _epoch_perm(sampler, round, n, dev, perm_seed)
+    tr.rank_counts.zero_()
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    steps = n // n_g
+    losses = []
+    for part in range(rescore):                  # parts of whole steps; the ragged tail is dropped as in train_epoch_ranked
+        s0, s1 = steps * part // rescore, steps * (part + 1) // rescore
+        if s1 == s0:
+            continue
+        users, items, valid = hard_epoch_groups(feeder, sampler, round, n_neg, shortlist, pool=pool,
+                                                index=perm[s0 * n_g:s1 * n_g], counts=counts, max_pairs=max_pairs)
+        losses += _ranked_steps(feeder, tr, gt, users, items, valid, n_g)
     if gt is not None and losses:
         losses = torch.cat(losses).cpu().tolist()
-    c0, c1 = tr.rank_counts.cpu().tolist()
-    tr.last_pairwise_acc = c0 / (2.0 * c1) if c1 else float("nan")
+    c = torch.cat([tr.rank_counts, counts]).cpu().tolist()
+    tr.last_pairwise_acc = c[0] / (2.0 * c[1]) if c[1] else float("nan")
+    tr.last_hard_rate = c[2] / (2.0 * c[3]) if c[3] else float("nan")
+    tr.last_pool_rate = c[4] / (2.0 * c[5]) if c[5] else float("nan")
     return losses
 
 
@@ -742,7 +843,7 @@ class EarlyStop(object):
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
-          objective="bce", n_neg=1):
+          objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -774,23 +875,39 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     ``negatives="resample"``.  An opt-in extension (the reference trains with cross-entropy only); the epoch record gains
     "pairwise_acc", the sampled pairwise accuracy of the epoch's training steps.  Evaluation, early stopping and
     ``topk_impl`` are the same under every objective.
+    ``negatives="hard"`` (with a ranking objective; single rank): dynamic negative sampling.  Every epoch draws ``pool`` (n_neg
+    .. 63) fresh candidates per positive, scores them with the current weights and trains on ``n_neg`` of the ``shortlist``
+    (n_neg .. pool; None = n_neg, the hardest; pool = uniform) highest-scored ones, picked on the device by
+    mvin_select_negatives (train_epoch_hard); ``rescore`` = k scores and picks again before each k-th of the epoch.  The epoch
+    record also gains "hard_rate" and "pool_rate": the share of the trained negatives, and of all pool candidates, that the
+    model scored above their positive.
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
     if ctr_impl not in ("host", "batched"):
         raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
-    if negatives not in ("fixed", "resample"):
-        raise ValueError(f"negatives={negatives!r}: expected 'fixed' or 'resample'")
+    if negatives not in ("fixed", "resample", "hard"):
+        raise ValueError(f"negatives={negatives!r}: expected 'fixed', 'resample' or 'hard'")
     if objective not in ("bce", "bpr", "softmax"):
         raise ValueError(f"objective={objective!r}: expected 'bce', 'bpr' or 'softmax'")
     ranked = objective != "bce"
+    hard = negatives == "hard"
+    if hard and not ranked:
+        raise ValueError("negatives='hard' picks the negatives of a ranking objective: it needs objective='bpr' or 'softmax'")
     if ranked:
-        if negatives != "resample":
-            raise ValueError(f"objective={objective!r} draws its negatives per epoch: it needs negatives='resample'")
+        if negatives == "fixed":
+            raise ValueError(f"objective={objective!r} draws its negatives per epoch: it needs negatives='resample' (or 'hard')")
         if int(n_neg) != n_neg or not 1 <= int(n_neg) <= 63:
             raise ValueError(f"n_neg={n_neg!r}: expected an integer in [1, 63]")
         if args.batch_size < 1 + int(n_neg):
             raise ValueError(f"batch_size={args.batch_size} holds no group of 1 + n_neg = {1 + int(n_neg)} rows")
+    if hard:
+        if int(pool) != pool or not int(n_neg) <= int(pool) <= 63:
+            raise ValueError(f"pool={pool!r}: expected an integer in [n_neg = {int(n_neg)}, 63]")
+        if shortlist is not None and (int(shortlist) != shortlist or not int(n_neg) <= int(shortlist) <= int(pool)):
+            raise ValueError(f"shortlist={shortlist!r}: expected an integer in [n_neg = {int(n_neg)}, pool = {int(pool)}] or None")
+        if int(rescore) != rescore or int(rescore) < 1:
+            raise ValueError(f"rescore={rescore!r}: expected an integer >= 1")
     from .model import MVIN
     n_user, n_item, n_entity, n_relation = data[0], data[1], data[2], data[3]
     train_data, eval_data, test_data = (np.asarray(d) for d in data[4:7])
@@ -813,16 +930,19 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     history = []
     train_data = train_data.copy()
     sampler = None
-    if negatives == "resample":
+    if negatives != "fixed":
         from .data_prep import NegativeSampler
-        sampler = NegativeSampler(train_data, n_user, n_item, exclude=(eval_data, test_data),
-                                  ratio=float(int(n_neg)) if ranked else 1.0, seed=getattr(args, "neg_seed", 1),
-                                  device=model.device)
+        ratio = float(int(pool)) if hard else float(int(n_neg)) if ranked else 1.0
+        sampler = NegativeSampler(train_data, n_user, n_item, exclude=(eval_data, test_data), ratio=ratio,
+                                  seed=getattr(args, "neg_seed", 1), device=model.device)
     if not ranked and model.trainer is not None:
         model.trainer.set_objective("bce")
     for epoch in range(getattr(args, "n_epochs", 20)):
         use_graph = (args.batch_size <= 2048) if graph == "auto" else bool(graph)
-        if ranked:
+        if hard:
+            losses = train_epoch_hard(feeder, sampler, args.batch_size, epoch, objective, int(n_neg), shortlist=shortlist,
+                                      rescore=int(rescore), graph=use_graph)
+        elif ranked:
             losses = train_epoch_ranked(feeder, sampler, args.batch_size, epoch, objective, graph=use_graph)
         elif sampler is not None:
             losses = train_epoch_resampled(feeder, sampler, args.batch_size, epoch, graph=use_graph)
@@ -831,6 +951,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         rec = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else float("nan")}
         if ranked:
             rec["pairwise_acc"] = model.trainer.last_pairwise_acc
+        if hard:
+            rec["hard_rate"], rec["pool_rate"] = model.trainer.last_hard_rate, model.trainer.last_pool_rate
         if show_topk:
             for mode in ("eval", "test"):
                 if topk_impl in ("batched", "ranked"):

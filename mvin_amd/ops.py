@@ -1333,6 +1333,43 @@ def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None,
     return scores, dscore, du, di
 
 
+def select_negatives(scores, items, valid, n_neg, shortlist, seed, round, group_key=None, counts=None, out_scores=False):
+    """mvin_select_negatives: the hard negatives of a ranking objective out of a scored pool, in one launch (include/mvin_hip.h
+    states the rule).  ``scores`` f32 / ``items`` int64 / ``valid`` f32 or None, all [n_groups, Gp]: slot 0 of a group is the
+    positive, slots 1.. its candidate negatives with the current model's scores.  Of the ``shortlist`` highest-scored valid
+    candidates of a group, ``n_neg`` are drawn uniformly as a pure function of (``seed``, ``round``, ``group_key[g]`` -- None:
+    g).  Returns (items int64 [n_groups, 1 + n_neg], valid f32 [n_groups, 1 + n_neg]) in the layout of data_prep.rank_groups,
+    the chosen hardest first, and with ``out_scores=True`` the chosen slots' score bits as a third tensor (quiet NaN where a
+    slot stays unfilled).  ``counts`` (int64 [4]) accumulates the exact integers behind "hard_rate" / "pool_rate".
+    Enqueues only."""
+    _chk(scores, F32, "scores"), _chk(items, torch.int64, "items"), _chk(valid, F32, "valid")
+    _chk(group_key, torch.int64, "group_key"), _chk(counts, torch.int64, "counts")
+    if scores is None or items is None:
+        raise ValueError("select_negatives: scores and items are required")
+    if scores.dim() != 2 or tuple(items.shape) != tuple(scores.shape):
+        raise ValueError(f"scores {tuple(scores.shape)} and items {tuple(items.shape)}: expected [n_groups, Gp] both")
+    n, Gp = scores.shape
+    if valid is not None and tuple(valid.shape) != (n, Gp):
+        raise ValueError(f"valid: {tuple(valid.shape)}, expected {(n, Gp)}")
+    if group_key is not None and group_key.numel() != n:
+        raise ValueError(f"group_key: {group_key.numel()} keys for {n} groups")
+    if counts is not None and counts.numel() != 4:
+        raise ValueError("counts: expected int64 [4]")
+    n_neg, shortlist = int(n_neg), int(shortlist)
+    if not 2 <= Gp <= 64 or not 1 <= n_neg <= Gp - 1 or not n_neg <= shortlist <= Gp - 1:
+        raise ValueError(f"Gp={Gp} n_neg={n_neg} shortlist={shortlist}: expected 2 <= Gp <= 64, 1 <= n_neg <= shortlist <= Gp - 1")
+    dev = scores.device
+    out_items = torch.empty((n, 1 + n_neg), dtype=torch.int64, device=dev)
+    out_valid = torch.empty((n, 1 + n_neg), dtype=F32, device=dev)
+    out_s = torch.empty((n, 1 + n_neg), dtype=F32, device=dev) if out_scores else None
+    if n > 0:                                   # an empty tensor has no address to pass
+        m64 = (1 << 64) - 1
+        _lib.check(_lib.load().mvin_select_negatives(_p(scores), _p(items), _p(valid), _p(group_key), n, Gp, n_neg, shortlist,
+                                                     int(seed) & m64, int(round) & m64, _p(out_items), _p(out_valid), _p(out_s),
+                                                     _p(counts), _stream()), "mvin_select_negatives")
+    return (out_items, out_valid, out_s) if out_scores else (out_items, out_valid)
+
+
 def count_ids(ids, nbins, out=None):
     """mvin_count_ids: float occurrence counts [nbins] of an int32 id list (no host sync); added to ``out``."""
     _chk(ids, I32, "ids")
