@@ -814,6 +814,43 @@ MVIN_API int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_
                                    int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status,
                                    void* stream);
 
+/* mvin_sample_negatives_weighted: the same call with the draws taken from an ALIAS TABLE (Walker / Vose; the caller builds it,
+ * data_prep.alias_table) instead of uniformly -- negatives in proportion to popularity^alpha, the word2vec proposal -- and
+ * with a catalogue-wide mask of ineligible items.  Integer-exact like the uniform rule.  Per user:
+ *  - alias_tab [n_item][2] uint32 = {thresh, alias} per bucket, 8-byte aligned; mask_bits [ceil(n_item / 32)] uint32 or NULL:
+ *    bit i % 32 of word i / 32 set = item i is ineligible for every user; bits at positions >= n_item of the last word are
+ *    ignored; NULL = no item is masked;
+ *  - X_u = the in-range ids of u's exclusion row (as above) united with the masked items; c_u = n_item - |X_u|,
+ *    m_eff = min(m[u], c_u);
+ *  - draw j takes two words of stream 6: head = rnd32_head(seed, 6, u, round), r0 = rnd32_tail(head, 2j),
+ *    r1 = rnd32_tail(head, 2j + 1); bucket i = (r0 * n_item) >> 32; x_j = i if r1 < thresh[i], else min(alias[i], n_item - 1).
+ *    The clamp is part of the rule: the table is caller memory, and every id the library takes is clamped.  One draw thus
+ *    produces item k with probability  sum over buckets i of mass(i) * (thresh[i] [k == i] + (2^32 - thresh[i]) [k == alias'[i]])
+ *    / 2^32, where mass(i) = #{r0 : (r0 * n_item) >> 32 == i} / 2^32 is floor or ceil(2^32 / n_item) / 2^32 and alias' the
+ *    clamped alias (data_prep.alias_probabilities computes it from the integers);
+ *  - the sequence is cut at j = 64 * n_item draws;
+ *  - the slots receive the first m_eff values of the sequence that are not in X_u and have not occurred earlier, IN SEQUENCE
+ *    ORDER: successive sampling without replacement from the table's distribution restricted to the eligible items (the
+ *    first accepted item has that distribution renormalised; later ones follow by conditioning);
+ *  - slots that stay unfilled hold -1: m[u] > c_u, or the cut was reached.  UNLIKE the uniform rule, the cut can be reached
+ *    by a legitimate request: an eligible item that carries a share p of the mass is still missing after 64 * n_item draws
+ *    with probability (1 - p)^(64 n_item), about e^(-64 n_item p) -- no concern for p = 1 / n_item, all but certain for a user
+ *    who asks for every eligible item when one of them carries 1e-9 of the mass (and an eligible item whose realised
+ *    probability is 0, e.g. one that only an unmasked zero-threshold bucket names, is never produced at all).  Such a user is
+ *    reported through status like one with m[u] > c_u; callers that need m items keep m well below the number of items of
+ *    non-negligible mass;
+ *  - status[0] = users with an unfilled slot, status[1] = slots left at -1 (both written by the call).
+ * The result is a pure function of the arguments: independent of the launch shape, the workgroup size and timing.  Equal
+ * weights give the uniform DISTRIBUTION, not the uniform call's bits (another stream, two words per draw).
+ * Errors (< 0, nothing launched): -1 for null counts / out_ptr / alias_tab / out_items / status or one of excl_ptr / excl_ids
+ * NULL without the other; -2 for n_user < 0; -3 for an unsupported n_item.  n_user == 0 launches nothing. */
+MVIN_API int mvin_sample_negatives_weighted_supported(int n_item);             /* 1 for 1 <= n_item <= MVIN_NEG_MAX_ITEMS */
+MVIN_API int mvin_sample_negatives_weighted(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts,
+                                            const int64_t* out_ptr, int n_user, int n_item,
+                                            const uint32_t* alias_tab,   /* [n_item][2] = {thresh, alias}, device */
+                                            const uint32_t* mask_bits,   /* [ceil(n_item/32)] or NULL, device */
+                                            uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status, void* stream);
+
 /* ---- KG exploration: which distinct KG edges lie within the model's receptive field of a seed set, and which of them the
  * sampled adjacencies have reached so far (the reference sketches the number in data_loader_user_set.py:208-239,
  * get_all_user_entity_count -> args.use_neighbor_rate, and leaves it commented out) --

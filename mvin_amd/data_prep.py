@@ -7,7 +7,8 @@ every stage-wise restart, main.py:16).  Here the KG becomes a CSR on the device 
 plumbing), and the two samplers are HIP kernels (mvin_sample_adjacency, mvin_build_ripple_sets)
 whose draws are a pure function of a seed, so adjacency can be re-sampled every epoch.  The training negatives
 (convert_rating, KGCN/preprocess.py:60-70) are drawn the same way by mvin_sample_negatives (sample_negatives,
-NegativeSampler), fresh for every epoch.  KGExploration counts, exactly and on the device, how much of the KG within the
+NegativeSampler), fresh for every epoch -- uniformly, or in proportion to popularity^alpha from an alias table
+(alias_table, mvin_sample_negatives_weighted).  KGExploration counts, exactly and on the device, how much of the KG within the
 model's receptive field the sampled adjacencies have covered (mvin_kg_field / mvin_kg_explore): the number that says whether
 another stage-wise restart, with its fresh adjacency, can show the model anything new.
 """
@@ -110,10 +111,98 @@ def interaction_csr(rows, n_user, device="cuda", labels=1):
     return torch.from_numpy(ptr).to(device), torch.from_numpy(ids).to(device)
 
 
-def sample_negatives(excl, n_item, counts, seed=1, round=0, check=True, total=None):
+def alias_table(weights, n_item=None):
+    """The alias table of mvin_sample_negatives_weighted for non-negative ``weights`` [n_item] (Vose's construction in float64
+    on the host, once per sampler; host plumbing like ``interaction_csr``).  Returns numpy arrays
+    (tab uint32 [n_item, 2] = {thresh, alias} per bucket, mask uint32 [ceil(n_item / 32)]):
+      * p_i = w_i * n_item / sum(w); the worklists of the items with p < 1 and with p >= 1 are processed in ascending item
+        order (an item that drops below 1 joins the end of the first list), so the table is a pure function of ``weights``;
+      * thresh = min(floor(p * 2^32), 2^32 - 1); a bucket that keeps probability 1 aliases to itself;
+      * a zero-weight item gets its mask bit set (bit i % 32 of word i / 32) and thresh = 0, and no bucket aliases to it: it is
+        never produced, and the mask makes it ineligible even if it were.
+    What one draw really produces is ``alias_probabilities(tab)``.  ValueError for weights that are negative, non-finite, all
+    zero, not one-dimensional, empty or (with ``n_item``) of another length."""
+    w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+    if w.ndim != 1 or w.size == 0 or (n_item is not None and w.size != int(n_item)):
+        raise ValueError(f"alias_table: weights of shape {w.shape}, expected ({'n_item' if n_item is None else int(n_item)},)")
+    if not np.isfinite(w).all():
+        raise ValueError("alias_table: weights must be finite")
+    if (w < 0).any():
+        raise ValueError("alias_table: weights must not be negative")
+    total = float(w.sum())
+    if not total > 0.0 or not np.isfinite(total):
+        raise ValueError("alias_table: the weights are all zero (or their sum overflows)")
+    n = w.size
+    p = (w * (n / total)).tolist()
+    alias = list(range(n))
+    small = [i for i in range(n) if p[i] < 1.0]
+    large = [i for i in range(n) if p[i] >= 1.0]
+    si = li = 0
+    while si < len(small) and li < len(large):
+        s, l = small[si], large[li]
+        si += 1
+        alias[s] = l
+        p[l] = (p[l] + p[s]) - 1.0
+        if p[l] < 1.0:
+            small.append(l)
+            li += 1
+    for i in large[li:]:
+        p[i] = 1.0
+    heaviest = int(np.argmax(w))
+    for i in small[si:]:                    # left over by round-off only: p is 1 up to that round-off
+        if w[i] > 0.0:
+            p[i] = 1.0
+        else:                               # (a zero-weight item never keeps a share, whatever the round-off)
+            alias[i] = heaviest
+    thresh = np.minimum(np.floor(np.clip(np.asarray(p, dtype=np.float64), 0.0, 1.0) * 4294967296.0), 4294967295.0)
+    thresh[w == 0.0] = 0.0
+    tab = np.stack([thresh.astype(np.uint32), np.asarray(alias, dtype=np.uint32)], axis=1)
+    bits = np.zeros(((n + 31) // 32) * 32, dtype=np.uint32)
+    bits[:n] = w == 0.0
+    mask = (bits.reshape(-1, 32) << np.arange(32, dtype=np.uint32)[None, :]).sum(axis=1, dtype=np.uint64).astype(np.uint32)
+    return np.ascontiguousarray(tab), np.ascontiguousarray(mask)
+
+
+def alias_probabilities(tab, exact=False):
+    """The probability with which ONE draw of mvin_sample_negatives_weighted produces each item, from the integers of
+    ``tab`` (uint32 [n_item, 2]): bucket i is hit by mass(i) = ceil((i + 1) 2^32 / n_item) - ceil(i 2^32 / n_item) of the 2^32
+    values of r0 (the multiply-high), keeps thresh[i] of the 2^32 values of r1 and sends the others to
+    min(alias[i], n_item - 1).  Returns float64 [n_item] (the exact numerators over 2^64, rounded once); ``exact=True``
+    returns the numerators as Python integers (they sum to 2^64).  This is what tests and documents compare against, not
+    the float weights the table was built from."""
+    t = np.asarray(tab.cpu() if torch.is_tensor(tab) else tab)
+    if t.ndim != 2 or t.shape[1] != 2 or t.shape[0] == 0:
+        raise ValueError(f"alias_probabilities: tab of shape {t.shape}, expected (n_item, 2)")
+    n = t.shape[0]
+    edges = [-((-(i << 32)) // n) for i in range(n + 1)] if n <= 4096 else None
+    if edges is None:                                                  # ceil(i 2^32 / n) without leaving uint64: i 2^32 < 2^52
+        i = np.arange(n + 1, dtype=np.uint64)
+        e = ((i << np.uint64(32)) + np.uint64(n - 1)) // np.uint64(n)
+    else:
+        e = np.array(edges, dtype=np.uint64)
+    mass = e[1:] - e[:-1]                                              # sums to 2^32
+    thresh = t[:, 0].astype(np.uint64)
+    alias = np.minimum(t[:, 1].astype(np.int64), n - 1)
+    rest = np.uint64(1 << 32) - thresh                                 # 1 .. 2^32
+    # mass * share < 2^64 may not fit and the sums certainly do not: carry the high and low 16 bits of the share apart
+    hi = np.zeros(n, dtype=np.uint64)
+    lo = np.zeros(n, dtype=np.uint64)
+    own = np.arange(n)
+    for idx, share in ((own, thresh), (alias, rest)):
+        np.add.at(hi, idx, mass * (share >> np.uint64(16)))
+        np.add.at(lo, idx, mass * (share & np.uint64(0xFFFF)))
+    if exact:
+        return [(int(h) << 16) + int(l) for h, l in zip(hi.tolist(), lo.tolist())]
+    return hi.astype(np.float64) / float(1 << 48) + lo.astype(np.float64) / float(1 << 64)
+
+
+def sample_negatives(excl, n_item, counts, seed=1, round=0, check=True, total=None, alias=None):
     """mvin_sample_negatives: for every user u, ``counts[u]`` items outside u's exclusion row, uniformly and without
     replacement, as a pure function of (``seed``, ``round``) -- include/mvin_hip.h states the rule.  ``excl``: an
     ``interaction_csr`` pair on the device, or None for no exclusions.  ``counts``: int array [nU], device or host.
+    ``alias`` = (tab, mask) of ``alias_table`` (numpy or tensors; ``mask`` may be None) routes the call to
+    mvin_sample_negatives_weighted: the draws follow the table's distribution and masked items are ineligible for every
+    user; None is the uniform call.
     Returns (neg_ptr int64 [nU+1] = the cumulative counts, neg_items int32 [neg_ptr[-1]]) on the device; user u's negatives
     are neg_items[neg_ptr[u]:neg_ptr[u+1]] in draw order.  A user with fewer eligible items than ``counts[u]`` keeps -1 in
     the slots that cannot be filled:
@@ -147,19 +236,49 @@ def sample_negatives(excl, n_item, counts, seed=1, round=0, check=True, total=No
             raise ValueError("sample_negatives: excl = (ptr int64 [nU+1], ids int32)")
         if ei is not None and ei.numel() == 0:      # nobody excludes anything: an empty tensor has no address to pass
             ep, ei = None, None
-        _lib.check(lib.mvin_sample_negatives(_p(ep), _p(ei), _p(cnt), _p(neg_ptr), n_user, int(n_item),
-                                             int(seed) & ((1 << 64) - 1), int(round) & ((1 << 64) - 1), _p(items), _p(status),
-                                             _stream()), "mvin_sample_negatives")
+        if alias is None:
+            _lib.check(lib.mvin_sample_negatives(_p(ep), _p(ei), _p(cnt), _p(neg_ptr), n_user, int(n_item),
+                                                 int(seed) & ((1 << 64) - 1), int(round) & ((1 << 64) - 1), _p(items), _p(status),
+                                                 _stream()), "mvin_sample_negatives")
+        else:
+            tab, mask = _alias_on(alias, int(n_item), dev)
+            _lib.check(lib.mvin_sample_negatives_weighted(_p(ep), _p(ei), _p(cnt), _p(neg_ptr), n_user, int(n_item), _p(tab),
+                                                          _p(mask), int(seed) & ((1 << 64) - 1), int(round) & ((1 << 64) - 1),
+                                                          _p(items), _p(status), _stream()), "mvin_sample_negatives_weighted")
     if not check:
         return neg_ptr, items, status
     short_users, short_slots = status.cpu().tolist()
     if short_users:
         u = int(torch.searchsorted(neg_ptr, torch.nonzero(items < 0)[0], right=True)[0]) - 1
         row = np.zeros(0, dtype=np.int64) if excl is None else excl[1][int(excl[0][u]):int(excl[0][u + 1])].cpu().numpy()
-        c = int(n_item) - np.unique(row[(row >= 0) & (row < n_item)]).size
+        taken = np.zeros(int(n_item), dtype=bool)
+        taken[row[(row >= 0) & (row < n_item)]] = True
+        if alias is not None and alias[1] is not None:
+            mask = np.asarray(alias[1].cpu() if torch.is_tensor(alias[1]) else alias[1]).astype(np.int64).reshape(-1)
+            taken |= ((mask[:, None] >> np.arange(32)[None, :]) & 1).astype(bool).reshape(-1)[:int(n_item)]
+        c = int(n_item) - int(taken.sum())
         raise ValueError(f"sample_negatives: {short_users} users fell short ({short_slots} slots left at -1); the first is user "
                          f"{u} with m={int(cnt[u])} requested and c={c} eligible items of {int(n_item)}")
     return neg_ptr, items
+
+
+def _alias_on(alias, n_item, dev):
+    """(tab, mask) of ``alias_table`` as contiguous device tensors holding the table's 32-bit words (mask None stays None)."""
+    def words(a, shape, what):
+        if a is None:
+            return None
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(np.asarray(a))
+            if a.dtype not in (np.uint32, np.int32):
+                raise ValueError(f"sample_negatives: alias {what} must hold 32-bit words, got {a.dtype}")
+            a = torch.from_numpy(a.view(np.int32))
+        elif a.dtype not in (torch.int32, torch.uint32):
+            raise ValueError(f"sample_negatives: alias {what} must hold 32-bit words, got {a.dtype}")
+        if tuple(a.shape) != shape:
+            raise ValueError(f"sample_negatives: alias {what} of shape {tuple(a.shape)}, expected {shape}")
+        return a.to(dev).contiguous()
+    tab, mask = alias
+    return words(tab, (n_item, 2), "table"), words(mask, ((n_item + 31) // 32,), "mask")
 
 
 class NegativeSampler(object):
@@ -171,9 +290,19 @@ class NegativeSampler(object):
     then taught as a negative), and the counts m[u] = floor(ratio * p_u + 0.5) with p_u = positives of u in ``train_data``
     (round half up, computed in float64; ``ratio=1.0`` is the reference's ``size=len(pos_item_set)``).  A user with fewer
     eligible items c_u = n_item - |distinct in-range exclusions| than m[u] gets m[u] = c_u; that is said once through
-    ``warnings.warn``.  ``epoch(round)`` is a pure function of (seed, round)."""
+    ``warnings.warn``.  ``epoch(round)`` is a pure function of (seed, round).
 
-    def __init__(self, train_data, n_user, n_item, exclude=(), ratio=1.0, seed=1, device="cuda"):
+    ``dist``: "uniform" draws uniformly over the eligible items (mvin_sample_negatives); "popularity" draws in proportion to
+    w_i = (count_i + smooth) ** alpha in float64 (``alpha`` around 0.75 is word2vec's choice), count_i = the label-1 rows of
+    ``train_data`` with item i -- never of the ``exclude`` splits, which would leak the held-out sets -- through an alias table
+    (``alias_table``, mvin_sample_negatives_weighted).  ``weights``: an explicit array [n_item], which overrides.  An item of
+    weight zero is masked: ineligible for every user, and c_u counts it out.  ``draw(round)`` is the one place the negatives
+    of a round come from: ``epoch``, ``rank_groups`` and ``hard_groups`` go through it and so follow the distribution."""
+
+    def __init__(self, train_data, n_user, n_item, exclude=(), ratio=1.0, seed=1, device="cuda", dist="uniform", alpha=0.75,
+                 smooth=0.0, weights=None):
+        if dist not in ("uniform", "popularity"):
+            raise ValueError(f"NegativeSampler: dist={dist!r}: expected 'uniform' or 'popularity'")
         d = np.asarray(train_data, dtype=np.int64).reshape(-1, 3)
         pos = d[d[:, 2] == 1]
         self.n_user, self.n_item, self.seed, self.ratio = int(n_user), int(n_item), int(seed), float(ratio)
@@ -185,7 +314,21 @@ class NegativeSampler(object):
         want = np.floor(self.ratio * n_pos_of.astype(np.float64) + 0.5).astype(np.int64)
         in_range = (ids >= 0) & (ids < self.n_item)
         row_of = np.repeat(np.arange(self.n_user), np.diff(ptr))
+        self.dist, self.alias, masked = dist, None, None
+        if weights is not None or dist == "popularity":
+            if weights is None:
+                if not (np.isfinite(alpha) and np.isfinite(smooth) and smooth >= 0):
+                    raise ValueError(f"NegativeSampler: alpha={alpha!r}, smooth={smooth!r}: expected finite numbers, smooth >= 0")
+                item = pos[:, 1]
+                count = np.bincount(item[(item >= 0) & (item < self.n_item)], minlength=self.n_item).astype(np.float64)
+                weights = (count + float(smooth)) ** float(alpha)
+            tab, mask = alias_table(weights, self.n_item)
+            self.alias = _alias_on((tab, mask), self.n_item, self.device)
+            masked = ((mask[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(-1)[:self.n_item]
+            in_range[in_range] = ~masked[ids[in_range]]                # a masked item of the row is counted once, by the mask
         eligible = self.n_item - np.bincount(row_of[in_range], minlength=self.n_user).astype(np.int64)
+        if masked is not None:
+            eligible -= int(masked.sum())
         m = np.minimum(want, eligible)
         self.clipped_users = int(np.count_nonzero(want > eligible))
         if self.clipped_users:
@@ -205,12 +348,19 @@ class NegativeSampler(object):
         self.pos_index = torch.from_numpy(idx).to(self.device)
         self.last_status = None
 
+    def draw(self, round):
+        """(neg_ptr int64 [nU+1], neg_items int32) of ``round`` on the device, from the sampler's distribution (uniform, or the
+        alias table's); ``last_status`` keeps the call's status tensor.  Nothing goes back to the host."""
+        kw = {} if self.alias is None else {"alias": self.alias}
+        neg_ptr, items, self.last_status = sample_negatives(self.excl, self.n_item, self.counts, seed=self.seed, round=round,
+                                                            check=False, total=self.n_neg, **kw)
+        return neg_ptr, items
+
     def epoch(self, round):
         """int64 [n_pos + n_neg, 3] (user, item, label) on the device: the positives first, in ``train_data`` order, then the
         negatives of ``round`` (label 0), user-major, each user's in draw order.  Nothing goes back to the host;
         ``last_status`` keeps the call's status tensor."""
-        _, items, self.last_status = sample_negatives(self.excl, self.n_item, self.counts, seed=self.seed, round=round,
-                                                      check=False, total=self.n_neg)
+        _, items = self.draw(round)
         rows = torch.empty((self.n_pos + self.n_neg, 3), dtype=torch.int64, device=self.device)
         rows[:self.n_pos] = self.pos_rows
         neg = rows[self.n_pos:]
@@ -227,7 +377,7 @@ def rank_groups(sampler, round):
     nothing goes to the host.
       slot 0         the positive item;
       slots 1..n_neg positive number j of user u (``sampler.pos_index``) takes entries j*n_neg .. j*n_neg + n_neg - 1 of u's
-                     negative row of ``round`` (``sample_negatives``: distinct items, none in the exclusion row), so no two
+                     negative row of ``round`` (``sampler.draw``: distinct items, none in the exclusion row), so no two
                      positives of a user share a negative;
       invalid slot   one that lies beyond the user's m[u] (the sampler clipped the row) or holds -1: ``valid`` is 0 there and
                      the slot carries the group's POSITIVE item id -- a valid id for every gather; a masked slot receives no
@@ -236,8 +386,7 @@ def rank_groups(sampler, round):
     n_neg = int(sampler.ratio)
     if n_neg != sampler.ratio or not 1 <= n_neg <= 63:
         raise ValueError(f"rank_groups: the sampler's ratio={sampler.ratio!r} must be an integer n_neg in [1, 63]")
-    neg_ptr, neg_items, sampler.last_status = sample_negatives(sampler.excl, sampler.n_item, sampler.counts, seed=sampler.seed,
-                                                               round=round, check=False, total=sampler.n_neg)
+    neg_ptr, neg_items = sampler.draw(round)
     dev = sampler.device
     users, pos_item = sampler.pos_rows[:, 0].contiguous(), sampler.pos_rows[:, 1:2]
     k = sampler.pos_index[:, None] * n_neg + torch.arange(n_neg, dtype=torch.int64, device=dev)[None, :]

@@ -843,7 +843,7 @@ class EarlyStop(object):
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
-          objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1):
+          objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -881,6 +881,11 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     mvin_select_negatives (train_epoch_hard); ``rescore`` = k scores and picks again before each k-th of the epoch.  The epoch
     record also gains "hard_rate" and "pool_rate": the share of the trained negatives, and of all pool candidates, that the
     model scored above their positive.
+    ``neg_dist``: the distribution the sampler of ``negatives="resample"`` / ``"hard"`` draws from: "uniform" over the items the
+    user has not watched, or "popularity": in proportion to (count_i + ``neg_smooth``) ** ``neg_alpha``, count_i = the label-1
+    rows of ``train_data`` with item i (data_prep.NegativeSampler(dist=...), mvin_sample_negatives_weighted; an item of weight
+    zero is never a negative).  It reaches every training mode through the sampler: cross-entropy epochs, the ranking
+    objectives' groups and the hard-negative pool.  An opt-in extension, like the ranking objectives.
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
@@ -890,6 +895,10 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         raise ValueError(f"negatives={negatives!r}: expected 'fixed', 'resample' or 'hard'")
     if objective not in ("bce", "bpr", "softmax"):
         raise ValueError(f"objective={objective!r}: expected 'bce', 'bpr' or 'softmax'")
+    if neg_dist not in ("uniform", "popularity"):
+        raise ValueError(f"neg_dist={neg_dist!r}: expected 'uniform' or 'popularity'")
+    if neg_dist != "uniform" and negatives == "fixed":
+        raise ValueError(f"neg_dist={neg_dist!r} is the distribution of the per-epoch sampler: it needs negatives='resample' or 'hard'")
     ranked = objective != "bce"
     hard = negatives == "hard"
     if hard and not ranked:
@@ -933,8 +942,9 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     if negatives != "fixed":
         from .data_prep import NegativeSampler
         ratio = float(int(pool)) if hard else float(int(n_neg)) if ranked else 1.0
+        dist_kw = {} if neg_dist == "uniform" else {"dist": neg_dist, "alpha": float(neg_alpha), "smooth": float(neg_smooth)}
         sampler = NegativeSampler(train_data, n_user, n_item, exclude=(eval_data, test_data), ratio=ratio,
-                                  seed=getattr(args, "neg_seed", 1), device=model.device)
+                                  seed=getattr(args, "neg_seed", 1), device=model.device, **dist_kw)
     if not ranked and model.trainer is not None:
         model.trainer.set_objective("bce")
     for epoch in range(getattr(args, "n_epochs", 20)):

@@ -4,6 +4,8 @@ harness.train_epoch_resampled).  Run on the GPU box; prints one JSON line.
 
   python scripts/bench_negatives.py                 # every leg
   python scripts/bench_negatives.py --sampler-only  # the sampler launches alone (for rocprofv3 --kernel-trace --stats)
+  python scripts/bench_negatives.py --no-host --dist popularity --alpha 0.75 [--zipf-weights]
+                                                    # the weighted kernel (mvin_sample_negatives_weighted), same shapes, same timing
 
 Synthetic positives-only interactions at the three data-set shapes (users x items, positives per user log-normal with a
 heavy tail, capped at 40 % of the catalogue): last-fm 23 553 x 48 091 with about 0.5 M positives (so about 1 M train pairs),
@@ -15,6 +17,11 @@ MovieLens-1M 6 036 x 2 445 with about 0.38 M, amazon-book 70 585 x 24 915 with a
     scaled to all users by the user count (the per-user cost is the catalogue-sized set difference; both the measured and
     the scaled time are in the output): numpy (per user setdiff1d +
     Generator.choice(replace=False)) and the straight loop over Python sets with np.random.choice(list(...)).
+--dist popularity draws the negatives in proportion to count^alpha through NegativeSampler(dist="popularity") -- the counts are
+those of the synthetic positives, which spread evenly over the items, so the table is nearly flat; --zipf-weights passes
+explicit weights (n_item / (1 + rank)) ** alpha over a random order of the items instead: the skew of a real catalogue, under
+which most lanes of a round draw the same few items.  Every shape also reports mean_rounds_per_user: the rounds of 256 draws the
+kernel runs for a user (from the draws the rule consumes, replayed on the host for --round-users sampled users).
 At the last-fm shape, batch 512, hipGraph steps: one train_epoch_device epoch over fixed negatives (the yardstick) against one
 train_epoch_resampled epoch, alternated.
 """
@@ -41,6 +48,11 @@ ap.add_argument("--iters", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--host-users", type=int, default=1000)
 ap.add_argument("--repeats", type=int, default=2, help="alternations of the fixed / resampled training epoch")
+ap.add_argument("--no-host", action="store_true", help="skip the host baselines and the training epochs, keep the epoch assembly")
+ap.add_argument("--dist", choices=("uniform", "popularity"), default="uniform")
+ap.add_argument("--alpha", type=float, default=0.75)
+ap.add_argument("--zipf-weights", action="store_true", help="with --dist popularity: explicit Zipf weights instead of the counts")
+ap.add_argument("--round-users", type=int, default=300, help="users sampled for mean_rounds_per_user")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 SHAPES = (("last-fm_50core", 500_000), ("MovieLens-1M", 380_000), ("amazon-book_20core", 850_000))
@@ -88,8 +100,54 @@ def host_sets(pos_of, n_item):
     return out
 
 
+def host_rounds(s, users, rnd, block=256):
+    """Mean rounds of ``block`` draws the kernel runs for the sampled users: the rule replayed with numpy (uniform: stream 4, one
+    word per draw; weighted: stream 6, two words and the alias table), counting draws until m[u] are accepted."""
+    ptr, ids, n_item = s.excl[0].cpu().numpy(), s.excl[1].cpu().numpy(), s.n_item
+    tab = mask = None
+    if s.alias is not None:
+        tab = s.alias[0].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        words = s.alias[1].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        mask = ((words[:, None] >> np.arange(32)[None, :]) & 1).astype(bool).reshape(-1)[:n_item]
+
+    def words32(head, c0, c1):
+        with np.errstate(over="ignore"):
+            z = np.uint64(head) ^ (np.arange(c0, c1, dtype=np.uint64) * np.uint64(0x165667B19E3779F9))
+            z = z + np.uint64(0x9E3779B97F4A7C15)
+            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            return (z ^ (z >> np.uint64(31))) >> np.uint64(32)
+
+    rounds = []
+    for u in users:
+        m = int(s.counts_host[u])
+        if m == 0:
+            continue
+        taken = np.zeros(n_item, dtype=bool) if mask is None else mask.copy()
+        taken[ids[ptr[u]:ptr[u + 1]]] = True
+        stream = 4 if tab is None else 6
+        head = (s.seed ^ (stream * 0xD1B54A32D192ED03) ^ (u * 0x9E3779B97F4A7C15) ^ (rnd * 0xC2B2AE3D27D4EB4F)) & ((1 << 64) - 1)
+        got, j = 0, 0
+        while got < m and j < 64 * n_item:
+            j1 = j + block
+            if tab is None:
+                x = ((words32(head, j, j1) * np.uint64(n_item)) >> np.uint64(32)).astype(np.int64)
+            else:
+                w = words32(head, 2 * j, 2 * j1)
+                i = ((w[0::2] * np.uint64(n_item)) >> np.uint64(32)).astype(np.int64)
+                x = np.where(w[1::2].astype(np.int64) < tab[i, 0], i, np.minimum(tab[i, 1], n_item - 1))
+            x = np.unique(x[~taken[x]])
+            taken[x] = True
+            got += x.size
+            j = j1
+        rounds.append(j // block)
+    return round(float(np.mean(rounds)), 3) if rounds else 0.0
+
+
 lib = _lib.load()
-result = {"iters": a.iters, "shapes": {}}
+result = {"iters": a.iters, "dist": a.dist, "shapes": {}}
+if a.dist == "popularity":
+    result.update(alpha=a.alpha, zipf_weights=bool(a.zipf_weights))
 samplers = {}
 for ds, n_pos in SHAPES:
     d = synth.DATASETS[ds]
@@ -97,7 +155,11 @@ for ds, n_pos in SHAPES:
     train = interactions(n_user, n_item, n_pos, seed=11)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        s = data_prep.NegativeSampler(train, n_user, n_item, seed=1, device=dev)
+        if a.dist == "uniform":
+            s = data_prep.NegativeSampler(train, n_user, n_item, seed=1, device=dev)
+        else:
+            wts = (n_item / (1.0 + np.random.default_rng(5).permutation(n_item))) ** a.alpha if a.zipf_weights else None
+            s = data_prep.NegativeSampler(train, n_user, n_item, seed=1, device=dev, dist="popularity", alpha=a.alpha, weights=wts)
     samplers[ds] = (s, train)
     neg_ptr = torch.zeros(n_user + 1, dtype=torch.int64, device=dev)
     neg_ptr[1:] = torch.cumsum(s.counts, 0)
@@ -107,13 +169,21 @@ for ds, n_pos in SHAPES:
 
     def kernel():
         rnd[0] += 1
-        _lib.check(lib.mvin_sample_negatives(_p(s.excl[0]), _p(s.excl[1]), _p(s.counts), _p(neg_ptr), n_user, n_item, 1, rnd[0],
-                                             _p(items), _p(status), _stream()), "mvin_sample_negatives")
+        if s.alias is None:
+            _lib.check(lib.mvin_sample_negatives(_p(s.excl[0]), _p(s.excl[1]), _p(s.counts), _p(neg_ptr), n_user, n_item, 1, rnd[0],
+                                                 _p(items), _p(status), _stream()), "mvin_sample_negatives")
+        else:
+            _lib.check(lib.mvin_sample_negatives_weighted(_p(s.excl[0]), _p(s.excl[1]), _p(s.counts), _p(neg_ptr), n_user, n_item,
+                                                          _p(s.alias[0]), _p(s.alias[1]), 1, rnd[0], _p(items), _p(status),
+                                                          _stream()), "mvin_sample_negatives_weighted")
 
     rec = {"users": n_user, "items": n_item, "positives": s.n_pos, "negatives": s.n_neg, "clipped_users": s.clipped_users,
            "max_per_user": int(s.counts_host.max())}
     rec["kernel_us"], rec["kernel_us_min"], rec["kernel_us_max"] = median_event_us(kernel, a.iters, a.warmup)
-    assert status.tolist() == [0, 0] and bool((items >= 0).all())
+    rec["status"] = status.tolist()                                   # under a skewed table a clipped user can reach the draw cut
+    assert a.dist != "uniform" or (rec["status"] == [0, 0] and bool((items >= 0).all()))
+    rec["mean_rounds_per_user"] = host_rounds(s, np.random.default_rng(9).choice(n_user, size=min(a.round_users, n_user),
+                                                                              replace=False).tolist(), rnd[0])
     for block in ("64", "128"):
         os.environ["MVIN_NEG_BLOCK"] = block
         rec[f"kernel_us_block{block}"] = median_event_us(kernel, a.iters, a.warmup)[0]
@@ -122,6 +192,7 @@ for ds, n_pos in SHAPES:
     if not a.sampler_only:
         rec["epoch_rows_us"] = median_event_us(lambda: harness.resampled_epoch_rows(s, rnd[0], dev), a.iters, a.warmup)[0]
         rec["epoch_only_us"] = median_event_us(lambda: s.epoch(rnd[0]), a.iters, a.warmup)[0]
+    if not a.sampler_only and not a.no_host:
         # the reference's rule on the host, on the first users
         hu = min(a.host_users, n_user)
         order = np.argsort(train[:, 0], kind="stable")
@@ -138,7 +209,7 @@ for ds, n_pos in SHAPES:
                    host_sets_s_scaled_by_users=round(t_sets * n_user / hu, 2))
     result["shapes"][ds] = rec
 
-if not a.sampler_only:
+if not a.sampler_only and not a.no_host:
     # ---- a training epoch at the last-fm shape (scripts/bench_ctr_eval.py's model), fixed negatives against resampled ones
     ds = "last-fm_50core"
     d = synth.DATASETS[ds]
