@@ -793,57 +793,52 @@ MVIN_API int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t
 /* ---- training negatives: the label-0 rows of convert_rating (KGCN/preprocess.py:60-70: for every user, as many items as the
  * user has positives, np.random.choice(list(item_set - pos - neg), replace=False)), drawn on the GPU as a pure function of
  * (seed, round) so that they can be redrawn every epoch --
- * mvin_sample_negatives: user u gets counts[u] = m[u] slots, out_items[out_ptr[u] .. out_ptr[u+1]).  The rule, per user:
- *  - X_u = the ids of u's exclusion row excl_ids[excl_ptr[u] .. excl_ptr[u+1]) that lie in [0, n_item); the row may be in any
- *    order and may repeat ids, ids outside the range are ignored (both arrays NULL = no exclusions);
+ * mvin_sample_negatives and mvin_sample_negatives_weighted are ONE rule over two draw sequences.  User u gets
+ * counts[u] = m[u] slots, out_items[out_ptr[u] .. out_ptr[u+1]).  The rule, per user:
+ *  - X_u = the ids of u's exclusion row excl_ids[excl_ptr[u] .. excl_ptr[u+1]) that lie in [0, n_item), united with the masked
+ *    items where the call takes a mask; the row may be in any order and may repeat ids, ids outside the range are ignored (both
+ *    arrays NULL = no exclusions);
  *  - c_u = n_item - |X_u|, m_eff = min(m[u], c_u);
- *  - the draw sequence is x_j = rnd_below(n_item, seed, 4, u, round, j), j = 0, 1, 2, ... (the draw function of the two samplers
- *    above, stream 4), cut at j = 64 * n_item draws;
+ *  - the call's draw sequence x_j, j = 0, 1, 2, ... (below), is cut at j = 64 * n_item draws;
  *  - the slots receive the first m_eff values of that sequence that are not in X_u and have not occurred earlier in the
- *    sequence, IN SEQUENCE ORDER: a uniform sample without replacement from the complement of X_u;
- *  - slots that stay unfilled hold -1: m[u] > c_u, or the cut was reached.  Collecting all c eligible values takes more than
- *    n_item * (ln c + t) draws with probability below e^-t and ln c < 21.5, so a valid request is cut with probability
- *    below e^-42 per user: the cut bounds the kernel's loop, nobody will see it;
+ *    sequence, IN SEQUENCE ORDER;
+ *  - slots that stay unfilled hold -1: m[u] > c_u, or the cut was reached;
  *  - status[0] = users with an unfilled slot, status[1] = slots left at -1 (both written by the call).
  * The result is a pure function of the arguments: independent of the launch shape, the workgroup size and timing.
- * Errors (< 0, nothing launched): -1 for null counts / out_ptr / out_items / status or one of excl_ptr / excl_ids NULL without
- * the other; -2 for n_user < 0; -3 for an unsupported n_item.  n_user == 0 launches nothing. */
+ * Errors (< 0, nothing launched): -1 for null counts / out_ptr / out_items / status (the weighted call: or alias_tab) or one of
+ * excl_ptr / excl_ids NULL without the other; -2 for n_user < 0; -3 for an unsupported n_item.  n_user == 0 launches nothing.
+ *
+ * The uniform draw (mvin_sample_negatives): x_j = rnd_below(n_item, seed, 4, u, round, j) (the draw function of the two
+ * samplers above, stream 4) -- a uniform sample without replacement from the complement of X_u.  Collecting all c eligible
+ * values takes more than n_item * (ln c + t) draws with probability below e^-t and ln c < 21.5, so a valid request is cut with
+ * probability below e^-42 per user: the cut bounds the kernel's loop, nobody will see it. */
 #define MVIN_NEG_MAX_ITEMS (1 << 20)    /* one bit per item in the workgroup's LDS: 128 KB of the 160 KB */
 MVIN_API int mvin_sample_negatives_supported(int n_item);                      /* 1 for 1 <= n_item <= MVIN_NEG_MAX_ITEMS */
 MVIN_API int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
                                    int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status,
                                    void* stream);
 
-/* mvin_sample_negatives_weighted: the same call with the draws taken from an ALIAS TABLE (Walker / Vose; the caller builds it,
- * data_prep.alias_table) instead of uniformly -- negatives in proportion to popularity^alpha, the word2vec proposal -- and
- * with a catalogue-wide mask of ineligible items.  Integer-exact like the uniform rule.  Per user:
+/* The alias draw (mvin_sample_negatives_weighted): the draws come from an ALIAS TABLE (Walker / Vose; the caller builds it,
+ * data_prep.alias_table) instead of uniformly -- negatives in proportion to popularity^alpha, the word2vec proposal -- and the
+ * call takes a catalogue-wide mask of ineligible items.  Integer-exact like the uniform draw.
  *  - alias_tab [n_item][2] uint32 = {thresh, alias} per bucket, 8-byte aligned; mask_bits [ceil(n_item / 32)] uint32 or NULL:
  *    bit i % 32 of word i / 32 set = item i is ineligible for every user; bits at positions >= n_item of the last word are
  *    ignored; NULL = no item is masked;
- *  - X_u = the in-range ids of u's exclusion row (as above) united with the masked items; c_u = n_item - |X_u|,
- *    m_eff = min(m[u], c_u);
  *  - draw j takes two words of stream 6: head = rnd32_head(seed, 6, u, round), r0 = rnd32_tail(head, 2j),
  *    r1 = rnd32_tail(head, 2j + 1); bucket i = (r0 * n_item) >> 32; x_j = i if r1 < thresh[i], else min(alias[i], n_item - 1).
  *    The clamp is part of the rule: the table is caller memory, and every id the library takes is clamped.  One draw thus
  *    produces item k with probability  sum over buckets i of mass(i) * (thresh[i] [k == i] + (2^32 - thresh[i]) [k == alias'[i]])
  *    / 2^32, where mass(i) = #{r0 : (r0 * n_item) >> 32 == i} / 2^32 is floor or ceil(2^32 / n_item) / 2^32 and alias' the
  *    clamped alias (data_prep.alias_probabilities computes it from the integers);
- *  - the sequence is cut at j = 64 * n_item draws;
- *  - the slots receive the first m_eff values of the sequence that are not in X_u and have not occurred earlier, IN SEQUENCE
- *    ORDER: successive sampling without replacement from the table's distribution restricted to the eligible items (the
- *    first accepted item has that distribution renormalised; later ones follow by conditioning);
- *  - slots that stay unfilled hold -1: m[u] > c_u, or the cut was reached.  UNLIKE the uniform rule, the cut can be reached
- *    by a legitimate request: an eligible item that carries a share p of the mass is still missing after 64 * n_item draws
- *    with probability (1 - p)^(64 n_item), about e^(-64 n_item p) -- no concern for p = 1 / n_item, all but certain for a user
- *    who asks for every eligible item when one of them carries 1e-9 of the mass (and an eligible item whose realised
- *    probability is 0, e.g. one that only an unmasked zero-threshold bucket names, is never produced at all).  Such a user is
- *    reported through status like one with m[u] > c_u; callers that need m items keep m well below the number of items of
- *    non-negligible mass;
- *  - status[0] = users with an unfilled slot, status[1] = slots left at -1 (both written by the call).
- * The result is a pure function of the arguments: independent of the launch shape, the workgroup size and timing.  Equal
- * weights give the uniform DISTRIBUTION, not the uniform call's bits (another stream, two words per draw).
- * Errors (< 0, nothing launched): -1 for null counts / out_ptr / alias_tab / out_items / status or one of excl_ptr / excl_ids
- * NULL without the other; -2 for n_user < 0; -3 for an unsupported n_item.  n_user == 0 launches nothing. */
+ *  - the rule above then is successive sampling without replacement from the table's distribution restricted to the eligible
+ *    items (the first accepted item has that distribution renormalised; later ones follow by conditioning);
+ *  - UNLIKE under the uniform draw, the cut can be reached by a legitimate request: an eligible item that carries a share p of
+ *    the mass is still missing after 64 * n_item draws with probability (1 - p)^(64 n_item), about e^(-64 n_item p) -- no
+ *    concern for p = 1 / n_item, all but certain for a user who asks for every eligible item when one of them carries 1e-9 of
+ *    the mass (and an eligible item whose realised probability is 0, e.g. one that only an unmasked zero-threshold bucket
+ *    names, is never produced at all).  Such a user is reported through status like one with m[u] > c_u; callers that need m
+ *    items keep m well below the number of items of non-negligible mass.
+ * Equal weights give the uniform DISTRIBUTION, not the uniform call's bits (another stream, two words per draw). */
 MVIN_API int mvin_sample_negatives_weighted_supported(int n_item);             /* 1 for 1 <= n_item <= MVIN_NEG_MAX_ITEMS */
 MVIN_API int mvin_sample_negatives_weighted(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts,
                                             const int64_t* out_ptr, int n_user, int n_item,

@@ -1624,35 +1624,36 @@ int mvin_build_ripple_sets(const int64_t* indptr, const int32_t* dst, const int3
     return hip_result(mvin::launch_ripple_build(r, (hipStream_t)stream), "mvin_build_ripple_sets");
 }
 
+// the two samplers' entry points: the uniform one passes no table and no mask
+static int sample_negatives_impl(const char* who, const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts,
+                                 const int64_t* out_ptr, int n_user, int n_item, const uint32_t* alias_tab, const uint32_t* mask_bits,
+                                 bool weighted, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status, void* stream) {
+    if (!counts || !out_ptr || (weighted && !alias_tab) || !out_items || !status)
+        return fail(-1, "%s: null pointer (counts / out_ptr / %sout_items / status)", who, weighted ? "alias_tab / " : "");
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together (both NULL = no exclusions)", who);
+    if (n_user < 0) return fail(-2, "%s: n_user=%d", who, n_user);
+    if (!mvin::sample_negatives_supported(n_item))
+        return fail(-3, "%s: unsupported n_item=%d (1..%d: the catalogue's bitmap lives in LDS)", who, n_item, MVIN_NEG_MAX_ITEMS);
+    return hip_result(mvin::launch_sample_negatives(excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, alias_tab, mask_bits, seed,
+                                                    round, out_items, status, (hipStream_t)stream), who);
+}
+
 int mvin_sample_negatives_supported(int n_item) { return mvin::sample_negatives_supported(n_item) ? 1 : 0; }
 
 int mvin_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
                           int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out_items, int64_t* status,
                           void* stream) {
-    const char* who = "mvin_sample_negatives";
-    if (!counts || !out_ptr || !out_items || !status) return fail(-1, "%s: null pointer (counts / out_ptr / out_items / status)", who);
-    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together (both NULL = no exclusions)", who);
-    if (n_user < 0) return fail(-2, "%s: n_user=%d", who, n_user);
-    if (!mvin::sample_negatives_supported(n_item))
-        return fail(-3, "%s: unsupported n_item=%d (1..%d: the catalogue's bitmap lives in LDS)", who, n_item, MVIN_NEG_MAX_ITEMS);
-    return hip_result(mvin::launch_sample_negatives(excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, seed, round, out_items,
-                                                    status, (hipStream_t)stream), who);
+    return sample_negatives_impl("mvin_sample_negatives", excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, nullptr, nullptr, false,
+                                 seed, round, out_items, status, stream);
 }
 
-int mvin_sample_negatives_weighted_supported(int n_item) { return mvin::sample_negatives_weighted_supported(n_item) ? 1 : 0; }
+int mvin_sample_negatives_weighted_supported(int n_item) { return mvin::sample_negatives_supported(n_item) ? 1 : 0; }
 
 int mvin_sample_negatives_weighted(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
                                    int n_user, int n_item, const uint32_t* alias_tab, const uint32_t* mask_bits, uint64_t seed,
                                    uint64_t round, int32_t* out_items, int64_t* status, void* stream) {
-    const char* who = "mvin_sample_negatives_weighted";
-    if (!counts || !out_ptr || !alias_tab || !out_items || !status)
-        return fail(-1, "%s: null pointer (counts / out_ptr / alias_tab / out_items / status)", who);
-    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together (both NULL = no exclusions)", who);
-    if (n_user < 0) return fail(-2, "%s: n_user=%d", who, n_user);
-    if (!mvin::sample_negatives_weighted_supported(n_item))
-        return fail(-3, "%s: unsupported n_item=%d (1..%d: the catalogue's bitmap lives in LDS)", who, n_item, MVIN_NEG_MAX_ITEMS);
-    return hip_result(mvin::launch_sample_negatives_weighted(excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, alias_tab, mask_bits,
-                                                             seed, round, out_items, status, (hipStream_t)stream), who);
+    return sample_negatives_impl("mvin_sample_negatives_weighted", excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, alias_tab,
+                                 mask_bits, true, seed, round, out_items, status, stream);
 }
 
 int mvin_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key, int64_t n_groups,

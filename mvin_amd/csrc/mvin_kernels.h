@@ -445,12 +445,9 @@ hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t
                              int64_t* out, hipStream_t st);
 bool sample_negatives_supported(int n_item);                  // per-user negatives without replacement (mvin_negatives.hip)
 hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
-                                   int n_user, int n_item, uint64_t seed, uint64_t round, int32_t* out, int64_t* status, hipStream_t st);
-bool sample_negatives_weighted_supported(int n_item);         // the same from an alias table, with a mask (mvin_negatives_weighted.hip)
-hipError_t launch_sample_negatives_weighted(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts,
-                                            const int64_t* out_ptr, int n_user, int n_item, const uint32_t* alias_tab,
-                                            const uint32_t* mask_bits, uint64_t seed, uint64_t round, int32_t* out,
-                                            int64_t* status, hipStream_t st);
+                                   int n_user, int n_item, const uint32_t* alias_tab, const uint32_t* mask_bits, uint64_t seed,
+                                   uint64_t round, int32_t* out, int64_t* status,
+                                   hipStream_t st);           // alias_tab NULL: the uniform draw (and no mask); else the alias draw
 hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
                             float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
                             hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip)

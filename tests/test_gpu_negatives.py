@@ -1,6 +1,8 @@
 """-m gpu: mvin_sample_negatives (data_prep.sample_negatives) bit for bit against the host restatement of its rule
 (tests/neg_oracle.py), its independence of the launch shape, and the resampled-negatives path of the harness
 (NegativeSampler, train_epoch_resampled, train(..., negatives="resample"))."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -90,6 +92,64 @@ def test_catalogue_smaller_than_one_round_of_draws(hip_lib, with_rows):
     rng = np.random.default_rng(8)
     rows = [rng.integers(0, 8, size=int(rng.integers(0, 4))).tolist() for _ in range(n_user)] if with_rows else None
     check(rows, [8] * n_user, 8, seed=3, round=1, oracle=no.sample_negatives_scalar)
+
+
+def against(case, seed, round):
+    """The kernel under the current launch shape against the case's scalar-oracle result (computed once per case)."""
+    rows, counts, n_item, want, want_status = case
+    items, status = gpu(rows, counts, n_item, seed, round)
+    assert items.dtype == np.int32 and items.shape == want.shape
+    assert np.array_equal(items, want), (n_item, np.argwhere(items != want)[:8].ravel())
+    assert status.tolist() == want_status.tolist()
+    return items, status
+
+
+@functools.lru_cache(maxsize=None)
+def duplicate_cases():
+    """A: n_item = 8, m = 8, no rows -- every draw of a round repeats a value of another lane, mostly of another wave.
+    B: n_item = 300, rows of 0 .. 100 ids, m = c_u -- dozens of distinct lost values per wave in the early rounds, hardly a
+    candidate in the late ones, until the catalogue is exhausted."""
+    a = (None, [8] * 60, 8) + no.sample_negatives_scalar(None, None, [8] * 60, 8, 3, 1)[1:]
+    rng = np.random.default_rng(300)
+    rows = [rng.integers(0, 300, size=int(rng.integers(0, 101))).tolist() for _ in range(12)]
+    counts = [300 - len(set(r)) for r in rows]
+    b = (rows, counts, 300) + no.sample_negatives_scalar(*csr(rows), counts, 300, 5, 2)[1:]
+    return a, b
+
+
+@pytest.mark.parametrize("block", ["64", "128", "256"])
+def test_in_round_duplicates_at_every_round_size(hip_lib, monkeypatch, block):
+    monkeypatch.setenv("MVIN_NEG_BLOCK", block)
+    a, b = duplicate_cases()
+    assert against(a, 3, 1)[1].tolist() == [0, 0]
+    items, status = against(b, 5, 2)
+    assert status.tolist() == [0, 0] and (items >= 0).all()
+
+
+@functools.lru_cache(maxsize=None)
+def bitmap_case():
+    """Eight users for ONE workgroup over 1 000 items (32 bitmap words): every other user asks for the whole catalogue, so a bit
+    that the user before left behind shows as a -1.  Before them: m = 1 without a row (a whole round's candidates set bits past
+    m_eff; only the last round's restore clears them), a row of 900 ids (the whole bitmap is reloaded), a row of 5 ids (the
+    touched words are restored), a row of ids all outside the catalogue."""
+    n_item = 1000
+    rng = np.random.default_rng(1000)
+    rows = [[], [], rng.permutation(n_item)[:900].tolist(), [], rng.permutation(n_item)[:5].tolist(), [],
+            [-1, n_item, n_item + 31, -(1 << 31), (1 << 31) - 1, 1 << 20], []]
+    counts = [1, n_item, 100, n_item, 3, n_item, 1, n_item]
+    return (rows, counts, n_item) + no.sample_negatives_scalar(*csr(rows), counts, n_item, 7, 2)[1:]
+
+
+@pytest.mark.parametrize("block", ["64", "256"])
+def test_the_bitmap_is_restored_between_the_users_of_one_workgroup(hip_lib, monkeypatch, block):
+    monkeypatch.setenv("MVIN_NEG_WGS", "1")
+    monkeypatch.setenv("MVIN_NEG_BLOCK", block)
+    case = bitmap_case()
+    items, status = against(case, 7, 2)
+    assert status.tolist() == [0, 0]
+    ptr = np.concatenate([[0], np.cumsum(case[1])])
+    for u in (1, 3, 5, 7):
+        assert sorted(items[ptr[u]:ptr[u + 1]].tolist()) == list(range(1000)), u
 
 
 def test_null_exclusion_pointers(hip_lib):

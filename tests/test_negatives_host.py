@@ -319,7 +319,8 @@ def _hipcc():
     return None
 
 
-def test_negatives_kernel_uses_no_scratch(tmp_path):
+def test_both_negatives_kernels_use_no_scratch(tmp_path):
+    """The one sampler source holds two instances of one kernel body, the uniform draw and the alias draw."""
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc not available")
@@ -329,12 +330,12 @@ def test_negatives_kernel_uses_no_scratch(tmp_path):
                    check=True, capture_output=True, timeout=600)
     text = out.read_text()
     kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S*sample_negatives_kernel\S*)\s*$(.*?)\.end_amdhsa_kernel", text, re.S | re.M)
-    assert len(kernels) == 1, [name for name, _ in kernels]
-    assert len(re.findall(r"^\s*\.amdhsa_kernel\s", text, re.M)) == 1          # nothing else in the unit
+    assert len(kernels) == 2 and len({name for name, _ in kernels}) == 2, [name for name, _ in kernels]
+    assert len(re.findall(r"^\s*\.amdhsa_kernel\s", text, re.M)) == 2          # nothing else in the unit
     for name, body in kernels:
         seg = re.search(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", body)
         assert seg is not None and int(seg.group(1)) == 0, name
         assert re.search(r"\.amdhsa_wavefront_size32\s+1", body) is None, name
     for key in ("vgpr_spill_count", "sgpr_spill_count"):
         found = re.findall(rf"\.{key}:\s*(\d+)", text)
-        assert found and all(int(v) == 0 for v in found), (key, found)
+        assert len(found) == 2 and all(int(v) == 0 for v in found), (key, found)
