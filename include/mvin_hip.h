@@ -632,6 +632,60 @@ MVIN_API int mvin_l2_adam_multi_dev(const mvin_param_seg* segs_device, int nseg,
                            float* v_flat, float* loss_accum, int apply_adam, const float* lr_t_device, float beta1,
                            float beta2, float eps, void* stream);
 
+/* Guard of the training step (an opt-in extension: the reference's model.py:414 is a bare minimize): the global norm of the
+ * gradient Adam is about to see, the number of its non-finite elements, and from them -- on the device, no host round trip --
+ * the clipping scale, whether the step is applied at all, and its bias-corrected step size.
+ *
+ * The element measured is e = fmaf(l2, x, g) where the segment's l2 != 0, else g: what mvin_l2_adam_multi feeds Adam.
+ * Each float32 e is squared and summed as double (the square of a float32 is exact in double).  No floating-point atomics:
+ * items_device is a static table of work items, ascending in `first`, none straddling a segment, len <= 4096; item i
+ * leaves partials_device[i] by a fixed tree inside one workgroup, a second one-workgroup launch adds every segment's
+ * partials in index order and then the segments in order.  state and partials are therefore bit-identical whatever the grid
+ * (grid_cap: workgroups of the first launch, 0 = automatic).  An item that does not lie inside its segment is not read and
+ * counts as one non-finite element.
+ *
+ * Decision, with clip (+inf: no clipping) and skip read from the state block:
+ *   ok = !(skip && nonfinite > 0);  clipped = nonfinite == 0 && sumsq > (double)clip * clip  (exact, no square root);
+ *   scale = clipped ? (float)((double)clip / sqrt(sumsq)) : 1.0f;
+ *   ok: applied += 1, lr_t = lr_table[min(applied, lr_table_len) - 1]     else: skipped_steps += 1, lr_t stays.
+ * The counters accumulate across calls; the host reads (and may rewrite) the block when it wants them. */
+#define MVIN_GUARD_MAX_ITEM 4096
+typedef struct {
+    int32_t seg;                   /* index into segs_device */
+    int32_t len;                   /* 1..MVIN_GUARD_MAX_ITEM elements */
+    int64_t first;                 /* first flat element */
+} mvin_guard_item;
+typedef struct {
+    double sumsq;
+    uint32_t nonfinite;
+    uint32_t pad_;                 /* written as 0 */
+} mvin_guard_partial;
+typedef struct {
+    float clip;                    /* in: clip_norm, +inf = none */
+    int32_t skip;                  /* in: skip a step with non-finite elements */
+    int32_t ok;                    /* last step: applied? */
+    int32_t clipped;               /* last step: scaled? */
+    float scale;                   /* last step: factor on the gradient */
+    float lr_t;                    /* step size of the last APPLIED step */
+    int64_t steps, clipped_steps, skipped_steps;
+    int64_t applied;               /* the optimizer's step count */
+    int64_t last_nonfinite;
+    int64_t finite_steps;          /* steps with a finite norm: ... */
+    double norm_sum, norm_max;     /* ... their sum and maximum */
+    double last_norm, last_sumsq;
+    double seg_sumsq[256];         /* last step, per segment */
+} mvin_guard_state;
+MVIN_API int mvin_grad_guard(const mvin_param_seg* segs_device, int nseg, int64_t total, const float* g_flat,
+                    const mvin_guard_item* items_device, int nitems, mvin_guard_partial* partials_device,
+                    const float* lr_table_device, int lr_table_len, mvin_guard_state* state_device, int grid_cap,
+                    void* stream);
+/* mvin_l2_adam_multi_dev under that state block: Adam sees fmaf(l2, x, g) * state->scale with the step size state->lr_t,
+ * and with state->ok == 0 x, m and v are not written.  The L2 loss term and the write-back of g (UNSCALED, where
+ * l2 != 0) are those of mvin_l2_adam_multi either way. */
+MVIN_API int mvin_l2_adam_multi_guarded(const mvin_param_seg* segs_device, int nseg, int64_t total, float* g_flat, float* m_flat,
+                               float* v_flat, float* loss_accum, int apply_adam, const mvin_guard_state* state_device,
+                               float beta1, float beta2, float eps, void* stream);
+
 /* dtable[ids[r], :] += alpha * x[r, :]  -- backward of tf.nn.embedding_lookup (ids int32 or int64). */
 MVIN_API int mvin_scatter_add_rows(float* dtable, const void* ids, int ids64, const float* x, int64_t rows, int D,
                           float alpha, void* stream);

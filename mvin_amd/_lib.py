@@ -201,6 +201,10 @@ SIGNATURES = {
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "mvin_l2_adam_multi_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_int,
                                          _c_f32p, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "mvin_grad_guard": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _c_f32p, C.c_void_p, C.c_int, C.c_void_p, _c_f32p, C.c_int,
+                                  C.c_void_p, C.c_int, C.c_void_p]),
+    "mvin_l2_adam_multi_guarded": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_int,
+                                             C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "mvin_eltwise": (C.c_int, [C.c_int, C.c_int64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_float,
                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "mvin_scatter_add_rows": (C.c_int, [_c_f32p, C.c_void_p, C.c_int, _c_f32p, C.c_int64, C.c_int, C.c_float,

@@ -1749,6 +1749,36 @@ int mvin_l2_adam_multi_dev(const mvin_param_seg* segs_device, int nseg, int64_t 
                               loss_accum, apply_adam, 0.f, lr_t_device, beta1, beta2, eps, stream);
 }
 
+int mvin_l2_adam_multi_guarded(const mvin_param_seg* segs_device, int nseg, int64_t total, float* g_flat, float* m_flat,
+                               float* v_flat, float* loss_accum, int apply_adam, const mvin_guard_state* state_device,
+                               float beta1, float beta2, float eps, void* stream) {
+    const char* who = "mvin_l2_adam_multi_guarded";
+    if (!segs_device || !g_flat || !state_device) return fail(-1, "%s: null pointer (segs / g / state)", who);
+    if (nseg <= 0 || nseg > 256) return fail(-2, "%s: nseg=%d (1..256)", who, nseg);
+    if (total <= 0) return fail(-2, "%s: total=%lld", who, (long long)total);
+    if (apply_adam && (!m_flat || !v_flat)) return fail(-1, "%s: Adam step needs the moment buffers", who);
+    return hip_result(mvin::launch_l2_adam_multi_guarded(segs_device, nseg, total, g_flat, m_flat, v_flat, loss_accum,
+                                                         apply_adam, state_device, beta1, beta2, eps,
+                                                         (hipStream_t)stream), who);
+}
+
+int mvin_grad_guard(const mvin_param_seg* segs_device, int nseg, int64_t total, const float* g_flat,
+                    const mvin_guard_item* items_device, int nitems, mvin_guard_partial* partials_device,
+                    const float* lr_table_device, int lr_table_len, mvin_guard_state* state_device, int grid_cap,
+                    void* stream) {
+    const char* who = "mvin_grad_guard";
+    if (!segs_device || !g_flat || !items_device || !partials_device || !lr_table_device || !state_device)
+        return fail(-1, "%s: null pointer (segs / g / items / partials / lr_table / state)", who);
+    if (nseg <= 0 || nseg > 256) return fail(-2, "%s: nseg=%d (1..256)", who, nseg);
+    if (total <= 0) return fail(-2, "%s: total=%lld", who, (long long)total);
+    if (nitems <= 0) return fail(-2, "%s: nitems=%d: an empty work table", who, nitems);
+    if (lr_table_len <= 0) return fail(-2, "%s: lr_table_len=%d", who, lr_table_len);
+    if (grid_cap < 0) return fail(-2, "%s: grid_cap=%d (0 = automatic)", who, grid_cap);
+    return hip_result(mvin::launch_grad_guard(segs_device, nseg, total, g_flat, items_device, nitems, partials_device,
+                                              lr_table_device, lr_table_len, state_device, grid_cap,
+                                              (hipStream_t)stream), who);
+}
+
 int mvin_scatter_add_rows(float* dtable, const void* ids, int ids64, const float* x, int64_t rows, int D, float alpha,
                           void* stream) {
     if (!dtable || !ids || !x) return fail(-1, "mvin_scatter_add_rows: null pointer");

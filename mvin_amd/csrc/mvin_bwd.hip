@@ -661,14 +661,26 @@ static int blocks_for(int64_t n, int per) {
 // g += l2 x) and, optionally, the tf.train.AdamOptimizer update (model.py:414).  Gradients and
 // the Adam moments live in flat buffers; a static segment table maps flat ranges to parameters.
 // ------------------------------------------------------------------------------------------
+// kGuarded (mvin_l2_adam_multi_guarded): the step is governed by the state block mvin_grad_guard left -- Adam sees the
+// gradient times guard->scale with the step size guard->lr_t, and with guard->ok == 0 it is the apply_adam = 0 pass: x, m
+// and v are neither read nor written.  g is written back unscaled and the L2 loss term is added either way.
+template <bool kGuarded>
 __global__ __launch_bounds__(256) void l2_adam_multi_kernel(const mvin_param_seg* __restrict__ segs, int nseg,
                                                             int64_t total, float* __restrict__ g,
                                                             float* __restrict__ mo, float* __restrict__ vo,
                                                             float* accum, int apply_adam, float lr_t,
                                                             const float* __restrict__ lr_dev, float b1,
-                                                            float b2, float eps) {
+                                                            float b2, float eps,
+                                                            const mvin_guard_state* __restrict__ guard) {
     __shared__ int64_t s_off[257];
-    if (lr_dev) lr_t = *lr_dev;              // step size kept on the device: a captured step replays unchanged
+    float scale = 1.f;
+    if constexpr (kGuarded) {
+        lr_t = guard->lr_t;
+        scale = guard->scale;
+        apply_adam = apply_adam && guard->ok;
+    } else {
+        if (lr_dev) lr_t = *lr_dev;          // step size kept on the device: a captured step replays unchanged
+    }
     for (int i = threadIdx.x; i < nseg; i += blockDim.x) s_off[i] = segs[i].off;
     if (threadIdx.x == 0) s_off[nseg] = total;
     __syncthreads();
@@ -689,8 +701,10 @@ __global__ __launch_bounds__(256) void l2_adam_multi_kernel(const mvin_param_seg
             local = fmaf(0.5f * l2 * x, x, local);
         }
         if (apply_adam) {
-            m = b1 * m + (1.f - b1) * gr;
-            v = b2 * v + (1.f - b2) * gr * gr;
+            float ga = gr;                   // gr itself goes back to g: last_grads stay the pre-clip gradients
+            if constexpr (kGuarded) ga = gr * scale;
+            m = b1 * m + (1.f - b1) * ga;
+            v = b2 * v + (1.f - b2) * ga * ga;
             x = x - lr_t * m / (sqrtf(v) + eps);
         }
         return x;
@@ -746,8 +760,16 @@ __global__ __launch_bounds__(256) void l2_adam_multi_kernel(const mvin_param_seg
 hipError_t launch_l2_adam_multi(const mvin_param_seg* segs, int nseg, int64_t total, float* g, float* mo, float* vo,
                                 float* accum, int apply_adam, float lr_t, const float* lr_dev, float b1, float b2,
                                 float eps, hipStream_t st) {
-    l2_adam_multi_kernel<<<blocks_for((total + 3) / 4, 4096), 256, 0, st>>>(segs, nseg, total, g, mo, vo, accum, apply_adam,
-                                                                  lr_t, lr_dev, b1, b2, eps);
+    l2_adam_multi_kernel<false><<<blocks_for((total + 3) / 4, 4096), 256, 0, st>>>(segs, nseg, total, g, mo, vo, accum,
+                                                                         apply_adam, lr_t, lr_dev, b1, b2, eps, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_l2_adam_multi_guarded(const mvin_param_seg* segs, int nseg, int64_t total, float* g, float* mo, float* vo,
+                                        float* accum, int apply_adam, const mvin_guard_state* guard, float b1, float b2,
+                                        float eps, hipStream_t st) {
+    l2_adam_multi_kernel<true><<<blocks_for((total + 3) / 4, 4096), 256, 0, st>>>(segs, nseg, total, g, mo, vo, accum,
+                                                                        apply_adam, 0.f, nullptr, b1, b2, eps, guard);
     return hipGetLastError();
 }
 

@@ -325,6 +325,13 @@ hipError_t launch_eltwise(const EltArgs& a, hipStream_t st);
 hipError_t launch_l2_adam_multi(const mvin_param_seg* segs, int nseg, int64_t total, float* g, float* mo, float* vo,
                                 float* accum, int apply_adam, float lr_t, const float* lr_dev, float b1, float b2,
                                 float eps, hipStream_t st);
+hipError_t launch_l2_adam_multi_guarded(const mvin_param_seg* segs, int nseg, int64_t total, float* g, float* mo, float* vo,
+                                        float* accum, int apply_adam, const mvin_guard_state* guard, float b1, float b2,
+                                        float eps, hipStream_t st);
+hipError_t launch_grad_guard(const mvin_param_seg* segs, int nseg, int64_t total, const float* g,
+                             const mvin_guard_item* items, int nitems, mvin_guard_partial* partials,
+                             const float* lr_table, int lr_table_len, mvin_guard_state* state, int grid_cap,
+                             hipStream_t st);
 hipError_t launch_scatter_add_rows(float* dtable, const int32_t* ids, int ids64, const float* x, int64_t rows, int D,
                                    float alpha, hipStream_t st);
 hipError_t launch_linear_wgrad(WgradArgs a, hipStream_t st);

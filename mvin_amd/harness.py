@@ -282,7 +282,8 @@ def _epoch_trainer(feeder, batch_size, graph):
         gt = getattr(model, "_graphed_trainer", None)
         if (gt is None or gt.tr is not model.trainer or gt.users.shape[0] != batch_size
                 or gt._storage_key() != gt._captured        # set_adjacency / a rebound parameter: capture again
-                or gt.objective != (model.trainer.objective, model.trainer.group_size)):     # ... or another head
+                or gt.objective != (model.trainer.objective, model.trainer.group_size)      # ... or another head
+                or gt.guard != model.trainer.guard_key()):                                   # ... or the guard on / off
             try:
                 gt = model._graphed_trainer = GraphedTrainer(model.trainer, batch_size)
             except RuntimeError as e:                       # capture failed: the same kernels, launched eagerly
@@ -843,7 +844,8 @@ class EarlyStop(object):
 
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
-          objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0):
+          objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0,
+          clip_norm=None, skip_nonfinite=False):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -886,6 +888,12 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     rows of ``train_data`` with item i (data_prep.NegativeSampler(dist=...), mvin_sample_negatives_weighted; an item of weight
     zero is never a negative).  It reaches every training mode through the sampler: cross-entropy epochs, the ranking
     objectives' groups and the hard-negative pool.  An opt-in extension, like the ranking objectives.
+    ``clip_norm`` / ``skip_nonfinite``: the guard of the optimizer step (training.Trainer.set_guard), set on the model's trainer
+    before the first epoch: gradients clipped to the global norm ``clip_norm`` (a finite number > 0) and / or a step with a
+    non-finite gradient left out, both decided on the device, so a step stays one graph replay.  With either set the epoch
+    record gains "grad_norm": {"mean", "max"} (over the epoch's steps with a finite norm), "clipped_steps" and
+    "skipped_steps", from one read-back per epoch; "loss" stays the mean over every step, so an epoch with skipped steps may
+    show nan there -- "skipped_steps" says why.  An opt-in extension: off, the steps are exactly the unguarded ones.
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
@@ -899,6 +907,11 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         raise ValueError(f"neg_dist={neg_dist!r}: expected 'uniform' or 'popularity'")
     if neg_dist != "uniform" and negatives == "fixed":
         raise ValueError(f"neg_dist={neg_dist!r} is the distribution of the per-epoch sampler: it needs negatives='resample' or 'hard'")
+    from .training import check_clip_norm
+    clip_norm = check_clip_norm(clip_norm)
+    if not isinstance(skip_nonfinite, (bool, np.bool_)):
+        raise ValueError(f"skip_nonfinite={skip_nonfinite!r}: expected True or False")
+    guard = clip_norm is not None or bool(skip_nonfinite)
     ranked = objective != "bce"
     hard = negatives == "hard"
     if hard and not ranked:
@@ -947,6 +960,13 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
                                   seed=getattr(args, "neg_seed", 1), device=model.device, **dist_kw)
     if not ranked and model.trainer is not None:
         model.trainer.set_objective("bce")
+    if guard and model.trainer is None:
+        from .training import Trainer
+        model.trainer = Trainer(model)
+    if model.trainer is not None:
+        model.trainer.set_guard(clip_norm, bool(skip_nonfinite))
+        if guard:
+            model.trainer.guard_stats(reset=True)            # the epoch records count from here
     for epoch in range(getattr(args, "n_epochs", 20)):
         use_graph = (args.batch_size <= 2048) if graph == "auto" else bool(graph)
         if hard:
@@ -963,6 +983,10 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
             rec["pairwise_acc"] = model.trainer.last_pairwise_acc
         if hard:
             rec["hard_rate"], rec["pool_rate"] = model.trainer.last_hard_rate, model.trainer.last_pool_rate
+        if guard:
+            gs = model.trainer.guard_stats(reset=True)
+            rec["grad_norm"] = {"mean": gs["norm_mean"], "max": gs["norm_max"]}
+            rec["clipped_steps"], rec["skipped_steps"] = gs["clipped_steps"], gs["skipped_steps"]
         if show_topk:
             for mode in ("eval", "test"):
                 if topk_impl in ("batched", "ranked"):

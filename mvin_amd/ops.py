@@ -7,6 +7,7 @@ there is no CPU / eager fallback.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1394,6 +1395,57 @@ def l2_adam_multi(segs, nseg, total, g, m, v, loss_accum, apply_adam, lr_t, beta
     _lib.check(lib.mvin_l2_adam_multi(_p(segs), nseg, total, _p(g), _p(m), _p(v), _p(loss_accum),
                                       1 if apply_adam else 0, lr_t, beta1, beta2, eps, _stream()),
                "mvin_l2_adam_multi")
+
+
+GUARD_MAX_ITEM = 4096                  # include/mvin_hip.h: MVIN_GUARD_MAX_ITEM
+GUARD_MAX_SEG = 256
+GUARD_ITEM = np.dtype([("seg", "<i4"), ("len", "<i4"), ("first", "<i8")])                       # mvin_guard_item
+GUARD_PARTIAL = np.dtype([("sumsq", "<f8"), ("nonfinite", "<u4"), ("pad", "<u4")])              # mvin_guard_partial
+GUARD_STATE = np.dtype([("clip", "<f4"), ("skip", "<i4"), ("ok", "<i4"), ("clipped", "<i4"), ("scale", "<f4"), ("lr_t", "<f4"),
+                        ("steps", "<i8"), ("clipped_steps", "<i8"), ("skipped_steps", "<i8"), ("applied", "<i8"),
+                        ("last_nonfinite", "<i8"), ("finite_steps", "<i8"), ("norm_sum", "<f8"), ("norm_max", "<f8"), ("last_norm", "<f8"),
+                        ("last_sumsq", "<f8"), ("seg_sumsq", "<f8", (GUARD_MAX_SEG,))])         # mvin_guard_state
+
+
+def guard_work_items(segments):
+    """The static work table of mvin_grad_guard for ``segments`` = [(off, n), ...] (flat offset and length, ascending and
+    contiguous like mvin_param_seg): items of at most GUARD_MAX_ITEM elements, ascending, none across a segment boundary;
+    at most total / GUARD_MAX_ITEM + nseg of them.  A numpy array of GUARD_ITEM."""
+    rows = []
+    for s, (off, n) in enumerate(segments):
+        for first in range(int(off), int(off) + int(n), GUARD_MAX_ITEM):
+            rows.append((s, min(GUARD_MAX_ITEM, int(off) + int(n) - first), first))
+    return np.array(rows, dtype=GUARD_ITEM)
+
+
+def grad_guard(segs, nseg, total, g, items, nitems, partials, lr_table, state, grid_cap=0):
+    """mvin_grad_guard (see include/mvin_hip.h): ``items`` / ``partials`` / ``state`` are uint8 device tensors holding
+    GUARD_ITEM[nitems] / GUARD_PARTIAL[nitems] / one GUARD_STATE, ``lr_table`` the fp32 step sizes of steps 1..T.
+    Two launches; enqueues only."""
+    _chk(g, F32, "g"), _chk(lr_table, F32, "lr_table")
+    for t, nm, need in ((items, "items", nitems * GUARD_ITEM.itemsize), (partials, "partials", nitems * GUARD_PARTIAL.itemsize),
+                        (state, "state", GUARD_STATE.itemsize)):
+        _chk(t, torch.uint8, nm)
+        if t is not None and t.numel() < need:
+            raise ValueError(f"grad_guard: {nm} holds {t.numel()} bytes, {need} needed")
+    if g is not None and g.numel() < total:
+        raise ValueError(f"grad_guard: g holds {g.numel()} floats, total={total}")
+    _lib.check(_lib.load().mvin_grad_guard(_p(segs), nseg, total, _p(g), _p(items), nitems, _p(partials), _p(lr_table),
+                                           0 if lr_table is None else lr_table.numel(), _p(state), int(grid_cap), _stream()),
+               "mvin_grad_guard")
+
+
+def l2_adam_multi_guarded(segs, nseg, total, g, m, v, loss_accum, apply_adam, state, beta1, beta2, eps):
+    """mvin_l2_adam_multi_guarded: ``l2_adam_multi`` with scale, step size and apply / skip read from the GUARD_STATE block
+    ``grad_guard`` left (uint8 device tensor)."""
+    for t, nm in ((g, "g"), (m, "m"), (v, "v"), (loss_accum, "loss_accum")):
+        _chk(t, F32, nm)
+    _chk(state, torch.uint8, "state")
+    if state is not None and state.numel() < GUARD_STATE.itemsize:
+        raise ValueError(f"l2_adam_multi_guarded: state holds {state.numel()} bytes, {GUARD_STATE.itemsize} needed")
+    _lib.check(_lib.load().mvin_l2_adam_multi_guarded(_p(segs), nseg, total, _p(g), _p(m), _p(v), _p(loss_accum),
+                                                      1 if apply_adam else 0, _p(state), beta1, beta2, eps, _stream()),
+               "mvin_l2_adam_multi_guarded")
 
 
 def axpby(alpha, x, beta, y):

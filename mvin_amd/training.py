@@ -16,6 +16,7 @@ Gradient identities used (see DESIGN.md 3.1 for the forward algebra they mirror)
     dS' = dZ.W_L^T feeds one gather-form mvin_agg_bwd that scatter-adds (p_k/K) dS' into dE[y_k];
   * key addressing: s_m = h_m . V[b, r_m], V = E[item].R_KGE[r]  =>  dR_KGE[r] = E[item]^T dV[:, r].
 """
+import numbers
 import os
 
 import numpy as np
@@ -25,6 +26,19 @@ from . import ops
 from .params import aggregator_keys
 
 F32 = torch.float32
+
+
+def check_clip_norm(clip_norm):
+    """``clip_norm`` of Trainer / harness.train: None, or a finite number > 0 (returned as float)."""
+    if clip_norm is None:
+        return None
+    if (not isinstance(clip_norm, (numbers.Real, np.floating, np.integer)) or isinstance(clip_norm, (bool, np.bool_))
+            or not np.isfinite(float(clip_norm)) or float(clip_norm) <= 0.0):
+        raise ValueError(f"clip_norm={clip_norm!r}: expected a finite number > 0 or None")
+    return float(clip_norm)
+
+
+GUARD_LR_TABLE_MAX = 1 << 20
 
 
 class _Grads(object):
@@ -61,7 +75,7 @@ class Trainer(object):
     OBJECTIVES = ("bce", "bpr", "softmax")
 
     def __init__(self, model, lr=None, beta1=0.9, beta2=0.999, eps=1e-8, group=None, world=1, objective="bce",
-                 group_size=None):
+                 group_size=None, clip_norm=None, skip_nonfinite=False):
         """``world`` > 1: data-parallel training, one process per GPU.  Every rank steps on its own
         1/world of the batch; the data-dependent gradients (and loss terms) of all ranks are summed
         with ONE all-reduce of the flat gradient buffer (RCCL: torch.distributed backend "nccl") before
@@ -69,7 +83,10 @@ class Trainer(object):
         parameters stay bit-identical across ranks.
 
         ``objective``: "bce" (the reference's sigmoid cross-entropy over independent rows, model.py:379-380) or a ranking
-        objective over groups of ``group_size`` = 1 + n_neg rows, "bpr" / "softmax" (``set_objective``)."""
+        objective over groups of ``group_size`` = 1 + n_neg rows, "bpr" / "softmax" (``set_objective``).
+
+        ``clip_norm`` / ``skip_nonfinite``: the guard of the step (``set_guard``), off by default."""
+        clip_norm = check_clip_norm(clip_norm)
         a = model.args
         self.group, self.world = group, int(world)
         if not a.wide_deep:
@@ -92,6 +109,131 @@ class Trainer(object):
         self.rank_counts = torch.zeros(2, dtype=torch.int64, device=model.device)
         self.last_pairwise_acc = None        # harness.train_epoch_ranked: rank_counts[0] / (2 rank_counts[1]) of its last epoch
         self.set_objective(objective, group_size)
+        self.clip_norm, self.skip_nonfinite = None, False
+        self._guard_state = self._guard_partials = self._lr_table = self._lr_table_of = None
+        self.set_guard(clip_norm, skip_nonfinite)
+
+    # ------------------------------------------------------------------ guard of the step
+    def set_guard(self, clip_norm=None, skip_nonfinite=False):
+        """Guard the optimizer step (an opt-in extension; the reference's model.py:414 is a bare minimize):
+          ``clip_norm``       a finite number > 0: when the global L2 norm of the gradient Adam is about to see -- every
+                              parameter, the per-parameter L2 terms included -- exceeds it, that gradient is scaled by
+                              clip_norm / norm;
+          ``skip_nonfinite``  a step whose gradient has a NaN or an infinity is not applied: parameters, both moments and
+                              the optimizer's step count stay exactly as they were.
+        The guard is ON when either is set.  Norm, count and decision are made on the device between the all-reduce and the
+        optimizer launch (mvin_grad_guard, mvin_l2_adam_multi_guarded): no host round trip, so a captured step stays one
+        graph replay.  ``clip_norm`` and ``skip_nonfinite`` live in a device state block: changing their VALUES needs no
+        recapture; switching the guard on or off changes the launches of the step (``guard_key``).  With the guard on the
+        optimizer's step count is the block's ``applied``; ``self.t`` counts attempted steps.  Switching the guard off
+        reads ``applied`` back into ``self.t`` (one synchronisation), so the bias correction goes on from the applied steps.
+        ``last_grads`` stay the unscaled gradients.  Data parallel: the guard sees the all-reduced buffer, so every rank
+        decides identically with no extra communication -- this has not run on more than one GPU."""
+        clip_norm = check_clip_norm(clip_norm)
+        skip_nonfinite = bool(skip_nonfinite)
+        on = clip_norm is not None or skip_nonfinite
+        was_on = self.guard_on
+        if on:
+            self._guard_lr_table()
+            if self._guard_state is None:
+                dev = self.m.device
+                self._guard_state = torch.zeros(ops.GUARD_STATE.itemsize, dtype=torch.uint8, device=dev)
+                self._guard_partials = torch.zeros(self._guard_nitems * ops.GUARD_PARTIAL.itemsize, dtype=torch.uint8,
+                                                   device=dev)
+            head = np.zeros(1, dtype=[("clip", "<f4"), ("skip", "<i4")])
+            head[0] = (np.inf if clip_norm is None else clip_norm, 1 if skip_nonfinite else 0)
+            self._guard_state[:8].copy_(torch.from_numpy(head.view(np.uint8)))
+            if not was_on:                     # the optimizer goes on from the steps it has applied so far
+                o = ops.GUARD_STATE.fields["applied"][1]
+                self._guard_state[o:o + 8].copy_(torch.from_numpy(np.array([self.t], dtype="<i8").view(np.uint8)))
+        elif was_on:
+            self.t = int(self._guard_block()["applied"])
+        self.clip_norm, self.skip_nonfinite = clip_norm, skip_nonfinite
+
+    @property
+    def guard_on(self):
+        return self.clip_norm is not None or self.skip_nonfinite
+
+    def guard_key(self):
+        """What a captured step depends on besides the objective: None with the guard off, else the addresses its two
+        extra launches read (GraphedTrainer records it; another key means another graph)."""
+        if not self.guard_on:
+            return None
+        return (self._guard_state.data_ptr(), self._lr_table.data_ptr(), self._lr_table.numel())
+
+    def lr_table(self):
+        """float32(lr_t(t)) for t = 1..T, T = the first t at which beta1**t and beta2**t (as float32 betas, like ``lr_t``) are
+        both below 2**-54: from there 1 - beta**t == 1 and lr_t(t) == lr exactly in float64, so the guard's device-side
+        step count indexes this table clamped at T.  ValueError when T > 2**20."""
+        b1, b2 = float(np.float32(self.b1)), float(np.float32(self.b2))
+        lim = 2.0 ** -54
+        T = 1
+        for b in (b1, b2):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"beta={b!r}: the guard's step-size table needs 0 <= beta < 1")
+            if b > 0.0:
+                est = np.log(lim) / np.log(b)
+                if est > GUARD_LR_TABLE_MAX + 2:
+                    raise ValueError(f"beta={b!r}: the guard's step-size table would need {est:.3g} entries (limit 2**20)")
+                t = max(1, int(est) - 2)
+                while b ** t >= lim:
+                    t += 1
+                while t > 1 and b ** (t - 1) < lim:
+                    t -= 1
+                T = max(T, t)
+        if T > GUARD_LR_TABLE_MAX:
+            raise ValueError(f"the guard's step-size table would need {T} entries (limit 2**20)")
+        return np.array([np.float32(self.lr_t(t)) for t in range(1, T + 1)], dtype=np.float32)
+
+    def _guard_lr_table(self):
+        """Upload ``lr_table`` once per (lr, beta1, beta2); a table of another length is a new tensor (``guard_key``)."""
+        of = (float(self.lr), float(self.b1), float(self.b2))
+        if self._lr_table_of == of:
+            return
+        tab = torch.from_numpy(self.lr_table())
+        if self._lr_table is not None and self._lr_table.numel() == tab.numel():
+            self._lr_table.copy_(tab)
+        else:
+            self._lr_table = tab.to(self.m.device)
+        self._lr_table_of = of
+
+    def _guard_block(self):
+        """The state block, copied back (one synchronising copy): a numpy record of ops.GUARD_STATE."""
+        if self._guard_state is None:
+            raise RuntimeError("the guard has never been on (set_guard): there is no state to read")
+        return self._guard_state.cpu().numpy().view(ops.GUARD_STATE)[0]
+
+    def guard_stats(self, reset=False):
+        """Counters of the guarded steps since the last reset, from ONE copy back: ``steps``, ``applied`` (the optimizer's
+        step count; never reset), ``clipped_steps``, ``skipped_steps``, ``norm_mean`` / ``norm_max`` over the steps with a
+        finite norm (nan / 0.0 when there is none), ``last_norm``, ``last_nonfinite``.  ``reset``: zero the counters and
+        the norm statistics afterwards."""
+        st = self._guard_block()
+        out = {"steps": int(st["steps"]), "applied": int(st["applied"]), "clipped_steps": int(st["clipped_steps"]),
+               "skipped_steps": int(st["skipped_steps"]), "norm_max": float(st["norm_max"]),
+               "last_norm": float(st["last_norm"]), "last_nonfinite": int(st["last_nonfinite"])}
+        n_finite = int(st["finite_steps"])
+        out["norm_mean"] = float(st["norm_sum"]) / n_finite if n_finite else float("nan")
+        if reset:
+            new = st.copy()
+            for k in ("steps", "clipped_steps", "skipped_steps", "finite_steps"):
+                new[k] = 0
+            new["norm_sum"] = new["norm_max"] = 0.0
+            head = np.frombuffer(new.tobytes(), dtype=np.uint8)[:ops.GUARD_STATE.fields["seg_sumsq"][1]].copy()
+            self._guard_state[:head.size].copy_(torch.from_numpy(head))
+        return out
+
+    def grad_norms(self):
+        """L2 norm per parameter of the gradient the last guarded step measured (L2 terms included, before clipping), by
+        parameter name; a list, one per level, for the stacked ``transfer_W`` / ``transfer_b``.  One copy back."""
+        seg = np.sqrt(self._guard_block()["seg_sumsq"][:self._nseg])
+        out = {}
+        for (name, level), v in zip(self._seg_names, seg):
+            if level is None:
+                out[name] = float(v)
+            else:
+                out.setdefault(name, []).append(float(v))
+        return out
 
     def set_objective(self, objective, group_size=None):
         """Choose the head of the step; parameters, Adam moments and the step counter are kept.
@@ -143,7 +285,7 @@ class Trainer(object):
         dev = self.m.device
         coef = self._l2_coefficients()
         segs, off = [], 0
-        self._slices = {}
+        self._slices, self._seg_names = {}, []
         for k, p in self.params.items():
             self._slices[k] = (off, p.numel())
             cs = coef[k]
@@ -151,8 +293,10 @@ class Trainer(object):
                 per = p.numel() // len(cs)
                 for e, ce in enumerate(cs):
                     segs.append((p.data_ptr() + 4 * e * per, off + e * per, per, ce))
+                    self._seg_names.append((k, e))
             else:
                 segs.append((p.data_ptr(), off, p.numel(), cs))
+                self._seg_names.append((k, None))
             off += p.numel()
         self._total = off
         self._g = torch.zeros(off, dtype=F32, device=dev)
@@ -165,6 +309,10 @@ class Trainer(object):
             table[i] = (ptr, o, n, c, 0)
         self._nseg = len(segs)
         self._segs = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
+        # static work table of the guard (mvin_grad_guard): <= 4096 elements of one segment per item
+        items = ops.guard_work_items([(o, n) for (_, o, n, _) in segs])
+        self._guard_nitems = len(items)
+        self._guard_items = torch.from_numpy(items.view(np.uint8).copy()).to(dev)
 
     # ------------------------------------------------------------------ parameters
     def _named_params(self):
@@ -575,22 +723,37 @@ class Trainer(object):
                         beta=1.0, D=D * D)
             ops.eltwise(7, nR * D * D, R.view(-1), z=cnt, accum=loss_acc, alpha=l2w, D=D * D)   # no host sync
 
+        self._apply_update(loss_acc, apply, lr_dev)
+        if apply:
+            self.m.invalidate()
+        self.last_grads = dP
+        return loss_acc
+
+    def _apply_update(self, loss_acc, apply, lr_dev=None):
+        """The tail of a step, on whatever the flat gradient buffer holds: the all-reduce of a data-parallel step, then the
+        per-parameter L2 terms and (``apply``) the optimizer -- under the guard when it is on (``set_guard``)."""
         # per-parameter L2 terms and (apply) the tf.train.AdamOptimizer step (dense; oracle/train_ref.AdamRef):
         # one launch over the flat gradient / moment buffers
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(self._g, group=self.group)        # one bucket: every gradient of the model
             dist.all_reduce(loss_acc, group=self.group)
-        lr_t = 0.0
-        if apply and lr_dev is None:
-            self.t += 1
-            lr_t = self.lr_t(self.t)
-        ops.l2_adam_multi(self._segs, self._nseg, self._total, self._g, self._m, self._v, loss_acc, apply,
-                          float(lr_t), self.b1, self.b2, self.eps, lr_dev=lr_dev if apply else None)
-        if apply:
-            self.m.invalidate()
-        self.last_grads = dP
-        return loss_acc
+        if apply and self.guard_on:
+            # guarded step (set_guard): norm, non-finite count and decision on the device, then the optimizer under them;
+            # the step size comes from the block's own count of APPLIED steps, self.t counts the attempts
+            if lr_dev is None:
+                self.t += 1
+            ops.grad_guard(self._segs, self._nseg, self._total, self._g, self._guard_items, self._guard_nitems,
+                           self._guard_partials, self._lr_table, self._guard_state)
+            ops.l2_adam_multi_guarded(self._segs, self._nseg, self._total, self._g, self._m, self._v, loss_acc, True,
+                                      self._guard_state, self.b1, self.b2, self.eps)
+        else:
+            lr_t = 0.0
+            if apply and lr_dev is None:
+                self.t += 1
+                lr_t = self.lr_t(self.t)
+            ops.l2_adam_multi(self._segs, self._nseg, self._total, self._g, self._m, self._v, loss_acc, apply,
+                              float(lr_t), self.b1, self.b2, self.eps, lr_dev=lr_dev if apply else None)
 
 
 class GraphedTrainer(object):
@@ -635,6 +798,7 @@ class GraphedTrainer(object):
         m.invalidate()                           # nothing ran during capture: no derived table is valid yet
         self._captured = self._storage_key()
         self.objective = (trainer.objective, trainer.group_size)     # the head the captured launches are
+        self.guard = trainer.guard_key()                             # ... and whether (and on what) the guard's launches run
 
     def _storage_key(self):
         """Addresses the captured launches read: a graph outlives neither ``set_adjacency`` nor a parameter tensor
@@ -663,8 +827,12 @@ class GraphedTrainer(object):
         if (tr.objective, tr.group_size) != self.objective:
             raise RuntimeError(f"the trainer's objective changed to {(tr.objective, tr.group_size)} since this step was "
                                f"captured with {self.objective}: build a new GraphedTrainer")
+        if tr.guard_key() != self.guard:
+            raise RuntimeError("the trainer's guard was switched on or off (set_guard) since this step was captured: "
+                               "build a new GraphedTrainer")
         tr.t += 1
-        self.lr_dev.fill_(float(tr.lr_t(tr.t)))
+        if self.guard is None:                   # a guarded step reads its step size from the guard's state block
+            self.lr_dev.fill_(float(tr.lr_t(tr.t)))
         self.graph.replay()
         tr.m.invalidate()                        # parameters changed: eager callers rebuild their derived tables
         return self.loss
