@@ -958,6 +958,21 @@ MVIN_API int mvin_kg_explore(const int64_t* eptr, const int32_t* edst, const int
 MVIN_API int mvin_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
                             float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum,
                             int64_t* counts /* [2] or NULL */, void* stream);
+/* mvin_rank_head_offset: mvin_rank_head with a per-row logit offset, offset [B] f32 or NULL (the logQ correction of a sampled
+ * softmax: offset = log of a negative's expected sampling count, data_prep.rank_offsets).  The same kernel, not a second one.
+ * The loss of both modes is evaluated on z[g,j] = s[g,j] - offset[g*G + j] for every valid slot, slot 0 included:
+ *   MVIN_RANK_SOFTMAX  the maximum, the exponentials, Z and l_g = log Z + m - z[g,0] all use z;
+ *   MVIN_RANK_BPR      x = z[g,j] - z[g,0]: there the offset is a per-negative MARGIN, offset[g,j] - offset[g,0] is taken off the
+ *                      score difference before the softplus (no sampling correction; BPR has none of this form).
+ * dscore is still the derivative with respect to s: the formulas above evaluated on z (dz/ds = 1).  scores written out stay the
+ * raw s, and counts compare the raw s: they keep their meaning and stay exact integers.  The offset of a masked slot
+ * (valid == 0) is never read: a NaN or an infinity there reaches no output.  offset == NULL and an offset of all 0.0f both give
+ * the bits of mvin_rank_head in every output but the order-dependent loss_accum, and the bit properties above hold with an
+ * offset: scores, dscore, du and di of a group are a pure function of its rows and its offsets.
+ * Errors: those of mvin_rank_head, under the name mvin_rank_head_offset. */
+MVIN_API int mvin_rank_head_offset(const float* user_o, const float* item_emb, const float* valid, const float* offset /* [B] or NULL */,
+                                   int64_t n_groups, int G, int D, int mode, float scale, float* scores, float* dscore, float* du,
+                                   float* di, float* loss_accum, int64_t* counts /* [2] or NULL */, void* stream);
 
 /* ---- hard negatives for the ranking objectives: pick the negatives a step trains on out of a scored pool (dynamic negative
  * sampling; an opt-in extension, the reference trains on the fixed negatives of its ratings file) --

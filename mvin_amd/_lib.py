@@ -190,6 +190,8 @@ SIGNATURES = {
                                                  C.c_uint64, C.c_uint64, _c_i32p, C.c_void_p, C.c_void_p]),
     "mvin_rank_head": (C.c_int, [_c_f32p, _c_f32p, _c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float] + [_c_f32p] * 5
                        + [C.c_void_p, C.c_void_p]),
+    "mvin_rank_head_offset": (C.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]
+                              + [_c_f32p] * 5 + [C.c_void_p, C.c_void_p]),
     "mvin_select_negatives": (C.c_int, [_c_f32p, C.c_void_p, _c_f32p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                         C.c_uint64, C.c_void_p, _c_f32p, _c_f32p, C.c_void_p, C.c_void_p]),
     "mvin_gather_attn_fwd_ex": (C.c_int, [_c_f32p, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p,

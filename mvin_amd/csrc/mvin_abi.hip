@@ -1672,17 +1672,30 @@ int mvin_select_negatives(const float* scores, const int64_t* items, const float
 }
 
 // ---------------------------------------------------------------------------- training
-int mvin_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode, float scale,
-                   float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts, void* stream) {
-    const char* who = "mvin_rank_head";
+static int rank_head_impl(const char* who, const float* user_o, const float* item_emb, const float* valid, const float* offset,
+                          int64_t n_groups, int G, int D, int mode, float scale, float* scores, float* dscore, float* du, float* di,
+                          float* loss_accum, int64_t* counts, void* stream) {
     if (!user_o || !item_emb || !scores || !dscore || !du || !di || !loss_accum)
         return fail(-1, "%s: null pointer (user_o / item_emb / scores / dscore / du / di / loss_accum)", who);
     if (G < 2 || G > 64) return fail(-2, "%s: G=%d (2..64)", who, G);
     if (D < 4 || D > 128 || (D & 3) != 0) return fail(-2, "%s: D=%d (a multiple of 4, 4..128)", who, D);
     if (mode != MVIN_RANK_SOFTMAX && mode != MVIN_RANK_BPR) return fail(-2, "%s: unknown mode=%d", who, mode);
     if (n_groups < 0) return fail(-2, "%s: n_groups=%lld", who, (long long)n_groups);
-    return hip_result(mvin::launch_rank_head(user_o, item_emb, valid, n_groups, G, D, mode, scale, scores, dscore, du, di, loss_accum,
-                                             counts, (hipStream_t)stream), who);
+    return hip_result(mvin::launch_rank_head(user_o, item_emb, valid, offset, n_groups, G, D, mode, scale, scores, dscore, du, di,
+                                             loss_accum, counts, (hipStream_t)stream), who);
+}
+
+int mvin_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode, float scale,
+                   float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts, void* stream) {
+    return rank_head_impl("mvin_rank_head", user_o, item_emb, valid, nullptr, n_groups, G, D, mode, scale, scores, dscore, du, di,
+                          loss_accum, counts, stream);
+}
+
+int mvin_rank_head_offset(const float* user_o, const float* item_emb, const float* valid, const float* offset, int64_t n_groups, int G,
+                          int D, int mode, float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum,
+                          int64_t* counts, void* stream) {
+    return rank_head_impl("mvin_rank_head_offset", user_o, item_emb, valid, offset, n_groups, G, D, mode, scale, scores, dscore, du,
+                          di, loss_accum, counts, stream);
 }
 
 int mvin_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, void* stream) {

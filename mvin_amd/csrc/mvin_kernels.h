@@ -455,9 +455,11 @@ hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_
                                    int n_user, int n_item, const uint32_t* alias_tab, const uint32_t* mask_bits, uint64_t seed,
                                    uint64_t round, int32_t* out, int64_t* status,
                                    hipStream_t st);           // alias_tab NULL: the uniform draw (and no mask); else the alias draw
-hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
-                            float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
-                            hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip)
+hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, const float* offset, int64_t n_groups,
+                            int G, int D, int mode, float scale, float* scores, float* dscore, float* du, float* di,
+                            float* loss_accum, int64_t* counts,
+                            hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip);
+                                                              // offset NULL: mvin_rank_head, else mvin_rank_head_offset
 hipError_t launch_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key,
                                    int64_t n_groups, int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round,
                                    int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts,

@@ -13,6 +13,10 @@
 // group only, and L2 / W follow from D / G alone, so scores, dscore, du and di of a group are a pure function of its rows:
 // the same whatever n_groups, the neighbours or the grid are.  Only loss_accum (float atomics) depends on order; the counts
 // are integers.
+//
+// Logit offsets (mvin_rank_head_offset): the SAME kernel with a.offset != NULL.  Phase 2 loads one more float per valid slot
+// and evaluates the loss on z = s - offset; the scores written out and the counts stay on the raw s.  a.offset is a kernel
+// argument, so the branch on it is uniform over the grid; with NULL no load is issued and z is s itself, today's bits.
 #include "mvin_kernels.h"
 
 namespace mvin {
@@ -25,6 +29,7 @@ struct RankHeadArgs {
     const float* user_o;
     const float* item_emb;
     const float* valid;      // [B] 0 / 1 or NULL
+    const float* offset;     // [B] subtracted from the logit of a valid slot, or NULL
     int64_t n_groups, group0;
     int G, D, mode;
     int ng;                  // groups per workgroup
@@ -85,15 +90,20 @@ __global__ __launch_bounds__(kRankBlock) void rank_head_kernel(RankHeadArgs a) {
         const float s0 = g < ng ? s_sc[g * G] : 0.f;
         const bool val = in && (slot == 0 || a.valid == nullptr || a.valid[row0 + r] != 0.f);
         const bool neg = val && slot > 0;
+        float z = s, z0 = s0;                                  // the logits the loss sees; an invalid slot's offset is never read
+        if (a.offset != nullptr) {
+            if (val) z = s - a.offset[row0 + r];
+            if (g < ng) z0 = s0 - a.offset[row0 + g * G];
+        }
         float ds = 0.f, lg = 0.f;
         if (a.mode == MVIN_RANK_SOFTMAX) {
-            const float m = group_max(val ? s : -INFINITY, w_l2);
-            const float e = val ? expf(s - m) : 0.f;
+            const float m = group_max(val ? z : -INFINITY, w_l2);
+            const float e = val ? expf(z - m) : 0.f;
             const float Z = group_sum(e, w_l2);
             if (val) ds = (e / Z - (slot == 0 ? 1.f : 0.f)) * a.scale;
-            lg = logf(Z) + (m - s0);
+            lg = logf(Z) + (m - z0);
         } else {
-            const float x = s - s0;
+            const float x = z - z0;
             const float ex = expf(-fabsf(x));
             const float n = group_sum(neg ? 1.f : 0.f, w_l2);
             const float sig = neg ? (x >= 0.f ? 1.f : ex) / (1.f + ex) / n : 0.f;      // sigma(x) / |N_g|
@@ -168,14 +178,15 @@ static hipError_t rank_head_launch(RankHeadArgs a, hipStream_t st) {
 }
 
 // G in [2, 64], D % 4 == 0, 4 <= D <= 128 (checked by the caller, mvin_abi.hip)
-hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, int64_t n_groups, int G, int D, int mode,
-                            float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
+hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, const float* offset, int64_t n_groups,
+                            int G, int D, int mode, float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
                             hipStream_t st) {
     if (n_groups == 0) return hipSuccess;
     RankHeadArgs a;
     a.user_o = user_o;
     a.item_emb = item_emb;
     a.valid = valid;
+    a.offset = offset;
     a.n_groups = n_groups;
     a.group0 = 0;
     a.G = G;

@@ -324,12 +324,18 @@ class NegativeSampler(object):
                 weights = (count + float(smooth)) ** float(alpha)
             tab, mask = alias_table(weights, self.n_item)
             self.alias = _alias_on((tab, mask), self.n_item, self.device)
+            self._alias_tab_host = tab
             masked = ((mask[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(-1)[:self.n_item]
             in_range[in_range] = ~masked[ids[in_range]]                # a masked item of the row is counted once, by the mask
         eligible = self.n_item - np.bincount(row_of[in_range], minlength=self.n_user).astype(np.int64)
         if masked is not None:
             eligible -= int(masked.sum())
         m = np.minimum(want, eligible)
+        # what log_proposal needs, on the host: c_u, the masked items and the (user, item) pairs the exclusion rows take out
+        self.eligible_host = eligible
+        self._masked_host = masked
+        self._excl_pairs_host = (row_of[in_range], ids[in_range].astype(np.int64))
+        self._log_proposal = None
         self.clipped_users = int(np.count_nonzero(want > eligible))
         if self.clipped_users:
             import warnings
@@ -347,6 +353,32 @@ class NegativeSampler(object):
         idx[order] = np.arange(pos.shape[0], dtype=np.int64) - first[pos[order, 0]]
         self.pos_index = torch.from_numpy(idx).to(self.device)
         self.last_status = None
+
+    def log_proposal(self):
+        """The log of the proposal the negatives are drawn from, (item_logp float32 [n_item], user_logmass float32 [n_user])
+        on the device; computed once, on the host, in float64, and cached.
+          item_logp[i]    = log p_i, p_i the probability with which ONE draw produces item i before any exclusion:
+                            1 / n_item for the uniform sampler, ``alias_probabilities(tab)`` for a weighted one -- the table's
+                            integers, not the float weights it was built from.  A masked item has p_i = 0 and -inf here; it is
+                            never drawn, so no valid slot ever looks it up.
+          user_logmass[u] = log of the sum of p_i over the items eligible for u: the catalogue minus the distinct in-range ids
+                            of u's exclusion row and minus the masked items (-inf for a user with no eligible item, who has
+                            no negatives either).
+        p_i / user_mass_u is q_u(i), the proposal of one draw conditioned on eligibility (``rank_offsets``)."""
+        if self._log_proposal is None:
+            if self.alias is None:
+                p = np.full(self.n_item, 1.0 / self.n_item, dtype=np.float64)
+            else:
+                p = alias_probabilities(self._alias_tab_host)
+                p[self._masked_host] = 0.0
+            rows, ids = self._excl_pairs_host
+            mass = p.sum() - np.bincount(rows, weights=p[ids], minlength=self.n_user)
+            mass[self.eligible_host <= 0] = 0.0
+            with np.errstate(divide="ignore"):
+                logs = (np.log(p), np.log(np.maximum(mass, 0.0)))
+            self._log_proposal64 = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(self.device) for t in logs)
+            self._log_proposal = tuple(t.to(torch.float32) for t in self._log_proposal64)
+        return self._log_proposal
 
     def draw(self, round):
         """(neg_ptr int64 [nU+1], neg_items int32) of ``round`` on the device, from the sampler's distribution (uniform, or the
@@ -400,6 +432,32 @@ def rank_groups(sampler, round):
     items = torch.cat([pos_item, neg], dim=1).contiguous()
     valid = torch.cat([torch.ones_like(pos_item, dtype=torch.float32), ok.to(torch.float32)], dim=1).contiguous()
     return users, items, valid
+
+
+def rank_offsets(sampler, users, items, valid):
+    """The logit offsets of the logQ-corrected sampled softmax (mvin_rank_head_offset, Trainer.set_objective(offset=True)) for
+    the groups ``users`` int64 [n] / ``items`` int64 [n, G] / ``valid`` f32 [n, G] of ``rank_groups(sampler, .)`` or a row
+    subset of it.  Returns float32 [n, G] on the sampler's device; nothing goes to the host.
+      slot 0            0: the positive is in its group with probability 1 and stays uncorrected;
+      an invalid slot   0 (the head never reads it);
+      a valid negative  log(n_g * p_item / user_mass_u): n_g = the valid negatives of the group, p and user_mass those of
+                        ``sampler.log_proposal()``.  log n_g + log p - log user_mass is evaluated in float64 (from the float64
+                        logs the sampler caches beside the float32 pair) and rounded once to float32.
+    With these offsets the group's softmax denominator is the importance-sampling estimate
+        Z ~ exp(s_0) + (1 / n_g) sum_j exp(s_j) / q_u(j),   q_u(j) = p_j / user_mass_u,
+    of the partition function over ALL of the user's eligible items plus the positive (Bengio & Senecal's sampled softmax;
+    the "logQ correction" of Yi et al. 2019), under a uniform proposal as much as under a popularity-weighted one.
+    An approximation, the usual practice, not exact: q_u is the proposal of ONE draw conditioned on eligibility.  The sampler
+    draws a user's negatives WITHOUT replacement, and all of that user's positives take theirs from one shared row, so the
+    true inclusion probability of an item differs from n_g * q_u by terms of order m_u * max q (m_u the user's negatives of
+    the epoch)."""
+    sampler.log_proposal()
+    logp, logmass = sampler._log_proposal64
+    neg = valid != 0
+    neg[:, 0] = False
+    n_g = neg.sum(dim=1, keepdim=True).to(torch.float64)
+    c = torch.log(n_g) + logp[items] - logmass[users][:, None]
+    return torch.where(neg, c, torch.zeros_like(c)).to(torch.float32).contiguous()
 
 
 def select_negatives(*args, **kwargs):

@@ -282,7 +282,7 @@ def _epoch_trainer(feeder, batch_size, graph):
         gt = getattr(model, "_graphed_trainer", None)
         if (gt is None or gt.tr is not model.trainer or gt.users.shape[0] != batch_size
                 or gt._storage_key() != gt._captured        # set_adjacency / a rebound parameter: capture again
-                or gt.objective != (model.trainer.objective, model.trainer.group_size)      # ... or another head
+                or gt.head != model.trainer.head_key()      # ... or another head (objective, group size, logit offset)
                 or gt.guard != model.trainer.guard_key()):                                   # ... or the guard on / off
             try:
                 gt = model._graphed_trainer = GraphedTrainer(model.trainer, batch_size)
@@ -354,23 +354,32 @@ def train_epoch_resampled(feeder, sampler, batch_size, round, graph=False, perm_
     return _run_epoch_on_device(feeder, data, batch_size, gt)
 
 
-def ranked_epoch_groups(sampler, round, device, perm_seed=None):
+def ranked_epoch_groups(sampler, round, device, perm_seed=None, logq=False):
     """The groups ``train_epoch_ranked`` trains on: ``data_prep.rank_groups(sampler, round)`` with the GROUPS permuted on the
-    device, seeded exactly like ``resampled_epoch_rows``.  (users [n], items [n, G], valid [n, G]); nothing goes to the host."""
-    from .data_prep import rank_groups
+    device, seeded exactly like ``resampled_epoch_rows``.  (users [n], items [n, G], valid [n, G]); nothing goes to the host.
+    ``logq=True`` appends the epoch's logit offsets, f32 [n, G]: ``data_prep.rank_offsets`` of the permuted groups."""
+    from .data_prep import rank_groups, rank_offsets
     users, items, valid = rank_groups(sampler, round)
     perm = _epoch_perm(sampler, round, users.shape[0], device, perm_seed)
-    return users[perm], items[perm], valid[perm]
+    users, items, valid = users[perm], items[perm], valid[perm]
+    if logq:
+        return users, items, valid, rank_offsets(sampler, users, items, valid)
+    return users, items, valid
 
 
-def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=False, perm_seed=None):
+def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=False, perm_seed=None, logq=False):
     """One epoch under a ranking objective ("bpr" / "softmax", training.Trainer.set_objective): every positive of ``sampler``
     (a data_prep.NegativeSampler built with ``ratio`` = n_neg) against its n_neg fresh negatives of ``round``, as groups of
     G = 1 + n_neg rows.  The groups are permuted on the device (``ranked_epoch_groups``) and a step takes
     ``batch_size // G`` whole groups -- full steps only, the ragged tail dropped.  Returns the losses like the other epoch
     functions.  ``Trainer.rank_counts`` is zeroed at the start and read back ONCE at the end: the epoch's sampled pairwise
     accuracy (negatives scored below their positive, ties half) is left in ``model.trainer.last_pairwise_acc`` (nan for an
-    epoch without a valid negative).  A pure function of (sampler, round, perm_seed), like ``train_epoch_resampled``."""
+    epoch without a valid negative).  A pure function of (sampler, round, perm_seed), like ``train_epoch_resampled``.
+    ``logq=True`` ("softmax" only): the logQ-corrected sampled softmax.  The epoch's logit offsets are built once from the
+    permuted groups (``data_prep.rank_offsets``: log of a negative's expected sampling count under the sampler's proposal)
+    and sliced per step like ``valid``; the head subtracts them before the softmax (mvin_rank_head_offset).  They are a pure
+    function of (sampler, round, perm_seed) like the groups, so every rank of a data-parallel run builds the same ones.
+    ``last_pairwise_acc`` keeps its meaning: it compares the raw scores."""
     import torch
     from .training import Trainer
     model = feeder.model
@@ -381,11 +390,13 @@ def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=Fals
     if model.trainer is None:
         model.trainer = Trainer(model)
     tr = model.trainer
-    tr.set_objective(objective, G)
+    if logq and objective != "softmax":
+        raise ValueError(f"logq=True corrects the sampled softmax: it needs objective='softmax', not {objective!r}")
+    tr.set_objective(objective, G, offset=bool(logq))
     gt = _epoch_trainer(feeder, n_g * G, graph)
-    users, items, valid = ranked_epoch_groups(sampler, round, model.device, perm_seed)
+    users, items, valid, *offsets = ranked_epoch_groups(sampler, round, model.device, perm_seed, logq=bool(logq))
     tr.rank_counts.zero_()
-    losses = _ranked_steps(feeder, tr, gt, users, items, valid, n_g)
+    losses = _ranked_steps(feeder, tr, gt, users, items, valid, n_g, offsets=offsets[0] if logq else None)
     if gt is not None and losses:
         losses = torch.cat(losses).cpu().tolist()
     c0, c1 = tr.rank_counts.cpu().tolist()
@@ -393,10 +404,11 @@ def train_epoch_ranked(feeder, sampler, batch_size, round, objective, graph=Fals
     return losses
 
 
-def _ranked_steps(feeder, tr, gt, users, items, valid, n_g):
+def _ranked_steps(feeder, tr, gt, users, items, valid, n_g, offsets=None):
     """The step loop of a ranked epoch (train_epoch_ranked, train_epoch_hard): ``n_g`` whole groups of ``users`` [n] /
-    ``items`` / ``valid`` [n, G] per step, full steps only.  Returns the step losses: floats of the eager step (``gt`` None),
-    device tensors of the replayed one (the caller reads them back once)."""
+    ``items`` / ``valid`` [n, G] (and ``offsets`` [n, G], the logit offsets of a logQ-corrected epoch, or None) per step, full
+    steps only.  Returns the step losses: floats of the eager step (``gt`` None), device tensors of the replayed one (the
+    caller reads them back once)."""
     G = items.shape[1]
     losses, start = [], 0
     while start + n_g <= users.shape[0]:
@@ -404,10 +416,11 @@ def _ranked_steps(feeder, tr, gt, users, items, valid, n_g):
         it = items[start:start + n_g].reshape(-1)
         v = valid[start:start + n_g].reshape(-1)
         mh, mr, mt = feeder.memories(u)
+        okw = {} if offsets is None else {"offset": offsets[start:start + n_g].reshape(-1)}
         if gt is not None:
-            losses.append(gt.step(u, it, v, mh, mr, mt).clone())
+            losses.append(gt.step(u, it, v, mh, mr, mt, **okw).clone())
         else:
-            losses.append(tr.step(u, it, v, mh, mr, mt))
+            losses.append(tr.step(u, it, v, mh, mr, mt, **okw))
         start += n_g
     return losses
 
@@ -845,7 +858,7 @@ class EarlyStop(object):
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
           objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0,
-          clip_norm=None, skip_nonfinite=False):
+          clip_norm=None, skip_nonfinite=False, logq=False):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -888,6 +901,14 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     rows of ``train_data`` with item i (data_prep.NegativeSampler(dist=...), mvin_sample_negatives_weighted; an item of weight
     zero is never a negative).  It reaches every training mode through the sampler: cross-entropy epochs, the ranking
     objectives' groups and the hard-negative pool.  An opt-in extension, like the ranking objectives.
+    ``logq``: True trains ``objective="softmax"`` with the logQ correction of a sampled softmax (Bengio & Senecal; Yi et al.
+    2019): the log of every negative's expected sampling count under the sampler's proposal is subtracted from its logit
+    before the softmax (train_epoch_ranked(logq=True), data_prep.rank_offsets, mvin_rank_head_offset), so that a
+    popularity-weighted proposal (``neg_dist="popularity"``) no longer pushes popular items down by about log q, and the loss
+    estimates the softmax over all of a user's eligible items under either proposal.  It needs ``negatives="resample"``;
+    "bce" / "bpr" have no softmax to correct, fixed negatives have no known proposal, and ``negatives="hard"`` picks from a
+    shortlist, a proposal this correction does not describe: each is refused.  The epoch record gains "logq": True;
+    "pairwise_acc" still compares raw scores.  Opt-in; off, nothing changes.
     ``clip_norm`` / ``skip_nonfinite``: the guard of the optimizer step (training.Trainer.set_guard), set on the model's trainer
     before the first epoch: gradients clipped to the global norm ``clip_norm`` (a finite number > 0) and / or a step with a
     non-finite gradient left out, both decided on the device, so a step stays one graph replay.  With either set the epoch
@@ -912,6 +933,19 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     if not isinstance(skip_nonfinite, (bool, np.bool_)):
         raise ValueError(f"skip_nonfinite={skip_nonfinite!r}: expected True or False")
     guard = clip_norm is not None or bool(skip_nonfinite)
+    if not isinstance(logq, (bool, np.bool_)):
+        raise ValueError(f"logq={logq!r}: expected True or False")
+    if logq:
+        if objective != "softmax":
+            raise ValueError(f"logq=True corrects the sampled softmax for its proposal: it needs objective='softmax', not "
+                             f"{objective!r}" + (" (the kernel's BPR offset is a margin; the harness exposes none)"
+                                                 if objective == "bpr" else ""))
+        if negatives == "fixed":
+            raise ValueError("logq=True needs the proposal the negatives were drawn from: negatives='fixed' rows have none, "
+                             "use negatives='resample'")
+        if negatives == "hard":
+            raise ValueError("logq=True does not describe negatives='hard': picking from a scored shortlist changes the "
+                             "proposal in a way the correction does not cover; use negatives='resample'")
     ranked = objective != "bce"
     hard = negatives == "hard"
     if hard and not ranked:
@@ -973,7 +1007,7 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
             losses = train_epoch_hard(feeder, sampler, args.batch_size, epoch, objective, int(n_neg), shortlist=shortlist,
                                       rescore=int(rescore), graph=use_graph)
         elif ranked:
-            losses = train_epoch_ranked(feeder, sampler, args.batch_size, epoch, objective, graph=use_graph)
+            losses = train_epoch_ranked(feeder, sampler, args.batch_size, epoch, objective, graph=use_graph, logq=bool(logq))
         elif sampler is not None:
             losses = train_epoch_resampled(feeder, sampler, args.batch_size, epoch, graph=use_graph)
         else:
@@ -981,6 +1015,8 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         rec = {"epoch": epoch, "loss": float(np.mean(losses)) if losses else float("nan")}
         if ranked:
             rec["pairwise_acc"] = model.trainer.last_pairwise_acc
+        if logq:
+            rec["logq"] = True
         if hard:
             rec["hard_rate"], rec["pool_rate"] = model.trainer.last_hard_rate, model.trainer.last_pool_rate
         if guard:

@@ -1295,7 +1295,7 @@ class MVIN(object):
             if g is False:
                 g = None
             elif g is not None and (g._storage_key() != g._captured
-                                    or g.objective != (self.trainer.objective, self.trainer.group_size)
+                                    or g.head != self.trainer.head_key()
                                     or g.guard != self.trainer.guard_key()):
                 g = None                   # adjacency / a parameter tensor replaced, another objective or guard: capture again
             if g is None and self._train_seen == B and self._train_graphs.get(B) is not False:

@@ -1296,12 +1296,15 @@ def eltwise(mode, n, x, y=None, z=None, w=None, accum=None, alpha=1.0, beta=0.0,
 RANK_MODES = {"softmax": 0, "bpr": 1}      # MVIN_RANK_SOFTMAX / MVIN_RANK_BPR
 
 
-def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None, counts=None, out=None):
+def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None, counts=None, out=None, offset=None):
     """mvin_rank_head: the grouped ranking head of the training step in one launch.  ``user_o`` / ``item_emb`` f32 [B, D],
     B = n_groups * ``group_size`` rows group-major (slot 0 of a group the positive, the others negatives of the same user);
     ``valid`` f32 [B] of 0 / 1 (None: every slot counts); ``mode`` "softmax" or "bpr" (include/mvin_hip.h states both).
     Adds ``scale`` * sum of the group losses to ``loss_accum`` (f32 [1]) and, when given, the pairwise-accuracy integers to
     ``counts`` (int64 [2]).  Returns (scores [B], dscore [B], du [B, D], di [B, D]); ``out`` may pass those four buffers in.
+    ``offset`` f32 [B] contiguous on the same device (None: no offset, the mvin_rank_head symbol): mvin_rank_head_offset, the
+    loss and its gradient are evaluated on score - offset for every valid slot while the scores returned and ``counts`` stay
+    on the raw scores (data_prep.rank_offsets builds the logQ correction of a sampled softmax).
     Enqueues only."""
     if mode not in RANK_MODES:
         raise ValueError(f"mode={mode!r}: expected 'softmax' or 'bpr'")
@@ -1317,6 +1320,12 @@ def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None,
         raise ValueError(f"valid: {valid.numel()} flags for {B} rows")
     if counts is not None and counts.numel() != 2:
         raise ValueError("counts: expected int64 [2]")
+    if offset is not None:
+        if not torch.is_tensor(offset) or offset.dtype != F32:
+            raise ValueError(f"offset: expected a float32 tensor, got {getattr(offset, 'dtype', type(offset))}")
+        if offset.numel() != B or offset.device != user_o.device or not offset.is_contiguous():
+            raise ValueError(f"offset: expected {B} contiguous values on {user_o.device}, got {tuple(offset.shape)} on "
+                             f"{offset.device}")
     if out is None:
         dev = user_o.device
         out = (torch.empty(B, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev),
@@ -1328,9 +1337,14 @@ def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None,
             raise ValueError(f"{nm}: {t.numel()} elements, expected {n}")
     if B == 0:                                  # an empty tensor has no address to pass
         return scores, dscore, du, di
-    _lib.check(_lib.load().mvin_rank_head(_p(user_o), _p(item_emb), _p(valid), B // G, G, D, RANK_MODES[mode], float(scale),
-                                          _p(scores), _p(dscore), _p(du), _p(di), _p(loss_accum), _p(counts), _stream()),
-               "mvin_rank_head")
+    if offset is None:
+        _lib.check(_lib.load().mvin_rank_head(_p(user_o), _p(item_emb), _p(valid), B // G, G, D, RANK_MODES[mode], float(scale),
+                                              _p(scores), _p(dscore), _p(du), _p(di), _p(loss_accum), _p(counts), _stream()),
+                   "mvin_rank_head")
+    else:
+        _lib.check(_lib.load().mvin_rank_head_offset(_p(user_o), _p(item_emb), _p(valid), _p(offset), B // G, G, D,
+                                                     RANK_MODES[mode], float(scale), _p(scores), _p(dscore), _p(du), _p(di),
+                                                     _p(loss_accum), _p(counts), _stream()), "mvin_rank_head_offset")
     return scores, dscore, du, di
 
 

@@ -235,7 +235,7 @@ class Trainer(object):
                 out.setdefault(name, []).append(float(v))
         return out
 
-    def set_objective(self, objective, group_size=None):
+    def set_objective(self, objective, group_size=None, offset=False):
         """Choose the head of the step; parameters, Adam moments and the step counter are kept.
           "bce"      sigmoid cross-entropy of every row against its label -- the reference's loss and the default;
           "softmax"  sampled softmax over groups of ``group_size`` consecutive rows: slot 0 of a group is a positive
@@ -245,9 +245,17 @@ class Trainer(object):
         always counts): a masked slot enters neither the loss nor any data gradient.  The data term is the mean of the group
         losses over the global batch's groups, 1 / (n_groups * world) each (include/mvin_hip.h: mvin_rank_head states both
         forms).  The regularisers of model.py:382-412 stay exactly as they are: over EVERY fed row, masked rows included --
-        a masked slot's ripple-set rows are still in the gathered-row L2 term."""
+        a masked slot's ripple-set rows are still in the gathered-row L2 term.
+        ``offset=True`` (ranking objectives only) declares a per-row logit offset: ``step`` / ``enqueue`` then REQUIRE
+        ``offset=`` a float32 [B] tensor and the head evaluates its loss on score - offset (mvin_rank_head_offset; the logQ
+        correction of a sampled softmax, data_prep.rank_offsets; under "bpr" a per-negative margin).  Off, the step makes
+        exactly the launches it made before the flag existed."""
         if objective not in self.OBJECTIVES:
             raise ValueError(f"objective={objective!r}: expected one of {self.OBJECTIVES}")
+        if not isinstance(offset, (bool, np.bool_)):
+            raise ValueError(f"offset={offset!r}: expected True or False")
+        if offset and objective == "bce":
+            raise ValueError("offset=True belongs to the ranking objectives ('bpr' / 'softmax'): 'bce' has no grouped head")
         if objective == "bce":
             if group_size is not None:
                 raise ValueError("group_size belongs to the ranking objectives ('bpr' / 'softmax')")
@@ -255,6 +263,12 @@ class Trainer(object):
             raise ValueError(f"group_size={group_size!r}: objective {objective!r} needs 1 + n_neg rows per group, 2..64")
         self.objective = objective
         self.group_size = None if objective == "bce" else int(group_size)
+        self.logit_offset = bool(offset)
+
+    def head_key(self):
+        """What the launches of the step's head depend on: (objective, group_size, logit offset declared).  A captured step is
+        replayed only under the key it was captured with."""
+        return (self.objective, self.group_size, self.logit_offset)
 
     def _l2_coefficients(self):
         """Coefficient c of the (c/2) sum(x^2) term of every parameter (slice), model.py:387-412."""
@@ -353,10 +367,10 @@ class Trainer(object):
         return ops.linear([table], None, table.shape[-1], ids=[ids])
 
     # ------------------------------------------------------------------ one step
-    def step(self, user_indices, item_indices, labels, memories_h, memories_r, memories_t, apply=True):
+    def step(self, user_indices, item_indices, labels, memories_h, memories_r, memories_t, apply=True, offset=None):
         """One training step on device-resident inputs.  Returns the loss (python float)."""
         return float(self.enqueue(user_indices, item_indices, labels, memories_h, memories_r, memories_t,
-                                  apply=apply).item())
+                                  apply=apply, offset=offset).item())
 
     def lr_t(self, t):
         """Bias-corrected step size of tf.train.AdamOptimizer at (1-based) step t.  From beta1 / beta2 as float32, which is
@@ -366,12 +380,13 @@ class Trainer(object):
         return self.lr * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
 
     def enqueue(self, user_indices, item_indices, labels, memories_h, memories_r, memories_t, apply=True,
-                lr_dev=None):
+                lr_dev=None, offset=None):
         """Enqueue one training step on the current stream without any host synchronisation; returns the
         1-element device tensor the loss is accumulated in.  ``lr_dev`` (1-element fp32 device tensor): the
         Adam step size is read from it when the optimizer kernel runs and the step counter is left to the
         caller -- the form GraphedTrainer captures.  Under a ranking objective (``set_objective``) the rows are whole
-        groups, group-major, and ``labels`` carries the slot validity."""
+        groups, group-major, and ``labels`` carries the slot validity; ``offset`` (float32 [B]) is required exactly when
+        ``set_objective(..., offset=True)`` declared it."""
         m, a = self.m, self.m.args
         dev = m.device
         D, K, H, M, P, nR = m.dim, m.n_neighbor, m.h_hop, m.n_mix_hop, m.p_hop, m.n_relation
@@ -379,6 +394,16 @@ class Trainer(object):
         B = item_indices.shape[0]
         if self.objective != "bce" and (B == 0 or B % self.group_size):
             raise ValueError(f"objective {self.objective!r}: a batch of {B} rows is not whole groups of {self.group_size}")
+        if offset is not None and not self.logit_offset:
+            raise ValueError(f"offset passed, but the objective {self.objective!r} was set without one: "
+                             f"set_objective(..., offset=True) declares it (ranking objectives only)")
+        if self.logit_offset:
+            if offset is None:
+                raise ValueError("set_objective(..., offset=True) declared a logit offset: pass offset= a float32 [B] tensor")
+            if not torch.is_tensor(offset) or offset.dtype != F32 or offset.numel() != B:
+                raise ValueError(f"offset: expected a float32 tensor of {B} values, got "
+                                 f"{getattr(offset, 'dtype', type(offset))} {tuple(getattr(offset, 'shape', ()))}")
+            offset = offset.contiguous().view(B)
         E, U, R = m.entity_emb_matrix, m.user_emb_matrix, m.relation_emb_KGE_matrix
         user = user_indices.contiguous()
         item = item_indices.contiguous()
@@ -682,7 +707,8 @@ class Trainer(object):
             # the mean over the GLOBAL batch's groups
             n_groups = B // self.group_size
             _, _, du, di = ops.rank_head(user_o, item_emb.view(B, D), self.group_size, self.objective,
-                                         1.0 / (n_groups * self.world), loss_acc, valid=labels, counts=self.rank_counts)
+                                         1.0 / (n_groups * self.world), loss_acc, valid=labels, counts=self.rank_counts,
+                                         offset=offset)
         G.add(user_o, du)
         G.add(item_emb, di.view_as(item_emb))
 
@@ -783,21 +809,26 @@ class GraphedTrainer(object):
         self.mr = [torch.zeros((B, Nm), dtype=torch.int32, device=dev) for _ in range(P)]
         self.mt = [torch.zeros((B, Nm), dtype=torch.int32, device=dev) for _ in range(P)]
         self.lr_dev = torch.zeros(1, dtype=F32, device=dev)
+        # the static logit offsets of a head captured with set_objective(..., offset=True); None: the captured launches are
+        # exactly those of a trainer without the flag
+        self.offset = torch.zeros(B, dtype=F32, device=dev) if trainer.logit_offset else None
+        okw = {} if self.offset is None else {"offset": self.offset}
         feed = (self.users, self.items, self.labels, self.mh, self.mr, self.mt)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):            # warm-up outside capture; apply=False leaves every parameter as is
             for _ in range(warmup):
-                trainer.enqueue(*feed, apply=False)
+                trainer.enqueue(*feed, apply=False, **okw)
         torch.cuda.current_stream().wait_stream(side)
         m.invalidate()                           # the derived tables are to be rebuilt INSIDE the graph
         self.graph = torch.cuda.CUDAGraph()
         from .graph import capture_without_gc
         with capture_without_gc(), torch.cuda.graph(self.graph):
-            self.loss = trainer.enqueue(*feed, apply=True, lr_dev=self.lr_dev)
+            self.loss = trainer.enqueue(*feed, apply=True, lr_dev=self.lr_dev, **okw)
         m.invalidate()                           # nothing ran during capture: no derived table is valid yet
         self._captured = self._storage_key()
         self.objective = (trainer.objective, trainer.group_size)     # the head the captured launches are
+        self.head = trainer.head_key()                               # ... with or without a logit offset
         self.guard = trainer.guard_key()                             # ... and whether (and on what) the guard's launches run
 
     def _storage_key(self):
@@ -807,8 +838,16 @@ class GraphedTrainer(object):
         return (m.adj_entity.data_ptr(), m.adj_relation.data_ptr(), m.entity_emb_matrix.data_ptr(),
                 m.user_emb_matrix.data_ptr(), m.relation_emb_KGE_matrix.data_ptr())
 
-    def load(self, users, items, labels, mem_h, mem_r, mem_t):
-        """Copy a batch (device tensors) into the graph's static input buffers."""
+    def load(self, users, items, labels, mem_h, mem_r, mem_t, offset=None):
+        """Copy a batch (device tensors) into the graph's static input buffers; ``offset`` exactly when the step was captured
+        with a logit offset."""
+        if (offset is None) != (self.offset is None):
+            raise ValueError("offset: this step was captured " + ("with" if self.offset is not None else "without")
+                             + " a logit offset (Trainer.set_objective(..., offset=...))")
+        if offset is not None:
+            if not torch.is_tensor(offset) or offset.dtype != F32 or offset.numel() != self.offset.numel():
+                raise ValueError(f"offset: expected a float32 tensor of {self.offset.numel()} values")
+            self.offset.copy_(offset.reshape(-1))
         self.users.copy_(users)
         self.items.copy_(items)
         self.labels.copy_(labels)
@@ -824,9 +863,9 @@ class GraphedTrainer(object):
         if self._storage_key() != self._captured:
             raise RuntimeError("the model's adjacency or a parameter tensor was replaced since this step was captured: "
                                "build a new GraphedTrainer")
-        if (tr.objective, tr.group_size) != self.objective:
-            raise RuntimeError(f"the trainer's objective changed to {(tr.objective, tr.group_size)} since this step was "
-                               f"captured with {self.objective}: build a new GraphedTrainer")
+        if tr.head_key() != self.head:
+            raise RuntimeError(f"the trainer's objective changed to {tr.head_key()} since this step was "
+                               f"captured with {self.head} (objective, group_size, logit offset): build a new GraphedTrainer")
         if tr.guard_key() != self.guard:
             raise RuntimeError("the trainer's guard was switched on or off (set_guard) since this step was captured: "
                                "build a new GraphedTrainer")
@@ -837,6 +876,6 @@ class GraphedTrainer(object):
         tr.m.invalidate()                        # parameters changed: eager callers rebuild their derived tables
         return self.loss
 
-    def step(self, users, items, labels, mem_h, mem_r, mem_t):
-        self.load(users, items, labels, mem_h, mem_r, mem_t)
+    def step(self, users, items, labels, mem_h, mem_r, mem_t, offset=None):
+        self.load(users, items, labels, mem_h, mem_r, mem_t, offset=offset)
         return self.replay()
