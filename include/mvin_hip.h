@@ -823,6 +823,42 @@ MVIN_API int mvin_rank_positives(const float* scores, int64_t rows, int64_t n, i
                                  void* ws, int32_t* out_counts /* [T,3] */, float* out_vals /* [T] */,
                                  int32_t* out_eligible /* [rows] */, void* stream);
 
+/* ---- per-user candidate lists: selection and exact ranks inside the segments of a flat score buffer --
+ * Reranking (every user arrives with a retrieved candidate list of its own length) and the sampled-candidate, leave-one-out
+ * evaluation protocol (every held-out item against n sampled ones).  Segment s is scores[seg_ptr[s] .. seg_ptr[s+1]) (seg_ptr
+ * [n_seg+1] int64, offsets into `scores` [total] and into `ids`; never written); a POSITION is an offset inside its segment.
+ * `ids` (int32 [total], may be NULL) is every entry's item id.  An entry is ELIGIBLE unless its id is negative (padding) or in
+ * the segment's exclusion row excl_ids[excl_ptr[s] .. excl_ptr[s+1]), ascending (excl_ptr [n_seg+1] int64; both NULL = no
+ * exclusions; exclusions need `ids`).  Scores compare as mvin_topk_rows orders them: -0.0 equals +0.0, every NaN is equal and
+ * below -inf, equal scores rank the lower position first.
+ *  - mvin_topk_segments: out_pos / out_vals / out_ids [n_seg, k] receive each segment's k best eligible entries, best first:
+ *    their positions, the input bits of their scores and (with `ids`; out_ids may be NULL without) their ids.  A segment with
+ *    fewer than k eligible entries ends in position -1, id -1, value -inf.  1 <= k <= 1024.
+ *  - mvin_rank_segments: segment s asks about the positions q_pos[q_ptr[s] .. q_ptr[s+1]), ascending and distinct (q_ptr
+ *    [n_seg+1] int64, offsets into q_pos [n_q] AND into the outputs).  out_counts[t] = (greater, equal_before, equal_after)
+ *    over the segment's eligible entries, out_vals[t] = the input bits of the query's score; a position outside the segment or
+ *    at an ineligible entry: (-1, -1, -1) and a quiet NaN (0x7FC00000) -- mvin_rank_positives' conventions.  out_eligible[s] =
+ *    the segment's eligible entries.  Queries that are not ascending and distinct get unspecified numbers, never an access out
+ *    of range.
+ * `max_len`: an upper bound on every segment's length, promised by the caller.  `form`: 0 = automatic (the wave form when
+ * max_len <= mvin_segments_wave_cap(), else the block form), 1 = wave form (a segment in the registers of a lane group),
+ * 2 = block form (one workgroup per segment, any length up to 2^31 - 1).  Every number is exact and independent of form, launch
+ * shape and max_len.  A segment longer than max_len, or whose pointers do not lie in [0, total] in order, is not read: its
+ * outputs are padding (its queries missing, its eligible count -1) and `status` (int64 [2], ACCUMULATED: zero it first) counts
+ * such segments in [0] and the output slots (top-K: k each) or queries left as padding because of it in [1].
+ * Errors (< 0, nothing launched): -2 for n_seg < 0 or >= 2^31, total < 0, n_q < 0, max_len < 0 or > 2^31 - 1, k out of range,
+ * form outside 0..2, form 1 with max_len above the cap; -1 for null scores (with total > 0) / seg_ptr / status / required
+ * outputs / q_ptr / q_pos, exactly one of excl_ptr / excl_ids, or exclusions without ids.  n_seg == 0 launches nothing.  No
+ * workspace. */
+MVIN_API int mvin_segments_wave_cap(void);                                      /* the longest segment the wave form takes */
+MVIN_API int mvin_topk_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                                const int64_t* excl_ptr, const int32_t* excl_ids, int k, int64_t max_len, int form,
+                                int32_t* out_pos, float* out_vals, int32_t* out_ids, int64_t* status, void* stream);
+MVIN_API int mvin_rank_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                                const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* q_ptr, const int32_t* q_pos,
+                                int64_t n_q, int64_t max_len, int form, int32_t* out_counts /* [n_q,3] */,
+                                float* out_vals /* [n_q] */, int32_t* out_eligible /* [n_seg] */, int64_t* status, void* stream);
+
 /* ---- CTR metrics: exact integer counts behind the reference's CTR evaluation (util.py:44-56: roc_auc_score, accuracy and
  * f1_score of every batch) for many segments at once --
  * mvin_ctr_counts: segment s is scores[s*ld .. s*ld+seg_len) (f32) with labels[s*ld .. s*ld+seg_len) (int32, 0 or 1); neither is

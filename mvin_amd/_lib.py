@@ -95,6 +95,11 @@ SIGNATURES = {
                        + [C.c_int] + [C.c_void_p] * 4),
     "mvin_rank_positives_ws_bytes": (C.c_int64, [C.c_int64] * 3),
     "mvin_rank_positives": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 9),
+    "mvin_segments_wave_cap": (C.c_int, []),
+    "mvin_topk_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int, C.c_int64, C.c_int]
+                           + [C.c_void_p] * 5),
+    "mvin_rank_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int]
+                           + [C.c_void_p] * 5),
     "mvin_kg_explore_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_kg_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
     "mvin_kg_explore": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,

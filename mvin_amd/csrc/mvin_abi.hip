@@ -485,6 +485,49 @@ int mvin_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld
                       who);
 }
 
+int mvin_segments_wave_cap(void) { return mvin::segments_wave_cap(); }
+
+// what mvin_topk_segments and mvin_rank_segments check alike
+static int segments_bad_args(const char* who, const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg,
+                             const int32_t* ids, const int64_t* excl_ptr, const int32_t* excl_ids, int64_t max_len, int form,
+                             const int64_t* status) {
+    if (n_seg < 0 || n_seg >= (int64_t(1) << 31) || total < 0 || max_len < 0 || max_len > (int64_t)0x7FFFFFFF)
+        return fail(-2, "%s: n_seg=%lld total=%lld max_len=%lld", who, (long long)n_seg, (long long)total, (long long)max_len);
+    if (form < 0 || form > 2) return fail(-2, "%s: form=%d (0 automatic, 1 wave, 2 block)", who, form);
+    if (form == 1 && max_len > mvin::segments_wave_cap())
+        return fail(-2, "%s: form=1 (wave) takes max_len <= %d, got %lld", who, mvin::segments_wave_cap(), (long long)max_len);
+    if (!seg_ptr || !status || (total > 0 && !scores)) return fail(-1, "%s: null scores / seg_ptr / status", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: null one of excl_ptr / excl_ids (they go together)", who);
+    if (excl_ptr && !ids) return fail(-1, "%s: null ids with exclusions (an exclusion row names item ids)", who);
+    return 0;
+}
+
+int mvin_topk_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                       const int64_t* excl_ptr, const int32_t* excl_ids, int k, int64_t max_len, int form, int32_t* out_pos,
+                       float* out_vals, int32_t* out_ids, int64_t* status, void* stream) {
+    const char* who = "mvin_topk_segments";
+    if (!mvin::topk_rows_supported(k)) return fail(-2, "%s: k=%d (1 <= k <= 1024)", who, k);
+    if (const int rc = segments_bad_args(who, scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, max_len, form, status)) return rc;
+    if (!out_pos || !out_vals || (ids && !out_ids)) return fail(-1, "%s: null out_pos / out_vals (/ out_ids with ids)", who);
+    return hip_result(mvin::launch_topk_segments(scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, k, max_len, form, out_pos,
+                                                 out_vals, ids ? out_ids : nullptr, status, (hipStream_t)stream),
+                      who);
+}
+
+int mvin_rank_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                       const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* q_ptr, const int32_t* q_pos, int64_t n_q,
+                       int64_t max_len, int form, int32_t* out_counts, float* out_vals, int32_t* out_eligible, int64_t* status,
+                       void* stream) {
+    const char* who = "mvin_rank_segments";
+    if (n_q < 0) return fail(-2, "%s: n_q=%lld", who, (long long)n_q);
+    if (const int rc = segments_bad_args(who, scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, max_len, form, status)) return rc;
+    if (!q_ptr || !out_eligible || (n_q > 0 && (!q_pos || !out_counts || !out_vals)))
+        return fail(-1, "%s: null q_ptr / q_pos / out_counts / out_vals / out_eligible", who);
+    return hip_result(mvin::launch_rank_segments(scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, q_ptr, q_pos, n_q, max_len,
+                                                 form, out_counts, out_vals, out_eligible, status, (hipStream_t)stream),
+                      who);
+}
+
 static bool kg_bad_sizes(int64_t n_entity, int64_t M) {
     return n_entity < 0 || n_entity > (int64_t)0x7FFFFFFF || M < 0 || M > (int64_t)0x7FFFFFFF;
 }

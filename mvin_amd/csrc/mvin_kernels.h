@@ -447,6 +447,14 @@ hipError_t launch_topk_rows(const float* scores, int64_t rows, int64_t n, int64_
 hipError_t launch_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
                                  const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* pos_ptr, const int32_t* pos_ids,
                                  int32_t* out_counts, float* out_vals, int32_t* out_eligible, hipStream_t st);   // exact ranks of named items (mvin_rank.hip)
+int segments_wave_cap();                                        // selection / ranking inside CSR segments (mvin_segments.hip)
+hipError_t launch_topk_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                                const int64_t* excl_ptr, const int32_t* excl_ids, int k, int64_t max_len, int form, int32_t* out_pos,
+                                float* out_vals, int32_t* out_ids, int64_t* status, hipStream_t st);
+hipError_t launch_rank_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                                const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* q_ptr, const int32_t* q_pos,
+                                int64_t n_q, int64_t max_len, int form, int32_t* out_counts, float* out_vals, int32_t* out_eligible,
+                                int64_t* status, hipStream_t st);
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);

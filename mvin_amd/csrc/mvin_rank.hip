@@ -20,10 +20,6 @@
 
 namespace mvin {
 
-constexpr int kRankPiece = 256;           // entries of a row handled per pass over the row
-constexpr int kRankGroups = kRankPiece / kWave;
-constexpr int kRankUnroll = 4;
-
 struct RankArgs {
     const float* scores;
     int64_t rows, n, ld;
@@ -150,67 +146,8 @@ __global__ __launch_bounds__(NT) void rank_positives_kernel(RankArgs a) {
             __syncthreads();
         }
 
-        // ---- count: lane (t & 63) of every wave keeps entry t's sums over the columns its wave saw
-        unsigned c_gt[kRankGroups], c_eb[kRankGroups], c_eq[kRankGroups];
-#pragma unroll
-        for (int g = 0; g < kRankGroups; ++g) c_gt[g] = c_eb[g] = c_eq[g] = 0u;
-        for (int64_t base = 0; base < n; base += (int64_t)kRankUnroll * NT) {
-            unsigned img[kRankUnroll];
-            int32_t col[kRankUnroll];
-            bool ok[kRankUnroll];
-#pragma unroll
-            for (int u = 0; u < kRankUnroll; ++u) {
-                const int64_t j = base + u * NT + tid;
-                ok[u] = j < n;
-                col[u] = (int32_t)j;
-                img[u] = 0u;
-                if (ok[u]) {
-                    img[u] = score_image(srow[j]);
-                    ok[u] = eligible(j);
-                }
-            }
-            if (q0 == 0) {
-#pragma unroll
-                for (int u = 0; u < kRankUnroll; ++u) n_elig += ok[u] ? 1u : 0u;
-            }
-#pragma unroll
-            for (int g = 0; g < kRankGroups; ++g) {
-                const int left = cnt - g * kWave;
-                const int m = left < kWave ? left : kWave;
-                for (int tt = 0; tt < m; ++tt) {         // (m <= 0: nothing)
-                    const int32_t jt = __builtin_amdgcn_readfirstlane(sCol[g * kWave + tt]);     // a broadcast read, kept scalar
-                    if (jt < 0) continue;
-                    const unsigned it = (unsigned)__builtin_amdgcn_readfirstlane((int)sImg[g * kWave + tt]);
-                    unsigned gt = 0, eb = 0, eq = 0;
-#pragma unroll
-                    for (int u = 0; u < kRankUnroll; ++u) {
-                        const bool e = ok[u] && img[u] == it;
-                        gt += (unsigned)__popcll(__ballot(ok[u] && img[u] > it));
-                        eq += (unsigned)__popcll(__ballot(e));
-                        eb += (unsigned)__popcll(__ballot(e && col[u] < jt));
-                    }
-                    if (lane == tt) {
-                        c_gt[g] += gt;
-                        c_eb[g] += eb;
-                        c_eq[g] += eq;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < kRankGroups; ++g) {
-            const int t = g * kWave + lane;
-            if (t < cnt && NW > 1) {
-                atomicAdd(&sCnt[t], c_gt[g]);
-                atomicAdd(&sCnt[kRankPiece + t], c_eb[g]);
-                atomicAdd(&sCnt[2 * kRankPiece + t], c_eq[g]);
-            } else if (t < cnt) {
-                sCnt[t] = c_gt[g];
-                sCnt[kRankPiece + t] = c_eb[g];
-                sCnt[2 * kRankPiece + t] = c_eq[g];
-            }
-        }
-        __syncthreads();
+        // ---- count (mvin_row_select.h): lane (t & 63) of every wave keeps entry t's sums over the columns its wave saw
+        rank_count_piece<NT>(srow, n, eligible, cnt, q0 == 0, sCol, sImg, sCnt, n_elig);
 
         // ---- write the piece: equal_after = equal - equal_before - 1 (the entry's own column is among the equal ones)
         for (int t = tid; t < cnt; t += NT) {

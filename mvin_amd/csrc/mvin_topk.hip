@@ -19,9 +19,6 @@
 
 namespace mvin {
 
-constexpr int kTopkMaxK = 1024;
-constexpr int kTopkUnroll = 4;
-
 struct TopkArgs {
     const float* scores;
     int64_t rows, n, ld;
@@ -100,134 +97,8 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(TopkArgs a) {
         return !topk_in_sorted(ex, E, a.cand_ids ? a.cand_ids[j] : (int32_t)(a.col_offset + j));
     };
 
-    // ---- radix select of the threshold image
-    unsigned prefix = 0, need = 0, c_gt = 0, m = 0;
-    int shift = 24;
-    for (int level = 0;; ++level) {
-        shift = 24 - 8 * level;
-        for (int i = tid; i < 256; i += NT) sHist[i] = 0u;
-        __syncthreads();
-        for (int64_t base = 0; base < T; base += (int64_t)kTopkUnroll * NT) {
-            unsigned img[kTopkUnroll];
-            bool ok[kTopkUnroll];
-#pragma unroll
-            for (int u = 0; u < kTopkUnroll; ++u) ok[u] = fetch(base + u * NT + tid, img[u]);
-#pragma unroll
-            for (int u = 0; u < kTopkUnroll; ++u)
-                if (ok[u] && (level == 0 || (img[u] >> (shift + 8)) == prefix)) atomicAdd(&sHist[(img[u] >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (wave == 0) {                                 // bin holding the need-th largest: suffix sums over 4 bins per lane
-            unsigned c[4], s = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                c[b] = sHist[4 * lane + b];
-                s += c[b];
-            }
-            unsigned suf = s;                            // sum over lanes >= lane
-#pragma unroll
-            for (int o = 1; o < kWave; o <<= 1) {
-                const unsigned t = __shfl_down(suf, o, kWave);
-                if (lane + o < kWave) suf += t;
-            }
-            const unsigned total = __shfl(suf, 0, kWave);
-            const unsigned want = level == 0 ? min((unsigned)k, total) : need - c_gt;
-            if (lane == 0) sMisc[3] = want;
-            unsigned above = suf - s;
-            if (want > 0 && above < want && want <= suf) {
-#pragma unroll
-                for (int b = 3; b >= 0; --b) {
-                    if (above + c[b] >= want) {
-                        sMisc[4] = 4 * lane + b;
-                        sMisc[5] = above;
-                        sMisc[6] = c[b];
-                        break;
-                    }
-                    above += c[b];
-                }
-            }
-            if (want == 0 && lane == 0) {                // nothing eligible: an empty bin 0, resolved at once
-                sMisc[4] = 0u;
-                sMisc[5] = 0u;
-                sMisc[6] = 0u;
-            }
-        }
-        __syncthreads();
-        if (level == 0) need = sMisc[3];
-        const unsigned bin = sMisc[4], above = sMisc[5], cnt = sMisc[6];
-        __syncthreads();                                 // sMisc / sHist are rewritten by the next level
-        c_gt += above;
-        prefix = (prefix << 8) | bin;
-        m = need - c_gt;
-        if (cnt == m || level == 3) break;               // the bucket is taken whole (also: nothing eligible), or resolved to 32 bits
-    }
-    // survivors: image >> shift above prefix (c_gt of them), plus the first m in position order equal to it
-
-    // ---- ordered compaction into sKey
-    if (tid == 0) sMisc[7] = 0u;
-    __syncthreads();
-    unsigned eq_base = 0;
-    int par = 0;
-    for (int64_t base = 0; base < T; base += (int64_t)kTopkUnroll * NT, par ^= 1) {
-        unsigned img[kTopkUnroll];
-        bool gt[kTopkUnroll], eq[kTopkUnroll];
-        unsigned pre[kTopkUnroll];
-#pragma unroll
-        for (int u = 0; u < kTopkUnroll; ++u) {
-            const bool ok = fetch(base + u * NT + tid, img[u]);
-            const unsigned top = img[u] >> shift;
-            gt[u] = ok && top > prefix;
-            eq[u] = ok && top == prefix;
-        }
-#pragma unroll
-        for (int u = 0; u < kTopkUnroll; ++u) {
-            const unsigned long long mask = __ballot(eq[u]);
-            pre[u] = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-            if (lane == 0) sWc[(par * kTopkUnroll + u) * NW + wave] = (unsigned)__popcll(mask);
-        }
-        __syncthreads();
-        unsigned run = eq_base;
-#pragma unroll
-        for (int u = 0; u < kTopkUnroll; ++u) {
-            unsigned before = 0, tot = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const unsigned c = sWc[(par * kTopkUnroll + u) * NW + w];
-                before += w < wave ? c : 0u;
-                tot += c;
-            }
-            const bool take = gt[u] || (eq[u] && run + before + pre[u] < m);
-            if (take) {
-                const int64_t e = base + u * NT + tid;
-                const unsigned slot = atomicAdd(&sMisc[7], 1u);
-                sKey[slot] = ((unsigned long long)img[u] << 32) | (0xFFFFFFFFull - (unsigned long long)e);
-            }
-            run += tot;
-        }
-        eq_base = run;
-    }
-    __syncthreads();
-
-    // ---- bitonic sort of the survivors, descending (padding keys are 0: below every candidate, whose low word is >= 1)
-    const int cnt = (int)sMisc[7];
-    int P = 1;
-    while (P < cnt) P <<= 1;
-    for (int i = cnt + tid; i < P; i += NT) sKey[i] = 0ull;
-    __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < P / 2; t += NT) {
-                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const unsigned long long x = sKey[i], y = sKey[j];
-                const bool desc = (i & size) == 0;
-                if ((x < y) == desc) {
-                    sKey[i] = y;
-                    sKey[j] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // ---- radix select, ordered compaction and bitonic sort of the survivors (mvin_row_select.h)
+    const int cnt = topk_select_sorted<NT>(fetch, T, k, sKey, sHist, sMisc, sWc);
 
     // ---- ids and values from where each survivor came from; staged in LDS so that every read of carry_* is done before out_*
     // (which may alias it) is written

@@ -434,6 +434,44 @@ def rank_groups(sampler, round):
     return users, items, valid
 
 
+def candidate_groups(sampler, round, n_neg):
+    """The groups of sampled-candidate evaluation (harness.sampled_rank_eval): one group of G = 1 + ``n_neg`` slots per positive
+    of ``sampler``, a ``NegativeSampler`` built over the split being evaluated with ``ratio`` = n_neg (an integer, 1..4095)
+    and every other split, train included, in ``exclude``.  Returns (users int64 [n_pos], items int64 [n_pos, G], ids int32
+    [n_pos, G], slot int32 [n_pos]) on the sampler's device, in the split's order.
+      negatives  assigned as ``rank_groups`` assigns them: positive number j of user u (``sampler.pos_index``) takes entries
+                 j*n_neg .. j*n_neg + n_neg - 1 of u's negative row of ``round``, in draw order;
+      slot       where the positive sits in its group: ``np.random.default_rng([seed, round]).integers(0, G, n_pos)[i]``, drawn
+                 once on the host.  NOT slot 0: ties rank the lower position first, so a positive at slot 0 would win every
+                 tie and a model whose scores saturate would show a hit ratio of 1.  The negatives fill the other slots in
+                 their order;
+      ids        the item id of every slot, -1 where the sampler could not fill it (beyond the user's clipped row, or a -1 of
+                 the draw): mvin_rank_segments counts no such slot;
+      items      what is scored: ``ids`` with the group's positive item in place of every -1, a valid id for every gather.
+    A pure function of (sampler.seed, round)."""
+    n_neg = int(n_neg)
+    if not 1 <= n_neg <= 4095 or sampler.ratio != n_neg:
+        raise ValueError(f"candidate_groups: n_neg={n_neg} must lie in [1, 4095] and equal the sampler's ratio={sampler.ratio!r}")
+    G = 1 + n_neg
+    neg_ptr, neg_items = sampler.draw(round)
+    dev = sampler.device
+    users, pos_item = sampler.pos_rows[:, 0].contiguous(), sampler.pos_rows[:, 1:2]
+    n_pos = users.shape[0]
+    k = sampler.pos_index[:, None] * n_neg + torch.arange(n_neg, dtype=torch.int64, device=dev)[None, :]
+    ok = k < sampler.counts.to(torch.int64)[users][:, None]                     # inside the user's (possibly clipped) row
+    if sampler.n_neg > 0:
+        neg = neg_items.to(torch.int64)[(neg_ptr[users][:, None] + k).clamp_(max=sampler.n_neg - 1)]
+        neg = torch.where(ok & (neg >= 0), neg, torch.full_like(neg, -1))
+    else:
+        neg = torch.full((n_pos, n_neg), -1, dtype=torch.int64, device=dev)
+    slot = torch.from_numpy(np.random.default_rng([sampler.seed, int(round)]).integers(0, G, n_pos).astype(np.int64)).to(dev)
+    col = torch.arange(G, dtype=torch.int64, device=dev)[None, :]
+    src = (col - (col > slot[:, None]).to(torch.int64)).clamp_(max=n_neg - 1)   # slot c holds negative c, or c - 1 past the positive
+    ids = torch.where(col == slot[:, None], pos_item.expand(-1, G), neg.gather(1, src))
+    items = torch.where(ids >= 0, ids, pos_item.expand(-1, G)).contiguous()
+    return users, items, ids.to(torch.int32).contiguous(), slot.to(torch.int32)
+
+
 def rank_offsets(sampler, users, items, valid):
     """The logit offsets of the logQ-corrected sampled softmax (mvin_rank_head_offset, Trainer.set_objective(offset=True)) for
     the groups ``users`` int64 [n] / ``items`` int64 [n, G] / ``valid`` f32 [n, G] of ``rank_groups(sampler, .)`` or a row

@@ -222,6 +222,121 @@ class DeviceFeeder(object):
                                out=(counts, vals, eligible[u0:u1]))
         return pos_ptr, pos_ids, counts, vals, eligible
 
+    def _score_lists(self, u, ptr, items, max_pairs):
+        """sigmoid scores of the expanded pair list (user i repeated over its list) as one flat device tensor [T]:
+        ``forward_users`` calls of at most ``max_pairs`` pairs each, ``distinct_users`` = the lists a piece touches."""
+        import torch
+        dev = self.model.device
+        T = int(ptr[-1])
+        flat = torch.empty((T,), dtype=torch.float32, device=dev)
+        if T == 0:
+            return flat
+        lens = torch.from_numpy(np.diff(ptr)).to(dev)
+        u_exp = u.repeat_interleave(lens, output_size=T)
+        for a in range(0, T, max_pairs):
+            b = min(T, a + max_pairs)
+            touched = int(np.searchsorted(ptr, b, side="left") - np.searchsorted(ptr, a, side="right") + 1)
+            flat[a:b] = self.model.forward_users(u_exp[a:b], items[a:b], self.uts, distinct_users=touched).scores_normalized
+        return flat
+
+    def recommend_lists(self, users, lists, k, exclude=None, max_pairs=524288):
+        """The ``k`` best items of every user's OWN candidate list -- the reranking stage of a two-stage recommender:
+        ``(items int64 [U, k], scores f32 [U, k], positions int32 [U, k])`` on the device, best first, ``positions`` the places
+        inside the user's list; equal scores keep the list's order; a list with fewer than ``k`` eligible items ends in item -1,
+        score -inf, position -1.  ``lists``: a CSR pair (a tuple ``(ptr [U+1], items [T])``, host or device) or a Python list of
+        per-user arrays; a negative item id is padding.  ``exclude`` as in ``recommend``.  The expanded pair list is scored into
+        one flat buffer in pieces of at most ``max_pairs`` pairs (a piece may cut a list), then ops.topk_segments runs once per
+        chunk of whole lists holding at most ``max_pairs`` pairs (one list when it is longer), with the chunk's own longest list
+        as the bound -- a chunk of short lists takes the wave form whatever another chunk holds.  Device pointers are copied to
+        the host once to cut the chunks; beyond that the call only enqueues: no copy back of any result."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        k, max_pairs = int(k), int(max_pairs)
+        if max_pairs < 1:
+            raise ValueError(f"max_pairs={max_pairs}")
+        if isinstance(exclude, dict):
+            if torch.is_tensor(users) and users.is_cuda:
+                raise ValueError("recommend_lists: an exclusion record needs host users (or pass feeder.exclusion_csr(users, record))")
+            exclude = self.exclusion_csr(users, exclude)
+        u = _dev_ids(users, dev)
+        U = u.shape[0]
+        ptr, items = _lists_csr(lists, U, dev)
+        flat = self._score_lists(u, ptr, items.clamp(min=0), max_pairs)      # padding is scored as item 0 and never eligible
+        ids = items.to(torch.int32)
+        seg_ptr = torch.from_numpy(ptr).to(dev)
+        out = (torch.empty((U, k), dtype=torch.int32, device=dev), torch.empty((U, k), dtype=torch.float32, device=dev),
+               torch.empty((U, k), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+        for s0, s1, longest in _segment_chunks(ptr, max_pairs):
+            ops.topk_segments(flat, seg_ptr[s0:s1 + 1], k, ids=ids,
+                              excl=None if exclude is None else (exclude[0][s0:s1 + 1], exclude[1]), max_len=longest,
+                              out=(out[0][s0:s1], out[1][s0:s1], out[2][s0:s1], out[3]))
+        return out[2].long(), out[1], out[0]
+
+    def rank_lists(self, users, lists, queries, exclude=None, max_pairs=524288):
+        """Where named entries of every user's OWN candidate list land in the user's ranking of that list: the device tensors
+        ``(q_ptr int64 [U+1], q_pos int32 [Q], counts int32 [Q, 3], vals f32 [Q], eligible int32 [U])`` of ``rank_positives``,
+        through ops.rank_segments.  ``lists`` and ``exclude`` as in ``recommend_lists``; ``queries`` names POSITIONS inside the
+        lists: a CSR pair (a tuple ``(q_ptr [U+1], q_pos [Q])``) or a Python list of per-user arrays, each ascending and
+        distinct.  A position beyond its list, or at a padded or excluded item, gets (-1, -1, -1) and NaN.  Scored and chunked
+        as ``recommend_lists`` does it; nothing is copied back."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        max_pairs = int(max_pairs)
+        if max_pairs < 1:
+            raise ValueError(f"max_pairs={max_pairs}")
+        if isinstance(exclude, dict):
+            if torch.is_tensor(users) and users.is_cuda:
+                raise ValueError("rank_lists: an exclusion record needs host users (or pass feeder.exclusion_csr(users, record))")
+            exclude = self.exclusion_csr(users, exclude)
+        u = _dev_ids(users, dev)
+        U = u.shape[0]
+        ptr, items = _lists_csr(lists, U, dev)
+        q_ptr_h, q_pos = _lists_csr(queries, U, dev)
+        q_ptr, q_pos = torch.from_numpy(q_ptr_h).to(dev), q_pos.to(torch.int32)
+        flat = self._score_lists(u, ptr, items.clamp(min=0), max_pairs)
+        ids = items.to(torch.int32)
+        seg_ptr = torch.from_numpy(ptr).to(dev)
+        Q = q_pos.numel()
+        out = (torch.empty((Q, 3), dtype=torch.int32, device=dev), torch.empty((Q,), dtype=torch.float32, device=dev),
+               torch.empty((U,), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+        for s0, s1, longest in _segment_chunks(ptr, max_pairs):
+            ops.rank_segments(flat, seg_ptr[s0:s1 + 1], (q_ptr[s0:s1 + 1], q_pos), ids=ids,
+                              excl=None if exclude is None else (exclude[0][s0:s1 + 1], exclude[1]), max_len=longest,
+                              out=(out[0], out[1], out[2][s0:s1], out[3]))
+        return q_ptr, q_pos, out[0], out[1], out[2]
+
+
+def _lists_csr(lists, U, dev):
+    """(ptr int64 [U+1] on the HOST, entries int64 [T] on the device) of per-user lists given as a CSR pair (a tuple of ptr and
+    entries, host or device: a device ptr is copied back once) or as a Python list of per-user arrays."""
+    import torch
+    if isinstance(lists, tuple):
+        if len(lists) != 2:
+            raise ValueError("lists: a CSR pair is a tuple (ptr, entries)")
+        ptr, entries = lists
+        ptr = np.ascontiguousarray(ptr.cpu().numpy() if torch.is_tensor(ptr) else np.asarray(ptr), dtype=np.int64).reshape(-1)
+        entries = _dev_ids(entries, dev)
+    else:
+        rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in lists]
+        ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum([r.size for r in rows])
+        entries = torch.from_numpy(np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)).to(dev)
+    if ptr.size != U + 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != entries.shape[0]:
+        raise ValueError(f"lists: expected {U} lists whose pointers run from 0 to the {entries.shape[0]} entries")
+    return ptr, entries
+
+
+def _segment_chunks(ptr, max_pairs):
+    """Cut segments 0 .. len(ptr) - 2 into runs of whole segments of at most ``max_pairs`` entries each (a longer segment is a
+    run of its own): yields (first, one past the last, the run's longest segment)."""
+    n, lens, s0 = ptr.size - 1, np.diff(ptr), 0
+    while s0 < n:
+        s1 = max(s0 + 1, int(np.searchsorted(ptr, ptr[s0] + max_pairs, side="right")) - 1)
+        yield s0, s1, int(lens[s0:s1].max())
+        s0 = s1
+
 
 def _candidate_ids(candidates, dev):
     """(ids int64 [N] on the device, int32 ids per column or None, first id): a host list that is a contiguous id range (the full
@@ -826,6 +941,112 @@ def full_ranking_eval(feeder, train_data, split_data, n_item, k_list=(20, 40, 60
                      max_pairs=max_pairs)
 
 
+def _sampled_summary(users, counts, vals, eligible, k_list):
+    """The sampled-candidate metrics of groups with ONE query each (group i belongs to ``users[i]``), from rank_segments'
+    integers on the host: every metric of ops.rank_metrics_from_counts and the AUC, averaged over the groups, and the same
+    under "by_user": the mean over users of each user's mean over its groups (an undefined AUC is left out of both means)."""
+    from . import ops
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    n = users.size
+    out = {m: [float("nan")] * len(k_list) for m in ops.RANK_METRICS}
+    out.update(auc=float("nan"), n_users=int(np.unique(users).size), n_groups=int(n))
+    out["by_user"] = {m: [float("nan")] * len(k_list) for m in ops.RANK_METRICS}
+    out["by_user"]["auc"] = float("nan")
+    if n == 0:
+        return out
+    import warnings
+    # a group's metrics depend on its three counts and its eligible count alone (one query: its value ties with no other
+    # query), so each DISTINCT (counts, eligible) goes through rank_metrics_from_counts once: a few thousand rows, not one
+    # per held-out interaction
+    c = np.asarray(counts).astype(np.int64).reshape(n, 3) + 1                  # -1 (missing) .. 4 096 -> 13 bits each
+    key = ((c[:, 0] << 39) | (c[:, 1] << 26) | (c[:, 2] << 13)) | (np.asarray(eligible).astype(np.int64).reshape(n) + 1)
+    _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", ops.UndefinedMetricWarning)            # a group of one eligible entry has no AUC
+        cls = ops.rank_metrics_from_counts(np.arange(first.size + 1), np.asarray(counts).reshape(n, 3)[first],
+                                           np.asarray(eligible).reshape(n)[first], k_list,
+                                           vals=np.asarray(vals, dtype=np.float32).reshape(n)[first])
+    per = {m: v[inv] for m, v in cls.items()}
+    _, inv = np.unique(users, return_inverse=True)
+    n_of = np.bincount(inv).astype(np.float64)
+    for m in ops.RANK_METRICS:
+        out[m] = [float(np.mean(per[m][:, q])) for q in range(len(k_list))]
+        out["by_user"][m] = [float(np.mean(np.bincount(inv, weights=per[m][:, q]) / n_of)) for q in range(len(k_list))]
+    ok = ~np.isnan(per["auc"])
+    if ok.any():
+        out["auc"] = float(np.mean(per["auc"][ok]))
+        have = np.bincount(inv[ok], minlength=n_of.size).astype(np.float64)
+        tot = np.bincount(inv[ok], weights=per["auc"][ok], minlength=n_of.size)
+        out["by_user"]["auc"] = float(np.mean(tot[have > 0] / have[have > 0]))
+    return out
+
+
+def sampled_rank_eval(feeder, train_data, split_data, other_splits, n_user, n_item, n_neg=99, k_list=(5, 10, 20), seed=1,
+                      round=0, max_pairs=524288):
+    """SAMPLED-candidate evaluation, the leave-one-out protocol of NCF (He et al. 2017): every label-1 row of ``split_data``
+    is ranked against ``n_neg`` (1..4095) sampled items the user has with label 1 in none of ``train_data``, ``split_data``
+    and ``other_splits`` (data_prep.candidate_groups over a NegativeSampler of the split: a pure function of (``seed``,
+    ``round``), the positive at a drawn slot so that ties are not handed to it).  The groups are scored through
+    ``forward_users`` and ranked by ops.rank_segments in chunks of whole groups of at most ``max_pairs`` pairs, and ONE packed
+    copy comes back.  Returns rank_eval's dict with every metric averaged over the held-out interactions (``n_users`` = the
+    distinct users among them), the same metrics under ``"by_user"`` (the mean over users of each user's mean), ``n_groups``
+    and ``n_short`` (slots the sampler could not fill: id -1, never eligible).
+    The metrics are SAMPLED: their values depend on ``n_neg`` and on the draw, they are systematically higher than -- and not
+    comparable with -- those of full ranking (rank_eval, full_ranking_eval; Krichene & Rendle 2020), and serve to follow one
+    model over its epochs at a fraction of full ranking's cost."""
+    import torch
+    from . import ops
+    from .data_prep import NegativeSampler, candidate_groups
+    import warnings
+    dev = feeder.model.device
+    n_neg, max_pairs = int(n_neg), int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError(f"max_pairs={max_pairs}")
+    split = np.asarray(split_data, dtype=np.int64).reshape(-1, 3)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)          # a clipped user is reported through n_short, not warned about
+        sampler = NegativeSampler(split, n_user, n_item, exclude=(np.asarray(train_data),) + tuple(np.asarray(o) for o in other_splits),
+                                  ratio=float(n_neg), seed=seed, device=dev)
+    users, items, ids, slot = candidate_groups(sampler, round, n_neg)
+    users_host = split[split[:, 2] == 1, 0]
+    n, G = int(users.shape[0]), 1 + n_neg
+    distinct = int(np.unique(users_host).size)
+    flat = torch.empty((n * G,), dtype=torch.float32, device=dev)
+    seg_ptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * G
+    q_ptr = torch.arange(n + 1, dtype=torch.int64, device=dev)
+    out = (torch.empty((n, 3), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
+           torch.empty((n,), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+    ids_flat, items_flat = ids.reshape(-1), items.reshape(-1)
+    per = max(1, max_pairs // G)
+    for g0 in range(0, n, per):
+        g1 = min(n, g0 + per)
+        lo, u_exp = g0 * G, users[g0:g1].repeat_interleave(G)
+        for a in range(lo, g1 * G, max_pairs):                 # one piece, unless a single group is larger than max_pairs
+            b = min(g1 * G, a + max_pairs)
+            flat[a:b] = feeder.model.forward_users(u_exp[a - lo:b - lo], items_flat[a:b], feeder.uts,
+                                                   distinct_users=min(distinct, g1 - g0)).scores_normalized
+        ops.rank_segments(flat, seg_ptr[g0:g1 + 1], (q_ptr[g0:g1 + 1], slot), ids=ids_flat, max_len=G,
+                          out=(out[0], out[1], out[2][g0:g1], out[3]))
+    n_short = (ids_flat < 0).sum().to(torch.int32).reshape(1)
+    packed = torch.cat([out[0].reshape(-1), out[1].view(torch.int32), out[2], n_short]).cpu().numpy()
+    res = _sampled_summary(users_host, packed[:3 * n].reshape(n, 3), packed[3 * n:4 * n].view(np.float32), packed[4 * n:5 * n],
+                           list(k_list))
+    res["n_short"] = int(packed[5 * n])
+    return res
+
+
+def topk_eval_sampled(feeder, train_data, eval_data, test_data, n_user, n_item, k_list, mode="test", n_neg=99, seed=1, round=0,
+                      max_pairs=524288):
+    """topk_eval_ranked's return shape from sampled-candidate evaluation (sampled_rank_eval) of the ``mode`` split: per k the
+    precision, recall and ndcg averaged over the held-out interactions of that split, each ranked against ``n_neg`` sampled
+    items.  With one truth item per group recall is the hit ratio.  SAMPLED numbers: not comparable with the other
+    ``topk_eval_*`` functions' (see sampled_rank_eval)."""
+    split, other = (eval_data, test_data) if mode == "eval" else (test_data, eval_data)
+    res = sampled_rank_eval(feeder, train_data, split, (other,), n_user, n_item, n_neg=n_neg, k_list=k_list, seed=seed,
+                            round=round, max_pairs=max_pairs)
+    return res["precision"], res["recall"], res["ndcg"], None, None
+
+
 # --------------------------------------------------------------------------- the train.py loop
 class EarlyStop(object):
     """train_util.py:20-61 (Early_stop_info): keep the best evaluation score, save the stage-wise
@@ -858,7 +1079,7 @@ class EarlyStop(object):
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
           objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0,
-          clip_norm=None, skip_nonfinite=False, logq=False):
+          clip_norm=None, skip_nonfinite=False, logq=False, eval_neg=None):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -876,7 +1097,11 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     scripts train at 512 / 1 024).
     ``topk_impl``: "host" ranks user by user on the host (topk_eval_device); "batched" ranks every user on the device in one
     call (topk_eval_batched; ties by ascending item id); "ranked" computes the same numbers as "batched", to the last bit, from
-    the exact ranks of the truth items (topk_eval_ranked, mvin_rank_positives: no selection, no bound on k).
+    the exact ranks of the truth items (topk_eval_ranked, mvin_rank_positives: no selection, no bound on k); "sampled" ranks
+    every held-out interaction of the split against ``eval_neg`` (1..4095, default 99) sampled items instead of the candidate
+    set (topk_eval_sampled, mvin_rank_segments; the same draw every epoch, seed ``args.neg_seed`` or 1): a fraction of the
+    work, and SAMPLED numbers that are not comparable with the other three's.  ``eval_neg`` with any other ``topk_impl`` is
+    refused.
     ``ctr_impl``: "host" evaluates CTR batch by batch with sklearn on the host (ctr_eval_device); "batched" scores each split
     into one device buffer and counts every batch's metrics exactly in one launch (ctr_eval_batched).
     ``negatives``: "fixed" trains on the label-0 rows ``train_data`` came with, every epoch; "resample" keeps the positives
@@ -918,6 +1143,14 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
+    if topk_impl not in ("host", "batched", "ranked", "sampled"):
+        raise ValueError(f"topk_impl={topk_impl!r}: expected 'host', 'batched', 'ranked' or 'sampled'")
+    if eval_neg is not None and topk_impl != "sampled":
+        raise ValueError(f"eval_neg={eval_neg!r} is the number of sampled candidates of topk_impl='sampled', not of {topk_impl!r}")
+    if topk_impl == "sampled":
+        eval_neg = 99 if eval_neg is None else eval_neg
+        if isinstance(eval_neg, (bool, np.bool_)) or int(eval_neg) != eval_neg or not 1 <= int(eval_neg) <= 4095:
+            raise ValueError(f"eval_neg={eval_neg!r}: expected an integer in [1, 4095]")
     if ctr_impl not in ("host", "batched"):
         raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
     if negatives not in ("fixed", "resample", "hard"):
@@ -972,8 +1205,6 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         model = MVIN(args, n_user, n_entity, n_relation, adj_entity, adj_relation, device=device, hoist=bool(hoist))
         if getattr(args, "load_pretrain_emb", False):
             model.restore_pretrain_emb()                                       # train.py:53-54
-    if topk_impl not in ("host", "batched", "ranked"):
-        raise ValueError(f"topk_impl={topk_impl!r}: expected 'host', 'batched' or 'ranked'")
     feeder = DeviceFeeder(model, uts)
     stop = EarlyStop(getattr(args, "tolerance", 2), getattr(args, "early_stop", 3),
                      getattr(args, "save_final_model", True))
@@ -1025,7 +1256,10 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
             rec["clipped_steps"], rec["skipped_steps"] = gs["clipped_steps"], gs["skipped_steps"]
         if show_topk:
             for mode in ("eval", "test"):
-                if topk_impl in ("batched", "ranked"):
+                if topk_impl == "sampled":
+                    p, r, n, _, _ = topk_eval_sampled(feeder, train_data, eval_data, test_data, n_user, n_item, k_list, mode=mode,
+                                                      n_neg=int(eval_neg), seed=getattr(args, "neg_seed", 1))
+                elif topk_impl in ("batched", "ranked"):
                     topk = topk_eval_ranked if topk_impl == "ranked" else topk_eval_batched
                     p, r, n, _, _ = topk(feeder, user_list, train_rec, eval_rec, test_rec, item_set, k_list, mode=mode)
                 else:

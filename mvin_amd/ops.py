@@ -642,6 +642,120 @@ def rank_positives(scores, pos, cand_ids=None, col_offset=0, excl=None, out=None
     return counts, vals, eligible
 
 
+def segments_wave_cap():
+    """mvin_segments_wave_cap: the longest segment the wave form of topk_segments / rank_segments takes."""
+    return int(_lib.load().mvin_segments_wave_cap())
+
+
+def _segments_common(scores, seg_ptr, ids, excl, max_len, form, name):
+    """The arguments topk_segments and rank_segments share, checked: (scores [T], seg_ptr, n_seg, ids, excl ptr, excl ids
+    pointer, max_len, form)."""
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise _lib.MvinHipError("scores: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    _chk(scores, F32, "scores")
+    if scores.dim() != 1:
+        raise ValueError("scores: expected a flat [T] tensor")
+    _chk(seg_ptr, torch.int64, "seg_ptr")
+    if seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise ValueError("seg_ptr: expected [n_seg + 1] offsets")
+    n_seg = seg_ptr.numel() - 1
+    if ids is not None:
+        _chk(ids, I32, "ids")
+        if ids.dim() != 1 or ids.numel() != scores.numel():
+            raise ValueError(f"ids: {ids.numel()} ids for {scores.numel()} scores")
+    eptr = eids_p = None
+    if excl is not None:
+        if ids is None:
+            raise ValueError(f"{name}: excl names item ids, so it needs ids")
+        eptr, eids = _rank_csr(excl, n_seg, "excl")
+        eids_p = _p(eids) if eids.numel() else _p(eptr)       # every row empty: any valid pointer, nothing is read through it
+    if form not in (None, "auto", "wave", "block", 0, 1, 2):
+        raise ValueError(f"form={form!r}: expected None / 'auto', 'wave' or 'block'")
+    form = {None: 0, "auto": 0, "wave": 1, "block": 2}.get(form, form)
+    if max_len is None:
+        max_len = int(torch.diff(seg_ptr).max()) if n_seg else 0          # the one synchronisation
+    return scores, seg_ptr, n_seg, ids, eptr, eids_p, int(max_len), int(form)
+
+
+def topk_segments(scores, seg_ptr, k, ids=None, excl=None, max_len=None, form=None, out=None):
+    """mvin_topk_segments: the ``k`` best eligible entries of every segment ``scores[seg_ptr[s]:seg_ptr[s+1]]`` of a flat f32
+    buffer -- per-user candidate lists of their own lengths -- best first, in topk_rows' order (higher score first, -0.0 equals
+    +0.0, NaN below -inf, equal scores by position).  ``seg_ptr`` int64 [n_seg+1]; ``ids`` int32 [T]: every entry's item id, a
+    negative id marks padding; ``excl``: a ``(ptr int64 [n_seg+1], ids int32)`` CSR of item ids excluded per segment, each row
+    ascending (needs ``ids``).  ``max_len``: an upper bound on the segment lengths; None reads it from ``seg_ptr``, which is ONE
+    synchronisation -- with ``max_len`` passed the call only enqueues.  ``form``: None / "auto", "wave" (a segment in the
+    registers of a lane group; ``max_len`` <= segments_wave_cap()) or "block" (a workgroup per segment); the numbers do not
+    depend on it.  Returns ``(pos int32 [n_seg, k], vals f32 [n_seg, k], ids int32 [n_seg, k] or None, status int64 [2])``
+    (``out``: the same four to write into; status is accumulated): positions inside the segment, the input bits of the scores
+    and the ids; a segment with fewer than k eligible entries ends in position -1, id -1, value -inf.  A segment longer than
+    ``max_len`` is all padding and is counted in status[0] (its k slots in status[1])."""
+    lib = _lib.load()
+    scores, seg_ptr, n_seg, ids, eptr, eids_p, max_len, form = _segments_common(scores, seg_ptr, ids, excl, max_len, form,
+                                                                                 "topk_segments")
+    k = int(k)
+    if not topk_rows_supported(k):
+        raise ValueError(f"k={k}: mvin_topk_segments takes 1 <= k <= 1024")
+    dev = scores.device
+    if out is None:
+        out = (torch.empty((n_seg, k), dtype=I32, device=dev), torch.empty((n_seg, k), dtype=F32, device=dev),
+               None if ids is None else torch.empty((n_seg, k), dtype=I32, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+    pos, vals, oid, status = out
+    _chk(pos, I32, "out pos")
+    _chk(vals, F32, "out vals")
+    _chk(oid, I32, "out ids")
+    _chk(status, torch.int64, "out status")
+    if tuple(pos.shape) != (n_seg, k) or tuple(vals.shape) != (n_seg, k) or (oid is not None and tuple(oid.shape) != (n_seg, k)) \
+            or (ids is not None and oid is None) or status.numel() != 2:
+        raise ValueError(f"out: expected pos / vals / ids [{n_seg}, {k}] (ids with ``ids``) and status [2]")
+    T = scores.numel()
+    anyp = _p(seg_ptr)                          # an empty array: any valid pointer, nothing is read or written through it
+    ids_p = None if ids is None else (_p(ids) if T else anyp)
+    _lib.check(lib.mvin_topk_segments(_p(scores) if T else None, T, _p(seg_ptr), n_seg, ids_p, _p(eptr), eids_p, k, max_len, form,
+                                      _p(pos) if n_seg else anyp, _p(vals) if n_seg else anyp,
+                                      None if ids is None else (_p(oid) if n_seg else anyp), _p(status), _stream()),
+               "mvin_topk_segments")
+    return pos, vals, oid, status
+
+
+def rank_segments(scores, seg_ptr, queries, ids=None, excl=None, max_len=None, form=None, out=None):
+    """mvin_rank_segments: where named entries of every segment land in the segment's ranking, without ranking it.  ``scores``,
+    ``seg_ptr``, ``ids``, ``excl``, ``max_len`` and ``form`` are topk_segments' (``max_len=None`` reads the bound from
+    ``seg_ptr``: ONE synchronisation; with ``max_len`` passed the call only enqueues).  ``queries``: a ``(q_ptr int64
+    [n_seg+1], q_pos int32 [Q])`` CSR of POSITIONS inside their segments, each row ascending and distinct; ``q_ptr`` holds
+    offsets into ``q_pos`` AND into the outputs, so slices ``seg_ptr[s0:s1+1]`` / ``q_ptr[s0:s1+1]`` rank segments s0 .. s1 into
+    their places of whole-size outputs.  Returns ``(counts int32 [Q, 3], vals f32 [Q], eligible int32 [n_seg], status int64
+    [2])`` (``out``: the same four; status is accumulated) with rank_positives' conventions -- (greater, equal_before,
+    equal_after) among the segment's eligible entries and the input bits of the score; (-1, -1, -1) and a quiet NaN for a
+    position outside its segment or at an ineligible entry -- so rank_metrics_from_counts takes them as they are.  A segment
+    longer than ``max_len`` has every query missing and eligible -1, and is counted in status[0] (its queries in status[1])."""
+    lib = _lib.load()
+    scores, seg_ptr, n_seg, ids, eptr, eids_p, max_len, form = _segments_common(scores, seg_ptr, ids, excl, max_len, form,
+                                                                                 "rank_segments")
+    if queries is None or len(queries) != 2:
+        raise ValueError("queries: expected a (q_ptr, q_pos) pair")
+    qptr, qpos = _rank_csr(queries, n_seg, "queries")
+    Q = qpos.numel()
+    dev = scores.device
+    if out is None:
+        out = (torch.empty((Q, 3), dtype=I32, device=dev), torch.empty((Q,), dtype=F32, device=dev),
+               torch.empty((n_seg,), dtype=I32, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+    counts, vals, eligible, status = out
+    _chk(counts, I32, "out counts")
+    _chk(vals, F32, "out vals")
+    _chk(eligible, I32, "out eligible")
+    _chk(status, torch.int64, "out status")
+    if tuple(counts.shape) != (Q, 3) or tuple(vals.shape) != (Q,) or tuple(eligible.shape) != (n_seg,) or status.numel() != 2:
+        raise ValueError(f"out: expected counts [{Q}, 3], vals [{Q}], eligible [{n_seg}] and status [2]")
+    T = scores.numel()
+    anyp = _p(seg_ptr)                          # an empty array: any valid pointer, nothing is read or written through it
+    ids_p = None if ids is None else (_p(ids) if T else anyp)
+    _lib.check(lib.mvin_rank_segments(_p(scores) if T else None, T, _p(seg_ptr), n_seg, ids_p, _p(eptr), eids_p,
+                                      _p(qptr), _p(qpos) if Q else anyp, Q, max_len, form, _p(counts) if Q else anyp,
+                                      _p(vals) if Q else anyp, _p(eligible) if n_seg else anyp, _p(status), _stream()),
+               "mvin_rank_segments")
+    return counts, vals, eligible, status
+
+
 def _score_image_host(vals):
     """mvin_score_image.h on the host: uint32 images of f32 scores (-0.0 = +0.0, every NaN = 0, below image(-inf))."""
     import numpy as np
