@@ -1040,6 +1040,46 @@ MVIN_API int mvin_select_negatives(const float* scores, const int64_t* items, co
                                    int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts /* [4] or NULL */,
                                    void* stream);
 
+/* ---- explaining a score: the merged, ranked knowledge-graph attention paths of every pair, and a per-relation profile --
+ * An extension beside the reference's case study (util.py:59-127 dumps every slot's attention weight as text): which paths
+ * item -rel0-> ent1 -rel1-> ent2 carried a pair's aggregation, and how much of it.  The inputs are what the i = 0 pass and
+ * mvin_expand_ids already produce, for a pair with fan-out K:
+ *   level-1 slots k1 = 0 .. K-1:       rel0[k1], ent1[k1] (int32 [B, K]) and the weight imp0[k1] (f32 [B, K]: probs_parent);
+ *   path slots    s = k1 * K + k2:     rel1[s], ent2[s] (int32 [B, K*K]) and the weight imp1[s] (f32 [B, K*K]: probs_child).
+ * ONE-HOP MODE: imp1 == rel1 == ent2 == NULL (h_hop = 1, where the reference's importance_list_1 is the int 0): the entries
+ * are the K level-1 slots, s = k1.
+ * WEIGHTS are cleaned first: NaN, +-inf and anything <= 0 become 0, anything above 1 becomes 1.  The MASS of slot s is the
+ * int64 floor(double(w0) * double(w1) * 2^40), in one-hop mode floor(double(w0) * 2^40): the product of two floats and the
+ * scaling are exact in double, so this is one number on every host and device, no rounding mode involved.
+ * MERGING: the sampler fills a row with repeats whenever an entity has fewer than K edges, so one real path is spread over
+ * many slots.  A distinct path is the key (rel0[k1], ent1[k1], rel1[s], ent2[s]) -- (rel0[k1], ent1[k1]) in one-hop mode; its
+ * mass is the integer sum over every slot that carries the key, its slot the lowest such s.  Nothing is assumed about level-1
+ * slots with equal ids having equal child rows.  The kernel packs (lowest level-1 slot with the same (rel0, ent1), rel1, ent2)
+ * into 6 + 25 + 31 bits: a path slot whose rel1 lies outside [0, 2^25) or whose ent2 is negative DOES NOT FIT and is dropped --
+ * its mass is 0 everywhere (total and rel_mass included), it joins no path and is not counted in out_distinct; everything else
+ * of its pair stays defined.  Level-1 ids are compared as they are, whatever their values.
+ * ORDER: mass descending, then slot ascending -- slots are unique, so the order is total and ties (paths with the same
+ * relation pattern carry identical weights: the logit is one number per relation) are resolved reproducibly.
+ * OUTPUTS per pair, the `top` best paths first: out_paths [B, top, 4] int32 = (rel0, ent1, rel1, ent2) (the last two -1 in
+ * one-hop mode), out_mass [B, top] int64, out_slot [B, top] int32; rows past the number of distinct paths hold ids -1, mass 0
+ * and slot -1.  out_distinct [B] int32 = the number of distinct paths, out_total [B] int64 = the sum of all masses of the pair.
+ * rel_mass (int64 [2, n_relation], may be NULL; ACCUMULATED with integer atomics: zero it first): rel_mass[0][r] += the masses
+ * floor(double(w0) * 2^40) of the level-1 slots with rel0 == r, rel_mass[1][r] += the path-slot masses with rel1 == r (row 1
+ * stays untouched in one-hop mode).  A relation id outside [0, n_relation) adds nothing (rel_mass only).
+ * Every output row is a pure function of its own pair's inputs: not of B, of other pairs, of the launch shape or of timing.
+ * Garbage ids and weights move nothing out of range.  One pair per lane group when the entries of a pair fit a wave (K*K <= 64,
+ * or one-hop mode), one workgroup per pair (sort in LDS) beyond.
+ * LIMITS: 1 <= K <= mvin_explain_paths_max_k() = 64 (BASELINE config C5's K = 128 is out of scope); 1 <= top <= K*K (<= K in
+ * one-hop mode); 0 <= B and B*K*K < 2^31; 0 <= n_relation < 2^25; with rel_mass n_relation >= 1 and B*K*K <= 2^22 -- cleaned
+ * weights are <= 1, so one call adds at most 2^62 whatever the inputs hold; sums across calls are the caller's business.
+ * Errors (nothing launched): -1 for a null required pointer or for one or two of imp1 / rel1 / ent2 being null; -2 for sizes out
+ * of range.  B == 0 launches nothing. */
+MVIN_API int mvin_explain_paths_max_k(void);
+MVIN_API int mvin_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0, const int32_t* ent1, const int32_t* rel1,
+                                const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths /* [B,top,4] */,
+                                int64_t* out_mass /* [B,top] */, int32_t* out_slot /* [B,top] */, int32_t* out_distinct /* [B] */,
+                                int64_t* out_total /* [B] */, int64_t* rel_mass /* [2,n_relation] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

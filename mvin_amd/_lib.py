@@ -199,6 +199,8 @@ SIGNATURES = {
                               + [_c_f32p] * 5 + [C.c_void_p, C.c_void_p]),
     "mvin_select_negatives": (C.c_int, [_c_f32p, C.c_void_p, _c_f32p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                         C.c_uint64, C.c_void_p, _c_f32p, _c_f32p, C.c_void_p, C.c_void_p]),
+    "mvin_explain_paths_max_k": (C.c_int, []),
+    "mvin_explain_paths": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7),
     "mvin_gather_attn_fwd_ex": (C.c_int, [_c_f32p, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p,
                                           _c_f32p, _c_f32p, _c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, _c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_int, C.c_void_p]),

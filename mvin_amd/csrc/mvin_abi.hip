@@ -1714,6 +1714,28 @@ int mvin_select_negatives(const float* scores, const int64_t* items, const float
                                                     out_items, out_valid, out_scores, counts, (hipStream_t)stream), who);
 }
 
+int mvin_explain_paths_max_k(void) { return mvin::explain_paths_max_k(); }
+
+int mvin_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0, const int32_t* ent1, const int32_t* rel1,
+                       const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths, int64_t* out_mass,
+                       int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, int64_t* rel_mass, void* stream) {
+    const char* who = "mvin_explain_paths";
+    if (!imp0 || !rel0 || !ent1 || !out_paths || !out_mass || !out_slot || !out_distinct || !out_total)
+        return fail(-1, "%s: null pointer (imp0 / rel0 / ent1 / out_paths / out_mass / out_slot / out_distinct / out_total)", who);
+    const int given = (imp1 != nullptr) + (rel1 != nullptr) + (ent2 != nullptr);
+    if (given != 0 && given != 3) return fail(-1, "%s: imp1 / rel1 / ent2 go together (all three, or none for one-hop mode)", who);
+    if (K < 1 || K > mvin::explain_paths_max_k()) return fail(-2, "%s: K=%d (1..%d)", who, K, mvin::explain_paths_max_k());
+    const int N = given ? K * K : K;
+    if (top < 1 || top > N) return fail(-2, "%s: top=%d (1..%d: K*K, or K in one-hop mode)", who, top, N);
+    if (B < 0 || B * K * K >= (int64_t(1) << 31)) return fail(-2, "%s: B=%lld with K=%d (0 <= B, B*K*K < 2^31)", who, (long long)B, K);
+    if (n_relation < 0 || n_relation >= (1 << 25)) return fail(-2, "%s: n_relation=%d (0 .. 2^25 - 1)", who, n_relation);
+    if (rel_mass && (n_relation < 1 || B * K * K > (int64_t(1) << 22)))
+        return fail(-2, "%s: rel_mass takes n_relation >= 1 and B*K*K <= 2^22 per call, got n_relation=%d B=%lld K=%d", who, n_relation,
+                    (long long)B, K);
+    return hip_result(mvin::launch_explain_paths(imp0, imp1, rel0, ent1, rel1, ent2, B, K, top, n_relation, out_paths, out_mass,
+                                                 out_slot, out_distinct, out_total, rel_mass, (hipStream_t)stream), who);
+}
+
 // ---------------------------------------------------------------------------- training
 static int rank_head_impl(const char* who, const float* user_o, const float* item_emb, const float* valid, const float* offset,
                           int64_t n_groups, int G, int D, int mode, float scale, float* scores, float* dscore, float* du, float* di,

@@ -468,6 +468,11 @@ hipError_t launch_rank_head(const float* user_o, const float* item_emb, const fl
                             float* loss_accum, int64_t* counts,
                             hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip);
                                                               // offset NULL: mvin_rank_head, else mvin_rank_head_offset
+int explain_paths_max_k();                                      // merged, ranked KG attention paths per pair (mvin_explain.hip)
+hipError_t launch_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0, const int32_t* ent1, const int32_t* rel1,
+                                const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths,
+                                int64_t* out_mass, int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, int64_t* rel_mass,
+                                hipStream_t st);
 hipError_t launch_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key,
                                    int64_t n_groups, int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round,
                                    int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts,

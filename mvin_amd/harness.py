@@ -307,6 +307,73 @@ class DeviceFeeder(object):
                               out=(out[0], out[1], out[2][s0:s1], out[3]))
         return q_ptr, q_pos, out[0], out[1], out[2]
 
+    def explain(self, users, items, top=10, profile=False, return_attention=False, max_pairs=65536):
+        """Which knowledge-graph paths carried the score of every pair (users[i], items[i]), and how much of it: the attention
+        outputs of the i = 0 pass merged and ranked on the device by ops.explain_paths (include/mvin_hip.h states the rule).  The
+        sampler repeats slots whenever an entity has fewer than K edges, so a path item -rel0-> ent1 -rel1-> ent2 is spread over
+        many of the K + K^2 slots the case study dumps; here slots with the same ids are ONE path with the integer sum of their
+        masses floor(w0 * w1 * 2^40), listed mass descending, then lowest slot ascending -- an exact, reproducible order although
+        ties are everywhere (the attention logit is one number per relation).  Returns a dict of device tensors:
+          scores [B] f32 (sigmoid; the ``want_probs`` pass takes another kernel form than ``scores``, so they agree to rounding),
+          paths [B, top, 4] int32 = (rel0, ent1, rel1, ent2), mass [B, top] int64, weight [B, top] f64 = mass / 2^40,
+          slot [B, top] int32, distinct [B] int32, total [B] int64 (rows past ``distinct``: ids -1, mass 0, slot -1);
+          ``profile=True``: rel_mass [2, n_relation] int64, the attention mass per relation at both levels, summed over the
+          chunks in int64 (a pair adds at most 2^40 per level: exact below 2^23 pairs);
+          ``return_attention=True``: imp0 [B, 1, K] and imp1 [B, K, K] (None at depth 1), the tensors the paths were cut from.
+        A model of depth 1 (h_hop = 1) takes one-hop mode: the entries are the K level-1 slots, the last two path columns -1.
+        With more than two levels the paths are those of the FIRST TWO, exactly what ``eval_case_study`` exposes.  The user side
+        (key addressing) writes no attention outputs and is not explained.  One ``forward_users(..., want_probs=True)`` and one
+        ``get_neighbors`` per chunk of at most ``max_pairs`` pairs (fewer where the kernel's bounds ask for it: B * K^2 <= 2^22
+        with ``profile``).  Enqueues only: nothing is copied back."""
+        import torch
+        from . import ops
+        m = self.model
+        dev = m.device
+        u, it = _dev_ids(users, dev), _dev_ids(items, dev)
+        if u.shape[0] != it.shape[0]:
+            raise ValueError(f"explain: {u.shape[0]} users for {it.shape[0]} items")
+        B, K, nR = u.shape[0], m.n_neighbor, m.n_relation
+        two = m.n_mix_hop * m.h_hop >= 2
+        N = K * K if two else K
+        top, max_pairs = int(top), int(max_pairs)
+        if max_pairs < 1 or not 1 <= top <= N:
+            raise ValueError(f"explain: max_pairs={max_pairs}, top={top} (1 <= top <= {N} entries per pair)")
+        if K > ops.explain_paths_max_k():
+            raise ValueError(f"explain: fan-out K={K} is beyond mvin_explain_paths' {ops.explain_paths_max_k()}")
+        chunk = max(1, min(max_pairs, (ops.EXPLAIN_PROFILE_SLOTS if profile else (1 << 31) - 1) // (K * K)))
+        res = dict(scores=torch.empty((B,), dtype=torch.float32, device=dev),
+                   paths=torch.empty((B, top, 4), dtype=torch.int32, device=dev),
+                   mass=torch.empty((B, top), dtype=torch.int64, device=dev),
+                   slot=torch.empty((B, top), dtype=torch.int32, device=dev),
+                   distinct=torch.empty((B,), dtype=torch.int32, device=dev),
+                   total=torch.empty((B,), dtype=torch.int64, device=dev))
+        if profile:
+            res["rel_mass"] = torch.zeros((2, nR), dtype=torch.int64, device=dev)
+        att0, att1 = [], []
+        for a in range(0, B, chunk):
+            b = min(B, a + chunk)
+            out = m.forward_users(u[a:b], it[a:b], self.uts, want_probs=True)
+            imp = out.importance_list
+            if not imp or imp[0] is None or (two and (len(imp) < 2 or imp[1] is None)):
+                raise ValueError("explain: this model's aggregator gives no attention outputs (importance_list is empty: "
+                                 "User_orient_rela off, or a pass without the i = 0 probabilities); there is nothing to explain")
+            imp0, imp1 = imp[0], imp[1] if two else None
+            ents, rels = m.get_neighbors(it[a:b], levels=2 if two else 1)
+            part = torch.zeros((2, nR), dtype=torch.int64, device=dev) if profile else None
+            ops.explain_paths(imp0, imp1, rels, ents, top, nR, rel_mass=part,
+                              out=(res["paths"][a:b], res["mass"][a:b], res["slot"][a:b], res["distinct"][a:b], res["total"][a:b]))
+            res["scores"][a:b] = out.scores_normalized
+            if profile:
+                res["rel_mass"] += part
+            if return_attention:
+                att0.append(imp0.reshape(b - a, 1, K))
+                att1.append(imp1.reshape(b - a, K, K) if two else None)
+        res["weight"] = res["mass"].to(torch.float64) / ops.EXPLAIN_SCALE
+        if return_attention:
+            res["imp0"] = torch.cat(att0) if att0 else torch.empty((0, 1, K), dtype=torch.float32, device=dev)
+            res["imp1"] = (torch.cat(att1) if att1 else torch.empty((0, K, K), dtype=torch.float32, device=dev)) if two else None
+        return res
+
 
 def _lists_csr(lists, U, dev):
     """(ptr int64 [U+1] on the HOST, entries int64 [T] on the device) of per-user lists given as a CSR pair (a tuple of ptr and
@@ -1505,3 +1572,53 @@ def ctr_eval_case_study(args, model, data, user_triplet_set, user_history_dict, 
                              zip(rname[1][nb * k: nb * (k + 1)], ename[2][nb * k: nb * (k + 1)], imp1[b, k])]
                     f.write("er rela pair 1 = " + "\n".join(pairs) + "\n")
             start += batch_size
+
+
+# --------------------------------------------------------------------------- explaining a score (an extension beside f-4)
+def explain_pairs(feeder, users, items, top, entity_names=None, relation_names=None):
+    """``DeviceFeeder.explain`` as plain Python records for printing: one dict per pair with ``user``, ``item``, ``item_name``,
+    ``score``, ``distinct`` (its number of distinct paths), ``total_weight`` (the sum of all its path weights; 1 up to the
+    float32 rounding of the two softmaxes) and ``paths``, the up to ``top`` heaviest distinct paths, heaviest first: dicts with
+    ``relations`` / ``entities`` (ids: (rel0, rel1) / (ent1, ent2); one entry each at depth 1), ``relation_names`` /
+    ``entity_names`` (through the lookup ``ctr_eval_case_study`` uses: ``table[str(id)]``, the id itself where the table has
+    none), ``weight`` (mass / 2^40), ``share`` (mass / the pair's total mass), ``mass`` and ``slot``.  Everything comes back in
+    ONE copy."""
+    import torch
+    res = feeder.explain(users, items, top=top)
+    B, top = res["mass"].shape
+    two = feeder.model.n_mix_hop * feeder.model.h_hop >= 2
+    packed = torch.cat([res["paths"].reshape(B, top * 4).long(), res["mass"], res["slot"].long(), res["distinct"].long()[:, None],
+                        res["total"][:, None], res["scores"].view(torch.int32).long()[:, None],
+                        _dev_ids(users, res["mass"].device)[:, None], _dev_ids(items, res["mass"].device)[:, None]], dim=1).cpu().numpy()
+    ent_tab = entity_names if entity_names is not None else {}
+    rel_tab = relation_names if relation_names is not None else {}
+    scale = float(1 << 40)
+    records = []
+    for row in packed:
+        paths, mass, slot = row[:top * 4].reshape(top, 4), row[top * 4:top * 5], row[top * 5:top * 6]
+        distinct, total, score_bits, user, item = (int(x) for x in row[top * 6:top * 6 + 5])
+        listed = []
+        for p in range(min(top, distinct)):
+            rel_ids = [int(paths[p, 0])] + ([int(paths[p, 2])] if two else [])
+            ent_ids = [int(paths[p, 1])] + ([int(paths[p, 3])] if two else [])
+            listed.append(dict(relations=rel_ids, entities=ent_ids, relation_names=_names(rel_ids, rel_tab),
+                               entity_names=_names(ent_ids, ent_tab), weight=int(mass[p]) / scale,
+                               share=int(mass[p]) / total if total else 0.0, mass=int(mass[p]), slot=int(slot[p])))
+        records.append(dict(user=user, item=item, item_name=_names([item], ent_tab)[0],
+                            score=float(np.int32(score_bits).view(np.float32)), distinct=distinct, total_weight=total / scale,
+                            paths=listed))
+    return records
+
+
+def relation_profile(feeder, data, batch_size):
+    """The share of attention mass per relation over a split: ``data`` [n, >= 2] rows of (user, item, ...), explained in
+    batches of ``batch_size`` pairs (``DeviceFeeder.explain(..., profile=True)``), the integer masses of both levels summed
+    over the batches.  Returns ``dict(mass int64 [2, n_relation], share float64 [2, n_relation], n_pairs)`` on the host: row 0
+    the level-1 slots (item -> neighbour), row 1 the path slots (neighbour -> neighbour's neighbour; all zero at depth 1);
+    ``share`` = a row of ``mass`` over its sum (zeros where the sum is 0)."""
+    data = np.asarray(data)
+    res = feeder.explain(data[:, 0], data[:, 1], top=1, profile=True, max_pairs=int(batch_size))
+    mass = res["rel_mass"].cpu().numpy()
+    tot = mass.sum(axis=1, keepdims=True)
+    share = np.divide(mass.astype(np.float64), tot, out=np.zeros(mass.shape, np.float64), where=tot > 0)
+    return dict(mass=mass, share=share, n_pairs=int(data.shape[0]))

@@ -1462,6 +1462,68 @@ def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None,
     return scores, dscore, du, di
 
 
+EXPLAIN_SCALE = float(1 << 40)                 # a mass is floor(w0 * w1 * 2^40); weight = mass / EXPLAIN_SCALE
+EXPLAIN_PROFILE_SLOTS = 1 << 22                # B * K * K of one call with rel_mass (mvin_explain_paths' bound)
+
+
+def explain_paths_max_k():
+    """mvin_explain_paths_max_k: the largest fan-out K mvin_explain_paths takes."""
+    return int(_lib.load().mvin_explain_paths_max_k())
+
+
+def explain_paths(imp0, imp1, rels, ents, top, n_relation, rel_mass=None, out=None):
+    """mvin_explain_paths: the merged, ranked knowledge-graph attention paths of every pair, in one launch (include/mvin_hip.h
+    states the rule).  ``imp0`` f32 [B, 1, K] (or [B, K]) and ``imp1`` f32 [B, K, K] (or [B, K*K]; None = ONE-HOP mode) are the
+    attention outputs of the i = 0 pass as ``forward_users(..., want_probs=True).importance_list`` holds them; ``rels`` /
+    ``ents`` the int32 id lists of ``MVIN.get_neighbors`` / ``expand_ids`` for the same items: ``rels[0]`` [B, K], ``ents[1]``
+    [B, K] and, with ``imp1``, ``rels[1]`` / ``ents[2]`` [B, K*K] (deeper levels are ignored).  Slots that carry the same
+    (rel0, ent1, rel1, ent2) are one path: its mass is the int64 sum of floor(w0 * w1 * 2^40) over them, its slot the lowest;
+    paths come mass descending, then slot ascending.  ``rel_mass``: int64 [2, n_relation] to ACCUMULATE the per-relation masses
+    of both levels into (zero it first; B * K * K <= 2^22 per call).  Returns ``(paths int32 [B, top, 4], mass int64 [B, top],
+    slot int32 [B, top], distinct int32 [B], total int64 [B])`` (``out``: the same five to write into); rows past ``distinct``
+    hold ids -1, mass 0, slot -1.  Enqueues only."""
+    lib = _lib.load()
+    for t, name in ((imp0, "imp0"), (imp1, "imp1")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if imp0 is None:
+        raise ValueError("explain_paths: imp0 is required")
+    _chk(imp0, F32, "imp0"), _chk(imp1, F32, "imp1"), _chk(rel_mass, torch.int64, "rel_mass")
+    two = imp1 is not None
+    B, K = imp0.shape[0], imp0.shape[-1]
+    N = K * K if two else K
+    if imp0.numel() != B * K or (two and (imp1.shape[0] != B or imp1.numel() != B * N)):
+        raise ValueError(f"imp0 {tuple(imp0.shape)} / imp1 {None if imp1 is None else tuple(imp1.shape)}: expected [B, 1, K] and [B, K, K]")
+    if len(rels) < (2 if two else 1) or len(ents) < (3 if two else 2):
+        raise ValueError("rels / ents: expected the lists of get_neighbors (rels[0], ents[1] and, with imp1, rels[1], ents[2])")
+    rel0, ent1 = _chk(rels[0], I32, "rels[0]"), _chk(ents[1], I32, "ents[1]")
+    rel1, ent2 = (_chk(rels[1], I32, "rels[1]"), _chk(ents[2], I32, "ents[2]")) if two else (None, None)
+    for t, n, name in ((rel0, K, "rels[0]"), (ent1, K, "ents[1]"), (rel1, N, "rels[1]"), (ent2, N, "ents[2]")):
+        if t is not None and (t.shape[0] != B or t.numel() != B * n):
+            raise ValueError(f"{name}: {tuple(t.shape)}, expected [{B}, {n}]")
+    top, n_relation = int(top), int(n_relation)
+    if not 1 <= K <= explain_paths_max_k() or not 1 <= top <= N:
+        raise ValueError(f"K={K} top={top}: mvin_explain_paths takes 1 <= K <= {explain_paths_max_k()} and 1 <= top <= {N}")
+    if rel_mass is not None and tuple(rel_mass.shape) != (2, n_relation):
+        raise ValueError(f"rel_mass: {tuple(rel_mass.shape)}, expected (2, {n_relation})")
+    dev = imp0.device
+    if out is None:
+        out = (torch.empty((B, top, 4), dtype=I32, device=dev), torch.empty((B, top), dtype=torch.int64, device=dev),
+               torch.empty((B, top), dtype=I32, device=dev), torch.empty((B,), dtype=I32, device=dev),
+               torch.empty((B,), dtype=torch.int64, device=dev))
+    paths, mass, slot, distinct, total = out
+    _chk(paths, I32, "out paths"), _chk(mass, torch.int64, "out mass"), _chk(slot, I32, "out slot")
+    _chk(distinct, I32, "out distinct"), _chk(total, torch.int64, "out total")
+    if tuple(paths.shape) != (B, top, 4) or tuple(mass.shape) != (B, top) or tuple(slot.shape) != (B, top) \
+            or tuple(distinct.shape) != (B,) or tuple(total.shape) != (B,):
+        raise ValueError(f"out: expected paths [{B}, {top}, 4], mass / slot [{B}, {top}], distinct / total [{B}]")
+    if B > 0:                                   # an empty tensor has no address to pass
+        _lib.check(lib.mvin_explain_paths(_p(imp0), _p(imp1), _p(rel0), _p(ent1), _p(rel1), _p(ent2), B, K, top, n_relation,
+                                          _p(paths), _p(mass), _p(slot), _p(distinct), _p(total), _p(rel_mass), _stream()),
+                   "mvin_explain_paths")
+    return paths, mass, slot, distinct, total
+
+
 def select_negatives(scores, items, valid, n_neg, shortlist, seed, round, group_key=None, counts=None, out_scores=False):
     """mvin_select_negatives: the hard negatives of a ranking objective out of a scored pool, in one launch (include/mvin_hip.h
     states the rule).  ``scores`` f32 / ``items`` int64 / ``valid`` f32 or None, all [n_groups, Gp]: slot 0 of a group is the
