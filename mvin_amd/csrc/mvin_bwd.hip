@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void count_ids_kernel(const int32_t* __restric
 
 hipError_t launch_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, hipStream_t st) {
     const int64_t nb = (n + 4095) / 4096;
-    count_ids_kernel<<<(int)(nb < 1 ? 1 : nb < 256 ? nb : 256), 256, 0, st>>>(ids, n, nbins, out);
+    count_ids_kernel<<<(int)persistent_grid(nb < 1 ? 1 : nb, 1), 256, 0, st>>>(ids, n, nbins, out);
     return hipGetLastError();
 }
 
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(kBlock) void key_addr_bwd_kernel(KeyAddrBwdArgs a) 
 // ------------------------------------------------------------------------------------------
 static int blocks_for(int64_t n, int per) {
     int64_t b = (n + per - 1) / per;
-    return (int)(b < 1 ? 1 : (b > 256 * 16 ? 256 * 16 : b));
+    return (int)persistent_grid(b < 1 ? 1 : b, 16);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -906,11 +906,7 @@ hipError_t launch_linear_wgrad(WgradArgs a, hipStream_t st) {
     const int64_t ntiles = (a.lin.rows + kTM - 1) / kTM;
     int gx = (int)(ntiles < 64 ? (ntiles < 1 ? 1 : ntiles) : 64);
     const size_t lds = ((size_t)kTM * (Din + 4) + (size_t)kTM * (a.lin.Dout + 1)) * sizeof(float);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_wgrad_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = grant_lds(linear_wgrad_kernel, lds); e != hipSuccess) return e;
     linear_wgrad_kernel<<<dim3(gx, ny, a.lin.nz > 0 ? a.lin.nz : 1), kBlock, lds, st>>>(a);
     return hipGetLastError();
 }
@@ -934,11 +930,8 @@ hipError_t launch_key_addr_bwd(const KeyAddrBwdArgs& a0, hipStream_t st) {
     a.dv_lds = (a.f.P > 0 && a.dV && lds + dv <= 48 * 1024 && getenv("MVIN_KAB_DV_GLOBAL") == nullptr) ? 1 : 0;
     if (a.dv_lds) lds += dv;
     if (a.Rk && !a.dv_lds) return hipErrorInvalidValue;      // the in-kernel item gradient reads the LDS copy of dV
-    if (lds > 64 * 1024) {       // n_memory beyond ~6 000: raise the dynamic-LDS limit (the ABI caps Nm at 8 192 = 80 KB)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(key_addr_bwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    // n_memory beyond ~6 000: raise the dynamic-LDS limit (the ABI caps Nm at 8 192 = 80 KB)
+    if (hipError_t e = grant_lds(key_addr_bwd_kernel, lds); e != hipSuccess) return e;
     key_addr_bwd_kernel<<<blocks_for(a.f.B * (a.f.P + (a.f.w ? 1 : 0)), 1), kBlock, lds, st>>>(a);
     return hipGetLastError();
 }

@@ -30,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kEtD = 64;
 constexpr int kEtLd = 68;           // row stride of a wave's LDS image of a tile, in floats
 constexpr int kEtRows = 16;         // entity rows per tile (the N of the transposed product)
-constexpr int kEtWgCap = 1024;      // resident workgroups: 256 CUs x 4 (four waves per SIMD)
+constexpr int kEtWgCap = kNumCUs * 4;       // resident workgroups: four per CU (four waves per SIMD)
 
 struct EntityTableArgs {
     const float* E;                 // [n_entity, 64]

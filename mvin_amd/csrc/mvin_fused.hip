@@ -555,13 +555,8 @@ size_t fused_l2_lds_bytes(int D, int NW, int K, int nR, int nbuf, int kTM, bool 
 template <int D, int NW, int KIT, bool BF, int TMV, bool GPC>
 static hipError_t launch_l2(const FusedL2Args& a, hipStream_t st) {
     const size_t lds = fused_l2_lds_bytes(D, NW, a.K, a.nR, KIT > 0 ? 2 : 1, TMV, GPC);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_attn_l2_kernel<D, NW, KIT, BF, TMV, GPC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const int64_t cap = 256 * 4 * (32 / TMV);  // persistent: 256 CUs x up to 4 resident 32-row workgroups
-    const int grid = (int)(a.P < cap ? a.P : cap);
+    if (hipError_t e = grant_lds(gather_attn_l2_kernel<D, NW, KIT, BF, TMV, GPC>, lds); e != hipSuccess) return e;
+    const int grid = (int)persistent_grid(a.P, 4 * (32 / TMV));      // persistent: up to 4 resident 32-row workgroups per CU
     gather_attn_l2_kernel<D, NW, KIT, BF, TMV, GPC><<<grid, NW * 64, lds, st>>>(a);
     return hipGetLastError();
 }

@@ -766,8 +766,7 @@ static hipError_t launch_fold_k(const FoldArgs& a, hipStream_t st) {
     if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
     if (plan.dev != dev || plan.nR != a.nR) {
         auto occupancy = [&](Kern k, size_t lds) {
-            int v = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(k), kAggWaves * 64, lds) != hipSuccess || v < 1) v = 0;
+            const int v = workgroups_per_cu(k, kAggWaves * 64, lds, 0);
             return v > 8 ? 8 : v;
         };
         const size_t lds1 = fused_agg_lds_bytes(a.nR, K), lds2 = lds1 + (size_t)kAggWaves * agg_list_words(K) * sizeof(float);
@@ -785,9 +784,9 @@ static hipError_t launch_fold_k(const FoldArgs& a, hipStream_t st) {
     }
     const int64_t nbatch = (a.B + 15) >> 4;
     const int64_t want = (nbatch + kAggWaves - 1) / kAggWaves;
-    int64_t cap = 256 * (int64_t)plan.per_cu;            // persistent grid
-    if (grid_cap > 0 && grid_cap < cap) cap = grid_cap;
-    plan.kern<<<(int)(want < cap ? want : cap), kAggWaves * 64, plan.lds, st>>>(a);
+    int64_t grid = persistent_grid(want, plan.per_cu);
+    if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
+    plan.kern<<<(int)grid, kAggWaves * 64, plan.lds, st>>>(a);
     return hipGetLastError();
 }
 
@@ -831,8 +830,7 @@ static hipError_t launch_entity_aggregates_k(const EntityAggArgs& a, hipStream_t
     const size_t lds = ((size_t)((a.nR + 3) & ~3) + (size_t)kAggWaves * agg_list_words(K)) * sizeof(float);
     const int64_t nquad = ((int64_t)a.n_entity + 3) >> 2;
     const int64_t want = (nquad + kAggWaves - 1) / kAggWaves;
-    const int64_t cap = 256 * 8;
-    entity_aggregates_kernel<K><<<(int)(want < cap ? want : cap), kAggWaves * 64, lds, st>>>(a);
+    entity_aggregates_kernel<K><<<(int)persistent_grid(want, 8), kAggWaves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 
@@ -921,17 +919,10 @@ hipError_t launch_fold_prepare(const float* W0, const float* b0, const float* W1
 template <int K>
 static hipError_t launch_agg_k(const FusedL2Args& a, hipStream_t st) {
     const size_t lds = fused_agg_lds_bytes(a.nR, K);
-    static thread_local int per_cu = 0;
-    if (per_cu == 0) {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(gather_attn_l2_agg_kernel<K>), kAggWaves * 64, lds) != hipSuccess || v < 1)
-            v = 4;
-        per_cu = v > 8 ? 8 : v;
-    }
+    const int v = workgroups_per_cu(gather_attn_l2_agg_kernel<K>, kAggWaves * 64, lds, 4);
     const int64_t nbatch = (a.P + 15) >> 4;
     const int64_t want = (nbatch + kAggWaves - 1) / kAggWaves;
-    const int64_t cap = 256 * (int64_t)per_cu;           // persistent grid
-    gather_attn_l2_agg_kernel<K><<<(int)(want < cap ? want : cap), kAggWaves * 64, lds, st>>>(a);
+    gather_attn_l2_agg_kernel<K><<<(int)persistent_grid(want, v > 8 ? 8 : v), kAggWaves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 

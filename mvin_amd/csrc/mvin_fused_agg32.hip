@@ -338,8 +338,7 @@ static hipError_t launch_ea32_k(const EntityAggArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)((a.nR + 3) & ~3) + (size_t)kAggWaves * a32_list_words(K)) * sizeof(float);
     const int64_t noct = ((int64_t)a.n_entity + 7) >> 3;
     const int64_t want = (noct + kAggWaves - 1) / kAggWaves;
-    const int64_t cap = 256 * 8;
-    entity_aggregates_d32_kernel<K><<<(int)(want < cap ? want : cap), kAggWaves * 64, lds, st>>>(a);
+    entity_aggregates_d32_kernel<K><<<(int)persistent_grid(want, 8), kAggWaves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 
@@ -354,17 +353,10 @@ hipError_t launch_entity_aggregates_d32(const EntityAggArgs& a, hipStream_t st) 
 template <int K>
 static hipError_t launch_fold32_k(const FoldArgs& a, hipStream_t st) {
     const size_t lds = fused_fold_d32_lds_bytes(a.nR, K);
-    static thread_local int per_cu = 0;
-    if (per_cu == 0) {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(score_l2_folded_d32_kernel<K>), kAggWaves * 64, lds) != hipSuccess || v < 1)
-            v = 3;
-        per_cu = v > 8 ? 8 : v;
-    }
+    const int v = workgroups_per_cu(score_l2_folded_d32_kernel<K>, kAggWaves * 64, lds, 3);
     const int64_t nbatch = (a.B + 15) >> 4;
     const int64_t want = (nbatch + kAggWaves - 1) / kAggWaves;
-    const int64_t cap = 256 * (int64_t)per_cu;           // persistent grid
-    score_l2_folded_d32_kernel<K><<<(int)(want < cap ? want : cap), kAggWaves * 64, lds, st>>>(a);
+    score_l2_folded_d32_kernel<K><<<(int)persistent_grid(want, v > 8 ? 8 : v), kAggWaves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 

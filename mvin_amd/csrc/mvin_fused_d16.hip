@@ -300,8 +300,7 @@ template <int K, bool BF>
 static hipError_t launch_d16(const FusedL2Args& a, hipStream_t st) {
     const size_t lds = fused_d16_lds_bytes(a.nR);
     const int64_t wgs = (a.P + kD16Waves - 1) / kD16Waves;
-    const int64_t cap = 256 * 8;                         // persistent: up to 32 waves per CU
-    const int grid = (int)(wgs < cap ? wgs : cap);
+    const int grid = (int)persistent_grid(wgs, 8);       // persistent: up to 32 waves per CU
     gather_attn_l2_d16_kernel<K, BF><<<grid, kD16Waves * 64, lds, st>>>(a);
     return hipGetLastError();
 }

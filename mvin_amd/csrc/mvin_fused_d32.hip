@@ -463,17 +463,8 @@ template <int K, bool BF, bool ENC, bool PRJ = false>
 static hipError_t launch_d32(const FusedL2Args& a, hipStream_t st) {
     const size_t lds = fused_d32_lds_bytes(a.nR, K);
     const int64_t wgs = (a.P + kD32Waves - 1) / kD32Waves;
-    static thread_local int per_cu = 0;
-    if (per_cu == 0) {
-        int v = 3;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(gather_attn_l2_d32_kernel<K, BF, ENC, PRJ>), kD32Waves * 64, lds) !=
-                hipSuccess || v < 1)
-            v = 3;
-        per_cu = v;
-    }
-    const int64_t cap = 256 * (int64_t)per_cu;           // persistent grid
-    const int grid = (int)(wgs < cap ? wgs : cap);
-    gather_attn_l2_d32_kernel<K, BF, ENC, PRJ><<<grid, kD32Waves * 64, lds, st>>>(a);
+    const int per_cu = workgroups_per_cu(gather_attn_l2_d32_kernel<K, BF, ENC, PRJ>, kD32Waves * 64, lds, 3);      // (no upper bound here)
+    gather_attn_l2_d32_kernel<K, BF, ENC, PRJ><<<(int)persistent_grid(wgs, per_cu), kD32Waves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 

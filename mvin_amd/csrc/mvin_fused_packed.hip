@@ -1000,10 +1000,7 @@ static hipError_t launch_packed(const FusedL2Args& a, hipStream_t st) {
     using G = PackGeom<D, KT, BF, NG>;
     const size_t lds = pack_lds(D, KT, a.nR, NG, BF, PRJ).total;
     auto kern = gather_attn_l2_packed_kernel<D, KT, BF, NG, PROF, PRJ>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = grant_lds(kern, lds); e != hipSuccess) return e;
     // parents per workgroup: enough workgroups to balance the tail (tiles per parent vary with the distinct counts),
     // few enough that the weight fragments and the id prologue are amortised
     static const char* env = getenv("MVIN_PACK_PPW");

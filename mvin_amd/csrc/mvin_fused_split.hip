@@ -573,15 +573,10 @@ static hipError_t launch_split(const FusedL2Args& a, hipStream_t st) {
     using G = SplitGeom<D, KT, BF, NG>;
     const size_t lds = fused_split_lds_bytes(D, KT, a.nR);
     auto kern = gather_attn_l2_split_kernel<D, KT, BF, NG, UNR, TRACE>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = grant_lds(kern, lds); e != hipSuccess) return e;
     int per_cu = G::MINW == 4 ? 16 / G::NW : 1;         // 4 waves per SIMD: 16 waves per CU
     while (per_cu > 1 && per_cu * lds > 160 * 1024) --per_cu;
-    const int64_t cap = 256 * per_cu;                   // persistent: one pipeline per resident workgroup
-    const int grid = (int)(a.P < cap ? a.P : cap);
-    kern<<<grid, G::NW * 64, lds, st>>>(a);
+    kern<<<(int)persistent_grid(a.P, per_cu), G::NW * 64, lds, st>>>(a);      // persistent: one pipeline per resident workgroup
     return hipGetLastError();
 }
 

@@ -390,17 +390,10 @@ bool fused_wpp_applies(const FusedL2Args& a, int D) {
 template <int K>
 static hipError_t launch_wpp_k(const FusedL2Args& a, hipStream_t st) {
     const size_t lds = fused_wpp_lds_bytes(a.nR, K);
-    static thread_local int per_cu = 0;
-    if (per_cu == 0) {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(gather_attn_l2_wpp_kernel<K>), kWppWaves * 64, lds) != hipSuccess || v < 1)
-            v = 4;
-        per_cu = v > 8 ? 8 : v;
-    }
+    const int v = workgroups_per_cu(gather_attn_l2_wpp_kernel<K>, kWppWaves * 64, lds, 4);
     const int64_t nbatch = (a.P + 15) >> 4;
     const int64_t want = (nbatch + kWppWaves - 1) / kWppWaves;
-    const int64_t cap = 256 * (int64_t)per_cu;           // persistent grid
-    gather_attn_l2_wpp_kernel<K><<<(int)(want < cap ? want : cap), kWppWaves * 64, lds, st>>>(a);
+    gather_attn_l2_wpp_kernel<K><<<(int)persistent_grid(want, v > 8 ? 8 : v), kWppWaves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 

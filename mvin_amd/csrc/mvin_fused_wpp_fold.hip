@@ -410,17 +410,10 @@ size_t fused_wppfold_lds_bytes(int nR, int K) {
 template <int K>
 static hipError_t launch_wppfold_k(const FoldArgs& a, hipStream_t st) {
     const size_t lds = fused_wppfold_lds_bytes(a.nR, K);
-    static thread_local int per_cu = 0;
-    if (per_cu == 0) {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(score_l2_wppfold_kernel<K>), kWppWaves * 64, lds) != hipSuccess || v < 1)
-            v = 3;
-        per_cu = v > 8 ? 8 : v;
-    }
+    const int v = workgroups_per_cu(score_l2_wppfold_kernel<K>, kWppWaves * 64, lds, 3);
     const int64_t nbatch = (a.B + 15) >> 4;
     const int64_t want = (nbatch + kWppWaves - 1) / kWppWaves;
-    const int64_t cap = 256 * (int64_t)per_cu;           // persistent grid
-    score_l2_wppfold_kernel<K><<<(int)(want < cap ? want : cap), kWppWaves * 64, lds, st>>>(a);
+    score_l2_wppfold_kernel<K><<<(int)persistent_grid(want, v > 8 ? 8 : v), kWppWaves * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 

@@ -92,8 +92,7 @@ __global__ __launch_bounds__(kBlock) void gather_mix_kernel(GatherMixArgs a) {
 
 hipError_t launch_gather_mix(const GatherMixArgs& a, hipStream_t st) {
     const int64_t nblk = (a.nodes + 3) / 4;
-    const int64_t cap = 256 * 8;   // 8 workgroups per CU: the kernel needs few registers
-    const int grid = (int)(nblk < cap ? nblk : cap);
+    const int grid = (int)persistent_grid(nblk, 8);     // 8 workgroups per CU: the kernel needs few registers
     const int kc = (a.K + kWave - 1) / kWave;
 #define MVIN_GM(KCV)                                                                   \
     if (a.table_bf16) gather_mix_kernel<KCV, true><<<grid, kBlock, 0, st>>>(a);        \

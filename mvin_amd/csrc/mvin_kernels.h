@@ -5,6 +5,7 @@
 
 #include "../../include/mvin_hip.h"
 #include "mvin_common.h"
+#include "mvin_launch.h"   // kNumCUs, persistent_grid, workgroups_per_cu, grant_lds
 
 namespace mvin {
 

@@ -389,17 +389,7 @@ static int nr_for(int Dout) {
     return kTM / p;              // NR in {1,2,4,8,16,32}
 }
 
-static int grid_for(int64_t ntiles) {
-    const int64_t cap = 256 * 8;  // 256 CUs x 8 workgroups
-    return (int)(ntiles < cap ? (ntiles < 1 ? 1 : ntiles) : cap);
-}
-
-template <typename KernelT>
-static hipError_t ensure_lds(KernelT kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+static int grid_for(int64_t ntiles) { return (int)persistent_grid(ntiles < 1 ? 1 : ntiles, 8); }      // 8 workgroups per CU
 
 #define MVIN_DISPATCH_NR(nr, CALL)            \
     switch (nr) {                             \
@@ -446,7 +436,7 @@ hipError_t launch_linear(const mvin_linear_args& a, hipStream_t st) {
     dim3 grid(grid_for(ntiles), a.nz > 0 ? a.nz : 1);
 #define CALL(NRV)                                                         \
     {                                                                     \
-        hipError_t e = ensure_lds(linear_kernel<NRV>, lds);               \
+        hipError_t e = grant_lds(linear_kernel<NRV>, lds);                \
         if (e != hipSuccess) return e;                                    \
         linear_kernel<NRV><<<grid, kBlock, lds, st>>>(a);                 \
     }
@@ -459,14 +449,14 @@ hipError_t launch_gather_attn(const GatherAttnArgs& a0, hipStream_t st) {
     const int nr = nr_for(a0.D);
     GatherAttnArgs a = a0;
     const size_t lds = (size_t)2 * kTM * (a.D + 4) * sizeof(float) + (size_t)4 * a.K * sizeof(int2);
-    a.tile_rows = (a.T + kTM - 1) / kTM < 256 ? 8 : kTM;
+    a.tile_rows = (a.T + kTM - 1) / kTM < kNumCUs ? 8 : kTM;
     const int64_t ntiles = (a.T + a.tile_rows - 1) / a.tile_rows;
     dim3 grid(grid_for(ntiles));
     const bool pre = ntiles <= 1024;
 #define CALL(NRV)                                                         \
     {                                                                     \
-        hipError_t e = pre ? ensure_lds(gather_attn_kernel<NRV, 8>, lds)  \
-                           : ensure_lds(gather_attn_kernel<NRV, 0>, lds); \
+        hipError_t e = pre ? grant_lds(gather_attn_kernel<NRV, 8>, lds)   \
+                           : grant_lds(gather_attn_kernel<NRV, 0>, lds);  \
         if (e != hipSuccess) return e;                                    \
         if (pre) gather_attn_kernel<NRV, 8><<<grid, kBlock, lds, st>>>(a);\
         else gather_attn_kernel<NRV, 0><<<grid, kBlock, lds, st>>>(a);    \
@@ -502,7 +492,7 @@ hipError_t launch_move_rows(void* table, const int32_t* ids, int64_t n, int row_
     if (n <= 0) return hipSuccess;
     const int words = row_bytes / 4;
     const int64_t nblk = (n * words + kBlock - 1) / kBlock;
-    const int grid = (int)(nblk < 256 * 32 ? nblk : 256 * 32);
+    const int grid = (int)persistent_grid(nblk, 32);
     if (scatter) move_rows_kernel<true><<<grid, kBlock, 0, st>>>((uint32_t*)table, ids, n, words, (uint32_t*)rows);
     else move_rows_kernel<false><<<grid, kBlock, 0, st>>>((uint32_t*)table, ids, n, words, (uint32_t*)rows);
     return hipGetLastError();
@@ -523,7 +513,7 @@ __global__ __launch_bounds__(kBlock) void shard_space_ids_kernel(const T* __rest
 hipError_t launch_shard_space_ids(const void* ids, bool is64, int64_t n, int world, int n_local, void* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     const int64_t nblk = (n + kBlock - 1) / kBlock;
-    const int grid = (int)(nblk < 256 * 8 ? nblk : 256 * 8);
+    const int grid = (int)persistent_grid(nblk, 8);
     if (is64) shard_space_ids_kernel<int64_t><<<grid, kBlock, 0, st>>>((const int64_t*)ids, n, world, n_local, (int64_t*)out);
     else shard_space_ids_kernel<int32_t><<<grid, kBlock, 0, st>>>((const int32_t*)ids, n, world, n_local, (int32_t*)out);
     return hipGetLastError();

@@ -246,15 +246,13 @@ __global__ __launch_bounds__(kBlock) void mix_urv_kernel(const float* __restrict
 hipError_t launch_mix_urv(const float* neigh, const float* rel, const float* user, const float* logits, int64_t nodes, int N, int K,
                           int D, float* out, float* probs, hipStream_t st) {
     const int64_t nblk = (nodes + 3) / 4;
-    const int64_t cap = 256 * 16;
-    mix_urv_kernel<<<(int)(nblk < cap ? nblk : cap), kBlock, 0, st>>>(neigh, rel, user, logits, nodes, N, K, D, out, probs);
+    mix_urv_kernel<<<(int)persistent_grid(nblk, 16), kBlock, 0, st>>>(neigh, rel, user, logits, nodes, N, K, D, out, probs);
     return hipGetLastError();
 }
 
 hipError_t launch_row_softmax(const float* x, int64_t rows, int n, float* out, hipStream_t st) {
     const int64_t nblk = (rows + 3) / 4;
-    const int64_t cap = 256 * 16;
-    row_softmax_kernel<<<(int)(nblk < cap ? nblk : cap), kBlock, 0, st>>>(x, rows, n, out);
+    row_softmax_kernel<<<(int)persistent_grid(nblk, 16), kBlock, 0, st>>>(x, rows, n, out);
     return hipGetLastError();
 }
 
@@ -272,8 +270,7 @@ hipError_t launch_key_addr(const KeyAddrArgs& a, int table_bf16, hipStream_t st)
     if (key_addr_stream_supported(a, table_bf16)) return launch_key_addr_stream(a, table_bf16, st);
     const int nj = key_addr_nj(a.Nm, a.D);
     const int64_t nblk = (a.B + 3) / 4;
-    const int64_t cap = 256 * 8;
-    const int grid = (int)(nblk < cap ? nblk : cap);
+    const int grid = (int)persistent_grid(nblk, 8);
     const bool own = nj <= (1 << a.lpr_log2);   // rows per lane <= lanes per row: one exp per lane
     const bool buf = !table_bf16 && a.table_bytes > 0 && a.table_bytes < (1ull << 32);
 #define MVIN_KA2(NJV, OWNV)                                                                        \

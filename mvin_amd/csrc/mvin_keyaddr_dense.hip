@@ -673,31 +673,18 @@ static hipError_t launch_kad(const KeyAddrGroupedArgs& a, int table_bf16, hipStr
     constexpr int kDW = ka_dense_waves(D);
     hipError_t e = hipSuccess;
     // persistent grid: as many workgroups as the CUs hold (registers, LDS and wave slots decide: 1 per CU at D >= 32)
-    auto grid_for = [&](const void* k) {
-        static thread_local const void* last_k = nullptr;      // the query is host-side arithmetic, but not free
-        static thread_local size_t last_lds = 0;
-        static thread_local int last_per_cu = 1;
-        if (k != last_k || L.total != last_lds) {
-            int per_cu = 1;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, kDW * 64, L.total) != hipSuccess || per_cu < 1) per_cu = 1;
-            last_k = k;
-            last_lds = L.total;
-            last_per_cu = per_cu;
-        }
-        const int cap = 256 * last_per_cu;
-        return a.nseg < cap ? a.nseg : cap;
-    };
+    auto grid_for = [&](auto k) { return (int)persistent_grid(a.nseg, workgroups_per_cu(k, kDW * 64, L.total, 1)); };
     if (table_bf16) {
         auto k = key_addr_dense_kernel<D, true, false, false>;
-        if (L.total > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
+        e = grant_lds(k, L.total);
         if (e != hipSuccess) return e;
-        k<<<grid_for(reinterpret_cast<const void*>(k)), kDW * 64, L.total, st>>>(a, L);
+        k<<<grid_for(k), kDW * 64, L.total, st>>>(a, L);
     } else {
         static const bool trace = getenv("MVIN_KA_TRACE") != nullptr;
         const bool dma = D == 64 && ka_dense_dma_applies(D, 0, a.P, a.Nm);
         auto k = dma ? ((D == 64 && trace) ? key_addr_dense_kernel<D, false, D == 64, D == 64> : key_addr_dense_kernel<D, false, false, D == 64>)
                      : ((D == 64 && trace) ? key_addr_dense_kernel<D, false, true, false> : key_addr_dense_kernel<D, false, false, false>);
-        if (L.total > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
+        e = grant_lds(k, L.total);
         if (e != hipSuccess) return e;
         KeyAddrGroupedArgs b = a;
         b.dbg = 0;
@@ -705,7 +692,7 @@ static hipError_t launch_kad(const KeyAddrGroupedArgs& a, int table_bf16, hipStr
             const char* tw = getenv("MVIN_KA_TRACE_WAVE");
             b.dbg = tw ? atoi(tw) % kDW : 0;
         }
-        k<<<grid_for(reinterpret_cast<const void*>(k)), kDW * 64, L.total, st>>>(b, L);
+        k<<<grid_for(k), kDW * 64, L.total, st>>>(b, L);
     }
     return hipGetLastError();
 }

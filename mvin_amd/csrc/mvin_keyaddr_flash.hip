@@ -559,16 +559,10 @@ static hipError_t launch_flash_n(const KaFlashArgs& a, const KaRecLayout& RL, bo
     }
     // per wave: two record-id buffers and the pair indices of a tile
     const size_t lds = prefetch ? (size_t)kFlashWaves * (2 * (1 + 2 * a.P) * RL.NmP + 32) * sizeof(int32_t) : 0;
-    static thread_local int per_cu[2][9] = {};               // (the prefetching form's LDS grows with the hop count)
-    int& pc = per_cu[has_set ? 1 : 0][a.P];
-    if (pc == 0) {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(k), kFlashWaves * 64, lds) != hipSuccess || v < 1) v = 2;
-        pc = v > 8 ? 8 : v;
-    }
+    const int pc = workgroups_per_cu(k, kFlashWaves * 64, lds, 2);      // (the prefetching form's LDS grows with the hop count)
     // persistent: every CU full; no more workgroups than slots' worth of waves
     const int64_t want = ((int64_t)a.nslots + kFlashWaves - 1) / kFlashWaves;
-    int grid = (int)(want < 256 * (int64_t)pc ? want : 256 * (int64_t)pc);
+    int grid = (int)persistent_grid(want, pc > 8 ? 8 : pc);
     if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
     k<<<grid, kFlashWaves * 64, lds, st>>>(a, RL);
     return hipGetLastError();

@@ -248,18 +248,14 @@ static hipError_t launch_kag(KeyAddrGroupedArgs a, int table_bf16, hipStream_t s
     a.NRL = nrl > 0 ? nrl : 1;
     const KaGroupedLds L = ka_grouped_layout(D, a.P, a.Nm, a.nR, a.NRL);
     const int per_cu = (int)((160 * 1024) / L.total) < 2 ? 1 : 2;
-    const int cap = 256 * per_cu;
-    const int grid = a.nseg < cap ? a.nseg : cap;
-    hipError_t e = hipSuccess;
+    const int grid = (int)persistent_grid(a.nseg, per_cu);
     if (table_bf16) {
         auto k = key_addr_grouped_kernel<D, true>;
-        if (L.total > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = grant_lds(k, L.total); e != hipSuccess) return e;
         k<<<grid, kGW * 64, L.total, st>>>(a, L);
     } else {
         auto k = key_addr_grouped_kernel<D, false>;
-        if (L.total > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = grant_lds(k, L.total); e != hipSuccess) return e;
         k<<<grid, kGW * 64, L.total, st>>>(a, L);
     }
     return hipGetLastError();

@@ -873,16 +873,14 @@ hipError_t launch_key_addr_static(const KeyAddrGroupedArgs& a, hipStream_t st) {
                       : key_addr_static_kernel<false, 0, 0, 0, true>)
                 : c3 ? (trace ? key_addr_static_kernel<true, 2, 64, 9> : key_addr_static_kernel<false, 2, 64, 9>)
                      : (trace ? key_addr_static_kernel<true, 0, 0, 0> : key_addr_static_kernel<false, 0, 0, 0>);
-    hipError_t e = hipSuccess;
-    if (L.total > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = grant_lds(k, L.total); e != hipSuccess) return e;
     KeyAddrGroupedArgs b = a;
     b.dbg = 0;
     if (trace) {
         const char* tw = getenv("MVIN_KA_TRACE_WAVE");
         b.dbg = tw ? atoi(tw) % kSW : 0;
     }
-    const int grid = a.nseg < 256 ? a.nseg : 256;            // persistent: one workgroup per CU
+    const int grid = (int)persistent_grid(a.nseg, 1);        // persistent: one workgroup per CU
     k<<<grid, kSW * 64, L.total, st>>>(b, RL, L);
     return hipGetLastError();
 }

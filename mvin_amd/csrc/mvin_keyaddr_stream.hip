@@ -299,8 +299,7 @@ bool key_addr_stream_supported(const KeyAddrArgs& a, int table_bf16) {
 template <int D, bool BF>
 static hipError_t launch_stream_nm(const KeyAddrArgs& a, hipStream_t st) {
     const int nmp = stream_nmp(a.Nm);
-    const int64_t cap = 256 * 16;
-    const int grid = (int)(a.B < cap ? a.B : cap);
+    const int grid = (int)persistent_grid(a.B, 16);
     constexpr int RB = D * (BF ? 2 : 4), RPI = 64 / (RB / 16);
     if (nmp == 16) {
         if constexpr (16 >= RPI) {

@@ -376,28 +376,15 @@ static hipError_t launch_kw(const KeyAddrGroupedArgs& a, int table_bf16, hipStre
     auto launch = [&](auto kernel) {
         // persistent grid: as many workgroups as the CUs hold (LDS decides: D = 16: 39 KB at nR = 9 -> 4 per CU = 16 waves,
         // 75 KB at nR = 39 -> 2; D = 32: one workgroup of 8 waves)
-        static thread_local const void* last_k = nullptr;
-        static thread_local size_t last_lds = 0;
-        static thread_local int last_per_cu = 1;
-        const void* k = reinterpret_cast<const void*>(kernel);
-        if (lds > 64 * 1024) {
-            err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (err != hipSuccess) return;
-        }
-        if (k != last_k || lds != last_lds) {
-            int per_cu = 1;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, NWV * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-            last_k = k;
-            last_lds = lds;
-            last_per_cu = per_cu;
-        }
+        err = grant_lds(kernel, lds);
+        if (err != hipSuccess) return;
+        const int held = workgroups_per_cu(kernel, NWV * 64, lds, 1);
         const int need = (a.nseg + NWV - 1) / NWV;
         static const int dbg = getenv("MVIN_KA_WAVE_DBG") ? atoi(getenv("MVIN_KA_WAVE_DBG")) : 0;      // measurement knobs
         KeyAddrGroupedArgs b = a;
         b.dbg = dbg;
-        const int per_cu = (dbg & 4) ? 1 : (dbg & 2) ? 2 : last_per_cu;
-        const int cap = 256 * (per_cu < last_per_cu ? per_cu : last_per_cu);
-        kernel<<<need < cap ? need : cap, NWV * 64, lds, st>>>(b);
+        const int per_cu = (dbg & 4) ? 1 : (dbg & 2) ? 2 : held;
+        kernel<<<(int)persistent_grid(need, per_cu < held ? per_cu : held), NWV * 64, lds, st>>>(b);
     };
     const bool hs = a.w != nullptr;
     const int nt = a.Nm <= 16 ? 1 : 4;

@@ -207,10 +207,8 @@ hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_
     if (grid > n_user) grid = n_user;
     const size_t lds = (size_t)((n_item + 31) >> 5) * sizeof(uint32_t);
     const auto kernel = alias_tab ? sample_negatives_kernel<true> : sample_negatives_kernel<false>;
-    if (lds > 32 * 1024) {      // above the default limit of dynamic LDS the size has to be granted to the kernel first
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    e = grant_lds(kernel, lds, 32 * 1024);
+    if (e != hipSuccess) return e;
     kernel<<<grid, block, lds, st>>>(excl_ptr, excl_ids, counts, out_ptr, n_user, n_item, reinterpret_cast<const uint2*>(alias_tab),
                                      mask_bits, seed, round, out, reinterpret_cast<unsigned long long*>(status));
     return hipGetLastError();

@@ -81,12 +81,8 @@ hipError_t launch_order_by_key(const int64_t* k64, const int32_t* k32, int64_t B
     int32_t* base = total + kOrdBuckets;
     hipError_t e = hipMemsetAsync(total, 0, (size_t)kOrdBuckets * sizeof(int32_t), st);
     if (e != hipSuccess) return e;
-    static thread_local bool attr = false;
-    if (!attr) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(order_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kOrdBuckets * 4);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    e = grant_lds(order_hist_kernel, kOrdBuckets * sizeof(int), 0);      // exactly 64 KB: this launcher has always granted it
+    if (e != hipSuccess) return e;
     order_hist_kernel<<<kOrdGrid, kOrdThreads, kOrdBuckets * sizeof(int), st>>>(k64, k32, B, total, base, rank);
     order_scan_kernel<<<1, kOrdThreads, 0, st>>>(total);
     order_scatter_kernel<<<kOrdGrid, kOrdThreads, 0, st>>>(k64, k32, B, total, base, rank, order);

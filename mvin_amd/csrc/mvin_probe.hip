@@ -64,8 +64,7 @@ __global__ __launch_bounds__(256) void gather_probe_l2_kernel(const void* __rest
 hipError_t launch_gather_probe_l2(const void* table, const int32_t* ids1, const int32_t* ids2, int64_t n_parents, int K,
                                   int D, int table_bf16, float* sums, hipStream_t st) {
     const int rb = D * (table_bf16 ? 2 : 4);
-    const int64_t cap = 256 * 8;                                 // 8 workgroups of 4 waves per CU
-    const int grid = (int)((n_parents + 3) / 4 < cap ? (n_parents + 3) / 4 : cap);
+    const int grid = (int)persistent_grid((n_parents + 3) / 4, 8);      // 8 workgroups of 4 waves per CU
 #define MVIN_PROBE(RBV, BFV) gather_probe_l2_kernel<RBV, BFV><<<grid, 256, 0, st>>>(table, ids1, ids2, n_parents, K, sums)
     if (table_bf16) {
         switch (rb) {

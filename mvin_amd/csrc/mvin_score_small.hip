@@ -1094,10 +1094,7 @@ int score_small_group(int D, int K, int P, int Nm, int nR, int has_hset, int64_t
 template <int D, int NMT, bool DBG>
 static hipError_t launch_small_d(const ScoreSmallArgs& a, const SmallLds& L, hipStream_t st) {
     auto k = score_small_kernel<D, NMT, DBG>;
-    if (L.total > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = grant_lds(k, L.total); e != hipSuccess) return e;
     const int64_t grid = (a.B + a.G - 1) / a.G;
     k<<<(int)grid, D * 4, (size_t)L.total, st>>>(a, L);
     return hipGetLastError();

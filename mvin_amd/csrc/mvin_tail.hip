@@ -362,8 +362,7 @@ __global__ __launch_bounds__(256) void l2_tail_fold_kernel(TailFoldArgs a) {
 hipError_t launch_l2_tail_fold(const TailFoldArgs& a, hipStream_t st) {
     const size_t lds = (size_t)(4 * 32 * 64 + 4 * 32) * 4;
     const int64_t ntiles = (a.B + 31) / 32;
-    const int64_t cap = 256 * 4;
-    l2_tail_fold_kernel<<<(int)(ntiles < cap ? ntiles : cap), 256, lds, st>>>(a);
+    l2_tail_fold_kernel<<<(int)persistent_grid(ntiles, 4), 256, lds, st>>>(a);
     return hipGetLastError();
 }
 
@@ -374,8 +373,7 @@ static hipError_t launch_tail_d(const TailArgs& a, hipStream_t st) {
     constexpr int NT = D / 16;
     const size_t lds = (size_t)(4 * 32 * (D == 64 ? D : D + 4) + NT * 32) * 4;
     const int64_t ntiles = (a.B + 31) / 32;
-    const int64_t cap = 256 * (D == 64 ? 4 : 8);
-    l2_tail_kernel<D><<<(int)(ntiles < cap ? ntiles : cap), NT * 64, lds, st>>>(a);
+    l2_tail_kernel<D><<<(int)persistent_grid(ntiles, D == 64 ? 4 : 8), NT * 64, lds, st>>>(a);
     return hipGetLastError();
 }
 

@@ -245,12 +245,7 @@ bool l2_tail_flash_applies(const TailArgs& a, int D) {
 
 hipError_t launch_l2_tail_flash(const TailArgs& a, hipStream_t st) {
     const size_t lds = (size_t)6 * 64 * 64 * sizeof(float);
-    static thread_local bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(l2_tail_flash_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    if (hipError_t e = grant_lds(l2_tail_flash_kernel, lds); e != hipSuccess) return e;      // 96 KB
     TailArgs b = a;
     {
         static const char* dbg = getenv("MVIN_TAIL_DBG");
@@ -258,7 +253,7 @@ hipError_t launch_l2_tail_flash(const TailArgs& a, hipStream_t st) {
     }
     const int64_t ntiles = (a.B + 16 * kTfRT - 1) / (16 * kTfRT);
     const int64_t want = (ntiles + kTfWaves - 1) / kTfWaves;
-    const int grid = (int)(want < 256 ? want : 256);
+    const int grid = (int)persistent_grid(want, 1);
     l2_tail_flash_kernel<<<grid, kTfWaves * 64, lds, st>>>(b);
     return hipGetLastError();
 }
