@@ -1080,6 +1080,55 @@ MVIN_API int mvin_explain_paths(const float* imp0, const float* imp1, const int3
                                 int64_t* out_mass /* [B,top] */, int32_t* out_slot /* [B,top] */, int32_t* out_distinct /* [B] */,
                                 int64_t* out_total /* [B] */, int64_t* rel_mass /* [2,n_relation] or NULL */, void* stream);
 
+/* ---- explaining the USER side of a score: the merged, ranked ripple-set memories of every pair, with signed contributions --
+ * mvin_explain_paths covers the item side.  A pair's user vector is read out of the user's ripple-set memories (h, r, t) by
+ * attention (MVIN._key_addressing, model.py:161-240; mvin_key_addressing_users_fwd above), and the score is ADDITIVE over them.
+ * With v' the pair's final item embedding, W [n_o*D, D] / bias [D] the user MLP, n_o = P + (w_h != NULL) blocks
+ * [ h-set | hop 0 | .. | hop P-1 ] and g = W . v' ([n_o*D], block c of it g_c):
+ *     score = user_o . v' = bias . v' + sum_c sum_m p[c,m] * (x[c,m] . g_c)
+ * p[c,m] the softmax probability of memory m in block c and x[c,m] the row the block sums (E[h] in the h-set block, E[t] in a hop
+ * block).  This entry point recomputes those reads for a small batch and keeps what the headline kernels drop.
+ * INPUTS: entity_emb [n_entity, D] f32; V [B, nR, D] f32 with V[b,r,:] = E[item_b] . R_KGE[r] (NULL when P == 0); w_h [D] (NULL:
+ * no h-set block); uts [n_user, max(1,P), 3, Nm] int32 (h | r | t per hop); users int64 [B]; G [B, n_o*D] f32 = g per pair;
+ * mlp_bias [D]; item_final [B, D].  One task is one (pair b, block c); memory m is slot m of the block's lists.
+ * IDS: h, r, t = uts[clamp(users[b]), hop, 0 / 1 / 2, m], hop = 0 for the h-set block.  For READS entity ids are clamped into
+ * [0, n_entity), relation ids into [0, nR) and user ids into [0, n_user), as mvin_key_addressing_users_fwd clamps them; the ids
+ * REPORTED and COMPARED are the raw stored ones.
+ * LOGIT: h-set block s_m = E[h_m] . w_h; hop block s_m = E[h_m] . V[b, r_m, :].  PROBABILITY: p_m = the float32 max-subtracted
+ * softmax of s over the Nm memories.  VALUE a_m = x_m . g_c and CONTRIBUTION c_m = p_m * a_m, both float32.
+ * MASS: the int64 floor(double(clean(p_m)) * 2^40), clean as for mvin_explain_paths (NaN, +-inf and anything <= 0 become 0,
+ * anything above 1 becomes 1): exact in double, one number on every host and device.
+ * MERGING: the ripple-set sampler draws with replacement, so a user with a short history carries the same triple in many slots.
+ * The key is h in the h-set block and (h, r, t) in a hop block; slots with equal keys are ONE memory: its mass the integer sum
+ * of its slots' masses, its slot the lowest of them, its contribution the float32 sum of its slots' c_m taken in ASCENDING SLOT
+ * ORDER starting from +0 (the order is part of the rule, so the number can be restated bit for bit).
+ * ORDER: per block, mass descending, then slot ascending.
+ * OUTPUTS per (pair, block), the `top` best memories first: out_mem [B, n_o, top, 3] int32 = (h, r, t), (h, -1, -1) in the h-set
+ * block; out_mass [B, n_o, top] int64; out_contrib [B, n_o, top] f32; out_slot [B, n_o, top] int32; rows past the number of
+ * distinct memories hold ids -1, mass 0, contribution 0 and slot -1.  out_distinct [B, n_o] int32; out_total [B, n_o] int64 = the
+ * sum of the block's masses; out_block [B, n_o] f32 = sum_m c_m in ascending slot order from +0 (the block's share of the logit);
+ * out_bias [B] f32 = mlp_bias . item_final[b].  out_block summed over c plus out_bias is the pair's logit up to float32 rounding.
+ * OPTIONAL (NULL: skipped): out_probs / out_slot_contrib [B, n_o, Nm] f32 = p_m / c_m per slot; rel_mass int64 [P, nR],
+ * ACCUMULATED with integer atomics (zero it first): rel_mass[hop][r] += the masses of hop block `hop`'s slots whose raw r_m == r;
+ * a raw relation id outside [0, nR) adds nothing (rel_mass only); the h-set block has no relation and adds nothing.
+ * Every output row is a pure function of its own pair's inputs: not of B, of other pairs, of the launch shape or of timing.
+ * Garbage ids move nothing out of range.  One wave per task, one memory per lane.
+ * LIMITS: 1 <= Nm <= mvin_explain_memories_max_nm() = 64; D a multiple of 4 in [4, 128]; 0 <= P <= 8 and n_o >= 1; 1 <= top <= Nm;
+ * 0 <= B and B*n_o*Nm < 2^31; n_entity >= 1, n_user >= 1, and nR >= 1 when P >= 1; with rel_mass P >= 1 and B*Nm <= 2^22 --
+ * cleaned probabilities are <= 1, so one call adds at most 2^62 to a bin whatever the inputs hold; sums across calls are the
+ * caller's business.  fp32 entity table only.
+ * Errors (nothing launched): -1 for a null required pointer (V with P >= 1 included); -2 for sizes out of range.  B == 0 launches
+ * nothing. */
+MVIN_API int mvin_explain_memories_max_nm(void);
+MVIN_API int mvin_explain_memories(const float* entity_emb, const float* V, const float* w_h, const int32_t* uts, const int64_t* users,
+                                   const float* G, const float* mlp_bias, const float* item_final, int64_t B, int P, int Nm, int D,
+                                   int nR, int n_entity, int n_user, int top, int32_t* out_mem /* [B,n_o,top,3] */,
+                                   int64_t* out_mass /* [B,n_o,top] */, float* out_contrib /* [B,n_o,top] */,
+                                   int32_t* out_slot /* [B,n_o,top] */, int32_t* out_distinct /* [B,n_o] */,
+                                   int64_t* out_total /* [B,n_o] */, float* out_block /* [B,n_o] */, float* out_bias /* [B] */,
+                                   float* out_probs /* [B,n_o,Nm] or NULL */, float* out_slot_contrib /* [B,n_o,Nm] or NULL */,
+                                   int64_t* rel_mass /* [P,nR] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

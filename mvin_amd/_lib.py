@@ -201,6 +201,8 @@ SIGNATURES = {
                                         C.c_uint64, C.c_void_p, _c_f32p, _c_f32p, C.c_void_p, C.c_void_p]),
     "mvin_explain_paths_max_k": (C.c_int, []),
     "mvin_explain_paths": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "mvin_explain_memories_max_nm": (C.c_int, []),
+    "mvin_explain_memories": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_int] * 7 + [C.c_void_p] * 12),
     "mvin_gather_attn_fwd_ex": (C.c_int, [_c_f32p, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p,
                                           _c_f32p, _c_f32p, _c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, _c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_int, C.c_void_p]),

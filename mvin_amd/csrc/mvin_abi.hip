@@ -1736,6 +1736,62 @@ int mvin_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0
                                                  out_slot, out_distinct, out_total, rel_mass, (hipStream_t)stream), who);
 }
 
+int mvin_explain_memories_max_nm(void) { return mvin::explain_memories_max_nm(); }
+
+int mvin_explain_memories(const float* entity_emb, const float* V, const float* w_h, const int32_t* uts, const int64_t* users,
+                          const float* G, const float* mlp_bias, const float* item_final, int64_t B, int P, int Nm, int D, int nR,
+                          int n_entity, int n_user, int top, int32_t* out_mem, int64_t* out_mass, float* out_contrib,
+                          int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, float* out_block, float* out_bias,
+                          float* out_probs, float* out_slot_contrib, int64_t* rel_mass, void* stream) {
+    const char* who = "mvin_explain_memories";
+    if (!entity_emb || !uts || !users || !G || !mlp_bias || !item_final || !out_mem || !out_mass || !out_contrib || !out_slot ||
+        !out_distinct || !out_total || !out_block || !out_bias)
+        return fail(-1, "%s: null pointer (entity_emb / uts / users / G / mlp_bias / item_final / a required output)", who);
+    if (P < 0 || P > 8) return fail(-2, "%s: P=%d (0..8)", who, P);
+    if (P >= 1 && !V) return fail(-1, "%s: null pointer (V with P=%d hop blocks)", who, P);
+    const int n_o = P + (w_h ? 1 : 0);
+    if (n_o < 1) return fail(-2, "%s: no block to explain (P=0 and no w_h)", who);
+    const int max_nm = mvin::explain_memories_max_nm();
+    if (Nm < 1 || Nm > max_nm) return fail(-2, "%s: Nm=%d (1..%d)", who, Nm, max_nm);
+    if (D < 4 || D > 128 || (D & 3) != 0) return fail(-2, "%s: D=%d (a multiple of 4, 4..128)", who, D);
+    if (top < 1 || top > Nm) return fail(-2, "%s: top=%d (1..Nm = %d)", who, top, Nm);
+    if (B < 0 || B * n_o * Nm >= (int64_t(1) << 31))
+        return fail(-2, "%s: B=%lld with n_o=%d Nm=%d (0 <= B, B*n_o*Nm < 2^31)", who, (long long)B, n_o, Nm);
+    if (n_entity < 1 || n_user < 1 || (P >= 1 && nR < 1))
+        return fail(-2, "%s: n_entity=%d n_user=%d nR=%d (each >= 1)", who, n_entity, n_user, nR);
+    if (rel_mass && (P < 1 || B * Nm > (int64_t(1) << 22)))
+        return fail(-2, "%s: rel_mass takes P >= 1 and B*Nm <= 2^22 per call, got P=%d B=%lld Nm=%d", who, P, (long long)B, Nm);
+    mvin::ExplainMemArgs a;
+    a.entity_emb = entity_emb;
+    a.V = V;
+    a.w_h = w_h;
+    a.uts = uts;
+    a.users = reinterpret_cast<const long long*>(users);
+    a.G = G;
+    a.mlp_bias = mlp_bias;
+    a.item_final = item_final;
+    a.B = B;
+    a.P = P;
+    a.Nm = Nm;
+    a.D = D;
+    a.nR = nR;
+    a.n_entity = n_entity;
+    a.n_user = n_user;
+    a.top = top;
+    a.out_mem = out_mem;
+    a.out_mass = reinterpret_cast<long long*>(out_mass);
+    a.out_contrib = out_contrib;
+    a.out_slot = out_slot;
+    a.out_distinct = out_distinct;
+    a.out_total = reinterpret_cast<long long*>(out_total);
+    a.out_block = out_block;
+    a.out_bias = out_bias;
+    a.out_probs = out_probs;
+    a.out_slot_contrib = out_slot_contrib;
+    a.rel_mass = reinterpret_cast<unsigned long long*>(rel_mass);
+    return hip_result(mvin::launch_explain_memories(a, (hipStream_t)stream), who);
+}
+
 // ---------------------------------------------------------------------------- training
 static int rank_head_impl(const char* who, const float* user_o, const float* item_emb, const float* valid, const float* offset,
                           int64_t n_groups, int G, int D, int mode, float scale, float* scores, float* dscore, float* du, float* di,

@@ -24,6 +24,7 @@
 // environment caps the grid (default and maximum 2048 workgroups); no output depends on it.
 #include <cstdlib>
 
+#include "mvin_explain_mass.h"
 #include "mvin_kernels.h"
 
 namespace mvin {
@@ -50,28 +51,6 @@ struct ExplainArgs {
     long long* out_total;
     unsigned long long* rel_mass;
 };
-
-// a cleaned weight as (M, E): value M * 2^(E - 150); NaN, +-inf, negatives and zeros give M = 0, anything above 1 is 1
-__device__ __forceinline__ void explain_weight(unsigned bits, unsigned& M, int& E) {
-    const unsigned e = (bits >> 23) & 0xFFu, m = bits & 0x7FFFFFu;
-    M = 0u;
-    E = 1;
-    if ((bits >> 31) != 0u || e == 0xFFu) return;
-    if (e >= 127u) {                                           // >= 1.0
-        M = 1u << 23;
-        E = 127;
-    } else if (e == 0u) {
-        M = m;                                                 // denormal (or +0)
-    } else {
-        M = m | (1u << 23);
-        E = (int)e;
-    }
-}
-
-__device__ __forceinline__ unsigned long long explain_mass1(unsigned M, int E) {      // floor(w * 2^40)
-    const int sh = 110 - E;                                    // E <= 127: a left shift of at most 17 bits of a 24-bit M
-    return sh >= 64 ? 0ull : (sh >= 0 ? ((unsigned long long)M >> sh) : ((unsigned long long)M << -sh));
-}
 
 __device__ __forceinline__ unsigned long long explain_mass2(unsigned M0, int E0, unsigned M1, int E1) {   // floor(w0 * w1 * 2^40)
     const int sh = 260 - E0 - E1;                              // >= 6

@@ -474,6 +474,31 @@ hipError_t launch_explain_paths(const float* imp0, const float* imp1, const int3
                                 const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths,
                                 int64_t* out_mass, int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, int64_t* rel_mass,
                                 hipStream_t st);
+struct ExplainMemArgs {                                       // merged, ranked ripple-set memories per pair and block (mvin_explain_mem.hip)
+    const float* entity_emb;                                  // [n_entity, D]
+    const float* V;                                           // [B, nR, D]; NULL when P == 0
+    const float* w_h;                                         // [D]; NULL: no h-set block
+    const int32_t* uts;                                       // [n_user, max(1,P), 3, Nm]
+    const long long* users;                                   // [B]
+    const float* G;                                           // [B, n_o * D]
+    const float* mlp_bias;                                    // [D]
+    const float* item_final;                                  // [B, D]
+    int64_t B;
+    int P, Nm, D, nR, n_entity, n_user, top;
+    int32_t* out_mem;                                         // [B, n_o, top, 3]
+    long long* out_mass;
+    float* out_contrib;
+    int32_t* out_slot;
+    int32_t* out_distinct;
+    long long* out_total;
+    float* out_block;
+    float* out_bias;
+    float* out_probs;                                         // optional
+    float* out_slot_contrib;                                  // optional
+    unsigned long long* rel_mass;                             // optional, [P, nR]
+};
+int explain_memories_max_nm();
+hipError_t launch_explain_memories(const ExplainMemArgs& a, hipStream_t st);
 hipError_t launch_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key,
                                    int64_t n_groups, int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round,
                                    int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts,

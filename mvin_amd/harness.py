@@ -322,7 +322,7 @@ class DeviceFeeder(object):
           ``return_attention=True``: imp0 [B, 1, K] and imp1 [B, K, K] (None at depth 1), the tensors the paths were cut from.
         A model of depth 1 (h_hop = 1) takes one-hop mode: the entries are the K level-1 slots, the last two path columns -1.
         With more than two levels the paths are those of the FIRST TWO, exactly what ``eval_case_study`` exposes.  The user side
-        (key addressing) writes no attention outputs and is not explained.  One ``forward_users(..., want_probs=True)`` and one
+        (key addressing) is explained by ``explain_memories``.  One ``forward_users(..., want_probs=True)`` and one
         ``get_neighbors`` per chunk of at most ``max_pairs`` pairs (fewer where the kernel's bounds ask for it: B * K^2 <= 2^22
         with ``profile``).  Enqueues only: nothing is copied back."""
         import torch
@@ -372,6 +372,91 @@ class DeviceFeeder(object):
         if return_attention:
             res["imp0"] = torch.cat(att0) if att0 else torch.empty((0, 1, K), dtype=torch.float32, device=dev)
             res["imp1"] = (torch.cat(att1) if att1 else torch.empty((0, K, K), dtype=torch.float32, device=dev)) if two else None
+        return res
+
+    def explain_memories(self, users, items, top=10, profile=False, return_attention=False, max_pairs=4096):
+        """Which of the user's ripple-set memories (h, r, t) the score of every pair (users[i], items[i]) was read from, and how
+        much each gave: the user side of ``explain``.  The logit is additive over the memories -- with v' the pair's final item
+        embedding and g = user_mlp_matrix . v', score = user_mlp_bias . v' + sum over blocks c and memories m of
+        p[c,m] * (x[c,m] . g_c) -- so every memory has an attention mass AND a signed contribution to the logit, and the
+        contributions plus the bias term are the score.  ops.explain_memories recomputes the attention of these pairs
+        (include/mvin_hip.h states the rule): the sampler draws ripple sets with replacement, so slots with the same key (h in
+        the h-set block, (h, r, t) in a hop block) are ONE memory with the integer sum of their masses floor(p * 2^40), listed
+        per block mass descending, then lowest slot ascending.  Blocks are [h-set (with PS_O_ft) | hop 0 | .. | hop P-1], n_o of
+        them.  Returns a dict of device tensors:
+          scores [B] f32 (the raw logit of the forward pass) and scores_normalized [B] f32 (its sigmoid),
+          score_parts [B, n_o + 1] f32 = [block .. | bias]: each block's share of the logit and the bias term; their sum is the
+          logit evaluated another way, equal to ``scores`` up to float32 rounding,
+          mem [B, n_o, top, 3] int32 = (h, r, t), (h, -1, -1) in the h-set block, mass [B, n_o, top] int64, weight f64 = mass / 2^40,
+          contrib [B, n_o, top] f32, slot [B, n_o, top] int32, distinct [B, n_o] int32, total [B, n_o] int64, block [B, n_o] f32,
+          bias [B] f32 (rows past ``distinct``: ids -1, mass 0, contribution 0, slot -1);
+          ``profile=True``: rel_mass [P, n_relation] int64, the attention mass per relation and hop, summed over the chunks;
+          ``return_attention=True``: probs and slot_contrib [B, n_o, Nm] f32, per slot.
+        Masses are per-block softmaxes and rank inside a block only; contributions are comparable across blocks.  Refuses
+        ``HO_only`` models (their user vector is the plain user embedding: no memory enters the score), ripple sets of more
+        than ops.explain_memories_max_nm() memories and bf16 entity tables.  One ``forward_users`` call, the V and G projections
+        and one kernel launch per chunk of at most ``max_pairs`` pairs.  Enqueues only: nothing is copied back."""
+        import torch
+        from . import ops
+        m = self.model
+        a = m.args
+        if a.HO_only:
+            raise ValueError("explain_memories: an HO_only model's user vector is the plain user embedding; no ripple-set memory "
+                             "enters its score, so there is nothing to explain")
+        if m.table_dtype == "bf16":
+            raise ValueError("explain_memories: table_dtype='bf16' is not supported (mvin_explain_memories takes fp32 tables only)")
+        P, Nm, D, nR = m.p_hop, m.n_memory, m.dim, m.n_relation
+        has_set = bool(a.PS_O_ft)
+        n_o = P + (1 if has_set else 0)
+        top, max_pairs = int(top), int(max_pairs)
+        if Nm > ops.explain_memories_max_nm():
+            raise ValueError(f"explain_memories: n_memory={Nm} is beyond mvin_explain_memories' {ops.explain_memories_max_nm()}")
+        if n_o < 1:
+            raise ValueError("explain_memories: the model reads no ripple set (p_hop = 0 without PS_O_ft)")
+        if max_pairs < 1 or not 1 <= top <= Nm:
+            raise ValueError(f"explain_memories: max_pairs={max_pairs}, top={top} (1 <= top <= {Nm} memories per block)")
+        dev = m.device
+        u, it = _dev_ids(users, dev), _dev_ids(items, dev)
+        if u.shape[0] != it.shape[0]:
+            raise ValueError(f"explain_memories: {u.shape[0]} users for {it.shape[0]} items")
+        B = u.shape[0]
+        chunk = max(1, min(max_pairs, (ops.EXPLAIN_MEM_PROFILE_SLOTS if profile else (1 << 31) - 1) // (Nm * n_o)))
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        res = dict(scores=torch.empty((B,), dtype=f32, device=dev), scores_normalized=torch.empty((B,), dtype=f32, device=dev),
+                   score_parts=torch.empty((B, n_o + 1), dtype=f32, device=dev),
+                   mem=torch.empty((B, n_o, top, 3), dtype=i32, device=dev), mass=torch.empty((B, n_o, top), dtype=i64, device=dev),
+                   contrib=torch.empty((B, n_o, top), dtype=f32, device=dev), slot=torch.empty((B, n_o, top), dtype=i32, device=dev),
+                   distinct=torch.empty((B, n_o), dtype=i32, device=dev), total=torch.empty((B, n_o), dtype=i64, device=dev),
+                   block=torch.empty((B, n_o), dtype=f32, device=dev), bias=torch.empty((B,), dtype=f32, device=dev))
+        if return_attention:
+            res["probs"] = torch.empty((B, n_o, Nm), dtype=f32, device=dev)
+            res["slot_contrib"] = torch.empty((B, n_o, Nm), dtype=f32, device=dev)
+        if profile:
+            res["rel_mass"] = torch.zeros((P, nR), dtype=i64, device=dev)
+        kernel_out = ops.EXPLAIN_MEM_OUT + (("probs", "slot_contrib") if return_attention else ())
+        w_h = m.h_emb_item_mlp_matrix.view(-1) if has_set else None
+        Wt = m.user_mlp_matrix.t().contiguous()                  # [D, n_o * D]: G = v' . W^T (the transpose is plumbing)
+        E = m.entity_emb_matrix
+        for lo in range(0, B, chunk):
+            hi = min(B, lo + chunk)
+            out = m.forward_users(u[lo:hi], it[lo:hi], self.uts)
+            v = out.item_embeddings.contiguous()
+            V = None
+            if P > 0:                                            # exactly as MVIN._key_addressing builds it
+                V = torch.empty((hi - lo, nR, D), dtype=f32, device=dev)
+                ops.linear([E], m.relation_emb_KGE_matrix, D, ids=[it[lo:hi]], rows=hi - lo, out=V, ldo=nR * D, nz=nR,
+                           w_zstride=D * D, out_zstride=D)
+            G = ops.linear([v], Wt, n_o * D)
+            part = torch.zeros((P, nR), dtype=i64, device=dev) if profile else None
+            ops.explain_memories(E, V, w_h, self.uts, u[lo:hi], G, m.user_mlp_bias, v, P, top, rel_mass=part,
+                                 want_slots=return_attention, out={k: res[k][lo:hi] for k in kernel_out})
+            res["scores"][lo:hi] = out.scores
+            res["scores_normalized"][lo:hi] = out.scores_normalized
+            if profile:
+                res["rel_mass"] += part
+        res["score_parts"][:, :n_o] = res["block"]
+        res["score_parts"][:, n_o] = res["bias"]
+        res["weight"] = res["mass"].to(torch.float64) / ops.EXPLAIN_SCALE
         return res
 
 
@@ -1618,6 +1703,70 @@ def relation_profile(feeder, data, batch_size):
     ``share`` = a row of ``mass`` over its sum (zeros where the sum is 0)."""
     data = np.asarray(data)
     res = feeder.explain(data[:, 0], data[:, 1], top=1, profile=True, max_pairs=int(batch_size))
+    mass = res["rel_mass"].cpu().numpy()
+    tot = mass.sum(axis=1, keepdims=True)
+    share = np.divide(mass.astype(np.float64), tot, out=np.zeros(mass.shape, np.float64), where=tot > 0)
+    return dict(mass=mass, share=share, n_pairs=int(data.shape[0]))
+
+
+def explain_user_memories(feeder, users, items, top, entity_names=None, relation_names=None):
+    """``DeviceFeeder.explain_memories`` as plain Python records for printing, shaped like ``explain_pairs``: one dict per pair
+    with ``user``, ``item``, ``item_name``, ``score`` (the raw logit), ``score_normalized`` (its sigmoid), ``bias`` (the bias
+    term of the logit) and ``blocks``, one dict per read of the user's ripple sets: ``block`` ("h_set", "hop0", ...),
+    ``contribution`` (the block's share of the logit), ``distinct``, ``total_weight`` and ``memories``, the up to ``top``
+    heaviest distinct memories, heaviest first: dicts with ``block``, ``h`` / ``r`` / ``t`` (ids; r and t None in the h-set
+    block), ``h_name`` / ``r_name`` / ``t_name`` (through the lookup ``explain_pairs`` uses), ``weight`` (mass / 2^40),
+    ``contribution`` (signed, in logit units), ``share`` (contribution / score; 0 where the score is 0), ``mass`` and ``slot``.
+    Everything comes back in ONE copy."""
+    import torch
+    res = feeder.explain_memories(users, items, top=top)
+    B, n_o, top = res["mass"].shape
+    dev = res["mass"].device
+    bits = lambda t: t.reshape(B, -1).contiguous().view(torch.int32).long()              # f32 -> its bits, exactly
+    packed = torch.cat([res["mem"].reshape(B, n_o * top * 3).long(), res["mass"].reshape(B, -1), res["slot"].reshape(B, -1).long(),
+                        bits(res["contrib"]), res["distinct"].long(), res["total"], bits(res["score_parts"]), bits(res["scores"]),
+                        bits(res["scores_normalized"]), _dev_ids(users, dev)[:, None], _dev_ids(items, dev)[:, None]],
+                       dim=1).cpu().numpy()
+    f32 = lambda x: np.asarray(x, np.int64).astype(np.int32).view(np.float32)
+    ent_tab = entity_names if entity_names is not None else {}
+    rel_tab = relation_names if relation_names is not None else {}
+    has_set = bool(feeder.model.args.PS_O_ft)
+    names = (["h_set"] if has_set else []) + [f"hop{i}" for i in range(n_o - (1 if has_set else 0))]
+    scale = float(1 << 40)
+    n = n_o * top
+    records = []
+    for row in packed:
+        mem, mass, slot, contrib, distinct, total, parts, tail = np.split(row, np.cumsum([3 * n, n, n, n, n_o, n_o, n_o + 1]))
+        mem, mass, slot, contrib = mem.reshape(n_o, top, 3), mass.reshape(n_o, top), slot.reshape(n_o, top), f32(contrib).reshape(n_o, top)
+        parts = f32(parts)
+        score, sig = (float(x) for x in f32(tail[:2]))
+        user, item = int(tail[2]), int(tail[3])
+        blocks = []
+        for c in range(n_o):
+            listed = []
+            for p in range(min(top, int(distinct[c]))):
+                h, r, t = (int(x) for x in mem[c, p])
+                hop = names[c] != "h_set"
+                listed.append(dict(block=names[c], h=h, r=r if hop else None, t=t if hop else None,
+                                   h_name=_names([h], ent_tab)[0], r_name=_names([r], rel_tab)[0] if hop else None,
+                                   t_name=_names([t], ent_tab)[0] if hop else None, weight=int(mass[c, p]) / scale,
+                                   contribution=float(contrib[c, p]), share=float(contrib[c, p]) / score if score else 0.0,
+                                   mass=int(mass[c, p]), slot=int(slot[c, p])))
+            blocks.append(dict(block=names[c], contribution=float(parts[c]), distinct=int(distinct[c]),
+                               total_weight=int(total[c]) / scale, memories=listed))
+        records.append(dict(user=user, item=item, item_name=_names([item], ent_tab)[0], score=score, score_normalized=sig,
+                            bias=float(parts[n_o]), blocks=blocks))
+    return records
+
+
+def memory_relation_profile(feeder, data, batch_size):
+    """The share of ripple-set attention mass per relation and hop over a split, mirroring ``relation_profile``: ``data``
+    [n, >= 2] rows of (user, item, ...), explained in batches of ``batch_size`` pairs
+    (``DeviceFeeder.explain_memories(..., profile=True)``), the integer masses summed over the batches.  Returns ``dict(mass
+    int64 [P, n_relation], share float64 [P, n_relation], n_pairs)`` on the host: row i the memories of hop i; ``share`` = a
+    row of ``mass`` over its sum (zeros where the sum is 0).  The h-set read has no relation and is not part of it."""
+    data = np.asarray(data)
+    res = feeder.explain_memories(data[:, 0], data[:, 1], top=1, profile=True, max_pairs=int(batch_size))
     mass = res["rel_mass"].cpu().numpy()
     tot = mass.sum(axis=1, keepdims=True)
     share = np.divide(mass.astype(np.float64), tot, out=np.zeros(mass.shape, np.float64), where=tot > 0)

@@ -1524,6 +1524,79 @@ def explain_paths(imp0, imp1, rels, ents, top, n_relation, rel_mass=None, out=No
     return paths, mass, slot, distinct, total
 
 
+EXPLAIN_MEM_PROFILE_SLOTS = 1 << 22            # B * Nm of one call with rel_mass (mvin_explain_memories' bound)
+EXPLAIN_MEM_OUT = ("mem", "mass", "contrib", "slot", "distinct", "total", "block", "bias")
+
+
+def explain_memories_max_nm():
+    """mvin_explain_memories_max_nm: the largest ripple-set size Nm mvin_explain_memories takes."""
+    return int(_lib.load().mvin_explain_memories_max_nm())
+
+
+def explain_memories(entity_emb, V, w_h, uts, users, G, mlp_bias, item_final, P, top, rel_mass=None, want_slots=False, out=None):
+    """mvin_explain_memories: the merged, ranked ripple-set memories behind every pair's user vector, with their signed
+    contributions to the logit, in one launch (include/mvin_hip.h states the rule).  ``entity_emb`` f32 [n_entity, D]; ``V`` f32
+    [B, nR, D] as MVIN._key_addressing builds it (None when ``P`` == 0); ``w_h`` f32 with at least D entries (None: no h-set
+    block); ``uts`` int32 [n_user, max(1, P), 3, Nm]; ``users`` int64 [B]; ``G`` f32 [B, n_o * D] = user_mlp_matrix . v' per
+    pair; ``mlp_bias`` f32 [D]; ``item_final`` f32 [B, D].  n_o = P + (w_h is not None).  ``rel_mass``: int64 [P, nR] to
+    ACCUMULATE the per-relation masses of the hop blocks into (zero it first; B * Nm <= 2^22 per call).  Returns a dict of
+    ``mem`` int32 [B, n_o, top, 3], ``mass`` int64 / ``contrib`` f32 / ``slot`` int32 [B, n_o, top], ``distinct`` int32 /
+    ``total`` int64 / ``block`` f32 [B, n_o], ``bias`` f32 [B] and, with ``want_slots``, ``probs`` / ``slot_contrib`` f32
+    [B, n_o, Nm] (``out``: such a dict to write into).  Enqueues only."""
+    lib = _lib.load()
+    for t, name in ((entity_emb, "entity_emb"), (uts, "uts"), (users, "users"), (G, "G"), (mlp_bias, "mlp_bias"),
+                    (item_final, "item_final")):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if entity_emb.dtype != F32:
+        raise ValueError(f"explain_memories: the entity table is {entity_emb.dtype}; mvin_explain_memories takes fp32 tables only")
+    P, top = int(P), int(top)
+    if entity_emb.dim() != 2 or uts.dim() != 4 or uts.shape[1] != max(1, P) or uts.shape[2] != 3:
+        raise ValueError(f"entity_emb {tuple(entity_emb.shape)} / uts {tuple(uts.shape)}: expected [n_entity, D] and "
+                         f"[n_user, {max(1, P)}, 3, Nm]")
+    (n_entity, D), n_user, Nm, B = entity_emb.shape, uts.shape[0], uts.shape[3], users.numel()
+    n_o = P + (1 if w_h is not None else 0)
+    if not 0 <= P <= 8 or n_o < 1:
+        raise ValueError(f"P={P} with{'' if w_h is not None else 'out'} w_h: mvin_explain_memories takes 0 <= P <= 8 and at least one block")
+    if not 1 <= Nm <= explain_memories_max_nm() or not 1 <= top <= Nm or D % 4 or not 4 <= D <= 128:
+        raise ValueError(f"Nm={Nm} top={top} D={D}: mvin_explain_memories takes 1 <= Nm <= {explain_memories_max_nm()}, "
+                         f"1 <= top <= Nm and D a multiple of 4 in [4, 128]")
+    if n_entity < 1 or n_user < 1 or B * n_o * Nm >= 1 << 31:
+        raise ValueError(f"n_entity={n_entity} n_user={n_user} B={B}: expected non-empty tables and B * n_o * Nm < 2^31")
+    nR = V.shape[1] if V is not None else 0
+    if P > 0 and (V is None or V.dim() != 3 or tuple(V.shape) != (B, nR, D) or nR < 1):
+        raise ValueError(f"V: {None if V is None else tuple(V.shape)}, expected [{B}, nR, {D}] with P={P}")
+    if w_h is not None and w_h.numel() < D:
+        raise ValueError(f"w_h: {w_h.numel()} entries, expected at least D={D}")
+    if tuple(G.shape) != (B, n_o * D) or tuple(item_final.shape) != (B, D) or mlp_bias.numel() != D:
+        raise ValueError(f"G {tuple(G.shape)} / item_final {tuple(item_final.shape)} / mlp_bias {tuple(mlp_bias.shape)}: expected "
+                         f"[{B}, {n_o * D}], [{B}, {D}] and [{D}]")
+    if rel_mass is not None and (P < 1 or tuple(rel_mass.shape) != (P, nR) or B * Nm > EXPLAIN_MEM_PROFILE_SLOTS):
+        raise ValueError(f"rel_mass: {tuple(rel_mass.shape)}, expected ({P}, {nR}) with P >= 1 and B * Nm <= 2^22 per call")
+    _chk(entity_emb, F32, "entity_emb"), _chk(V, F32, "V"), _chk(w_h, F32, "w_h"), _chk(uts, I32, "uts")
+    _chk(users, torch.int64, "users"), _chk(G, F32, "G"), _chk(mlp_bias, F32, "mlp_bias"), _chk(item_final, F32, "item_final")
+    _chk(rel_mass, torch.int64, "rel_mass")         # after the shapes: those are refused the same with and without a GPU
+    dev = entity_emb.device
+    shapes = dict(mem=((B, n_o, top, 3), I32), mass=((B, n_o, top), torch.int64), contrib=((B, n_o, top), F32),
+                  slot=((B, n_o, top), I32), distinct=((B, n_o), I32), total=((B, n_o), torch.int64), block=((B, n_o), F32),
+                  bias=((B,), F32))
+    if want_slots:
+        shapes.update(probs=((B, n_o, Nm), F32), slot_contrib=((B, n_o, Nm), F32))
+    if out is None:
+        out = {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in shapes.items()}
+    for k, (s, d) in shapes.items():
+        if k not in out or tuple(out[k].shape) != s:
+            raise ValueError(f"out[{k!r}]: expected shape {s}")
+        _chk(out[k], d, f"out {k}")
+    if B > 0:                                   # an empty tensor has no address to pass
+        _lib.check(lib.mvin_explain_memories(_p(entity_emb), _p(V), _p(w_h), _p(uts), _p(users), _p(G), _p(mlp_bias), _p(item_final),
+                                             B, P, Nm, D, nR, n_entity, n_user, top, *[_p(out[k]) for k in EXPLAIN_MEM_OUT],
+                                             _p(out.get("probs") if want_slots else None),
+                                             _p(out.get("slot_contrib") if want_slots else None), _p(rel_mass), _stream()),
+                   "mvin_explain_memories")
+    return out
+
+
 def select_negatives(scores, items, valid, n_neg, shortlist, seed, round, group_key=None, counts=None, out_scores=False):
     """mvin_select_negatives: the hard negatives of a ranking objective out of a scored pool, in one launch (include/mvin_hip.h
     states the rule).  ``scores`` f32 / ``items`` int64 / ``valid`` f32 or None, all [n_groups, Gp]: slot 0 of a group is the
