@@ -319,7 +319,17 @@ __global__ __launch_bounds__(kAggWaves * 64, K == 64 ? 3 : 4) void gather_attn_l
 //     168 registers of three waves per SIMD), and with the (offset, weight) lists double-buffered (MODE 2: where the LDS allows it)
 //     quad it + 1's softmax weights and lists are computed UNDER quad it's row requests instead of between two quads' requests.
 // The arithmetic and the order of every sum are those of the per-batch order: a pair's G rows enter a01 / a23 in list order, in the same
-// rounds of four (up to the batch's longest list rounded up to eight) -- results are bit-identical.
+// rounds of four -- results are bit-identical.
+// QUADS BY LIST LENGTH (both orders).  A quad sums rounds of four up to its LONGEST list rounded up to four, for all four groups; a slot
+// behind a pair's own list is a load beyond the buffer (zeros, no traffic) with weight 0, which still takes its issue slot, its address
+// cycles, a place in the ring and its share of sum4.  So the batch's 16 pairs are sorted by list length (one 4-byte load per pair at the
+// batch's top: the count in its row's first relation word; 16 comparisons per lane behind the first chain's last weight request; two
+// ds_permute) and quad `it`, group g takes the pair at sorted position 4 it + g; pairs past B count as length 0 and come first, so the
+// quads in front of the first real pair are skipped.  Only WHICH pair a group works on changes -- its t | v rows, its out0 | Z2 rows and
+// its H0 row go by the pair's own index in the batch, the product chains see the same rows at the same places -- and adding a
+// zero-weighted zero row leaves an fp32 accumulator as it is, so every bit of the results is that of the batch-order quads.  On the
+// benchmark's batch (last-fm, fan-out 32, 6.61 real rows per pair) a pair's quad runs 9.43 row slots instead of 13.94.  A half round
+// is requested only where it lies below the quad's round count, so the lists' padding (kAggPad) is not read by this kernel any more.
 // TRACE: wave 0 of workgroup 0 stamps its first batches' stage boundaries (MVIN_FOLD_TRACE=1, scripts/trace_fold.py); the "... there"
 // stamps drain the wave's loads first, so the build's shares are meaningful, not its run time.
 constexpr int kFoldTraceBatches = 16, kFoldTraceSlots = 20;
@@ -396,6 +406,11 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
             else x0u = (unsigned)a.items[pr * a.pid_stride];
             x0u = x0u < a.max_id ? x0u : a.max_id;
             const int x0c = (int)x0u;
+            // the length of pair c's list (the distinct-slot count in its row's first relation word): wanted behind the first chain,
+            // where the batch's pairs are dealt to the quads
+            const unsigned len_word = __builtin_amdgcn_raw_buffer_load_b32(adjR, x0u * (unsigned)(K * 4), 0, 0);
+            const int ninv = 16 - (int)min((int64_t)16, a.B - p_base);      // pairs past B: the batch's last ones
+            const int it0 = (a.dbg & 8) ? 4 : ninv >> 2;                   // the first quad with a pair in it
             unsigned woff = ((unsigned)(4 * g) * (unsigned)D + (unsigned)c * 4u) * 4u;      // Wperm[4 g][c][0]
             unsigned boff = (unsigned)g * 16u;
             unsigned roff = (unsigned)pr * (unsigned)(D * 4) + (unsigned)g * 16u;     // floats [4 g, 4 g + 4) of row `pr` of a [B][64] array
@@ -453,16 +468,34 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                 unsigned ce[SPL], cr[SPL];
                 float4 s0;
             };
-            auto quad_load = [&](int it) -> Quad {       // group g's pair of step `it`: j = 4 it + g
+            // The batch's pairs are dealt to the quads BY LIST LENGTH: a quad runs its longest list's rounds for all four groups, so
+            // pairs of like length go together.  Sorted position s of the batch -- ascending (length, pair), pairs past B first with
+            // length 0 -- belongs to quad s / 4, group s % 4.  The keys are distinct, so a pair's rank (16 comparisons) is a permutation
+            // whatever the count words hold; lane c of every group pushes its pair's item id and index to lane `rank` of its group.
+            int xs = 0, pm = 0;                          // lane (g, s): the item id and the index of the pair at sorted position s
+            auto deal = [&]() {
+                int len = (int)(len_word >> 24);
+                len = len < 1 ? 1 : (len > K ? K : len);
+                const int key = cvalid ? (len << 4 | c) : c;
+                int rank = 0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) rank += __builtin_amdgcn_readlane(key, i) < key ? 1 : 0;
+                const int dst = ((lane & 48) + rank) << 2;
+                xs = __builtin_amdgcn_ds_permute(dst, x0c);
+                pm = __builtin_amdgcn_ds_permute(dst, c);
+            };
+            auto quad_load = [&](int it) -> Quad {       // group g's pair of step `it`: the one at sorted position 4 it + g
                 Quad qd;
-                const unsigned x0 = (unsigned)__builtin_amdgcn_ds_bpermute(((lane & 48) + 4 * it + g) << 2, x0c);
+                const unsigned x0 = (unsigned)__builtin_amdgcn_ds_bpermute(((lane & 48) + 4 * it + g) << 2, xs);
                 agg_load_slots<SPL>(adjE, adjR, (x0 * (unsigned)K + (unsigned)(SPL * c)) * 4u, qd.ce, qd.cr);
                 qd.s0 = agg_row4(aggS, x0 * (unsigned)(D * 4) + c16);
                 return qd;
             };
+            auto pair_of = [&](int it) { return __builtin_amdgcn_ds_bpermute(((lane & 48) + 4 * it + g) << 2, pm); };      // its index in the batch
             Quad q0, q1;                                 // (PIPE) the adjacency + H0 rows of the current quad and the one behind it
             auto late1 = [&](auto s_) {                  // (every id of the batch is a real one -- `pr` is clamped --, so neither load needs a test)
-                if constexpr (PIPE && decltype(s_)::value == 0) q0 = quad_load(0), q1 = quad_load(1);
+                if constexpr (PIPE && decltype(s_)::value == 0) deal();
+                if constexpr (PIPE && decltype(s_)::value == 1) q0 = quad_load(it0 & 3), q1 = quad_load(min(it0 + 1, 3));
             };
             f32x4 qm[4], qb[4];
             {
@@ -485,7 +518,7 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                     }
                 };
                 bias4(a.bm, qm);
-                if (a.dbg & 4) late1(std::integral_constant<int, 0>{});
+                if (a.dbg & 4) late1(std::integral_constant<int, 0>{}), late1(std::integral_constant<int, 1>{});
                 else
                     chain(std::integral_constant<int, 3>{}, [&](auto j_) { return decltype(j_)::value == 0 ? a.Wq : decltype(j_)::value == 1 ? a.Wv : a.Wqm; },
                           [&](auto) -> const f32x4 (&)[4] { return qb; },
@@ -500,7 +533,6 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             stamp(2, false);
 
-            const int nquad = (a.dbg & 8) ? 0 : (int)((min((int64_t)16, a.B - p_base) + 3) >> 2);
             auto issue = [&](const unsigned* lo, int k, float4 (&r)[4]) {
                 const uint4 o4 = *reinterpret_cast<const uint4*>(lo + k);
                 r[0] = agg_row4(aggG, o4.x + c16), r[1] = agg_row4(aggG, o4.y + c16);
@@ -516,10 +548,14 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                     a23 = __builtin_elementwise_fma(w2, f32x2{fmaxf(o23[0], 0.f), fmaxf(o23[1], 0.f)}, a23);
                 }
             };
+            auto zero4 = [&](float4 (&r)[4]) {           // (a buffer that one path leaves undefined costs ten spilled registers)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) r[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+            };
             // a quad's (offset, weight) lists from its adjacency row, into the list buffer `ob` words behind the first; returns the
-            // batch's longest list of this quad (wave-uniform)
+            // quad's longest list (wave-uniform)
             auto lists = [&](const Quad& qd, int it, int ob) -> int {
-                const bool pvalid = p_base + 4 * it + g < a.B;
+                const bool pvalid = 4 * it + g >= ninv;  // (the pairs past B hold the first sorted positions)
                 float wk[SPL];
                 agg_row_weights<SPL, FAST>(qd.cr, att1, sT, rmax, invK, wk);
                 int cc = (int)(qd.cr[0] >> 24);
@@ -536,58 +572,49 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 return (a.dbg & 1) ? 0 : __builtin_amdgcn_readfirstlane(agg_xor32_imax(agg_xor16_imax(cc)));
             };
+            // The rounds of four children that a quad sums: list entries below its longest list rounded up to FOUR.  Half round h (entries
+            // 4 h .. 4 h + 3) is requested only when 4 h < kr: a slot behind a pair's own list points beyond the buffer and costs no
+            // memory traffic, but it takes a load's issue slot and its share of sum4 -- so no half round past the longest list is
+            // requested, and the lists' padding behind the K-th entry is never read here.
             if constexpr (PIPE) {
-                int kmax = lists(q0, 0, 0);
-                for (int it = 0; it < nquad; ++it) {
+                int kmax = it0 < 4 ? lists(q0, it0, (it0 & 1) ? lb : 0) : 0;
+                for (int it = it0; it < 4; ++it) {
                     stamp(3 + 3 * it, false);
                     const int cur = (it & 1) ? lb : 0;
-                    float* rowT = sUV + (4 * it + g) * kAggUvLd + 4 * c;
+                    float* rowT = sUV + pair_of(it) * kAggUvLd + 4 * c;
                     const float4 vv = *reinterpret_cast<const float4*>(rowT + D);
                     const f32x2 v01 = {vv.x, vv.y}, v23 = {vv.z, vv.w};
                     f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-                    // the rounds of four children that are summed: list entries below the longest list rounded up to eight, as in the
-                    // per-batch order; the first three rounds are in flight at once
-                    const int kr = (kmax + 7) & ~7;
+                    const int kr = (kmax + 3) & ~3;      // (the first three half rounds are in flight at once)
                     float4 r0[4], r1[4], r2[4];
                     auto wts = [&](int k) { return *reinterpret_cast<const float4*>(sLw + cur + k); };      // (read where they are used: 16 registers less)
                     // the next quad's adjacency + H0 rows IN FRONT of this quad's G rows: loads return in order, so the lists below wait
-                    // for these alone (quad 1's came with quad 0's)
+                    // for these alone (the second quad's came with the first one's)
                     const float4 s0 = q0.s0;
-                    if (it > 0 && it + 1 < nquad) q1 = quad_load(it + 1);
+                    if (it > it0 && it + 1 < 4) q1 = quad_load(it + 1);
                     issue(sLo + cur, 0, r0);
-                    issue(sLo + cur, 4, r1);
-                    if (kr > 8) issue(sLo + cur, 8, r2);
+                    if (4 < kr) issue(sLo + cur, 4, r1);
+                    else zero4(r1);
+                    if (8 < kr) issue(sLo + cur, 8, r2);
                     stamp(4 + 3 * it, true);
                     __builtin_amdgcn_sched_barrier(0);
                     int kmax_n = 0;
-                    if (db && it + 1 < nquad) kmax_n = lists(q1, it + 1, lb - cur);      // under the row requests
+                    if (db && it + 1 < 4) kmax_n = lists(q1, it + 1, lb - cur);      // under the row requests
                     __builtin_amdgcn_sched_barrier(0);
-                    for (int k0 = 0; k0 < kr; k0 += 24) {      // rounds k0 .. k0 + 20 through the three buffers; kr is a multiple of 8
+                    for (int k0 = 0; k0 < kr; k0 += 12) {      // half rounds k0, k0 + 4, k0 + 8 through the three buffers, each refilled as it is summed
                         sum4(r0, wts(k0), v01, v23, a01, a23);
                         __builtin_amdgcn_sched_barrier(0);
                         if (k0 + 12 < kr) issue(sLo + cur, k0 + 12, r0);
                         __builtin_amdgcn_sched_barrier(0);
-                        sum4(r1, wts(k0 + 4), v01, v23, a01, a23);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (k0 + 8 < kr) {
+                        if (k0 + 4 < kr) {
+                            sum4(r1, wts(k0 + 4), v01, v23, a01, a23);
+                            __builtin_amdgcn_sched_barrier(0);
                             if (k0 + 16 < kr) issue(sLo + cur, k0 + 16, r1);
                             __builtin_amdgcn_sched_barrier(0);
-                            sum4(r2, wts(k0 + 8), v01, v23, a01, a23);
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (k0 + 16 < kr) issue(sLo + cur, k0 + 20, r2);
-                            __builtin_amdgcn_sched_barrier(0);
-                            sum4(r0, wts(k0 + 12), v01, v23, a01, a23);
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (k0 + 16 < kr) {
-                                if (k0 + 24 < kr) issue(sLo + cur, k0 + 24, r0);
+                            if (k0 + 8 < kr) {
+                                sum4(r2, wts(k0 + 8), v01, v23, a01, a23);
                                 __builtin_amdgcn_sched_barrier(0);
-                                sum4(r1, wts(k0 + 16), v01, v23, a01, a23);
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (k0 + 24 < kr) issue(sLo + cur, k0 + 28, r1);
-                                __builtin_amdgcn_sched_barrier(0);
-                                sum4(r2, wts(k0 + 20), v01, v23, a01, a23);
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (k0 + 32 < kr) issue(sLo + cur, k0 + 32, r2);
+                                if (k0 + 20 < kr) issue(sLo + cur, k0 + 20, r2);
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                         }
@@ -597,42 +624,47 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_kernel(Fold
                     const float4 o0 = make_float4(fmaxf(s0.x + tt.x, 0.f), fmaxf(s0.y + tt.y, 0.f), fmaxf(s0.z + tt.z, 0.f), fmaxf(s0.w + tt.w, 0.f));
                     *reinterpret_cast<float4*>(rowT) = o0;
                     *reinterpret_cast<float4*>(rowT + D) = make_float4(a01[0] + o0.x, a01[1] + o0.y, a23[0] + o0.z, a23[1] + o0.w);
-                    if (!db && it + 1 < nquad) kmax_n = lists(q1, it + 1, 0);            // (one list buffer: behind this quad's last read of it)
+                    if (!db && it + 1 < 4) kmax_n = lists(q1, it + 1, 0);                // (one list buffer: behind this quad's last read of it)
                     kmax = kmax_n;
                     q0 = q1;
                     stamp(5 + 3 * it, false);
                 }
             } else {
-                Quad nx = quad_load(0);
-                for (int it = 0; it < nquad; ++it) {
+                deal();
+                Quad nx = quad_load(it0 & 3);
+                for (int it = it0; it < 4; ++it) {
                     stamp(3 + 3 * it, false);
                     const Quad qd = nx;
-                    if (it + 1 < nquad) nx = quad_load(it + 1);
-                    float* rowT = sUV + (4 * it + g) * kAggUvLd + 4 * c;
+                    if (it + 1 < 4) nx = quad_load(it + 1);
+                    float* rowT = sUV + pair_of(it) * kAggUvLd + 4 * c;
                     const float4 tt = *reinterpret_cast<const float4*>(rowT);
                     const float4 vv = *reinterpret_cast<const float4*>(rowT + D);
-                    const int kmax = lists(qd, it, 0);
+                    const int kr = (lists(qd, it, 0) + 3) & ~3;
                     const f32x2 v01 = {vv.x, vv.y}, v23 = {vv.z, vv.w};
                     f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
                     float4 ra[4], rb[4];
                     float4 wa, wb;
                     auto wts = [&](int k) { return *reinterpret_cast<const float4*>(sLw + k); };
-                    // (half rounds of four children, one in flight while the other is summed; both are issued unconditionally: slots
-                    //  behind a pair's distinct count -- and the four list entries behind the K-th -- point beyond the buffer)
+                    // (half rounds of four children, one in flight while the other is summed)
                     issue(sLo, 0, ra), wa = wts(0);
                     if constexpr (TRACE) {
-                        issue(sLo, 4, rb), wb = wts(4);
+                        if (4 < kr) issue(sLo, 4, rb), wb = wts(4);
+                        else zero4(rb);
                         stamp(4 + 3 * it, true);
                     }
-                    for (int k0 = 0; k0 < kmax; k0 += 8) {
-                        if (!TRACE || k0 > 0) issue(sLo, k0 + 4, rb), wb = wts(k0 + 4);
+                    for (int k0 = 0; k0 < kr; k0 += 8) {
+                        const bool second = k0 + 4 < kr;
+                        if ((!TRACE || k0 > 0) && second) issue(sLo, k0 + 4, rb), wb = wts(k0 + 4);
+                        else if (!TRACE) zero4(rb);
                         __builtin_amdgcn_sched_barrier(0);
                         sum4(ra, wa, v01, v23, a01, a23);
                         __builtin_amdgcn_sched_barrier(0);
-                        issue(sLo, k0 + 8, ra), wa = wts(k0 + 8);
-                        __builtin_amdgcn_sched_barrier(0);
-                        sum4(rb, wb, v01, v23, a01, a23);
-                        __builtin_amdgcn_sched_barrier(0);
+                        if (second) {
+                            if (k0 + 8 < kr) issue(sLo, k0 + 8, ra), wa = wts(k0 + 8);
+                            __builtin_amdgcn_sched_barrier(0);
+                            sum4(rb, wb, v01, v23, a01, a23);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
                     }
                     // out0 = relu(H0[x] + t) ; Z2 = out0 + nagg1: this pair's two rows of the block, in place of t and v
                     const float4 o0 = make_float4(fmaxf(qd.s0.x + tt.x, 0.f), fmaxf(qd.s0.y + tt.y, 0.f), fmaxf(qd.s0.z + tt.z, 0.f),
