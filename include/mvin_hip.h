@@ -80,7 +80,11 @@ MVIN_API int mvin_rel_score(const float* relation_emb, const float* urh_weights,
  * relu((self + neighbors_agg) . weights + bias) of aggregators.py:108-116 when neighbors_agg
  * was produced by mvin_gather_attn_l2_fwd.
  * Covers: user-oriented projection (model.py:270-283), mix-hop combiner (:310-315),
- * user MLP (:232-236), the per-relation item projection of _key_addressing (:211-220). */
+ * user MLP (:232-236), the per-relation item projection of _key_addressing (:211-220).
+ * Limits (-2 before anything is launched): Dsrc % 4 == 0, 1 <= Dout <= 256, nsrc * Dsrc <= 4096, the fused score needs
+ * Dout <= Din + 4 (Din = nsrc * Dsrc, or Dsrc with sum_sources), and Din <= 1276 wherever the matrix-core kernel does
+ * not take the shape (it takes Dout in {16, 32, 64} with Din / Dout in {1, 2, 3, 4} and Dout = 128 with {1, 2}): the
+ * other kernel stages 32 rows of Din + 4 floats in LDS, 160 KB at most. */
 typedef struct {
     const float* src[MVIN_MAX_SRC];
     const int32_t* ids[MVIN_MAX_SRC];
@@ -103,8 +107,10 @@ typedef struct {
     float* score_out;          /* [rows] or NULL */
     float* sigmoid_out;        /* [rows] or NULL */
     int src_bf16;              /* bit s set: src[s] is a bf16 table (read as bf16, widened to fp32) */
-    int64_t src_rows;          /* rows of the gathered sources (those with ids[s] != NULL): ids are clamped to
-                                  [0, src_rows) like every device-resident id; 0 = unknown, no clamp */
+    int64_t src_rows;          /* rows of the gathered sources (those with ids[s] != NULL): an id outside
+                                  [0, src_rows) reads row src_rows - 1, the LAST row -- a negative id too (one
+                                  unsigned compare; mvin_expand_ids sends a negative item to row 0 instead);
+                                  0 = unknown, no clamp */
 } mvin_linear_args;
 MVIN_API int mvin_linear_fwd(const mvin_linear_args* args, void* stream);
 
@@ -590,7 +596,9 @@ MVIN_API int mvin_gather_mix_fwd(const void* table, const int32_t* adj_entity, c
  * backward / optimizer kernels.  Gradients are ACCUMULATED into caller-zeroed buffers. ------------ */
 
 /* mvin_gather_attn_fwd / mvin_agg_fwd with two extra optional outputs:
- * s_out [T,D] = (1/K) sum_k p_k child_k (before the projection), z_out [T,D] = self + neighbors_agg. */
+ * s_out [T,D] = (1/K) sum_k p_k child_k (before the projection), z_out [T,D] = self + neighbors_agg.
+ * Limits of all four (-2 before anything is launched): K <= 4096 and 256 * (D + 4) + 32 * K <= 160 KB of LDS, which
+ * is K <= 3040 at D = 256 and no further limit at D <= 124. */
 MVIN_API int mvin_gather_attn_fwd_ex(const void* table, const int32_t* adj_entity, const int32_t* adj_relation,
                             const int32_t* node_ids, const float* rel_score, const float* self_vec,
                             const float* Wc, const float* c_child, const float* Wagg, const float* bagg,

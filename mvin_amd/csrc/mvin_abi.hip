@@ -137,6 +137,9 @@ int mvin_linear_fwd(const mvin_linear_args* a, void* stream) {
     if (a->rowbias && a->rows_per_group < 1) return fail(-2, "mvin_linear_fwd: rows_per_group < 1");
     if (a->score_u && a->Dout > (a->sum_sources ? 1 : a->nsrc) * a->Dsrc + 4)
         return fail(-2, "mvin_linear_fwd: fused score needs Dout <= Din + 4");
+    if (mvin::linear_takes_valu(*a) && mvin::linear_valu_lds_bytes(*a) > mvin::kLdsLimit)
+        return fail(-2, "mvin_linear_fwd: Din=%d needs %zu bytes of LDS (limit %zu: Din <= 1276)",
+                    (a->sum_sources ? 1 : a->nsrc) * a->Dsrc, mvin::linear_valu_lds_bytes(*a), mvin::kLdsLimit);
     if (a->rows == 0) return 0;
     return hip_result(mvin::launch_linear(*a, (hipStream_t)stream), "mvin_linear_fwd");
 }
@@ -145,6 +148,9 @@ static int agg_common(mvin::GatherAttnArgs& g, int B, int N, int K, int D, const
     if (B <= 0 || N <= 0 || K <= 0) return fail(-2, "%s: bad sizes B=%d N=%d K=%d", who, B, N, K);
     if (bad_dim(D)) return fail(-2, "%s: D=%d (need %%4==0, 4..%d)", who, D, MVIN_MAX_DIM);
     if (K > 4096) return fail(-2, "%s: K=%d > 4096", who, K);
+    if (mvin::gather_attn_lds_bytes(D, K) > mvin::kLdsLimit)
+        return fail(-2, "%s: D=%d K=%d needs %zu bytes of LDS (limit %zu)", who, D, K, mvin::gather_attn_lds_bytes(D, K),
+                    mvin::kLdsLimit);
     if (!g.self_vec || !g.Wagg || !g.out) return fail(-1, "%s: null self_vec/Wagg/out", who);
     g.T = (int64_t)B * N;
     g.N = N;

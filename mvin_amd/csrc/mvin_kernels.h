@@ -354,6 +354,16 @@ hipError_t launch_expand(const int32_t* adj_e, const int32_t* adj_r, const int64
 hipError_t launch_rel_score(const float* rel, const float* urh_w, int nR, int D, float* t,
                             hipStream_t st);
 hipError_t launch_linear(const mvin_linear_args& a, hipStream_t st);
+// Dynamic LDS of the two tile kernels of mvin_kernels.hip, shared by their launchers and by the entry points' validation: a
+// shape above kLdsLimit is refused (-2) before anything is launched.
+constexpr size_t kLdsLimit = 160 * 1024;      // LDS of a gfx950 CU
+inline size_t linear_valu_lds_bytes(const mvin_linear_args& a) {     // linear_kernel: [kTM][Din + 4] floats
+    return (size_t)kTM * ((a.sum_sources ? 1 : a.nsrc) * a.Dsrc + 4) * sizeof(float);
+}
+inline size_t gather_attn_lds_bytes(int D, int K) {                 // gather_attn_kernel: sS, sZ [kTM][D + 4] floats + [4 waves][K] int2
+    return (size_t)2 * kTM * (D + 4) * sizeof(float) + (size_t)4 * K * sizeof(int2);
+}
+bool linear_takes_valu(const mvin_linear_args& a);                   // MVIN_LINEAR_VALU set, or a shape outside the MFMA set
 bool linear_mfma_supported(const mvin_linear_args& a);
 hipError_t launch_linear_mfma(const mvin_linear_args& a, hipStream_t st);
 hipError_t launch_gather_attn(const GatherAttnArgs& a, hipStream_t st);

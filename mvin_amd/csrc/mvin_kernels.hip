@@ -427,11 +427,15 @@ hipError_t launch_rel_score(const float* rel, const float* urh_w, int nR, int D,
     return hipGetLastError();
 }
 
-hipError_t launch_linear(const mvin_linear_args& a, hipStream_t st) {
+bool linear_takes_valu(const mvin_linear_args& a) {
     static const bool no_mfma = getenv("MVIN_LINEAR_VALU") != nullptr;
-    if (!no_mfma && linear_mfma_supported(a)) return launch_linear_mfma(a, st);
+    return no_mfma || !linear_mfma_supported(a);
+}
+
+hipError_t launch_linear(const mvin_linear_args& a, hipStream_t st) {
+    if (!linear_takes_valu(a)) return launch_linear_mfma(a, st);
     const int nr = nr_for(a.Dout);
-    const size_t lds = (size_t)kTM * ((a.sum_sources ? 1 : a.nsrc) * a.Dsrc + 4) * sizeof(float);
+    const size_t lds = linear_valu_lds_bytes(a);
     const int64_t ntiles = (a.rows + kTM - 1) / kTM;
     dim3 grid(grid_for(ntiles), a.nz > 0 ? a.nz : 1);
 #define CALL(NRV)                                                         \
@@ -448,7 +452,7 @@ hipError_t launch_linear(const mvin_linear_args& a, hipStream_t st) {
 hipError_t launch_gather_attn(const GatherAttnArgs& a0, hipStream_t st) {
     const int nr = nr_for(a0.D);
     GatherAttnArgs a = a0;
-    const size_t lds = (size_t)2 * kTM * (a.D + 4) * sizeof(float) + (size_t)4 * a.K * sizeof(int2);
+    const size_t lds = gather_attn_lds_bytes(a.D, a.K);
     a.tile_rows = (a.T + kTM - 1) / kTM < kNumCUs ? 8 : kTM;
     const int64_t ntiles = (a.T + a.tile_rows - 1) / a.tile_rows;
     dim3 grid(grid_for(ntiles));
@@ -469,6 +473,8 @@ hipError_t launch_gather_attn(const GatherAttnArgs& a0, hipStream_t st) {
 hipError_t launch_ripple(const RippleArgs& a, hipStream_t st) {
     const size_t lds = (size_t)4 * a.Nm * sizeof(float);
     const int64_t nblk = (a.B + 3) / 4;
+    hipError_t e = grant_lds(ripple_attn_kernel, lds);      // Nm > 4096 is above 64 KB
+    if (e != hipSuccess) return e;
     ripple_attn_kernel<<<grid_for(nblk), kBlock, lds, st>>>(a);
     return hipGetLastError();
 }

@@ -1374,8 +1374,9 @@ def _fill_linear_args(a, srcs, ids, Dout, rows, nz, sum_sources):
 
 def gather_attn_ex(table, adj_entity, adj_relation, node_ids, rel_score_t, self_vec, Wc, c_child, Wagg, bagg,
                    B, N, K, D):
-    """mvin_gather_attn_fwd_ex -> (out, probs | None, s_out, z_out)."""
+    """mvin_gather_attn_fwd_ex -> (out, probs | None, s_out, z_out).  ``table``: fp32 or bf16."""
     lib = _lib.load()
+    bf = _chk_table(table, "table")
     dev = table.device
     out = torch.empty((B, N, D), dtype=F32, device=dev)
     probs = torch.empty((B, N, K), dtype=F32, device=dev) if rel_score_t is not None else None
@@ -1383,21 +1384,22 @@ def gather_attn_ex(table, adj_entity, adj_relation, node_ids, rel_score_t, self_
     z_out = torch.empty((B * N, D), dtype=F32, device=dev)
     _lib.check(lib.mvin_gather_attn_fwd_ex(_p(table), _p(adj_entity), _p(adj_relation), _p(node_ids), _p(rel_score_t),
                                            _p(self_vec), _p(Wc), _p(c_child), _p(Wagg), _p(bagg), B, N, K, D,
-                                           table.shape[0], _p(out), _p(probs), _p(s_out), _p(z_out), 0, _stream()),
+                                           table.shape[0], _p(out), _p(probs), _p(s_out), _p(z_out), bf, _stream()),
                "mvin_gather_attn_fwd_ex")
     return out, probs, s_out, z_out
 
 
-def agg_ex(self_vec, neigh, rel_ids, rel_score_t, Wagg, bagg, B, N, K, D):
-    """mvin_agg_fwd_ex -> (out, probs | None, z_out)."""
+def agg_ex(self_vec, neigh, rel_ids, rel_score_t, Wagg, bagg, B, N, K, D, want_s=False):
+    """mvin_agg_fwd_ex -> (out, probs | None, z_out), or with ``want_s`` (out, probs | None, s_out, z_out)."""
     lib = _lib.load()
     dev = self_vec.device
     out = torch.empty((B, N, D), dtype=F32, device=dev)
     probs = torch.empty((B, N, K), dtype=F32, device=dev) if rel_score_t is not None else None
+    s_out = torch.empty((B * N, D), dtype=F32, device=dev) if want_s else None
     z_out = torch.empty((B * N, D), dtype=F32, device=dev)
     _lib.check(lib.mvin_agg_fwd_ex(_p(self_vec), _p(neigh), _p(rel_ids), _p(rel_score_t), _p(Wagg), _p(bagg), B, N, K,
-                                   D, _p(out), _p(probs), None, _p(z_out), _stream()), "mvin_agg_fwd_ex")
-    return out, probs, z_out
+                                   D, _p(out), _p(probs), _p(s_out), _p(z_out), _stream()), "mvin_agg_fwd_ex")
+    return (out, probs, s_out, z_out) if want_s else (out, probs, z_out)
 
 
 def eltwise(mode, n, x, y=None, z=None, w=None, accum=None, alpha=1.0, beta=0.0, beta1=0.0, beta2=0.0, eps=0.0,

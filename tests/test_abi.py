@@ -75,6 +75,44 @@ def test_argument_errors_are_reported_not_thrown(hip_lib):
         _lib.check(rc, "mvin_ripple_attn_fwd")
 
 
+def test_tile_kernels_refuse_shapes_above_the_lds_limit(hip_lib):
+    """linear_kernel stages 32 rows of Din + 4 floats, gather_attn_kernel 2 * 32 * (D + 4) floats + 32 * K bytes: above 160 KB
+    the entry points answer -2 and launch nothing.  Nothing is launched for the accepted shapes either: the linear ones have
+    no rows (0 after validation), the aggregator ones a null self_vec (-1, the check after the sizes)."""
+    from mvin_amd import _lib
+    one = C.c_void_p(16)
+
+    def lin(nsrc, Dsrc, Dout, sum_sources=0):
+        a = _lib.LinearArgs()
+        a.nsrc, a.Dsrc, a.Dout, a.rows, a.ldo, a.sum_sources = nsrc, Dsrc, Dout, 0, Dout, sum_sources
+        for s in range(nsrc):
+            a.src[s] = 16
+        a.W = a.out = 16
+        return hip_lib.mvin_linear_fwd(C.byref(a), None)
+
+    assert 32 * (1276 + 4) * 4 == 160 * 1024
+    assert lin(1, 1276, 8) == 0 and lin(4, 316, 256) == 0 and lin(3, 1276, 8, sum_sources=1) == 0       # Din = 1276, 1264, 1276
+    assert lin(1, 1280, 8) == -2 and b"LDS" in hip_lib.mvin_last_error() and b"1280" in hip_lib.mvin_last_error()
+    assert lin(4, 320, 256) == -2 and lin(8, 512, 1) == -2
+    assert lin(8, 512, 8, sum_sources=1) == 0                       # summed sources: Din = Dsrc
+    assert lin(3, 1280, 8, sum_sources=1) == -2
+    assert lin(4, 64, 64) == 0 and lin(2, 128, 128) == 0            # the matrix-core kernel's widest inputs: no such limit
+
+    def aggs(D, K):
+        g = hip_lib.mvin_gather_attn_fwd_ex(one, one, one, one, None, None, None, None, one, None, 2, 2, K, D, 10, one, None, None,
+                                            None, 0, None)
+        d = hip_lib.mvin_agg_fwd_ex(None, one, None, None, one, None, 2, 2, K, D, one, None, None, None, None)
+        assert g == d, (g, d)
+        return g
+
+    assert 2 * 32 * (256 + 4) * 4 + 32 * 3040 == 160 * 1024
+    assert aggs(256, 3040) == -1 and b"null" in hip_lib.mvin_last_error()
+    assert aggs(256, 3041) == -2 and b"LDS" in hip_lib.mvin_last_error()
+    assert aggs(256, 4096) == -2 and aggs(128, 4065) == -2
+    assert aggs(128, 4064) == -1 and aggs(124, 4096) == -1 and aggs(4, 4096) == -1
+    assert aggs(4, 4097) == -2 and b"4096" in hip_lib.mvin_last_error()
+
+
 def test_round6_entry_points_validate_before_launching(hip_lib):
     """The aggregates / folded-tail entry points (ABI 12): sizes and shape support are plain host arithmetic, null pointers and
     unsupported shapes come back as error codes before anything is launched."""
