@@ -459,7 +459,10 @@ MVIN_API int mvin_mix_neighbor_vectors_fwd(const float* neighbor_vectors, const 
  *   item_emb = [ev0 | out0 | out2] Wmix + bmix                                        model.py:310-315
  *   scores = sum_d user_o * item_emb ; sig = sigmoid(scores)                          model.py:158-159
  * nagg0 / nagg1 [B, D]: the outputs of mvin_gather_attn_l2_fwd with parents_per_pair = 1.  D in {16, 32, 64}
- * (-3 otherwise: use mvin_linear_fwd per stage).  item_emb and sig may be NULL. */
+ * (-3 otherwise: use mvin_linear_fwd per stage).  item_emb and sig may be NULL.
+ * Item ids: exactly one of items_i64 / items_i32.  An id is read WHOLE, as an unsigned 64-bit number (an int32 id sign-extended
+ * first), and clamped to n_entity - 1: negative ids and ids >= 2^32 both read the table's LAST row, in every kernel behind this
+ * entry point (the folded entry points above read the low 32-bit word instead). */
 MVIN_API int mvin_l2_tail_fwd(const void* entity_emb, const int64_t* items_i64, const int32_t* items_i32, const float* q,
                      const float* user_o, const float* nagg0, const float* nagg1, const float* W0, const float* b0,
                      const float* A0, const float* a0, const float* A1, const float* a1, const float* Wmix,

@@ -289,8 +289,9 @@ __global__ __launch_bounds__(256) void l2_tail_fold_kernel(TailFoldArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t gr = min(r0 + 16 * m + 4 * q16 + r, a.B - 1);
-                int64_t it = a.items64 ? a.items64[gr] : (int64_t)a.items32[gr];
-                it = (int64_t)min((uint64_t)it, (uint64_t)(a.n_entity - 1));      // clamped into the table
+                // the folded entry points' rule, and what the pair kernel that wrote out0 / Z2 read: the LOW 32-bit word, unsigned
+                const unsigned lo = a.items64 ? (unsigned)(uint64_t)a.items64[gr] : (unsigned)a.items32[gr];
+                const int64_t it = (int64_t)min(lo, (unsigned)(a.n_entity - 1));      // clamped into the table
                 nm0[m][r] = a.M0[it * D + col];
                 nuo[m][r] = a.user_o[gr * D + col];
             }

@@ -88,8 +88,9 @@ __global__ __launch_bounds__(kTfWaves * 64, kTfWaves / 4) void l2_tail_flash_ker
         for (int rt = 0; rt < kTfRT; ++rt) {
             const int64_t p = t * (16 * kTfRT) + 16 * rt + l16;
             row[rt] = p < a.B ? p : a.B - 1;
-            const unsigned id = a.items64 ? reinterpret_cast<const unsigned*>(a.items64)[2 * row[rt]] : (unsigned)a.items32[row[rt]];
-            item[rt] = (int64_t)min(id, emax);
+            // the entry point's rule (include/mvin_hip.h): the WHOLE id as an unsigned 64-bit number (int32 ids sign-extended)
+            const uint64_t id = (uint64_t)(a.items64 ? a.items64[row[rt]] : (int64_t)a.items32[row[rt]]);
+            item[rt] = (int64_t)min(id, (uint64_t)emax);
         }
     };
     int64_t rowN[kTfRT], itemN[kTfRT];

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""us per mvin_l2_tail_fwd call at dim 64 on 524 288 pairs (MVIN_TAIL_FLASH=0: the tile-image kernel)."""
+"""us per mvin_l2_tail_fwd call at dim 64 on 524 288 pairs (MVIN_TAIL_FLASH unset or 0: the tile-image kernel, the default; 1: the flash
+kernel)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -16,4 +17,6 @@ e0.record()
 for _ in range(20):
     ops.l2_tail(*args)
 e1.record(); torch.cuda.synchronize()
-print(f"l2_tail B={B} MVIN_TAIL_FLASH={os.environ.get('MVIN_TAIL_FLASH', '1')}: {e0.elapsed_time(e1) / 20 * 1e3:.1f} us")
+flash = os.environ.get("MVIN_TAIL_FLASH", "0").strip() == "1"      # (opt-in, as l2_tail_flash_applies reads it)
+print(f"l2_tail B={B} MVIN_TAIL_FLASH={os.environ.get('MVIN_TAIL_FLASH', 'unset')} ({'flash' if flash else 'tile-image'} kernel): "
+      f"{e0.elapsed_time(e1) / 20 * 1e3:.1f} us")

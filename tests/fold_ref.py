@@ -18,12 +18,13 @@ def slot_weights(t, rel, dt):
 
 
 def tail_reference(E, x, q, user_o, nagg0, nagg1, W0, b0, A0, a0, A1, a1, Wmix, bmix, dtype=torch.float64):
-    """mvin_l2_tail_fwd's formulas for the (clamped) items x: -> item_emb [n, D], scores [n], sigmoid(scores) [n]."""
+    """mvin_l2_tail_fwd's formulas for the (clamped) items x: -> item_emb [n, D], scores [n], sigmoid(scores) [n].  W0 = None (User_orient
+    off): ev0 = E[x]; q and b0 are not used."""
     f = lambda t: t.to(dtype)                                 # noqa: E731
     z = lambda t: 0 if t is None else t.to(dtype)             # noqa: E731
-    ev0 = (f(E[x]) + f(q)) @ f(W0) + z(b0)
-    out0 = torch.relu((ev0 + nagg0) @ f(A0) + z(a0))
-    out2 = torch.relu((out0 + nagg1) @ f(A1) + z(a1))
+    ev0 = f(E[x]) if W0 is None else (f(E[x]) + f(q)) @ f(W0) + z(b0)
+    out0 = torch.relu((ev0 + f(nagg0)) @ f(A0) + z(a0))
+    out2 = torch.relu((out0 + f(nagg1)) @ f(A1) + z(a1))
     item = torch.cat([ev0, out0, out2], dim=1) @ f(Wmix) + z(bmix)
     s = (f(user_o) * item).sum(1)
     return item, s, torch.sigmoid(s)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import bench
-from fold_ref import clamp_ids, fold_reference, fold_tables_reference
+from fold_ref import clamp_ids, fold_reference, fold_tables_reference, tail_reference
 from test_gpu_tail import _reference as tail_reference_f64
 
 D, K, N_ENTITY, NR, B = 8, 3, 11, 4, 5
@@ -79,6 +79,29 @@ def test_equals_the_two_references_it_composes():
     ri, rs, rg = tail_reference_f64(c["E"], c["items"], c["q"], c["uo"], r0, r1, c["W0"], c["b0"], c["A0"], c["a0"], c["A1"], c["a1"], c["Wmix"], c["bmix"])
     for got, want in ((n0, r0), (n1, r1), (item, ri), (s, rs), (sg, rg)):
         assert got.dtype == torch.float64 and float((got - want).abs().max()) <= 1e-12
+
+
+@pytest.mark.parametrize("bias", [True, False], ids=["biases", "no-biases"])
+def test_tail_reference_without_the_projection(bias):
+    """W0 = None (User_orient off): ev0 = E[x], q and b0 unused -- against plain torch float64 ops, and in its fp32 evaluation."""
+    c = _instance(6, bias)
+    d = lambda t: 0 if t is None else t.double()              # noqa: E731
+    x = torch.tensor([0, 10, 2, 2, 7])
+    n0, n1 = c["q"] * 0.5 + 0.1, c["uo"] * 0.7 - 0.2         # any [B, D] rows
+    ev0 = c["E"].double()[x]
+    out0 = torch.relu((ev0 + n0.double()) @ c["A0"].double() + d(c["a0"]))
+    out2 = torch.relu((out0 + n1.double()) @ c["A1"].double() + d(c["a1"]))
+    item = ev0 @ c["Wmix"][:D].double() + out0 @ c["Wmix"][D:2 * D].double() + out2 @ c["Wmix"][2 * D:].double() + d(c["bmix"])
+    s = (c["uo"].double() * item).sum(1)
+    tail = (c["A0"], c["a0"], c["A1"], c["a1"], c["Wmix"], c["bmix"])
+    for q, b0 in ((None, None), (c["q"], c["b0"])):           # neither may enter
+        got = tail_reference(c["E"], x, q, c["uo"], n0, n1, None, b0, *tail)
+        for g_, w_ in zip(got, (item, s, torch.sigmoid(s))):
+            assert g_.dtype == torch.float64 and float((g_ - w_).abs().max()) <= 1e-12
+    with_w0 = tail_reference(c["E"], x, c["q"], c["uo"], n0, n1, c["W0"], c["b0"], *tail)
+    assert float((with_w0[0] - item).abs().max()) > 1e-3      # ... and the projection does change the result
+    lo = tail_reference(c["E"], x, None, c["uo"], n0, n1, None, None, *tail, dtype=torch.float32)
+    assert all(t.dtype == torch.float32 for t in lo) and 0 < float((lo[0].double() - item).abs().max()) < 1e-5
 
 
 @pytest.mark.parametrize("bias", [True, False], ids=["biases", "no-biases"])

@@ -4,7 +4,8 @@ mvin_fold_tables -> mvin_score_l2_folded_fwd (dim 64: mvin_fused_agg.hip, dim 32
 mvin_score_l2_folded_gather_fwd (mvin_fused_wpp_fold.hip) against tests/fold_ref.py -- the UNFOLDED formulas of include/mvin_hip.h on the plain
 adjacency, which shares neither a projected table nor the encoded adjacency with them.  Batches of 16 pairs, quads of 4 (octets of 8 at dim 32)
 and tiles of 32 each full, one short and one over; both softmax forms, one-sided (the entry points take t0 and t1 independently) and no
-attention; with / without biases; both id widths; runs of one item; ids out of range; user_o being q itself; want_item_emb = False; one
+attention; with / without biases; both id widths; runs of one item; ids out of range (int64 ids with a high word set among them: the folded
+entry points read the low 32-bit word; the two-launch variant of dim 64 is held to the same in test_gpu_fold_two_launch.py); user_o being q itself; want_item_emb = False; one
 relation and the LDS limit of 2 600; tables below and just above one 16-row tile of the table builders.  Every launch runs twice and must give
 the same bits.
 
@@ -36,7 +37,7 @@ import numpy as np
 import pytest
 import torch
 
-from fold_ref import compare, fold_reference, fold_tables_reference, report
+from fold_ref import clamp_ids, compare, fold_reference, fold_tables_reference, report
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,18 @@ STATS = {}
 
 def batch_sizes(K):
     return [1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 4 * K + 37]
+
+
+def pattern_cases(K):
+    """(B, attention, int64 ids, user_o is q, biases) of test_item_patterns_against_float64, per pattern."""
+    return ((4 * K + 37, "unit", True, False, True), (4 * K + 37, "none", False, True, False), (33, "sharp", False, False, True),
+            (17, "t1", True, True, True))
+
+
+def small_table_cases(K):
+    """(B, attention, relations, int64 ids, biases) of test_tables_around_one_tile_of_rows, per table size."""
+    return ((1, "unit", 7, True, True), (5, "none", 1, False, False), (17, "unit", 1, False, True), (33, "t0", 7, True, False),
+            (4 * K + 37, "unit", 7, True, True))
 
 
 @functools.lru_cache(maxsize=None)
@@ -214,8 +227,9 @@ def _axes(bi, ai, att):
                 nR=1 if idx % 7 == 3 and att != "sharp" else 7)
 
 
-def _run_case(fid, w, kind, c, att, bias, what, fails, tables=False):
-    """One case: tables (where asked), reference and yardstick once, every order of the launch against them."""
+def _run_case(fid, w, kind, c, att, bias, what, fails, tables=False, keep=None):
+    """One case: tables (where asked), reference and yardstick once, every order of the launch against them.  ``keep``: a list that
+    receives the outputs of every launch."""
     t0, t1 = _logits(w, att)
     ws = _tables(w, kind, t0, bias)
     if tables:
@@ -224,6 +238,8 @@ def _run_case(fid, w, kind, c, att, bias, what, fails, tables=False):
     for oname, order in _orders(kind, c.items):
         got = _launch(w, kind, ws, c.items, t0, t1, c.q, c.uo, bias, order=order)
         _compare(fid, f"{what} order={oname}", got, refs, fails)
+        if keep is not None:
+            keep.append(got)
 
 
 @pytest.mark.parametrize("att", ATTENTION)
@@ -252,8 +268,7 @@ def test_item_patterns_against_float64(form, pattern, hip_lib):
     fid = "%s-D%dK%d" % form
     w = _world(D, K, N_ENTITY, 7, "counts")
     fails = []
-    for n, (B, att, i64, uo_is_q, bias) in enumerate(((4 * K + 37, "unit", True, False, True), (4 * K + 37, "none", False, True, False),
-                                                      (33, "sharp", False, False, True), (17, "t1", True, True, True))):
+    for n, (B, att, i64, uo_is_q, bias) in enumerate(pattern_cases(K)):
         c = _case(w, pattern, B, i64, uo_is_q, seed=77 + n, item_seed=n)
         _run_case(fid, w, kind, c, att, bias, f"{fid} {pattern} B={B} att={att} i64={i64} uo_is_q={uo_is_q} bias={bias}", fails)
     _report(fid)
@@ -267,8 +282,7 @@ def test_tables_around_one_tile_of_rows(form, n_entity, hip_lib):
     kind, D, K = form
     fid = "%s-D%dK%d" % form
     fails = []
-    for n, (B, att, nR, i64, bias) in enumerate(((1, "unit", 7, True, True), (5, "none", 1, False, False), (17, "unit", 1, False, True),
-                                                 (33, "t0", 7, True, False), (4 * K + 37, "unit", 7, True, True))):
+    for n, (B, att, nR, i64, bias) in enumerate(small_table_cases(K)):
         w = _world(D, K, n_entity, nR, "random")
         c = _case(w, "stride" if n % 2 == 0 else "runs", B, i64, n == 3, seed=300 + n)
         _run_case(fid, w, kind, c, att, bias, f"{fid} n_entity={n_entity} B={B} att={att} nR={nR}", fails, tables=True)
@@ -276,28 +290,44 @@ def test_tables_around_one_tile_of_rows(form, n_entity, hip_lib):
     assert not fails, "\n".join(fails)
 
 
-@pytest.mark.parametrize("idt", [torch.int64, torch.int32], ids=["i64", "i32"])
-@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
-def test_out_of_range_ids_equal_the_clamped_ids_bit_for_bit(form, idt, hip_lib):
-    """Every 7th id beyond the table (n_entity + 12345; int32: also -1, an unsigned word above every id): the outputs of the same batch
-    with those ids set to n_entity - 1."""
+HIGH_WORD_IDS = (2 ** 32 + 5, 2 ** 40 + 3, -2 ** 32)          # int64 ids with a high word: the folded entry points read the LOW word (5, 3, 0)
+
+
+def out_of_range_ids_check(form, i64):
+    """-> the outputs whose bits differ between a batch with ids out of range and the same batch with those ids clamped on the host
+    (fold_ref.clamp_ids: the low 32-bit word, unsigned, clamped to n_entity - 1)."""
     kind, D, K = form
     w = _world(D, K, N_ENTITY, 7, "counts")
     B = 4 * K + 37
-    i64 = idt == torch.int64
     bad = _items("oob", B, N_ENTITY, i64)
     good = _items("stride", B, N_ENTITY, i64)
     good[::7] = N_ENTITY - 1
     assert int((bad != good).sum()) == (B + 6) // 7 and (i64 or int((bad == -1).sum()) == (B + 13) // 14)
+    if i64:
+        high = torch.tensor(HIGH_WORD_IDS * 3, dtype=torch.int64, device=DEV)
+        bad[1::7][: len(high)] = high
+        good[1::7][: len(high)] = clamp_ids(high, N_ENTITY)
+        assert clamp_ids(high, N_ENTITY)[:3].tolist() == [5, 3, 0] and int((bad != good).sum()) == (B + 6) // 7 + len(high)
+    assert torch.equal(clamp_ids(bad, N_ENTITY), good.long())
     t0, t1 = _logits(w, "unit")
     c = _case(w, "stride", B, i64, False, seed=5)
     ws = _tables(w, kind, t0, True)
     orders = [None] if kind == "fold" else [None, torch.flip(torch.arange(B, dtype=torch.int32, device=DEV), dims=[0])]
+    differ = []
     for order in orders:
         x = _launch(w, kind, ws, bad, t0, t1, c.q, c.uo, True, order=order)
         y = _launch(w, kind, ws, good, t0, t1, c.q, c.uo, True, order=order)
-        for nm, a, b in zip(("item_emb", "scores", "sigmoid"), x, y):
-            assert torch.equal(a, b), f"{nm}: ids out of range are not the clamped ids"
+        differ += [nm for nm, a, b in zip(("item_emb", "scores", "sigmoid"), x, y) if not torch.equal(a, b)]
+    return differ
+
+
+@pytest.mark.parametrize("idt", [torch.int64, torch.int32], ids=["i64", "i32"])
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+def test_out_of_range_ids_equal_the_clamped_ids_bit_for_bit(form, idt, hip_lib):
+    """Every 7th id beyond the table (n_entity + 12345; int32: also -1, an unsigned word above every id; int64: also ids with a high word
+    set, of which the low word counts): the outputs of the same batch with those ids clamped on the host."""
+    differ = out_of_range_ids_check(form, idt == torch.int64)
+    assert not differ, f"{differ}: ids out of range are not the clamped ids"
 
 
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)

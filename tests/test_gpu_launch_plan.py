@@ -213,8 +213,9 @@ print("TWO DEVICES OK")
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices")
 def test_one_thread_drives_two_devices(tmp_path, hip_lib):
-    """mvin_order_by_key and mvin_l2_tail_fwd in its tile-image form (MVIN_TAIL_FLASH=1, read once per process: hence the child) on device
-    0 and then on device 1 from one thread: the LDS grant belongs to each device's copy of the function."""
+    """mvin_order_by_key and mvin_l2_tail_fwd in its FLASH form (l2_tail_flash_kernel, 96 KB of LDS: opt-in with MVIN_TAIL_FLASH=1, read once
+    per process: hence the child) on device 0 and then on device 1 from one thread: the LDS grant belongs to each device's copy of the
+    function.  Values: tests/test_gpu_tail.py."""
     script = tmp_path / "two_devices.py"
     script.write_text(TWO_DEVICES)
     env = dict(os.environ, MVIN_TAIL_FLASH="1")
