@@ -891,6 +891,50 @@ MVIN_API int64_t mvin_ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);     /
 MVIN_API int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, void* stream);
 
+/* ---- CTR report: probabilistic quality of the scores (logloss, Brier, reliability bins), one Newton iteration of a Platt
+ * fit, and the CTR counts of segments of their own lengths (per-user AUC).  An extension: the reference reports none of these --
+ * mvin_ctr_calib: mvin_ctr_counts' layout (segment s is logits[s*ld .. s*ld+seg_len) with labels[...]; the gaps between rows
+ * are never read).  A pair is VALID when its logit z is finite and its label is 0 or 1.  For a valid pair, in double:
+ *   t = fma(a, (double)z, b);  e = exp(-|t|);  p = t >= 0 ? 1/(1+e) : e/(1+e);  y = label ? y1 : y0;
+ *   l = max(t, 0) + log1p(e) - y*t;  r = p - y;  w = e/(1+e)^2.
+ *  - out_sums [n_seg, 8] double: sum l, sum r^2, sum r, sum r*z, sum w, sum w*z, sum w*z^2, sum p over the valid pairs: the
+ *    loss, the Brier sum, the gradient (in b, a) and the Hessian of the loss, so one call is one Newton iteration of the fit
+ *    p = sigmoid(a*z + b);
+ *  - out_counts [n_seg, 2] int64: valid pairs, and bad = non-finite logits plus labels other than 0 and 1.  Bad pairs are
+ *    in no sum and no bin;
+ *  - out_bins [n_seg, n_bins, 3] int64: per bin its valid pairs, those with label 1, and the confidence mass
+ *    sum floor(p * 2^40).  The bin of a pair is #{j: edges[j] <= z}: f32 comparisons on the logit itself (-0.0 equals +0.0)
+ *    against `edges` (f32 [n_bins - 1], ascending, no NaN; may be NULL with n_bins == 1), whatever (a, b): the caller maps
+ *    probability edges to z.  Counts and positives are exact.
+ * A segment's sums are a fixed function of the segment: chunks of 4096 pairs, thread t of 256 adds pairs t, t + 256, ... in
+ * order, a fixed butterfly over the wave, the four waves in order, then the chunks c, c + 256, ... per thread and the same
+ * tree.  No floating-point atomics: the same bits for every `max_groups` (a cap on the first launch's workgroups, 0 =
+ * automatic) and on every launch.  `ws`: mvin_ctr_calib_ws_bytes(n_seg, seg_len) bytes, never NULL with n_seg > 0.
+ * Errors (< 0, nothing launched): -2 for mvin_ctr_counts' size rules, n_bins outside 1..MVIN_CTR_CALIB_MAX_BINS or
+ * max_groups < 0; -1 for null logits / labels / ws / outputs, or null edges with n_bins > 1.  n_seg == 0 launches nothing.
+ *
+ * mvin_ctr_counts_segments: mvin_ctr_counts' six integers (n_pos, n_neg, tp, fp, u2, bad; the same image and tie rule) for the
+ * segments scores[seg_ptr[s] .. seg_ptr[s+1]) of a flat buffer (labels [total] alike; seg_ptr [n_seg+1] int64), with
+ * prediction = (score >= threshold) compared in f32: 0.5 for sigmoid scores, 0 for logits.  mvin_rank_segments'
+ * conventions: `max_len` promised by the caller; `form` 0 = automatic, 1 = lane-group form (max_len <=
+ * mvin_segments_wave_cap(): a segment in registers, cross-lane counting, no LDS, several segments per workgroup), 2 = workgroup
+ * form (one workgroup per segment, its negatives' images sorted in LDS).  Every number is an integer independent of form, launch
+ * shape and max_len; an empty segment gives zeros.  A segment longer than max_len, or whose pointers do not lie in [0, total] in
+ * order, is not read: its row is -1 everywhere and `status` (int64 [2], ACCUMULATED: zero it first) counts it in [0] and its six
+ * slots in [1].  LIMIT: max_len <= MVIN_CTR_SEG_CAP.
+ * Errors (< 0, nothing launched): -2 for n_seg < 0 or >= 2^31, total < 0, max_len < 0 or > MVIN_CTR_SEG_CAP, form outside
+ * 0..2, form 1 with max_len above the cap of the lane-group form, a NaN threshold; -1 for null scores / labels (with total > 0)
+ * / seg_ptr / out / status.  n_seg == 0 launches nothing.  No workspace. */
+#define MVIN_CTR_CALIB_MAX_BINS 64
+MVIN_API int64_t mvin_ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len);      /* < 0: invalid sizes */
+MVIN_API int mvin_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a,
+                            double b, double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws,
+                            double* out_sums /* [n_seg,8] */, int64_t* out_counts /* [n_seg,2] */,
+                            int64_t* out_bins /* [n_seg,n_bins,3] */, void* stream);
+MVIN_API int mvin_ctr_counts_segments(const float* scores, const int32_t* labels, int64_t total, const int64_t* seg_ptr,
+                                      int64_t n_seg, float threshold, int64_t max_len, int form, int64_t* out /* [n_seg,6] */,
+                                      int64_t* status, void* stream);
+
 /* ---- training negatives: the label-0 rows of convert_rating (KGCN/preprocess.py:60-70: for every user, as many items as the
  * user has positives, np.random.choice(list(item_set - pos - neg), replace=False)), drawn on the GPU as a pure function of
  * (seed, round) so that they can be redrawn every epoch --

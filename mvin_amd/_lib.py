@@ -106,6 +106,11 @@ SIGNATURES = {
                                   C.c_int] + [C.c_void_p] * 4),
     "mvin_ctr_counts_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_ctr_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvin_ctr_calib_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mvin_ctr_calib": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_double] * 4
+                       + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "mvin_ctr_counts_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_int64, C.c_int]
+                                 + [C.c_void_p] * 3),
     "mvin_order_by_key_ws_elems": (C.c_size_t, [C.c_int64]),
     "mvin_order_by_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvin_gather_attn_l2_prj_ordered_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 3),

@@ -590,6 +590,42 @@ int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, i
     return hip_result(mvin::launch_ctr_counts(scores, labels, n_seg, seg_len, ld, ws, out, (hipStream_t)stream), who);
 }
 
+int64_t mvin_ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len) {
+    if (ctr_bad_sizes(n_seg, seg_len)) return fail(-2, "mvin_ctr_calib_ws_bytes: n_seg=%lld seg_len=%lld", (long long)n_seg, (long long)seg_len);
+    return mvin::ctr_calib_ws_bytes(n_seg, seg_len);
+}
+
+int mvin_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b, double y0,
+                   double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums, int64_t* out_counts,
+                   int64_t* out_bins, void* stream) {
+    const char* who = "mvin_ctr_calib";
+    if (ctr_bad_sizes(n_seg, seg_len) || ld < seg_len)
+        return fail(-2, "%s: n_seg=%lld seg_len=%lld ld=%lld", who, (long long)n_seg, (long long)seg_len, (long long)ld);
+    if (n_bins < 1 || n_bins > MVIN_CTR_CALIB_MAX_BINS || max_groups < 0)
+        return fail(-2, "%s: n_bins=%d (1..%d) max_groups=%d (>= 0)", who, n_bins, MVIN_CTR_CALIB_MAX_BINS, max_groups);
+    if (!logits || !labels || !out_sums || !out_counts || !out_bins) return fail(-1, "%s: null logits / labels / out_sums / out_counts / out_bins", who);
+    if (!edges && n_bins > 1) return fail(-1, "%s: null edges with n_bins=%d", who, n_bins);
+    if (!ws && n_seg > 0) return fail(-1, "%s: null ws (mvin_ctr_calib_ws_bytes)", who);
+    return hip_result(mvin::launch_ctr_calib(logits, labels, n_seg, seg_len, ld, a, b, y0, y1, edges, n_bins, max_groups, ws, out_sums,
+                                             out_counts, out_bins, (hipStream_t)stream), who);
+}
+
+int mvin_ctr_counts_segments(const float* scores, const int32_t* labels, int64_t total, const int64_t* seg_ptr, int64_t n_seg,
+                             float threshold, int64_t max_len, int form, int64_t* out, int64_t* status, void* stream) {
+    const char* who = "mvin_ctr_counts_segments";
+    if (n_seg < 0 || n_seg >= (int64_t(1) << 31) || total < 0 || max_len < 0 || max_len > MVIN_CTR_SEG_CAP)
+        return fail(-2, "%s: n_seg=%lld total=%lld max_len=%lld (max_len <= %d)", who, (long long)n_seg, (long long)total,
+                    (long long)max_len, MVIN_CTR_SEG_CAP);
+    if (form < 0 || form > 2) return fail(-2, "%s: form=%d (0 automatic, 1 lane group, 2 workgroup)", who, form);
+    if (form == 1 && max_len > mvin::segments_wave_cap())
+        return fail(-2, "%s: form=1 (lane group) takes max_len <= %d, got %lld", who, mvin::segments_wave_cap(), (long long)max_len);
+    if (threshold != threshold) return fail(-2, "%s: threshold is NaN", who);
+    if (!seg_ptr || !status || (n_seg > 0 && !out) || (total > 0 && (!scores || !labels)))
+        return fail(-1, "%s: null scores / labels / seg_ptr / out / status", who);
+    return hip_result(mvin::launch_ctr_counts_segments(scores, labels, total, seg_ptr, n_seg, threshold, max_len, form, out, status,
+                                                       (hipStream_t)stream), who);
+}
+
 int mvin_gather_attn_l2_prj_ordered_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, int adjacency_encoded,
                                         const void* parent_ids, int parent_ids_i64, const int32_t* order, const float* t0, const float* t1,
                                         const float* q, int B, int parents_per_pair, int K, int D, int n_entity, int nR, float* nagg0,

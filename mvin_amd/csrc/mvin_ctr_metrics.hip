@@ -12,94 +12,12 @@
 //     positive searches its segment's sorted negatives in global memory.  A sequence of launches on one stream, nothing
 //     waits on another workgroup inside a launch.
 #include "mvin_kernels.h"
-#include "mvin_score_image.h"
+#include "mvin_ctr_bodies.h"
 
 namespace mvin {
 
-constexpr int64_t kCtrSegCap = MVIN_CTR_SEG_CAP;   // the longest segment (and the long path's tile) sorted in LDS: 64 KiB of keys
-constexpr unsigned kCtrSentinel = 0xFFFFFFFFu;  // not a negative (score_image never returns it)
 constexpr int kCtrSearchPerThread = 8;          // pairs per thread of the long path's search launch
 constexpr int64_t kCtrMaxGroups = int64_t(1) << 20;   // workgroups per launch (the grid is cut into launches of at most this)
-
-// #{i < n: k[i] < x} (inclusive = false) or #{i < n: k[i] <= x} (inclusive = true), k ascending.  Branch-free lower bound.
-template <typename T, typename P>
-__device__ __forceinline__ T ctr_rank(P k, T n, unsigned x, bool inclusive) {
-    T lo = 0, len = n;
-    while (len > 0) {
-        const T half = len >> 1;
-        const unsigned v = k[lo + half];
-        const bool right = inclusive ? v <= x : v < x;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
-    return lo;
-}
-
-// pairs [0, len) of one segment row into LDS keys[0, P) (negatives' images, else the sentinel), counting into c[]
-template <int NT>
-__device__ __forceinline__ void ctr_load(const float* srow, const int32_t* lrow, int len, int P, unsigned* keys,
-                                         unsigned (&c)[6]) {
-    for (int i = threadIdx.x; i < P; i += NT) {
-        unsigned key = kCtrSentinel;
-        if (i < len) {
-            const float s = srow[i];
-            const int32_t l = lrow[i];
-            const bool pos = l == 1, neg = l == 0, pred = s >= 0.5f;
-            const bool finite = (__float_as_uint(s) & 0x7F800000u) != 0x7F800000u;
-            c[0] += pos;
-            c[1] += neg;
-            c[2] += pos && pred;
-            c[3] += neg && pred;
-            c[5] += (unsigned)!finite + (unsigned)!(pos || neg);
-            if (neg) key = score_image(s);
-        }
-        keys[i] = key;
-    }
-}
-
-// ascending bitonic sort of keys[0, P), P a power of two
-template <int NT>
-__device__ __forceinline__ void ctr_sort(unsigned* keys, int P) {
-    __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < P / 2; t += NT) {
-                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const unsigned x = keys[i], y = keys[j];
-                const bool asc = (i & size) == 0;
-                if ((x > y) == asc) {
-                    keys[i] = y;
-                    keys[j] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// workgroup sums of v[0..5] into red (LDS, >= 6 * NT / kWave u64, 8-byte aligned; free to overwrite); valid in threads 0..5
-template <int NT>
-__device__ __forceinline__ unsigned long long ctr_block_sum(unsigned long long (&v)[6], unsigned long long* red) {
-    constexpr int NW = NT / kWave;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, kWave);
-    }
-    __syncthreads();                                   // red may alias keys another wave is still reading
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) red[wave * 6 + q] = v[q];
-    }
-    __syncthreads();
-    unsigned long long s = 0;
-    if (threadIdx.x < 6) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) s += red[w * 6 + threadIdx.x];
-    }
-    return s;
-}
 
 struct CtrArgs {
     const float* scores;
@@ -122,7 +40,7 @@ __global__ __launch_bounds__(NT) void ctr_seg_kernel(CtrArgs a) {
     const float* srow = a.scores + seg * a.ld;
     const int32_t* lrow = a.labels + seg * a.ld;
     unsigned c[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    ctr_load<NT>(srow, lrow, len, a.P, keys, c);
+    ctr_load<NT>(srow, lrow, len, a.P, 0.5f, keys, c);
     ctr_sort<NT>(keys, a.P);
     unsigned long long u2 = 0;
     for (int i = threadIdx.x; i < len; i += NT) {
@@ -145,7 +63,7 @@ __global__ __launch_bounds__(NT) void ctr_tile_kernel(CtrArgs a) {
     const int64_t t0 = tile * kCtrSegCap;
     const int len = (int)min(kCtrSegCap, a.seg_len - t0);
     unsigned c[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    ctr_load<NT>(a.scores + seg * a.ld + t0, a.labels + seg * a.ld + t0, len, (int)kCtrSegCap, keys, c);
+    ctr_load<NT>(a.scores + seg * a.ld + t0, a.labels + seg * a.ld + t0, len, (int)kCtrSegCap, 0.5f, keys, c);
     ctr_sort<NT>(keys, (int)kCtrSegCap);
     unsigned* dst = a.keys_out + seg * (a.ntiles * kCtrSegCap) + t0;
     for (int i = threadIdx.x; i < (int)kCtrSegCap; i += NT) dst[i] = keys[i];

@@ -469,7 +469,13 @@ hipError_t launch_rank_segments(const float* scores, int64_t total, const int64_
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);
-bool sample_negatives_supported(int n_item);                  // per-user negatives without replacement (mvin_negatives.hip)
+hipError_t launch_ctr_counts_segments(const float* scores, const int32_t* labels, int64_t total, const int64_t* seg_ptr, int64_t n_seg,
+                                      float threshold, int64_t max_len, int form, int64_t* out, int64_t* status, hipStream_t st);
+int64_t ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len);    // calibration sums and reliability bins (mvin_ctr_calib.hip)
+hipError_t launch_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b,
+                            double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums,
+                            int64_t* out_counts, int64_t* out_bins, hipStream_t st);
+bool sample_negatives_supported(int n_item);                 // per-user negatives without replacement (mvin_negatives.hip)
 hipError_t launch_sample_negatives(const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* counts, const int64_t* out_ptr,
                                    int n_user, int n_item, const uint32_t* alias_tab, const uint32_t* mask_bits, uint64_t seed,
                                    uint64_t round, int32_t* out, int64_t* status,

@@ -16,6 +16,8 @@ and the attention case-study dump.  The epoch loop, early stopping and log book-
 users live on the GPU once ([n_user, P, 3, Nm] int32) and a batch's memories are gathered there,
 so the per-step host work of train.py:117-120 (3*P python lists of B numpy rows) disappears.
 """
+import collections
+
 import numpy as np
 
 
@@ -86,6 +88,19 @@ class DeviceFeeder(object):
         it = torch.as_tensor(np.asarray(items) if not torch.is_tensor(items) else items).to(dev).long()
         return self.model.forward_users(u, it, self.uts).scores_normalized     # feeds assembled inside the kernels
 
+    def _forward_pairs(self, users, items):
+        """The ``forward_users`` call ``scores`` makes, whole: its ``.scores`` are the logits, ``.scores_normalized`` their
+        sigmoid."""
+        import torch
+        dev = self.model.device
+        u = torch.as_tensor(np.asarray(users) if not torch.is_tensor(users) else users).to(dev).long()
+        it = torch.as_tensor(np.asarray(items) if not torch.is_tensor(items) else items).to(dev).long()
+        return self.model.forward_users(u, it, self.uts)
+
+    def logits(self, users, items):
+        """raw scores (the logits ``scores`` takes the sigmoid of) of (users[i], items[i]) as a device tensor: the ``.scores``
+        of the same ``forward_users`` call."""
+        return self._forward_pairs(users, items).scores
 
     def scores_user(self, user, items):
         """sigmoid scores of ONE user against ``items``: the shared-user form of the path (the
@@ -933,6 +948,182 @@ def ctr_eval_split(feeder, data, max_pairs=524288):
     return float(auc[0]), float(acc[0]), float(f1[0])
 
 
+# --------------------------------------------------------------------------- CTR report: calibration and per-user AUC
+def _score_split_both(feeder, data, max_pairs):
+    """_score_split with both results of its forward calls kept: ``(logits, sigmoid scores, labels)`` of every pair of ``data``
+    on the device, each slice scored ONCE.  The slices are _score_split's, so the sigmoid scores are ctr_eval_split's bits."""
+    import torch
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError(f"max_pairs={max_pairs}")
+    dev = feeder.model.device
+    cols = np.asarray(data)
+    m = cols.shape[0]
+    users = torch.from_numpy(np.ascontiguousarray(cols[:, 0], dtype=np.int64)).to(dev)
+    items = torch.from_numpy(np.ascontiguousarray(cols[:, 1], dtype=np.int64)).to(dev)
+    lab = cols[:, 2]
+    labels = torch.from_numpy(np.where((lab == 0) | (lab == 1), lab, 2).astype(np.int32)).to(dev)
+    logits = torch.empty((m,), dtype=torch.float32, device=dev)
+    scores = torch.empty((m,), dtype=torch.float32, device=dev)
+    for s0 in range(0, m, max_pairs):
+        s1 = min(m, s0 + max_pairs)
+        out = feeder._forward_pairs(users[s0:s1], items[s0:s1])
+        logits[s0:s1] = out.scores.reshape(-1)
+        scores[s0:s1] = out.scores_normalized.reshape(-1)
+    return logits, scores, labels
+
+
+Calibration = collections.namedtuple("Calibration", "a b iterations converged logloss_before logloss_after")
+Calibration.__doc__ = """A Platt map ``p = sigmoid(a z + b)`` of the logit z (fit_calibration): the map, the Newton iterations it
+took, whether the Newton step fell below the tolerance, and the logloss (0 / 1 targets) of the fitted split before and after."""
+
+
+def platt_fit(evaluate, max_iter=50, tol=1e-10):
+    """Newton with backtracking on the Platt map ``(a, b)`` from ``(1, 0)``.  ``evaluate(a, b)`` returns ``(sums, n)``: one
+    row of mvin_ctr_calib's 8 sums over ``n`` valid pairs under that map (ops.ctr_calib, or a host restatement of it).  Each
+    iteration takes ops.platt_step's direction and halves the step until the loss sum l / n has decreased enough (Armijo,
+    1e-4).  Converged: the larger component of the step about to be taken is below ``tol``.  Returns ``(a, b, iterations, converged)``; pure
+    host code around ``evaluate``."""
+    from . import ops
+    a, b = 1.0, 0.0
+    s, n = evaluate(a, b)
+    s = np.asarray(s, dtype=np.float64).reshape(-1)
+    loss = s[0] / n
+    converged, it = False, 0
+    for it in range(int(max_iter) + 1):
+        if not np.isfinite(loss):
+            break
+        da, db, slope = ops.platt_step(s, n)
+        dmax = max(abs(da), abs(db))
+        if dmax < tol:                              # the Newton step is about the distance to the minimum
+            converged = True
+            break
+        if it == int(max_iter):
+            break
+        step, moved = 1.0, False
+        while step >= 2.0 ** -40:
+            s2, n2 = evaluate(a + step * da, b + step * db)
+            s2 = np.asarray(s2, dtype=np.float64).reshape(-1)
+            loss2 = s2[0] / n2
+            if np.isfinite(loss2) and loss2 <= loss + 1e-4 * step * slope:
+                a, b, s, n, loss, moved = a + step * da, b + step * db, s2, n2, loss2, True
+                break
+            step *= 0.5
+        if not moved:                               # no representable decrease is left along the direction
+            converged = dmax < np.sqrt(tol)
+            break
+    return float(a), float(b), int(it), bool(converged)
+
+
+def fit_calibration(feeder, data, smooth=True, max_iter=50, tol=1e-10, max_pairs=524288, name="split"):
+    """Fit the Platt map ``p = sigmoid(a z + b)`` to the logits of ``data`` (usually the eval split): the split is scored once
+    and stays on the device; every evaluation of the Newton loop (platt_fit) is ONE mvin_ctr_calib launch over it as one segment
+    and one copy back of its row of sums.  ``smooth``: Platt's targets y1 = (N+ + 1) / (N+ + 2), y0 = 1 / (N- + 2) instead of
+    1 / 0, so that a separable split cannot send ``a`` to infinity.  Returns a ``Calibration``; its two loglosses are on 0 / 1
+    targets, the numbers ctr_report gives.  A fit that ends at ``a <= 0`` (scores that rank the split backwards) raises
+    ValueError naming ``name``; so does a split with a non-finite logit or a label other than 0 / 1."""
+    from . import ops
+    cols = np.asarray(data)
+    n = cols.shape[0]
+    if n == 0:
+        raise ValueError(f"fit_calibration: empty {name}")
+    logits, _, labels = _score_split_both(feeder, data, max_pairs)
+    n_pos, n_neg = int((cols[:, 2] == 1).sum()), int((cols[:, 2] == 0).sum())
+    targets = (1.0 / (n_neg + 2.0), (n_pos + 1.0) / (n_pos + 2.0)) if smooth else (0.0, 1.0)
+    checked = []
+
+    def evaluate(a, b, tg=targets):
+        sums, counts, _ = ops.ctr_calib(logits, labels, n, a=a, b=b, targets=tg)
+        if not checked:
+            c = counts.cpu().numpy()
+            if c[0, 1] > 0:
+                raise ValueError(f"fit_calibration: {name} holds {int(c[0, 1])} non-finite logit(s) or label(s) other than 0 / 1")
+            checked.append(int(c[0, 0]))
+        return sums.cpu().numpy()[0], checked[0]
+
+    before = evaluate(1.0, 0.0, (0.0, 1.0))
+    a, b, iterations, converged = platt_fit(evaluate, max_iter=max_iter, tol=tol)
+    if not (a > 0.0 and np.isfinite(a) and np.isfinite(b)):
+        raise ValueError(f"fit_calibration: the fit on {name} ended at a={a}, b={b}: a map with a <= 0 would reverse the ranking")
+    after = evaluate(a, b, (0.0, 1.0))
+    return Calibration(a, b, iterations, converged, float(before[0][0] / before[1]), float(after[0][0] / after[1]))
+
+
+def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288):
+    """The CTR report of a split as ONE population (an extension: the reference reports none of these but the per-batch means
+    of auc / acc / f1).  The split is scored once (logits and sigmoid scores of the same forward calls); everything else is
+    reductions over the resident buffers and one copy back per result tensor.  Returns a dict:
+      * ``auc``, ``acc``, ``f1``: ops.ctr_counts on the sigmoid scores -- ctr_eval_split's numbers bit for bit without
+        ``calibration``;
+      * ``logloss``, ``brier``, ``ne`` (logloss over the base rate's entropy), ``mean_pred``, ``base_rate``, ``ece``, ``mce``
+        and ``bins`` = {"edges" (the n_bins - 1 z-edges), "count", "rate", "conf"} over ``n_bins`` uniform probability bins
+        (ops.ctr_calib, ops.ctr_calibration_from_sums);
+      * ``gauc`` (with ``gauc=True``) = {"weighted", "mean", "users", "skipped_users"}: every user's own AUC over the user's
+        rows (ops.ctr_counts_segments on the logits gathered into user order, a stable argsort on the host;
+        ops.gauc_from_counts).  LIMIT: a user with more than ops.CTR_SEG_CAP = 16 384 rows in the split raises ValueError.
+    ``calibration``: a Calibration or an ``(a, b)`` pair with a > 0.  The calibration numbers are then those of
+    p = sigmoid(a z + b), and ``acc`` / ``f1`` those of the prediction z >= float32(-b / a), i.e. a z + b >= 0; ``auc`` and
+    ``gauc`` do not change under an increasing map."""
+    import torch
+    from . import ops
+    cols = np.asarray(data)
+    n = cols.shape[0]
+    if n == 0:
+        raise ValueError("ctr_report: empty split")
+    a, b = (1.0, 0.0) if calibration is None else (float(calibration[0]), float(calibration[1]))
+    edges = ops.calib_edges(n_bins, a, b)                       # refuses a <= 0
+    seg_ptr = order = None
+    if gauc:
+        users = np.ascontiguousarray(cols[:, 0], dtype=np.int64)
+        lo = int(users.min())
+        if n < (1 << 31) and int(users.max()) - lo < (1 << 31):    # the stable argsort as ONE sort of (user, row) keys
+            order = np.sort((users - lo) * n + np.arange(n, dtype=np.int64)) % n
+        else:
+            order = np.argsort(users, kind="stable")
+        su = users[order]
+        first = np.flatnonzero(np.concatenate(([True], su[1:] != su[:-1])))
+        ids, rows = su[first], np.diff(np.concatenate((first, [n])))
+        if rows.max() > ops.CTR_SEG_CAP:
+            u = int(ids[int(np.argmax(rows))])
+            raise ValueError(f"ctr_report: user {u} has {int(rows.max())} rows in the split; per-user AUC takes at most "
+                             f"{ops.CTR_SEG_CAP}")
+        seg_ptr = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
+    logits, scores, labels = _score_split_both(feeder, data, max_pairs)
+    dev = logits.device
+    counts = ops.ctr_counts(scores, labels, n)
+    sums, valid, bins = ops.ctr_calib(logits, labels, n, a=a, b=b, edges=edges)
+    cut = None
+    if calibration is not None:                                 # the two sides of a z + b = 0: tp and fp of the calibrated map
+        cut = ops.ctr_calib(logits, labels, n, a=a, b=b, edges=np.array([-b / a], np.float32))[2]
+    ucounts = None
+    if gauc:
+        od = torch.from_numpy(order).to(dev)
+        ucounts, _ = ops.ctr_counts_segments(logits.index_select(0, od), labels.index_select(0, od),
+                                             torch.from_numpy(seg_ptr).to(dev), threshold=0.0, max_len=int(rows.max()))
+    counts = counts.cpu().numpy()
+    auc, acc, f1 = ops.ctr_metrics_from_counts(counts)
+    cal = ops.ctr_calibration_from_sums(sums.cpu().numpy(), valid.cpu().numpy(), bins.cpu().numpy())
+    rep = {"auc": float(auc[0]), "acc": float(acc[0]), "f1": float(f1[0])}
+    if cut is not None:
+        cut = cut.cpu().numpy()[0]
+        c2 = counts.copy()
+        c2[0, 2], c2[0, 3] = cut[1, 1], cut[1, 0] - cut[1, 1]
+        _, acc2, f12 = ops.ctr_metrics_from_counts(c2)
+        rep["acc"], rep["f1"] = float(acc2[0]), float(f12[0])
+    for k in ("logloss", "brier", "ne", "ece", "mce", "mean_pred", "base_rate"):
+        rep[k] = float(cal[k][0])
+    rep["n"] = int(cal["n"][0])
+    rep["calibration"] = (a, b)
+    rep["bins"] = {"edges": edges.tolist(), "count": cal["bin_count"][0].tolist(), "rate": cal["bin_rate"][0].tolist(),
+                   "conf": cal["bin_conf"][0].tolist()}
+    if gauc:
+        rep["gauc"] = ops.gauc_from_counts(ucounts.cpu().numpy())
+    return rep
+
+
+_ctr_report = ctr_report                                        # train() takes an option of the same name
+
+
 def topk_settings(train_data, eval_data, test_data, n_item, user_num=250, k_list=(1, 2, 5, 10, 25, 50, 100)):
     """util.py:14-41 without the pickle round trip: the ``user_num`` users with the most
     positive train interactions among those present in all three splits."""
@@ -1231,7 +1422,7 @@ class EarlyStop(object):
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
           objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0,
-          clip_norm=None, skip_nonfinite=False, logq=False, eval_neg=None):
+          clip_norm=None, skip_nonfinite=False, logq=False, eval_neg=None, ctr_report=False, calibrate=False):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -1292,6 +1483,12 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     record gains "grad_norm": {"mean", "max"} (over the epoch's steps with a finite norm), "clipped_steps" and
     "skipped_steps", from one read-back per epoch; "loss" stays the mean over every step, so an epoch with skipped steps may
     show nan there -- "skipped_steps" says why.  An opt-in extension: off, the steps are exactly the unguarded ones.
+    ``ctr_report``: True (with ``ctr_impl="batched"``, not with ``show_topk``) adds to every split's record the numbers of
+    harness.ctr_report over the whole split: "logloss", "brier", "ece" and "gauc" ({"weighted", "mean", "users",
+    "skipped_users"}); "auc" / "acc" / "f1" stay the per-batch means.  ``calibrate``: True (needs ``ctr_report``) fits a Platt
+    map on the eval split every epoch (fit_calibration) and gives the test record "calibrated": {"a", "b", "logloss", "acc",
+    "f1"} under that map.  An opt-in extension (the reference reports none of these): off, the records are exactly the ones
+    without it.
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
@@ -1305,6 +1502,14 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
             raise ValueError(f"eval_neg={eval_neg!r}: expected an integer in [1, 4095]")
     if ctr_impl not in ("host", "batched"):
         raise ValueError(f"ctr_impl={ctr_impl!r}: expected 'host' or 'batched'")
+    if not isinstance(ctr_report, (bool, np.bool_)) or not isinstance(calibrate, (bool, np.bool_)):
+        raise ValueError(f"ctr_report={ctr_report!r}, calibrate={calibrate!r}: expected True or False")
+    if ctr_report and ctr_impl != "batched":
+        raise ValueError(f"ctr_report=True reads the scores a split leaves on the device: it needs ctr_impl='batched', not {ctr_impl!r}")
+    if ctr_report and show_topk:
+        raise ValueError("ctr_report=True reports on the CTR evaluation, which show_topk=True replaces")
+    if calibrate and not ctr_report:
+        raise ValueError("calibrate=True reports the calibrated numbers in the CTR report: it needs ctr_report=True")
     if negatives not in ("fixed", "resample", "hard"):
         raise ValueError(f"negatives={negatives!r}: expected 'fixed', 'resample' or 'hard'")
     if objective not in ("bce", "bpr", "softmax"):
@@ -1424,6 +1629,13 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
                 ctr = ctr_eval_batched if ctr_impl == "batched" else ctr_eval_device
                 _, _, _, auc, acc, f1 = ctr(feeder, d, args.batch_size)
                 rec[name] = {"auc": auc, "acc": acc, "f1": f1}
+                if ctr_report:
+                    rep = _ctr_report(feeder, d)
+                    rec[name].update({k: rep[k] for k in ("logloss", "brier", "ece", "gauc")})
+            if calibrate:
+                cal = fit_calibration(feeder, eval_data, name="the eval split")
+                rep = _ctr_report(feeder, test_data, calibration=cal, gauc=False)
+                rec["test"]["calibrated"] = {"a": cal.a, "b": cal.b, "logloss": rep["logloss"], "acc": rep["acc"], "f1": rep["f1"]}
             score = rec["eval"]["auc"]                                          # Eval_score_info.eval_st_score
         history.append(rec)
         if log:

@@ -506,6 +506,201 @@ def ctr_metrics_from_counts(counts):
     return auc, acc, f1
 
 
+CTR_CALIB_MAX_BINS = 64      # MVIN_CTR_CALIB_MAX_BINS
+CTR_CALIB_SUMS = ("loss", "r2", "r", "rz", "w", "wz", "wz2", "p")
+CTR_MASS_ONE = float(1 << 40)          # the confidence mass of p = 1 (mvin_ctr_calib: floor(p * 2^40) per pair)
+
+
+def calib_edges(n_bins, a=1.0, b=0.0):
+    """The z-space edges of ``n_bins`` uniform probability bins under the map ``p = sigmoid(a z + b)``: a float32 numpy array
+    [n_bins - 1], edge k = (logit(k / n_bins) - b) / a computed in float64 and rounded to float32 (mvin_ctr_calib bins the f32
+    logit itself against them).  ``a <= 0`` raises ValueError: the map must be increasing."""
+    import numpy as np
+    n_bins, a, b = int(n_bins), float(a), float(b)
+    if not 1 <= n_bins <= CTR_CALIB_MAX_BINS:
+        raise ValueError(f"n_bins={n_bins}: expected 1 .. {CTR_CALIB_MAX_BINS}")
+    if not (a > 0.0 and np.isfinite(a) and np.isfinite(b)):
+        raise ValueError(f"calibration map a={a}, b={b}: expected a finite map with a > 0")
+    q = np.arange(1, n_bins, dtype=np.float64) / n_bins
+    return ((np.log(q) - np.log1p(-q) - b) / a).astype(np.float32)
+
+
+def ctr_calib(logits, labels, seg_len, a=1.0, b=0.0, targets=(0.0, 1.0), edges=None, max_groups=0):
+    """mvin_ctr_calib: calibration sums and reliability bins of every segment under ``p = sigmoid(a z + b)``.  ``logits`` f32 and
+    ``labels`` int32 as ctr_counts takes them (1-D of S * seg_len pairs, or [S, seg_len] with dense rows).  ``targets`` =
+    (y0, y1), the regression targets of label 0 / 1 ((0, 1), or Platt's smoothed ones).  ``edges``: ascending f32 z-edges
+    (calib_edges; a device tensor, a host array or None = one bin).  Returns ``(sums f64 [S, 8] (CTR_CALIB_SUMS), counts int64
+    [S, 2] (valid, bad), bins int64 [S, n_bins, 3] (count, positives, confidence mass))`` on the device.  Enqueues only when
+    ``edges`` is a device tensor or None; the sums are the same bits for every ``max_groups``.  LIMIT: the confidence mass is an
+    int64 sum of values up to 2^40, exact while a bin holds fewer than 2^23 pairs."""
+    import numpy as np
+    lib = _lib.load()
+    seg_len = int(seg_len)
+    if seg_len < 1:
+        raise ValueError(f"seg_len={seg_len}: expected >= 1")
+    if isinstance(logits, torch.Tensor) and logits.dim() == 1:
+        if logits.numel() % seg_len:
+            raise ValueError(f"logits: {logits.numel()} pairs are not whole segments of {seg_len}")
+        _chk(logits, F32, "logits")
+        logits = logits.view(-1, seg_len)
+    if isinstance(labels, torch.Tensor) and labels.dim() == 1:
+        _chk(labels, I32, "labels")
+        labels = labels.view(-1, seg_len) if labels.numel() % seg_len == 0 else labels
+    _ctr_rows(logits, "logits", F32)
+    _ctr_rows(labels, "labels", I32)
+    if tuple(logits.shape) != tuple(labels.shape) or logits.shape[1] != seg_len:
+        raise ValueError(f"logits {tuple(logits.shape)} and labels {tuple(labels.shape)}: expected [S, {seg_len}] both")
+    S = logits.shape[0]
+    ld = logits.stride(0) if S > 1 else seg_len
+    if S > 1 and labels.stride(0) != ld:
+        raise ValueError(f"labels: row stride {labels.stride(0)}, logits: {ld}; the two must share one layout")
+    dev = logits.device
+    if edges is None:
+        edges = torch.empty((0,), dtype=F32, device=dev)
+    elif not isinstance(edges, torch.Tensor):
+        e = np.ascontiguousarray(edges, dtype=np.float32)
+        if e.ndim != 1 or (e.size > 1 and not (np.diff(e) >= 0).all()) or np.isnan(e).any():
+            raise ValueError("edges: expected an ascending 1-D array without NaN")
+        edges = torch.from_numpy(e).to(dev)
+    _chk(edges, F32, "edges")
+    if edges.dim() != 1 or edges.numel() + 1 > CTR_CALIB_MAX_BINS:
+        raise ValueError(f"edges: expected [n_bins - 1] with n_bins <= {CTR_CALIB_MAX_BINS}")
+    n_bins = edges.numel() + 1
+    y0, y1 = (float(t) for t in targets)
+    sums = torch.empty((S, 8), dtype=torch.float64, device=dev)
+    counts = torch.empty((S, 2), dtype=torch.int64, device=dev)
+    bins = torch.empty((S, n_bins, 3), dtype=torch.int64, device=dev)
+    if S == 0:
+        return sums, counts, bins
+    nws = lib.mvin_ctr_calib_ws_bytes(S, seg_len)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_ctr_calib_ws_bytes")
+    ws = torch.empty(((nws + 7) // 8,), dtype=torch.int64, device=dev)
+    _lib.check(lib.mvin_ctr_calib(_p(logits), _p(labels), S, seg_len, ld, float(a), float(b), y0, y1,
+                                  _p(edges) if n_bins > 1 else None, n_bins, int(max_groups), _p(ws), _p(sums), _p(counts),
+                                  _p(bins), _stream()), "mvin_ctr_calib")
+    return sums, counts, bins
+
+
+def ctr_calibration_from_sums(sums, counts, bins):
+    """The calibration report of every segment from ctr_calib's three results copied to the host ([S, 8] / [S, 2] /
+    [S, n_bins, 3], or one segment's rows), in float64.  Returns a dict of arrays over the segments: ``logloss`` = sum l / n,
+    ``brier`` = sum r^2 / n, ``mean_pred``, ``base_rate``, ``ne`` = logloss over the entropy of the base rate (NaN with one
+    class), ``ece`` = sum_k (c_k / n) |pos_k / c_k - conf_k / c_k|, ``mce`` = the largest such gap over the non-empty bins,
+    ``n``, and per bin ``bin_count``, ``bin_rate`` and ``bin_conf`` (NaN in empty bins).  A segment with ``bad > 0`` raises
+    ValueError, as ctr_metrics_from_counts does."""
+    import numpy as np
+    s = np.asarray(sums, dtype=np.float64)
+    c = np.asarray(counts).astype(np.int64, copy=False)
+    k = np.asarray(bins).astype(np.int64, copy=False)
+    if s.ndim == 1:
+        s, c, k = s.reshape(1, -1), c.reshape(1, -1), k.reshape((1,) + k.shape)
+    if s.ndim != 2 or s.shape[1] != 8 or c.shape != (s.shape[0], 2) or k.ndim != 3 or k.shape[0] != s.shape[0] or k.shape[2] != 3:
+        raise ValueError(f"expected sums [S, 8], counts [S, 2], bins [S, n_bins, 3]; got {s.shape}, {c.shape}, {k.shape}")
+    bad = c[:, 1]
+    if (bad > 0).any():
+        i = int(np.flatnonzero(bad > 0)[0])
+        raise ValueError(f"segment {i}: {int(bad[i])} non-finite logit(s) or label(s) other than 0 / 1")
+    n = c[:, 0].astype(np.float64)
+    cnt = k[:, :, 0].astype(np.float64)
+    pos = k[:, :, 1].astype(np.float64)
+    conf = k[:, :, 2].astype(np.float64) / CTR_MASS_ONE
+    with np.errstate(divide="ignore", invalid="ignore"):
+        logloss = s[:, 0] / n
+        brier = s[:, 1] / n
+        mean_pred = s[:, 7] / n
+        base = pos.sum(axis=1) / n
+        h = -(base * np.log(base) + (1.0 - base) * np.log1p(-base))
+        ne = np.where((base > 0) & (base < 1), logloss / h, np.nan)
+        rate = np.where(cnt > 0, pos / cnt, np.nan)
+        mconf = np.where(cnt > 0, conf / cnt, np.nan)
+        gap = np.where(cnt > 0, np.abs(rate - mconf), 0.0)
+        ece = (cnt / n[:, None] * gap).sum(axis=1)
+        mce = np.where(n > 0, gap.max(axis=1), np.nan)
+        ece = np.where(n > 0, ece, np.nan)
+    return dict(logloss=logloss, brier=brier, mean_pred=mean_pred, base_rate=base, ne=ne, ece=ece, mce=mce, n=c[:, 0].copy(),
+                bin_count=k[:, :, 0].copy(), bin_rate=rate, bin_conf=mconf)
+
+
+def platt_step(sums, n):
+    """One damped Newton direction of the Platt fit from one segment's ctr_calib sums (a host row of 8) over ``n`` valid pairs.
+    With the loss L(a, b) = sum l / n: gradient g = (sum r z, sum r) / n, Hessian H = [[sum w z^2, sum w z], [sum w z, sum w]] /
+    n.  Returns ``(da, db, slope)``: the direction -H^-1 g and its slope g . d < 0; a Hessian that is singular (det H <= 1e-12
+    H_aa H_bb) or indefinite, or a direction that does not descend, falls back to -g.  A pure host function."""
+    import numpy as np
+    s = np.asarray(sums, dtype=np.float64).reshape(-1)
+    if s.size != 8 or n <= 0:
+        raise ValueError("platt_step: expected one row of 8 sums and n > 0")
+    n = float(n)
+    ga, gb = s[3] / n, s[2] / n
+    haa, hab, hbb = s[6] / n, s[5] / n, s[4] / n
+    det = haa * hbb - hab * hab
+    da, db = -ga, -gb
+    if np.isfinite(det) and haa > 0.0 and hbb > 0.0 and det > 1e-12 * haa * hbb:
+        na, nb = -(hbb * ga - hab * gb) / det, -(haa * gb - hab * ga) / det
+        if np.isfinite(na) and np.isfinite(nb) and ga * na + gb * nb < 0.0:
+            da, db = na, nb
+    return float(da), float(db), float(ga * da + gb * db)
+
+
+def ctr_counts_segments(scores, labels, seg_ptr, threshold=0.5, max_len=None, form=0, out=None):
+    """mvin_ctr_counts_segments: ctr_counts' six integers (int64 [n_seg, 6], ``CTR_COLUMNS``) for the segments
+    ``scores[seg_ptr[s]:seg_ptr[s+1]]`` of a flat f32 buffer with int32 ``labels`` -- the rows of every user of a split, for
+    per-user AUC (gauc_from_counts).  tp / fp count ``score >= threshold`` (0.5 for sigmoid scores, 0 for logits).
+    ``max_len`` and ``form`` are rank_segments' (``max_len=None`` reads the bound from ``seg_ptr``: ONE synchronisation); LIMIT:
+    ``max_len`` <= CTR_SEG_CAP.  Returns ``(counts, status int64 [2])`` (``out``: the same two; status is accumulated): a segment
+    longer than ``max_len`` or with pointers out of order is a row of -1 and is counted in status[0]."""
+    lib = _lib.load()
+    scores, seg_ptr, n_seg, _, _, _, max_len, form = _segments_common(scores, seg_ptr, None, None, max_len, form,
+                                                                      "ctr_counts_segments")
+    _chk(labels, I32, "labels")
+    if labels is None or labels.dim() != 1 or labels.numel() != scores.numel():
+        raise ValueError(f"labels: expected int32 [{scores.numel()}]")
+    if max_len > CTR_SEG_CAP:
+        raise ValueError(f"max_len={max_len}: mvin_ctr_counts_segments takes segments of at most {CTR_SEG_CAP} entries")
+    dev = scores.device
+    if out is None:
+        out = (torch.empty((n_seg, 6), dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+    counts, status = out
+    _chk(counts, torch.int64, "out counts")
+    _chk(status, torch.int64, "out status")
+    if tuple(counts.shape) != (n_seg, 6) or status.numel() != 2:
+        raise ValueError(f"out: expected counts [{n_seg}, 6] and status [2]")
+    T = scores.numel()
+    anyp = _p(seg_ptr)                          # an empty array: any valid pointer, nothing is read or written through it
+    _lib.check(lib.mvin_ctr_counts_segments(_p(scores) if T else None, _p(labels) if T else None, T, _p(seg_ptr), n_seg,
+                                            float(threshold), max_len, form, _p(counts) if n_seg else anyp, _p(status), _stream()),
+               "mvin_ctr_counts_segments")
+    return counts, status
+
+
+def gauc_from_counts(counts):
+    """GAUC from ctr_counts_segments rows (a host array [U, 6], one row per user): a dict of ``weighted`` -- the
+    impression-weighted mean of the users' AUCs, w_u = n_pos + n_neg -- ``mean`` (unweighted), ``users`` (those with both
+    classes, the only ones averaged) and ``skipped_users`` (one class or no rows).  Both means are NaN without such a user.  A
+    row with ``bad > 0`` or a padding row (-1) raises ValueError."""
+    import numpy as np
+    c = np.asarray(counts)
+    if c.ndim == 1:
+        c = c.reshape(1, -1)
+    if c.ndim != 2 or c.shape[1] != 6:
+        raise ValueError(f"counts: expected [U, 6], got {c.shape}")
+    c = c.astype(np.int64, copy=False)
+    if (c[:, 5] != 0).any():
+        u = int(np.flatnonzero(c[:, 5] != 0)[0])
+        raise ValueError(f"segment {u}: " + ("not counted (longer than max_len, or pointers out of order)" if c[u, 5] < 0 else
+                                             f"{int(c[u, 5])} non-finite score(s) or label(s) other than 0 / 1"))
+    n_pos, n_neg, u2 = c[:, 0].astype(np.float64), c[:, 1].astype(np.float64), c[:, 4].astype(np.float64)
+    both = (c[:, 0] > 0) & (c[:, 1] > 0)
+    users = int(both.sum())
+    if users == 0:
+        return dict(weighted=float("nan"), mean=float("nan"), users=0, skipped_users=int(c.shape[0]))
+    auc = u2[both] / (2.0 * n_pos[both] * n_neg[both])
+    w = n_pos[both] + n_neg[both]
+    return dict(weighted=float((w * auc).sum() / w.sum()), mean=float(auc.mean()), users=users,
+                skipped_users=int(c.shape[0]) - users)
+
+
 def _kg_index(index, seeds):
     eptr, edst, erel = index
     _chk(eptr, torch.int64, "eptr")
