@@ -142,8 +142,15 @@ MVIN_API int mvin_gather_attn_fwd(const float* table, const int32_t* adj_entity,
  *     p0 = softmax_n(t0[adj_relation[parent, n]]), p1 = softmax_n(t1[adj_relation[parent, n]])
  *     nagg0[parent] = (1/K) sum_n p0[n] self1[n]   -> neighbors_agg of aggregator (0,.) at hop L-2
  *     nagg1[parent] = (1/K) sum_n p1[n] out1[n]    -> neighbors_agg of aggregator (1,.) at hop L-2
- * (model.py:295-305 with i = 0 and i = 1).  probs_parent [P,K] = p0 and probs_child [P*K,K] = p are
- * optional (model.py:294,304).  table_bf16 = 1: the entity table holds bf16 rows (BASELINE config C5);
+ * (model.py:295-305 with i = 0 and i = 1).  b = parent / parents_per_pair is the parent's query row; an absent bias counts as
+ * zero; an absent logit table (t0 / t1 NULL, each on its own) means slot weights of ONE -- sum_k p[n,k] = K, the plain mean of
+ * aggregators.py:148-152 -- not a softmax of zeros (weights 1/K).  W1 == W2 == NULL (User_orient off, model.py:269: the levels
+ * stay raw embeddings; given together or not at all) in full:
+ *     self1[n] = table[x1[n]]
+ *     Z[n]     = self1[n] + (sum_k p[n,k] table[y[n,k]]) / K
+ * with out1, nagg0 and nagg1 as above; q, b1 and b2 are not read.  A parent id is read as its low 32-bit word, unsigned, and
+ * clamped to n_entity - 1.  probs_parent [P,K] = p0 and probs_child [P*K,K] = p are
+ * optional (model.py:294,304; -2 without t0).  table_bf16 = 1: the entity table holds bf16 rows (BASELINE config C5);
  * arithmetic stays fp32.  Returns -3 when (D, K) is outside the fused kernel's range
  * (D in {16,32,64,128}, K a power of two in [4,256]); callers then use the per-level entry points. */
 MVIN_API int mvin_gather_attn_l2_fwd(const void* table, const int32_t* adj_entity, const int32_t* adj_relation,
@@ -286,7 +293,10 @@ MVIN_API int mvin_score_l2_folded_fwd(const float* ws, const int32_t* enc_entity
  * probs, adjacency and outputs below 2 GiB), 3 = the wave-per-parent kernel for D = 16, K in {4, 8, 16} (the
  * reference's shipped settings: no workgroup phases at all; no probs, table below 4 GiB), 4 = the wave-per-parent
  * kernel for D = 32, K in {8, 16} (BASELINE config C2; same conditions; it takes these shapes ahead of the pipeline).
- * n_parents = B * parents_per_pair.  For tests and benchmarks. */
+ * n_parents = B * parents_per_pair.  For tests and benchmarks.  The query takes no nR: it answers for relation tables that fit
+ * the wave-per-parent kernels' LDS (two logit tables of nR floats beside the waves' tiles in 64 KiB: a few thousand relations).
+ * With more, the launcher gives a call answered 4 to the role-split pipeline (D = 32, K = 16) or the symmetric kernel
+ * (D = 32, K = 8); an answer of 3 always holds (the D = 16 kernel's LDS takes the entry points' limit of 4096 relations). */
 MVIN_API int mvin_gather_attn_l2_variant(int D, int K, int64_t n_parents, int n_entity, int want_probs);     /* fp32 table */
 MVIN_API int mvin_gather_attn_l2_variant_ex(int D, int K, int64_t n_parents, int n_entity, int want_probs, int table_bf16);
 /* Measurement aid: the row gathers of mvin_gather_attn_l2_fwd and nothing else, written the plain way (one wave per
