@@ -519,7 +519,9 @@ typedef struct {
     const int64_t* users;          /*   (mvin_key_addressing_users_fwd); NULL = the per-pair arrays above */
     float* V;                      /* workspace [B, nR, D] */
     float* o_cat;                  /* workspace [B, (P + (h_set_w != NULL)) * D] */
-    int32_t* parents;              /* unused since the depth-2 kernel reads `items` in place; kept for layout */
+    int32_t* parents;              /* workspace, at least one int32.  mvin_score_l2_fwd's folded form (fold_ws, dim 64) keeps a device word in
+                                      parents[0]: 1 + the batch's largest item id (ids clamped as its kernels clamp them), written and read
+                                      on the device by every call, never by the host.  The depth-2 kernels read `items` in place */
     float* nagg0;                  /* workspace [B, D] */
     float* nagg1;
     float* user_o;                 /* out [B, D] */
@@ -562,7 +564,11 @@ typedef struct {
     float* fold_ws;                /* mvin_score_l2_fwd only, or NULL: workspace of mvin_fold_tables_elems(nE, D) floats -- with the encoded
                                       adjacency, User_orient on, an fp32 table and a shape mvin_score_l2_folded_supported takes, everything
                                       above key addressing runs as mvin_fold_tables -> mvin_score_l2_folded_fwd (nagg0 / nagg1 are its
-                                      scratch rows); takes precedence over prj_tables / agg_tables.  Rewritten by every call */
+                                      scratch rows); takes precedence over prj_tables / agg_tables.  Rewritten by every call.  H0 is read
+                                      at a pair's item row only, so this call builds it below 1 + the batch's largest item id alone (dim
+                                      64): after the call the rows of H0 at or above that bound are UNDEFINED -- whatever the workspace held
+                                      -- while TA1 | TA2 | T0A | M0 | G are whole.  A caller that wants whole tables calls mvin_fold_tables;
+                                      MVIN_ITEM_ROWS=0 in the environment builds every row here too */
     int fold_gather;               /* with fold_ws: 1 = the form in which every pair gathers its own rows (mvin_fold_tables_ex without
                                       aggregates -> mvin_score_l2_folded_gather_fwd, in item order when item_order_ws is given) */
 } mvin_score_l2_args;

@@ -749,9 +749,9 @@ static int fold_tables_block(const char* who, const float* t0, const float* W0, 
                                                 (hipStream_t)stream), who);
 }
 
-// H0 | G from the four tables
+// H0 | G from the four tables (rows_s: a device word or NULL -- the rows of H0 below it only, dim 64: EntityAggArgs)
 static int fold_tables_aggregates(const char* who, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, int K, int D,
-                                  int n_entity, int nR, float* ws, void* stream) {
+                                  int n_entity, int nR, float* ws, void* stream, const int32_t* rows_s = nullptr) {
     const size_t tab = (size_t)n_entity * D;
     mvin::EntityAggArgs f{};
     f.tabS = ws;                              // H0[e] = T0A[e] + sum_k w_k TA1[y_k]
@@ -769,13 +769,27 @@ static int fold_tables_aggregates(const char* who, const int32_t* enc_entity, co
     f.nR = nR;
     f.table_bytes = (uint64_t)tab * 4;
     f.adj_bytes = (uint64_t)n_entity * (uint64_t)K * 4;
+    f.rows_s = rows_s;
     return hip_result(mvin::launch_entity_aggregates(f, (hipStream_t)stream), who);
 }
+
+static int fold_tables_impl(const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, const float* W0,
+                            const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0, const float* a0,
+                            const float* Wmix, const float* bmix, const float* A1, int aggregates, int K, int D, int n_entity, int nR, float* ws,
+                            void* stream, const int32_t* rows_s);
 
 int mvin_fold_tables_ex(const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, const float* W0,
                         const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0, const float* a0,
                         const float* Wmix, const float* bmix, const float* A1, int aggregates, int K, int D, int n_entity, int nR, float* ws,
                         void* stream) {
+    return fold_tables_impl(entity_emb, enc_entity, enc_relation, t0, W0, b0, W1, b1, W2, b2, A0, a0, Wmix, bmix, A1, aggregates, K, D, n_entity,
+                            nR, ws, stream, nullptr);      // (a standalone build: every row of every table)
+}
+
+static int fold_tables_impl(const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, const float* W0,
+                            const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0, const float* a0,
+                            const float* Wmix, const float* bmix, const float* A1, int aggregates, int K, int D, int n_entity, int nR, float* ws,
+                            void* stream, const int32_t* rows_s) {
     const char* who = "mvin_fold_tables";
     if (int rc = fold_tables_check(who, entity_emb, enc_entity, enc_relation, W0, W1, W2, A0, Wmix, A1, aggregates, K, D, n_entity, nR, ws)) return rc;
     if (int rc = fold_tables_block(who, t0, W0, b0, W1, b1, W2, b2, A0, a0, Wmix, bmix, A1, K, D, n_entity, ws, stream)) return rc;
@@ -799,7 +813,7 @@ int mvin_fold_tables_ex(const float* entity_emb, const int32_t* enc_entity, cons
         if (int rc = mvin_linear_fwd(&l, stream)) return rc;
     }
     if (!aggregates) return 0;                // (the gather form: per-row tables only, every pair walks its own children)
-    return fold_tables_aggregates(who, enc_entity, enc_relation, t0, K, D, n_entity, nR, ws, stream);
+    return fold_tables_aggregates(who, enc_entity, enc_relation, t0, K, D, n_entity, nR, ws, stream, rows_s);
 }
 
 int mvin_score_l2_folded_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, const int64_t* items_i64,
@@ -1134,6 +1148,9 @@ int mvin_l2_tail_fwd(const void* entity_emb, const int64_t* items_i64, const int
 
 static int flash_prepare_impl(const char* who, const float* entity_emb, const float* relation_kge, const float* w, const float* user_mlp_W,
                               int n_entity, int nR, int D, int P, float* ws, float* fold_ws, void* stream);
+static int group_pairs_impl(const int64_t* users_i64, const int32_t* users_i32, int64_t B, int n_user, int32_t* workspace, int32_t* seg_user,
+                            int32_t* seg_ptr, int32_t* nseg, int32_t* pair_index, void* stream, const int64_t* items64, unsigned max_id,
+                            int32_t* item_rows);
 
 int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
     const char* who = "mvin_score_l2_fwd";
@@ -1171,6 +1188,18 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
     const int fold_form = !fold_ok ? 0 : a->fold_gather ? (fold_gather_applies(D, a->K, a->n_entity, nR, a->B) ? 2 : 0)
                                                         : (fold_applies(D, a->K, a->n_entity, nR, a->B) ? 1 : 0);
     bool fold_built = false;                  // its four tables left the flash form's table launch
+    // ITEM ROWS.  H0 is read at a pair's item row only (score_l2_folded_kernel) and the items are the low entity ids, so the
+    // aggregates launch of the folded form builds H0 below 1 + the batch's largest item id alone: a device word (args->parents[0],
+    // recomputed by every call -- a graph replay over other items included -- and never read by the host), out of the grouping's
+    // own passes over the batch, or of a launch of its own where the batch is not grouped.  Dim 64 (the dim-32 aggregates kernel
+    // writes every row).  MVIN_ITEM_ROWS=0 (read once per process): whole tables from the same binary.
+    static const bool item_rows_on = !(getenv("MVIN_ITEM_ROWS") && atoi(getenv("MVIN_ITEM_ROWS")) == 0);
+    int32_t* const item_rows = fold_form == 1 && D == 64 && item_rows_on ? a->parents : nullptr;
+    const unsigned item_max = (unsigned)(a->n_entity - 1);
+    if (item_rows && !grouped) {
+        rc = hip_result(mvin::launch_item_rows(reinterpret_cast<const int32_t*>(a->items), 2, a->B, item_max, item_rows, (hipStream_t)stream), who);
+        if (rc) return rc;
+    }
     if (grouped) {
         // the batch in user order (device-side counting sort, no host sync), then a user's rows staged once per segment
         int32_t* ws = a->group_ws;
@@ -1178,7 +1207,7 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
         int32_t* seg_ptr = seg_user + a->B;
         int32_t* nseg = seg_ptr + a->B + 2;
         int32_t* pair_index = nseg + 1;
-        rc = mvin_group_pairs_by_user(a->users, nullptr, a->B, a->n_user, ws, seg_user, seg_ptr, nseg, pair_index, stream);
+        rc = group_pairs_impl(a->users, nullptr, a->B, a->n_user, ws, seg_user, seg_ptr, nseg, pair_index, stream, a->items, item_max, item_rows);
         if (rc) return rc;
         if (a->ka_flash && a->user_records && !a->table_bf16 && mvin::key_addr_flash_supported(D, a->P, a->Nm, nR, a->n_entity)) {
             // flash form: per-call tables (R_KGE[r] . E[e], E . Wmlp blocks) from the CURRENT parameters, then ONE barrier-free kernel
@@ -1267,10 +1296,11 @@ int mvin_score_l2_fwd(const mvin_score_l2_args* a, void* stream) {
     if (fold_form == 1) {
         // folded-tail form: four per-entity tables + the aggregates H0 | G from the CURRENT parameters, then two launches per batch
         if (fold_built)
-            rc = fold_tables_aggregates("mvin_fold_tables", a->enc_entity, a->enc_relation, a->t0, a->K, D, a->n_entity, nR, a->fold_ws, stream);
+            rc = fold_tables_aggregates("mvin_fold_tables", a->enc_entity, a->enc_relation, a->t0, a->K, D, a->n_entity, nR, a->fold_ws, stream,
+                                        item_rows);
         else
-            rc = mvin_fold_tables(reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->t0, a->W0, a->b0, a->W1, a->b1,
-                                  a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1, a->K, D, a->n_entity, nR, a->fold_ws, stream);
+            rc = fold_tables_impl(reinterpret_cast<const float*>(a->entity_emb), a->enc_entity, a->enc_relation, a->t0, a->W0, a->b0, a->W1, a->b1,
+                                  a->W2, a->b2, a->A0, a->a0, a->Wmix, a->bmix, a->A1, 1, a->K, D, a->n_entity, nR, a->fold_ws, stream, item_rows);
         if (rc) return rc;
         return mvin_score_l2_folded_fwd(a->fold_ws, a->enc_entity, a->enc_relation, a->items, nullptr, a->t0, a->t1, a->user_o, a->user_o, a->A1,
                                         a->a1, a->Wmix, a->B, a->K, D, a->n_entity, nR, a->nagg0, a->nagg1, a->item_emb, a->scores, a->sig,
@@ -1406,15 +1436,27 @@ int mvin_shard_space_ids(const void* ids, int ids_are_i64, int64_t n, int world,
     return hip_result(mvin::launch_shard_space_ids(ids, ids_are_i64 != 0, n, world, n_local, out, (hipStream_t)stream), who);
 }
 
+// (items64 + item_rows: mvin_score_l2_fwd's device word 1 + the batch's largest item id, out of the grouping's own passes)
+static int group_pairs_impl(const int64_t* users_i64, const int32_t* users_i32, int64_t B, int n_user, int32_t* workspace, int32_t* seg_user,
+                            int32_t* seg_ptr, int32_t* nseg, int32_t* pair_index, void* stream, const int64_t* items64, unsigned max_id,
+                            int32_t* item_rows);
+
 int mvin_group_pairs_by_user(const int64_t* users_i64, const int32_t* users_i32, int64_t B, int n_user, int32_t* workspace,
                              int32_t* seg_user, int32_t* seg_ptr, int32_t* nseg, int32_t* pair_index, void* stream) {
+    return group_pairs_impl(users_i64, users_i32, B, n_user, workspace, seg_user, seg_ptr, nseg, pair_index, stream, nullptr, 0, nullptr);
+}
+
+static int group_pairs_impl(const int64_t* users_i64, const int32_t* users_i32, int64_t B, int n_user, int32_t* workspace, int32_t* seg_user,
+                            int32_t* seg_ptr, int32_t* nseg, int32_t* pair_index, void* stream, const int64_t* items64, unsigned max_id,
+                            int32_t* item_rows) {
     const char* who = "mvin_group_pairs_by_user";
     if ((!users_i64 && !users_i32) || !workspace || !seg_user || !seg_ptr || !nseg || !pair_index)
         return fail(-1, "%s: null pointer", who);
     if (B <= 0 || B > 0x7fffffff || n_user <= 0) return fail(-2, "%s: bad sizes B=%lld n_user=%d", who, (long long)B, n_user);
     return hip_result(mvin::launch_group_pairs(users_i64, users_i32, B, n_user, workspace, workspace + n_user, workspace + 2 * (size_t)n_user,
                                                seg_user, seg_ptr,
-                                               nseg, pair_index, (hipStream_t)stream), who);
+                                               nseg, pair_index, (hipStream_t)stream, reinterpret_cast<const int32_t*>(items64), 2, max_id,
+                                               item_rows), who);
 }
 
 int mvin_key_addressing_grouped_supported(int D, int P, int Nm, int nR) {

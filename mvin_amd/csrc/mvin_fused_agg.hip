@@ -25,6 +25,11 @@ namespace mvin {
 
 // ---- outS | outG over all entities (four entities per wave and step): the aggregates form S0 | G (tabS = T1, no selfS), the
 //      folded-tail form H0 | G (tabS = TA1, selfS = T0A) ----
+// ROWS OF outS (rows_s given: mvin_score_l2_fwd's folded form).  H0 is read at a pair's ITEM row only, and the items are the low
+// entity ids: a wave whose four entities all lie at or above *rows_s (1 + the batch's largest item id, a device word) skips the S
+// half -- the selfS row, the tabS rows and their FMAs, the outS store -- and runs the G half alone, in the same rounds of four and
+// the same FMA order, so every row that is written holds the bits of the whole build.  The test is wave-uniform: the quad that
+// straddles the bound computes all four entities.  Without rows_s the loop compiled is the one without the test.
 template <int K>
 __global__ __launch_bounds__(kAggWaves * 64) void entity_aggregates_kernel(EntityAggArgs a) {
     constexpr int D = 64, SPL = K / 16;
@@ -54,16 +59,19 @@ __global__ __launch_bounds__(kAggWaves * 64) void entity_aggregates_kernel(Entit
     const unsigned n_entity = (unsigned)a.n_entity;
     const unsigned nquad = (n_entity + 3u) >> 2;
 
-    auto run = [&](auto fast_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value;
+    const unsigned rows_s = a.rows_s ? (unsigned)*a.rows_s : n_entity;
+    auto run = [&](auto fast_tag, auto bound_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value, BOUND = decltype(bound_tag)::value;
         for (unsigned quad = blockIdx.x * kAggWaves + wave; quad < nquad; quad += gridDim.x * kAggWaves) {
+            const bool doS = !BOUND || __builtin_amdgcn_readfirstlane(quad * 4u < rows_s ? 1 : 0) != 0;
             const unsigned e = quad * 4u + (unsigned)g;
             const bool valid = e < n_entity;
             unsigned ce[SPL], cr[SPL];
             agg_load_slots<SPL>(adjE, adjR, valid ? (e * (unsigned)K + (unsigned)(SPL * c)) * 4u : kAggOob, ce, cr);
             const unsigned so = valid ? e * (unsigned)(D * 4) + c16 : kAggPadRow;
             const float4 sg = agg_row4(selfG, so);
-            const float4 ss = agg_row4(selfS, so);       // (no selfS: an empty buffer, zeros)
+            float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (doS) ss = agg_row4(selfS, so);           // (no selfS: an empty buffer, zeros)
             float wk[SPL];
             agg_row_weights<SPL, FAST>(cr, att, sT, (unsigned)(a.nR - 1), invK, wk);
             int cc = (int)(cr[0] >> 24);                 // the row's distinct-slot count (in every slot word)
@@ -80,7 +88,8 @@ __global__ __launch_bounds__(kAggWaves * 64) void entity_aggregates_kernel(Entit
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int kmax = __builtin_amdgcn_readfirstlane(agg_xor32_imax(agg_xor16_imax(cc)));
             f32x2 s01 = {0.f, 0.f}, s23 = {0.f, 0.f}, g01 = {0.f, 0.f}, g23 = {0.f, 0.f};
-            for (int k0 = 0; k0 < kmax; k0 += 4) {       // (slots behind a group's own count point beyond the buffers)
+            auto round4 = [&](int k0, auto s_tag) {      // one round of four slots: both halves, or the G half alone
+                constexpr bool S = decltype(s_tag)::value;
                 const uint4 o4 = *reinterpret_cast<const uint4*>(sLo + k0);
                 const float4 w4 = *reinterpret_cast<const float4*>(sLw + k0);
                 const unsigned off[4] = {o4.x, o4.y, o4.z, o4.w};
@@ -88,29 +97,41 @@ __global__ __launch_bounds__(kAggWaves * 64) void entity_aggregates_kernel(Entit
                 float4 r1[4], r2[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    r1[t] = agg_row4(tabS, off[t] + c16);
+                    if constexpr (S) r1[t] = agg_row4(tabS, off[t] + c16);
                     r2[t] = agg_row4(tabG, off[t] + c16);
                 }
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const f32x2 w2 = {ws_[t], ws_[t]};
-                    s01 = __builtin_elementwise_fma(w2, f32x2{r1[t].x, r1[t].y}, s01);
-                    s23 = __builtin_elementwise_fma(w2, f32x2{r1[t].z, r1[t].w}, s23);
+                    if constexpr (S) {
+                        s01 = __builtin_elementwise_fma(w2, f32x2{r1[t].x, r1[t].y}, s01);
+                        s23 = __builtin_elementwise_fma(w2, f32x2{r1[t].z, r1[t].w}, s23);
+                    }
                     g01 = __builtin_elementwise_fma(w2, f32x2{r2[t].x, r2[t].y}, g01);
                     g23 = __builtin_elementwise_fma(w2, f32x2{r2[t].z, r2[t].w}, g23);
                 }
-            }
+            };
+            // (slots behind a group's own count point beyond the buffers)
+            if (doS)
+                for (int k0 = 0; k0 < kmax; k0 += 4) round4(k0, std::true_type{});
+            else
+                for (int k0 = 0; k0 < kmax; k0 += 4) round4(k0, std::false_type{});
             const unsigned oo = valid ? e * (unsigned)(D * 4) + c16 : kAggOob;      // (a store beyond the buffer is dropped)
             const u32x4 vs = {__float_as_uint(s01[0] + ss.x), __float_as_uint(s01[1] + ss.y), __float_as_uint(s23[0] + ss.z),
                               __float_as_uint(s23[1] + ss.w)};
             const u32x4 vg = {__float_as_uint(g01[0] + sg.x), __float_as_uint(g01[1] + sg.y), __float_as_uint(g23[0] + sg.z),
                               __float_as_uint(g23[1] + sg.w)};
-            __builtin_amdgcn_raw_buffer_store_b128(vs, outS, oo, 0, 0);
+            if (doS) __builtin_amdgcn_raw_buffer_store_b128(vs, outS, oo, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b128(vg, outG, oo, 0, 0);
         }
     };
-    if (fast) run(std::true_type{});
-    else run(std::false_type{});
+    if (a.rows_s) {
+        if (fast) run(std::true_type{}, std::true_type{});
+        else run(std::false_type{}, std::true_type{});
+    } else {
+        if (fast) run(std::true_type{}, std::false_type{});
+        else run(std::false_type{}, std::false_type{});
+    }
 }
 
 // ---- nagg0 = S0[x] + c0 u1, nagg1 = sum_c (p1_c / K) relu(G[x_c] + v) per parent: sixteen parents' query terms per wave and batch

@@ -183,6 +183,8 @@ struct EntityAggArgs {
     int n_entity, K, nR;
     uint64_t table_bytes, adj_bytes;
     int D;                     // 64 (0: 64) or 32 (mvin_fused_agg32.hip)
+    const int32_t* rows_s;     // device word or NULL (all rows): only the rows of outS below *rows_s are wanted -- a wave whose four
+                               // entities all lie at or above it leaves outS alone (dim 64; the dim-32 kernel writes every row)
 };
 
 // l2_tail_fold_kernel (mvin_tail.hip): the part of aggregate_delta_whole above the folded pair kernel
@@ -446,8 +448,14 @@ bool fused_split_supported(int D, int K);      // role-split variant (mvin_fused
 bool fused_split_applies(const FusedL2Args& a, int D);
 hipError_t launch_gather_probe_l2(const void* table, const int32_t* ids1, const int32_t* ids2, int64_t n_parents, int K,
                                   int D, int table_bf16, float* sums, hipStream_t st);   // mvin_probe.hip
+// (item_rows given: the device word *item_rows = 1 + the batch's largest item id, ids clamped as the folded score kernels clamp them,
+//  leaves the grouping's own pass over the batch -- see launch_item_rows)
 hipError_t launch_group_pairs(const int64_t* u64, const int32_t* u32, int64_t B, int n_user, int32_t* count, int32_t* offs,
-                              int32_t* rank, int32_t* seg_user, int32_t* seg_ptr, int32_t* nseg, int32_t* pair_index, hipStream_t st);   // mvin_group.hip
+                              int32_t* rank, int32_t* seg_user, int32_t* seg_ptr, int32_t* nseg, int32_t* pair_index, hipStream_t st,
+                              const int32_t* items = nullptr, int item_stride = 1, unsigned max_id = 0, int32_t* item_rows = nullptr);   // mvin_group.hip
+// *item_rows = 1 + max over the batch of min((unsigned)items[i * item_stride], max_id): the rows [0, *item_rows) of a per-entity
+// table are the only ones a pair's ITEM can address.  A memset of the word and one launch; no host synchronisation
+hipError_t launch_item_rows(const int32_t* items, int item_stride, int64_t B, unsigned max_id, int32_t* item_rows, hipStream_t st);
 hipError_t launch_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, hipStream_t st);   // mvin_bwd.hip
 bool fused_d32_supported(int D, int K);        // wave-per-parent variant for D = 32, K in {8, 16} (mvin_fused_d32.hip)
 bool fused_d32_applies(const FusedL2Args& a, int D);
