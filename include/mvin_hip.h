@@ -584,7 +584,21 @@ MVIN_API int mvin_score_l2_fwd(const mvin_score_l2_args* args, void* stream);
  * duplicate-slot encoding (distinct rows only).  group <= 0: chosen from the batch size (1 .. 16 pairs per workgroup).
  * args->depth = 1: the one-hop tree (model.py:286-317 with h_hop = 1: aggregator (0,0) at hop 0, combiner over [ev0 | out0]).
  * D in {16, 32, 64}, K <= 64, P in 1..4, Nm <= 64, fp32 table and adjacency below 4 GiB: -3 otherwise
- * (mvin_score_small_supported). */
+ * (mvin_score_small_supported).
+ * RELATIONS.  A workgroup keeps V[g, r, :] of all nR relations of its pairs in LDS, so nR is limited by the 160 KiB of a
+ * workgroup: the shape is supported while the layout of ONE pair per workgroup with the h-set read fits (the rest of the
+ * layout depends on K, P and Nm; V alone is nR * D floats: nR of about 580 at D = 64, 1150 at D = 32, 2300 at D = 16).
+ * Beyond that mvin_score_small_supported answers 0 and this entry point returns -3 before anything is launched (callers
+ * take mvin_score_l2_fwd).  A `group` whose layout passes 64 KiB is halved until it fits.
+ * IDS, as this kernel reads them:
+ *   items      read WHOLE as unsigned 64-bit numbers and clamped to n_entity - 1: a negative id, or one with a high word
+ *              set, reads the table's LAST row (as mvin_l2_tail_fwd does);
+ *   memories   head and tail ids (mem_h / mem_t, or the uts rows) are 32-bit words clamped UNSIGNED to n_entity - 1: a
+ *              negative id reads the last row;
+ *   relations  the ripple sets' relation ids and the adjacency's are clamped as unsigned words to nR - 1;
+ *   users      (users feed) clamped SIGNED into [0, n_user): a negative id reads user 0, one >= n_user the last user.
+ * adj_relation == NULL (with the plain adjacency): every slot's relation reads as 0, so every relation-attention softmax
+ * is uniform over the K slots (weights 1 / K where t0 / t1 are given, weights of one where they are not). */
 MVIN_API int mvin_score_small_fwd(const mvin_score_l2_args* args, int group, void* stream);
 MVIN_API int mvin_score_small_supported(int D, int K, int P, int Nm, int nR);
 

@@ -1364,7 +1364,8 @@ int mvin_score_small_fwd(const mvin_score_l2_args* a, int group, void* stream) {
     const char* who = "mvin_score_small_fwd";
     if (!a) return fail(-1, "%s: null args", who);
     if (!mvin::score_small_supported(a->D, a->K, a->P, a->Nm, a->n_relation))
-        return fail(-3, "%s: unsupported shape D=%d K=%d P=%d Nm=%d nR=%d", who, a->D, a->K, a->P, a->Nm, a->n_relation);
+        return fail(-3, "%s: unsupported shape D=%d K=%d P=%d Nm=%d nR=%d (or V of nR relations beyond the workgroup's LDS)", who, a->D, a->K,
+                    a->P, a->Nm, a->n_relation);
     if (a->depth < 0 || a->depth > 2) return fail(-2, "%s: depth=%d (1 or 2)", who, a->depth);
     const bool d1 = a->depth == 1;
     if (!a->entity_emb || !a->adj_entity || !a->relation_kge || !a->user_mlp_W || !a->A0 || (!d1 && !a->A1) || !a->Wmix || !a->items ||

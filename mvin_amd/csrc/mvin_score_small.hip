@@ -520,8 +520,10 @@ __global__ __launch_bounds__(D * 4, 2) void score_small_kernel(ScoreSmallArgs a,
             }
         }
         // what did not fit the registers (more relations than RFM per wave, more shared ones than NSH): streamed, one exposed
-        // latency per batch
-        for (int b = RFM * KBN; b < v_nb; ++b) {
+        // latency per batch.  (From the first batch that has no register slot: a wave with fewer whole-relation batches than slots --
+        // nR = 2, 3, 6, 7 at D = 64 -- still has its second and third shared relation to do; starting at RFM * KBN left their
+        // partial sums unwritten and V of those relations was whatever the LDS held.)
+        for (int b = v_bfull < RFM * KBN ? v_bfull : RFM * KBN; b < v_nb; ++b) {
             if (b >= v_bfull && b - v_bfull < NSH) continue;
             ld_rv(b, rR[0]);
             int r, kb;
@@ -1058,13 +1060,6 @@ __global__ __launch_bounds__(D * 4, 2) void score_small_kernel(ScoreSmallArgs a,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-bool score_small_supported(int D, int K, int P, int Nm, int nR) {
-    if (!(D == 16 || D == 32 || D == 64)) return false;
-    const int lpr = D / 4, rpw = 64 / lpr;
-    const int klm = (128 / lpr) < 16 ? (128 / lpr) : 16;
-    return K >= 1 && K <= klm * lpr && K <= 64 && P >= 1 && P <= 4 && Nm >= 1 && Nm <= 16 * rpw && Nm <= 64 && nR >= 1 && nR <= 4096;
-}
-
 // parts a (pair, hop) of the reads stage is cut into (the kernel's SP for the instance this shape takes)
 static int small_parts(int D, int Nm) {
     const int nmt = Nm <= 16 ? 16 : 64, njf = nmt * D / 256;
@@ -1072,6 +1067,19 @@ static int small_parts(int D, int Nm) {
 }
 static SmallLds small_lds_for(int D, int G, int K, int nR, int P, int has_hset, int Nm) {
     return small_lds(D, G, K, nR, P + (has_hset ? 1 : 0), G * (P + (has_hset ? 1 : 0)) * small_parts(D, Nm));
+}
+
+// the launch's LDS limit (gfx950: 160 KiB per workgroup)
+constexpr int kSmallLdsMax = 160 * 1024;
+
+bool score_small_supported(int D, int K, int P, int Nm, int nR) {
+    if (!(D == 16 || D == 32 || D == 64)) return false;
+    const int lpr = D / 4, rpw = 64 / lpr;
+    const int klm = (128 / lpr) < 16 ? (128 / lpr) : 16;
+    if (!(K >= 1 && K <= klm * lpr && K <= 64 && P >= 1 && P <= 4 && Nm >= 1 && Nm <= 16 * rpw && Nm <= 64 && nR >= 1 && nR <= 4096)) return false;
+    // V[g, r, :] of a pair's nR relations is staged in LDS: one pair per workgroup, with the h-set read, must fit the launch's limit
+    // (D = 64: nR of about 580; 32: 1150; 16: 2300 -- the rest of the layout depends on K, P and Nm)
+    return small_lds_for(D, 1, K, nR, P, 1, Nm).total <= kSmallLdsMax;
 }
 
 // pairs per workgroup: enough workgroups to fill the chip (>= 2 per CU while the batch allows), groups as large as the LDS of
@@ -1114,7 +1122,7 @@ hipError_t launch_score_small(ScoreSmallArgs a, int D, hipStream_t st) {
     while (a.G > 1 && (small_lds_for(D, a.G, a.K, a.nR, a.P, a.w_h != nullptr, a.Nm).total > 64 * 1024 || a.G * a.K > 2048))
         a.G /= 2;                                        // a caller's group, as far as it fits
     const SmallLds L = small_lds_for(D, a.G, a.K, a.nR, a.P, a.w_h != nullptr, a.Nm);
-    if (L.total > 160 * 1024) return hipErrorInvalidValue;
+    if (L.total > kSmallLdsMax) return hipErrorInvalidValue;
     static const char* dbg = getenv("MVIN_SMALL_DBG");   // timing experiments only: return after stage N (results are garbage)
     a.dbg = dbg ? atoi(dbg) : 0;
     const int rpw = 64 / (D / 4);

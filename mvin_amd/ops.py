@@ -162,6 +162,63 @@ def score_small_supported(D, K, P, Nm, nR):
     return bool(_lib.load().mvin_score_small_supported(int(D), int(K), int(P), int(Nm), int(nR)))
 
 
+def score_small(entity_emb, adj_entity, adj_relation, relation_kge, h_set_w, user_mlp_W, user_mlp_b, t0, t1, W0, b0, W1, b1, W2, b2,
+                A0, a0, A1, a1, Wmix, bmix, items, *, mem_h=None, mem_r=None, mem_t=None, uts=None, users=None, P, K, nR, depth=2,
+                group=0, enc_entity=None, enc_relation=None, want_item_emb=True, want_sig=True):
+    """mvin_score_small_fwd: the whole get_scores pass as ONE launch, on plain tensors (MVIN._score_small_native fills the same
+    argument block for the model).  Feed: the per-pair lists ``mem_h`` / ``mem_r`` / ``mem_t`` (P int32 tensors [B, Nm] each) or
+    ``uts`` [n_user, P, 3, Nm] int32 + ``users`` [B] int64.  ``adj_relation`` None: every relation reads as 0;
+    ``enc_entity`` / ``enc_relation``: the duplicate-slot encoding (taken instead of the plain adjacency).  Every optional
+    weight or bias may be None (the entry point's own rules decide which combinations it takes); ``depth`` 1 or 2; ``group`` pairs
+    per workgroup (0: chosen from the batch); ``want_item_emb`` / ``want_sig`` False pass NULL for that output.
+    -> (user_o [B, D], item_emb [B, D] | None, scores [B], sigmoid [B] | None)."""
+    lib = _lib.load()
+    _chk(entity_emb, F32, "entity_emb")
+    for t, nm in ((adj_entity, "adj_entity"), (adj_relation, "adj_relation"), (enc_entity, "enc_entity"), (enc_relation, "enc_relation"),
+                  (uts, "uts")):
+        _chk(t, I32, nm)
+    for t, nm in ((relation_kge, "relation_kge"), (h_set_w, "h_set_w"), (user_mlp_W, "user_mlp_W"), (user_mlp_b, "user_mlp_b"), (t0, "t0"),
+                  (t1, "t1"), (W0, "W0"), (b0, "b0"), (W1, "W1"), (b1, "b1"), (W2, "W2"), (b2, "b2"), (A0, "A0"), (a0, "a0"), (A1, "A1"),
+                  (a1, "a1"), (Wmix, "Wmix"), (bmix, "bmix")):
+        _chk(t, F32, nm)
+    _chk(items, torch.int64, "items"), _chk(users, torch.int64, "users")
+    n_entity, D = entity_emb.shape
+    B = items.shape[0]
+    s = _lib.ScoreL2Args()
+    s.entity_emb, s.adj_entity, s.adj_relation = _p(entity_emb), _p(adj_entity), _p(adj_relation)
+    s.enc_entity, s.enc_relation = _p(enc_entity), _p(enc_relation)
+    s.relation_kge, s.h_set_w, s.user_mlp_W, s.user_mlp_b, s.t0, s.t1 = (_p(t) for t in (relation_kge, h_set_w, user_mlp_W, user_mlp_b, t0, t1))
+    s.W0, s.b0, s.W1, s.b1, s.W2, s.b2 = (_p(t) for t in (W0, b0, W1, b1, W2, b2))
+    s.A0, s.a0, s.A1, s.a1, s.Wmix, s.bmix = (_p(t) for t in (A0, a0, A1, a1, Wmix, bmix))
+    s.items = _p(items)
+    hold = None
+    if uts is not None:
+        if users is None or uts.dim() != 4 or uts.shape[1] != max(1, P) or uts.shape[2] != 3:
+            raise ValueError("uts [n_user, P, 3, Nm] needs users [B]")
+        s.uts, s.users, s.n_user, Nm = _p(uts), _p(users), uts.shape[0], uts.shape[3]
+    else:
+        for lst, nm in ((mem_h, "mem_h"), (mem_r, "mem_r"), (mem_t, "mem_t")):
+            if lst is None or len(lst) < P:
+                raise ValueError(f"{nm}: P tensors [B, Nm] (or uts + users)")
+            for t in lst[:P]:
+                _chk(t, I32, nm)
+        arr = C.c_void_p * P
+        hold = tuple(arr(*[t.data_ptr() for t in lst[:P]]) for lst in (mem_h, mem_r, mem_t))
+        s.mem_h, s.mem_r, s.mem_t = (C.addressof(h) for h in hold)
+        Nm = mem_h[0].shape[1]
+    dev = entity_emb.device
+    user_o = torch.empty((B, D), dtype=F32, device=dev)
+    item_emb = torch.empty((B, D), dtype=F32, device=dev) if want_item_emb else None
+    scores = torch.empty(B, dtype=F32, device=dev)
+    sig = torch.empty(B, dtype=F32, device=dev) if want_sig else None
+    s.user_o, s.item_emb, s.scores, s.sig = _p(user_o), _p(item_emb), _p(scores), _p(sig)
+    s.B, s.D, s.K, s.P, s.Nm, s.n_entity, s.n_relation, s.table_bf16, s.depth = B, D, K, P, Nm, n_entity, nR, 0, depth
+    rc = lib.mvin_score_small_fwd(C.byref(s), int(group), _stream())
+    del hold
+    _lib.check(rc, "mvin_score_small_fwd")
+    return user_o, item_emb, scores, sig
+
+
 def gather_attn(table, adj_entity, adj_relation, node_ids, rel_score_t, self_vec, Wc, c_child,
                 Wagg, bagg, B, N, K, D, want_probs=False):
     """mvin_gather_attn_fwd(_ex): deepest hop, children gathered from ``table`` (fp32 or bf16)

@@ -145,6 +145,47 @@ def test_round6_entry_points_validate_before_launching(hip_lib):
     assert rc == -3
 
 
+def test_single_launch_pass_refuses_on_the_host(hip_lib):
+    """mvin_score_small_fwd validates before it launches: each refusal below comes back as a code with nothing but fake pointers given,
+    and the predicate and the entry point agree about the relations a workgroup's LDS holds."""
+    from mvin_amd import _lib
+    from small_cases import small_lds_bytes, small_nr_limit
+    fn, ok = hip_lib.mvin_score_small_fwd, hip_lib.mvin_score_small_supported
+    assert fn(None, 0, None) == -1 and b"null" in hip_lib.mvin_last_error()
+
+    def args(**kw):
+        a = _lib.ScoreL2Args()
+        for name in ("entity_emb", "adj_entity", "adj_relation", "relation_kge", "h_set_w", "user_mlp_W", "user_mlp_b", "t0", "t1", "W0", "b0", "W1",
+                     "b1", "W2", "b2", "A0", "a0", "A1", "a1", "Wmix", "bmix", "items", "uts", "users", "user_o", "item_emb", "scores", "sig"):
+            setattr(a, name, 16)
+        a.B, a.D, a.K, a.P, a.Nm, a.n_entity, a.n_relation, a.n_user, a.depth = 0, 64, 8, 2, 16, 100, 9, 5, 2     # B = 0: refused last, -2
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    call = lambda **kw: fn(C.byref(args(**kw)), 0, None)      # noqa: E731
+    assert call() == -2 and b"bad sizes" in hip_lib.mvin_last_error()          # everything before the sizes passed
+    assert call(D=48) == -3 and call(K=65) == -3 and call(P=5) == -3 and call(P=0) == -3 and call(Nm=65) == -3 and call(n_relation=0) == -3
+    assert b"unsupported shape" in hip_lib.mvin_last_error()
+    assert call(depth=3) == -2 and b"depth" in hip_lib.mvin_last_error()
+    assert call(depth=1, W2=None, b2=None, A1=None, a1=None, t1=None) == -2 and b"bad sizes" in hip_lib.mvin_last_error()
+    assert call(A1=None) == -1
+    assert call(W1=None) == -1 and b"W0 / W1" in hip_lib.mvin_last_error()
+    assert call(W0=None) == -1 and call(W2=None) == -1 and call(W0=None, W1=None, W2=None) == -2
+    assert call(depth=1, W2=None) == -2                        # a one-hop tree has no W2
+    assert call(users=None) == -1 and b"uts + users" in hip_lib.mvin_last_error()
+    assert call(uts=None, users=None) == -1                    # neither feed
+    assert call(table_bf16=1, B=3) == -3 and b"fp32" in hip_lib.mvin_last_error()
+    # the relations a workgroup's LDS holds: V of one pair is nR * D floats beside the rest of the layout
+    for D, K, P, Nm in ((64, 8, 2, 16), (64, 64, 4, 64), (32, 32, 2, 64), (16, 8, 1, 4), (16, 64, 4, 64)):
+        lim = small_nr_limit(D, K, P, Nm)
+        assert 160 * 1024 - 4 * 4 * D < small_lds_bytes(D, 1, K, lim, P + 1, Nm) <= 160 * 1024 < small_lds_bytes(D, 1, K, lim + 1, P + 1, Nm)
+        assert ok(D, K, P, Nm, lim) == 1 and ok(D, K, P, Nm, lim + 1) == 0 and ok(D, K, P, Nm, 4096) == 0
+        assert call(D=D, K=K, P=P, Nm=Nm, n_relation=lim) == -2              # accepted up to the sizes
+        assert call(D=D, K=K, P=P, Nm=Nm, n_relation=lim + 1, B=3) == -3 and b"LDS" in hip_lib.mvin_last_error()
+    assert 500 < small_nr_limit(64, 32, 2, 64) < 640 and 1000 < small_nr_limit(32, 16, 2, 64) < 1280 and 2000 < small_nr_limit(16, 8, 2, 64) < 2560
+
+
 def test_ops_refuse_cpu_tensors(hip_lib):
     import torch
     from mvin_amd import _lib, ops
