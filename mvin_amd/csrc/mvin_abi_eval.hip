@@ -1,0 +1,276 @@
+// extern "C" boundary, evaluation: top-K and exact ranks over rows and segments, KG exploration, the CTR counts and calibration,
+// and the explanations of a score.
+#include "mvin_abi_util.h"
+
+using namespace mvin::abi;
+
+extern "C" {
+
+int mvin_topk_rows_supported(int k) { return mvin::topk_rows_supported(k) ? 1 : 0; }
+
+int64_t mvin_topk_rows_ws_bytes(int64_t rows, int64_t n, int k) {
+    (void)rows;
+    (void)n;
+    (void)k;
+    return 0;                                             // one workgroup per row, everything it keeps sits in LDS
+}
+
+int mvin_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                   const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals, int k, void* ws,
+                   int32_t* out_ids, float* out_vals, void* stream) {
+    (void)ws;
+    const char* who = "mvin_topk_rows";
+    if (!mvin::topk_rows_supported(k)) return fail(-2, "%s: k=%d (1 <= k <= 1024)", who, k);
+    if (rows < 0 || rows >= (int64_t(1) << 31) || n < 0 || n >= (int64_t(1) << 31) || ld < n)
+        return fail(-2, "%s: rows=%lld n=%lld ld=%lld", who, (long long)rows, (long long)n, (long long)ld);
+    if (!out_ids || !out_vals || (n > 0 && !scores)) return fail(-1, "%s: null scores / out_ids / out_vals", who);
+    if ((carry_ids == nullptr) != (carry_vals == nullptr)) return fail(-1, "%s: carry_ids and carry_vals go together", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together", who);
+    if (!cand_ids && (col_offset < 0 || col_offset + n > (int64_t)0x7FFFFFFF))
+        return fail(-2, "%s: col_offset=%lld: implicit ids col_offset + j must be int32", who, (long long)col_offset);
+    return hip_result(mvin::launch_topk_rows(scores, rows, n, ld, cand_ids, col_offset, excl_ptr, excl_ids, carry_ids, carry_vals, k,
+                                             out_ids, out_vals, (hipStream_t)stream),
+                      who);
+}
+
+static bool rank_bad_sizes(int64_t rows, int64_t n) {
+    return rows < 0 || rows >= (int64_t(1) << 31) || n < 0 || n > (int64_t)0x7FFFFFFF;
+}
+
+int64_t mvin_rank_positives_ws_bytes(int64_t rows, int64_t n, int64_t n_pos) {
+    if (rank_bad_sizes(rows, n) || n_pos < 0)
+        return fail(-2, "mvin_rank_positives_ws_bytes: rows=%lld n=%lld n_pos=%lld", (long long)rows, (long long)n, (long long)n_pos);
+    return 0;                                             // one workgroup per row, everything it keeps sits in LDS
+}
+
+int mvin_rank_positives(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
+                        const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* pos_ptr, const int32_t* pos_ids, void* ws,
+                        int32_t* out_counts, float* out_vals, int32_t* out_eligible, void* stream) {
+    (void)ws;                                             // mvin_rank_positives_ws_bytes is 0 for every valid shape
+    const char* who = "mvin_rank_positives";
+    if (rank_bad_sizes(rows, n) || ld < n)
+        return fail(-2, "%s: rows=%lld n=%lld ld=%lld", who, (long long)rows, (long long)n, (long long)ld);
+    if (!pos_ptr || !pos_ids || !out_counts || !out_vals || !out_eligible || (n > 0 && !scores))
+        return fail(-1, "%s: null scores / pos_ptr / pos_ids / out_counts / out_vals / out_eligible", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: null one of excl_ptr / excl_ids (they go together)", who);
+    if (!cand_ids && (col_offset < 0 || col_offset + n > (int64_t)0x7FFFFFFF))
+        return fail(-2, "%s: col_offset=%lld: implicit ids col_offset + j must be int32", who, (long long)col_offset);
+    return hip_result(mvin::launch_rank_positives(scores, rows, n, ld, cand_ids, col_offset, excl_ptr, excl_ids, pos_ptr, pos_ids,
+                                                  out_counts, out_vals, out_eligible, (hipStream_t)stream),
+                      who);
+}
+
+int mvin_segments_wave_cap(void) { return mvin::segments_wave_cap(); }
+
+// what mvin_topk_segments and mvin_rank_segments check alike
+static int segments_bad_args(const char* who, const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg,
+                             const int32_t* ids, const int64_t* excl_ptr, const int32_t* excl_ids, int64_t max_len, int form,
+                             const int64_t* status) {
+    if (n_seg < 0 || n_seg >= (int64_t(1) << 31) || total < 0 || max_len < 0 || max_len > (int64_t)0x7FFFFFFF)
+        return fail(-2, "%s: n_seg=%lld total=%lld max_len=%lld", who, (long long)n_seg, (long long)total, (long long)max_len);
+    if (form < 0 || form > 2) return fail(-2, "%s: form=%d (0 automatic, 1 wave, 2 block)", who, form);
+    if (form == 1 && max_len > mvin::segments_wave_cap())
+        return fail(-2, "%s: form=1 (wave) takes max_len <= %d, got %lld", who, mvin::segments_wave_cap(), (long long)max_len);
+    if (!seg_ptr || !status || (total > 0 && !scores)) return fail(-1, "%s: null scores / seg_ptr / status", who);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: null one of excl_ptr / excl_ids (they go together)", who);
+    if (excl_ptr && !ids) return fail(-1, "%s: null ids with exclusions (an exclusion row names item ids)", who);
+    return 0;
+}
+
+int mvin_topk_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                       const int64_t* excl_ptr, const int32_t* excl_ids, int k, int64_t max_len, int form, int32_t* out_pos,
+                       float* out_vals, int32_t* out_ids, int64_t* status, void* stream) {
+    const char* who = "mvin_topk_segments";
+    if (!mvin::topk_rows_supported(k)) return fail(-2, "%s: k=%d (1 <= k <= 1024)", who, k);
+    if (const int rc = segments_bad_args(who, scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, max_len, form, status)) return rc;
+    if (!out_pos || !out_vals || (ids && !out_ids)) return fail(-1, "%s: null out_pos / out_vals (/ out_ids with ids)", who);
+    return hip_result(mvin::launch_topk_segments(scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, k, max_len, form, out_pos,
+                                                 out_vals, ids ? out_ids : nullptr, status, (hipStream_t)stream),
+                      who);
+}
+
+int mvin_rank_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                       const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* q_ptr, const int32_t* q_pos, int64_t n_q,
+                       int64_t max_len, int form, int32_t* out_counts, float* out_vals, int32_t* out_eligible, int64_t* status,
+                       void* stream) {
+    const char* who = "mvin_rank_segments";
+    if (n_q < 0) return fail(-2, "%s: n_q=%lld", who, (long long)n_q);
+    if (const int rc = segments_bad_args(who, scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, max_len, form, status)) return rc;
+    if (!q_ptr || !out_eligible || (n_q > 0 && (!q_pos || !out_counts || !out_vals)))
+        return fail(-1, "%s: null q_ptr / q_pos / out_counts / out_vals / out_eligible", who);
+    return hip_result(mvin::launch_rank_segments(scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, q_ptr, q_pos, n_q, max_len,
+                                                 form, out_counts, out_vals, out_eligible, status, (hipStream_t)stream),
+                      who);
+}
+
+static bool kg_bad_sizes(int64_t n_entity, int64_t M) {
+    return n_entity < 0 || n_entity > (int64_t)0x7FFFFFFF || M < 0 || M > (int64_t)0x7FFFFFFF;
+}
+
+int64_t mvin_kg_explore_ws_bytes(int64_t n_entity, int64_t M) {
+    if (kg_bad_sizes(n_entity, M)) return fail(-2, "mvin_kg_explore_ws_bytes: n_entity=%lld M=%lld", (long long)n_entity, (long long)M);
+    return mvin::kg_explore_ws_bytes((int)n_entity, M);
+}
+
+int mvin_kg_field(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int64_t n_entity, int64_t M, const int32_t* seeds,
+                  int64_t n_seed, int hops, void* ws, uint32_t* field_bits, int64_t* out_counts, void* stream) {
+    const char* who = "mvin_kg_field";
+    if (kg_bad_sizes(n_entity, M) || n_seed < 0 || hops < 1 || hops > 8)
+        return fail(-2, "%s: n_entity=%lld M=%lld n_seed=%lld hops=%d (hops in 1..8, sizes within int32)", who, (long long)n_entity,
+                    (long long)M, (long long)n_seed, hops);
+    if (!eptr || !out_counts || (n_seed > 0 && !seeds)) return fail(-1, "%s: null eptr / seeds / out_counts", who);
+    if (M > 0 && (!edst || !erel || !ws || !field_bits)) return fail(-1, "%s: null edst / erel / ws / field_bits with M=%lld", who, (long long)M);
+    return hip_result(mvin::launch_kg_field(eptr, edst, erel, (int)n_entity, M, seeds, n_seed, hops, ws, field_bits, out_counts,
+                                            (hipStream_t)stream), who);
+}
+
+int mvin_kg_explore(const int64_t* eptr, const int32_t* edst, const int32_t* erel, int64_t n_entity, int64_t M,
+                    const int32_t* adj_entity, const int32_t* adj_relation, int K, const int32_t* seeds, int64_t n_seed, int hops,
+                    void* ws, uint32_t* explored_bits, int64_t* out_counts, void* stream) {
+    const char* who = "mvin_kg_explore";
+    if (kg_bad_sizes(n_entity, M) || n_seed < 0 || hops < 1 || hops > 8 || K < 1)
+        return fail(-2, "%s: n_entity=%lld M=%lld n_seed=%lld hops=%d K=%d (hops in 1..8, K >= 1, sizes within int32)", who,
+                    (long long)n_entity, (long long)M, (long long)n_seed, hops, K);
+    if (!eptr || !out_counts || (n_seed > 0 && !seeds) || !adj_entity || !adj_relation)
+        return fail(-1, "%s: null eptr / seeds / adj_entity / adj_relation / out_counts", who);
+    if (M > 0 && (!edst || !erel || !ws || !explored_bits))
+        return fail(-1, "%s: null edst / erel / ws / explored_bits with M=%lld", who, (long long)M);
+    return hip_result(mvin::launch_kg_explore(eptr, edst, erel, (int)n_entity, M, adj_entity, adj_relation, K, seeds, n_seed, hops, ws,
+                                              explored_bits, out_counts, (hipStream_t)stream), who);
+}
+
+static bool ctr_bad_sizes(int64_t n_seg, int64_t seg_len) {     // also: at most 2^40 pairs in all
+    return seg_len < 1 || seg_len > (int64_t)0x7FFFFFFF || n_seg < 0 || n_seg > ((int64_t)1 << 40) / seg_len;
+}
+
+int64_t mvin_ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len) {
+    if (ctr_bad_sizes(n_seg, seg_len)) return fail(-2, "mvin_ctr_counts_ws_bytes: n_seg=%lld seg_len=%lld", (long long)n_seg, (long long)seg_len);
+    return mvin::ctr_counts_ws_bytes(n_seg, seg_len);
+}
+
+int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws, int64_t* out,
+                    void* stream) {
+    const char* who = "mvin_ctr_counts";
+    if (ctr_bad_sizes(n_seg, seg_len) || ld < seg_len)
+        return fail(-2, "%s: n_seg=%lld seg_len=%lld ld=%lld", who, (long long)n_seg, (long long)seg_len, (long long)ld);
+    if (!scores || !labels || !out) return fail(-1, "%s: null scores / labels / out", who);
+    if (!ws && n_seg > 0 && mvin::ctr_counts_ws_bytes(n_seg, seg_len) > 0)
+        return fail(-1, "%s: null ws (seg_len=%lld needs mvin_ctr_counts_ws_bytes)", who, (long long)seg_len);
+    return hip_result(mvin::launch_ctr_counts(scores, labels, n_seg, seg_len, ld, ws, out, (hipStream_t)stream), who);
+}
+
+int64_t mvin_ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len) {
+    if (ctr_bad_sizes(n_seg, seg_len)) return fail(-2, "mvin_ctr_calib_ws_bytes: n_seg=%lld seg_len=%lld", (long long)n_seg, (long long)seg_len);
+    return mvin::ctr_calib_ws_bytes(n_seg, seg_len);
+}
+
+int mvin_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b, double y0,
+                   double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums, int64_t* out_counts,
+                   int64_t* out_bins, void* stream) {
+    const char* who = "mvin_ctr_calib";
+    if (ctr_bad_sizes(n_seg, seg_len) || ld < seg_len)
+        return fail(-2, "%s: n_seg=%lld seg_len=%lld ld=%lld", who, (long long)n_seg, (long long)seg_len, (long long)ld);
+    if (n_bins < 1 || n_bins > MVIN_CTR_CALIB_MAX_BINS || max_groups < 0)
+        return fail(-2, "%s: n_bins=%d (1..%d) max_groups=%d (>= 0)", who, n_bins, MVIN_CTR_CALIB_MAX_BINS, max_groups);
+    if (!logits || !labels || !out_sums || !out_counts || !out_bins) return fail(-1, "%s: null logits / labels / out_sums / out_counts / out_bins", who);
+    if (!edges && n_bins > 1) return fail(-1, "%s: null edges with n_bins=%d", who, n_bins);
+    if (!ws && n_seg > 0) return fail(-1, "%s: null ws (mvin_ctr_calib_ws_bytes)", who);
+    return hip_result(mvin::launch_ctr_calib(logits, labels, n_seg, seg_len, ld, a, b, y0, y1, edges, n_bins, max_groups, ws, out_sums,
+                                             out_counts, out_bins, (hipStream_t)stream), who);
+}
+
+int mvin_ctr_counts_segments(const float* scores, const int32_t* labels, int64_t total, const int64_t* seg_ptr, int64_t n_seg,
+                             float threshold, int64_t max_len, int form, int64_t* out, int64_t* status, void* stream) {
+    const char* who = "mvin_ctr_counts_segments";
+    if (n_seg < 0 || n_seg >= (int64_t(1) << 31) || total < 0 || max_len < 0 || max_len > MVIN_CTR_SEG_CAP)
+        return fail(-2, "%s: n_seg=%lld total=%lld max_len=%lld (max_len <= %d)", who, (long long)n_seg, (long long)total,
+                    (long long)max_len, MVIN_CTR_SEG_CAP);
+    if (form < 0 || form > 2) return fail(-2, "%s: form=%d (0 automatic, 1 lane group, 2 workgroup)", who, form);
+    if (form == 1 && max_len > mvin::segments_wave_cap())
+        return fail(-2, "%s: form=1 (lane group) takes max_len <= %d, got %lld", who, mvin::segments_wave_cap(), (long long)max_len);
+    if (threshold != threshold) return fail(-2, "%s: threshold is NaN", who);
+    if (!seg_ptr || !status || (n_seg > 0 && !out) || (total > 0 && (!scores || !labels)))
+        return fail(-1, "%s: null scores / labels / seg_ptr / out / status", who);
+    return hip_result(mvin::launch_ctr_counts_segments(scores, labels, total, seg_ptr, n_seg, threshold, max_len, form, out, status,
+                                                       (hipStream_t)stream), who);
+}
+
+int mvin_explain_paths_max_k(void) { return mvin::explain_paths_max_k(); }
+
+int mvin_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0, const int32_t* ent1, const int32_t* rel1,
+                       const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths, int64_t* out_mass,
+                       int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, int64_t* rel_mass, void* stream) {
+    const char* who = "mvin_explain_paths";
+    if (!imp0 || !rel0 || !ent1 || !out_paths || !out_mass || !out_slot || !out_distinct || !out_total)
+        return fail(-1, "%s: null pointer (imp0 / rel0 / ent1 / out_paths / out_mass / out_slot / out_distinct / out_total)", who);
+    const int given = (imp1 != nullptr) + (rel1 != nullptr) + (ent2 != nullptr);
+    if (given != 0 && given != 3) return fail(-1, "%s: imp1 / rel1 / ent2 go together (all three, or none for one-hop mode)", who);
+    if (K < 1 || K > mvin::explain_paths_max_k()) return fail(-2, "%s: K=%d (1..%d)", who, K, mvin::explain_paths_max_k());
+    const int N = given ? K * K : K;
+    if (top < 1 || top > N) return fail(-2, "%s: top=%d (1..%d: K*K, or K in one-hop mode)", who, top, N);
+    if (B < 0 || B * K * K >= (int64_t(1) << 31)) return fail(-2, "%s: B=%lld with K=%d (0 <= B, B*K*K < 2^31)", who, (long long)B, K);
+    if (n_relation < 0 || n_relation >= (1 << 25)) return fail(-2, "%s: n_relation=%d (0 .. 2^25 - 1)", who, n_relation);
+    if (rel_mass && (n_relation < 1 || B * K * K > (int64_t(1) << 22)))
+        return fail(-2, "%s: rel_mass takes n_relation >= 1 and B*K*K <= 2^22 per call, got n_relation=%d B=%lld K=%d", who, n_relation,
+                    (long long)B, K);
+    return hip_result(mvin::launch_explain_paths(imp0, imp1, rel0, ent1, rel1, ent2, B, K, top, n_relation, out_paths, out_mass,
+                                                 out_slot, out_distinct, out_total, rel_mass, (hipStream_t)stream), who);
+}
+
+int mvin_explain_memories_max_nm(void) { return mvin::explain_memories_max_nm(); }
+
+int mvin_explain_memories(const float* entity_emb, const float* V, const float* w_h, const int32_t* uts, const int64_t* users,
+                          const float* G, const float* mlp_bias, const float* item_final, int64_t B, int P, int Nm, int D, int nR,
+                          int n_entity, int n_user, int top, int32_t* out_mem, int64_t* out_mass, float* out_contrib,
+                          int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, float* out_block, float* out_bias,
+                          float* out_probs, float* out_slot_contrib, int64_t* rel_mass, void* stream) {
+    const char* who = "mvin_explain_memories";
+    if (!entity_emb || !uts || !users || !G || !mlp_bias || !item_final || !out_mem || !out_mass || !out_contrib || !out_slot ||
+        !out_distinct || !out_total || !out_block || !out_bias)
+        return fail(-1, "%s: null pointer (entity_emb / uts / users / G / mlp_bias / item_final / a required output)", who);
+    if (P < 0 || P > 8) return fail(-2, "%s: P=%d (0..8)", who, P);
+    if (P >= 1 && !V) return fail(-1, "%s: null pointer (V with P=%d hop blocks)", who, P);
+    const int n_o = P + (w_h ? 1 : 0);
+    if (n_o < 1) return fail(-2, "%s: no block to explain (P=0 and no w_h)", who);
+    const int max_nm = mvin::explain_memories_max_nm();
+    if (Nm < 1 || Nm > max_nm) return fail(-2, "%s: Nm=%d (1..%d)", who, Nm, max_nm);
+    if (D < 4 || D > 128 || (D & 3) != 0) return fail(-2, "%s: D=%d (a multiple of 4, 4..128)", who, D);
+    if (top < 1 || top > Nm) return fail(-2, "%s: top=%d (1..Nm = %d)", who, top, Nm);
+    if (B < 0 || B * n_o * Nm >= (int64_t(1) << 31))
+        return fail(-2, "%s: B=%lld with n_o=%d Nm=%d (0 <= B, B*n_o*Nm < 2^31)", who, (long long)B, n_o, Nm);
+    if (n_entity < 1 || n_user < 1 || (P >= 1 && nR < 1))
+        return fail(-2, "%s: n_entity=%d n_user=%d nR=%d (each >= 1)", who, n_entity, n_user, nR);
+    if (rel_mass && (P < 1 || B * Nm > (int64_t(1) << 22)))
+        return fail(-2, "%s: rel_mass takes P >= 1 and B*Nm <= 2^22 per call, got P=%d B=%lld Nm=%d", who, P, (long long)B, Nm);
+    mvin::ExplainMemArgs a;
+    a.entity_emb = entity_emb;
+    a.V = V;
+    a.w_h = w_h;
+    a.uts = uts;
+    a.users = reinterpret_cast<const long long*>(users);
+    a.G = G;
+    a.mlp_bias = mlp_bias;
+    a.item_final = item_final;
+    a.B = B;
+    a.P = P;
+    a.Nm = Nm;
+    a.D = D;
+    a.nR = nR;
+    a.n_entity = n_entity;
+    a.n_user = n_user;
+    a.top = top;
+    a.out_mem = out_mem;
+    a.out_mass = reinterpret_cast<long long*>(out_mass);
+    a.out_contrib = out_contrib;
+    a.out_slot = out_slot;
+    a.out_distinct = out_distinct;
+    a.out_total = reinterpret_cast<long long*>(out_total);
+    a.out_block = out_block;
+    a.out_bias = out_bias;
+    a.out_probs = out_probs;
+    a.out_slot_contrib = out_slot_contrib;
+    a.rel_mass = reinterpret_cast<unsigned long long*>(rel_mass);
+    return hip_result(mvin::launch_explain_memories(a, (hipStream_t)stream), who);
+}
+
+}  // extern "C"

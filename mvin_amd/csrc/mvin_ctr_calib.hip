@@ -211,7 +211,7 @@ int64_t ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len) {
     return (nch > 1 ? n_seg * nch : 1) * (int64_t)sizeof(CalibPartial);       // never 0: one rule for the caller's pointer
 }
 
-// sizes as mvin_ctr_counts', 1 <= n_bins <= kCalibMaxBins, max_groups >= 0 (checked by the caller, mvin_abi.hip)
+// sizes as mvin_ctr_counts', 1 <= n_bins <= kCalibMaxBins, max_groups >= 0 (checked by the caller, mvin_abi_eval.hip)
 hipError_t launch_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double ca, double cb,
                             double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums,
                             int64_t* out_counts, int64_t* out_bins, hipStream_t st) {

@@ -368,7 +368,7 @@ static int64_t explain_max_blocks() {
     return v < 1 ? 1 : (v > kExplainMaxBlocks ? kExplainMaxBlocks : v);
 }
 
-// 1 <= K <= 64, 1 <= top <= N, B * K * K < 2^31, imp1 / rel1 / ent2 all given or all NULL (checked by the caller, mvin_abi.hip)
+// 1 <= K <= 64, 1 <= top <= N, B * K * K < 2^31, imp1 / rel1 / ent2 all given or all NULL (checked by the caller, mvin_abi_eval.hip)
 hipError_t launch_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0, const int32_t* ent1, const int32_t* rel1,
                                 const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths,
                                 int64_t* out_mass, int32_t* out_slot, int32_t* out_distinct, int64_t* out_total, int64_t* rel_mass,

@@ -166,7 +166,7 @@ static int64_t explain_mem_max_blocks(int64_t planned) {
     return v < 1 ? 1 : (v < planned ? v : planned);
 }
 
-// sizes are checked by the caller (mvin_abi.hip)
+// sizes are checked by the caller (mvin_abi_eval.hip)
 hipError_t launch_explain_memories(const ExplainMemArgs& a, hipStream_t st) {
     const int n_o = a.P + (a.w_h != nullptr ? 1 : 0);
     const int64_t n_tasks = a.B * n_o;

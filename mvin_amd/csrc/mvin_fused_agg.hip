@@ -20,6 +20,7 @@
 // the 16-lane row; the (row offset, weight) list of its distinct slots through LDS, read back as broadcasts) -- no exchange between
 // groups, full-wave stores.
 #include "mvin_fused_agg.h"
+#include "mvin_workspaces.h"
 
 namespace mvin {
 
@@ -911,12 +912,7 @@ __global__ void fold_prepare_kernel(const float* __restrict__ W0, const float* _
                                     const float* __restrict__ A0, const float* __restrict__ a0, const float* __restrict__ Wmix,
                                     const float* __restrict__ bmix, const float* __restrict__ A1, float c, int D, float* __restrict__ blk) {
     const int i = blockIdx.x, j = threadIdx.x;
-    float* Wstack = blk;
-    float* Wv = blk + (size_t)4 * D * D;
-    float* Wq = Wv + (size_t)D * D;
-    float* bv = Wq + (size_t)D * D;
-    float* bq = bv + D;
-    float* bm = bq + D;
+    const FoldBlock L(D);                                // (mvin_workspaces.h: the layout the host hands on to the next launches)
     if (j >= D) return;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, sm = 0.f;
     for (int k0 = 0; k0 < D; k0 += 8) {                  // (eight steps' operands loaded before their FMAs)
@@ -938,28 +934,27 @@ __global__ void fold_prepare_kernel(const float* __restrict__ W0, const float* _
         }
     }
     if (i < D) {
-        Wstack[(size_t)i * D + j] = s1;
-        Wstack[(size_t)D * D + (size_t)i * D + j] = s2;
-        Wstack[(size_t)2 * D * D + (size_t)i * D + j] = s0;
-        Wstack[(size_t)3 * D * D + (size_t)i * D + j] = sm;
-        Wv[(size_t)i * D + j] = fmaf(c, s2, s1);
-        Wq[(size_t)i * D + j] = fmaf(c, s1, s0);
+        const size_t ij = (size_t)i * D + j;
+        blk[L.Wstack(0) + ij] = s1;
+        blk[L.Wstack(1) + ij] = s2;
+        blk[L.Wstack(2) + ij] = s0;
+        blk[L.Wstack(3) + ij] = sm;
+        blk[L.Wv() + ij] = fmaf(c, s2, s1);
+        blk[L.Wq() + ij] = fmaf(c, s1, s0);
         if (D == 64 || D == 32) {
-            float* Wperm = bm + D;
             const size_t o = (size_t)i * D + (size_t)(j & 15) * (D / 16) + (size_t)(j >> 4);
-            const size_t DD = (size_t)D * D;
-            Wperm[o] = fmaf(c, s1, s0);
-            Wperm[DD + o] = fmaf(c, s2, s1);
-            Wperm[2 * DD + o] = sm;
-            Wperm[3 * DD + o] = A1[(size_t)i * D + j];
-            Wperm[4 * DD + o] = Wmix[DD + (size_t)i * D + j];
-            Wperm[5 * DD + o] = Wmix[2 * DD + (size_t)i * D + j];
+            blk[L.Wperm(0) + o] = fmaf(c, s1, s0);
+            blk[L.Wperm(1) + o] = fmaf(c, s2, s1);
+            blk[L.Wperm(2) + o] = sm;
+            blk[L.Wperm(3) + o] = A1[ij];
+            blk[L.Wperm(4) + o] = Wmix[L.DD + ij];           // Wm1, Wm2: the second and third D rows of Wmix [3 D, D]
+            blk[L.Wperm(5) + o] = Wmix[2 * L.DD + ij];
         }
     } else {
         const float av0 = a0 ? a0[j] : 0.f;
-        bv[j] = fmaf(c, s2, s1) + av0;
-        bq[j] = fmaf(c, s1, s0) + av0;
-        bm[j] = (bmix ? bmix[j] : 0.f) + sm;
+        blk[L.bv() + j] = fmaf(c, s2, s1) + av0;
+        blk[L.bq() + j] = fmaf(c, s1, s0) + av0;
+        blk[L.bm() + j] = (bmix ? bmix[j] : 0.f) + sm;
     }
 }
 

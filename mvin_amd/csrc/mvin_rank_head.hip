@@ -177,7 +177,7 @@ static hipError_t rank_head_launch(RankHeadArgs a, hipStream_t st) {
     return hipSuccess;
 }
 
-// G in [2, 64], D % 4 == 0, 4 <= D <= 128 (checked by the caller, mvin_abi.hip)
+// G in [2, 64], D % 4 == 0, 4 <= D <= 128 (checked by the caller, mvin_abi_train.hip)
 hipError_t launch_rank_head(const float* user_o, const float* item_emb, const float* valid, const float* offset, int64_t n_groups,
                             int G, int D, int mode, float scale, float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts,
                             hipStream_t st) {

@@ -394,7 +394,7 @@ static SegArgs seg_args(const float* scores, int64_t total, const int64_t* seg_p
     return a;
 }
 
-// k in [1, 1024], 0 <= n_seg < 2^31, 0 <= max_len < 2^31, form 1 only with max_len <= the cap (checked by the caller, mvin_abi.hip)
+// k in [1, 1024], 0 <= n_seg < 2^31, 0 <= max_len < 2^31, form 1 only with max_len <= the cap (checked by the caller, mvin_abi_eval.hip)
 hipError_t launch_topk_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
                                 const int64_t* excl_ptr, const int32_t* excl_ids, int k, int64_t max_len, int form, int32_t* out_pos,
                                 float* out_vals, int32_t* out_ids, int64_t* status, hipStream_t st) {

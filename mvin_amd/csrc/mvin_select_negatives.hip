@@ -150,7 +150,7 @@ static hipError_t select_negatives_launch(const SelectArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-// Gp in [2, 64], 1 <= n_neg <= shortlist <= Gp - 1, n_groups >= 0 (checked by the caller, mvin_abi.hip)
+// Gp in [2, 64], 1 <= n_neg <= shortlist <= Gp - 1, n_groups >= 0 (checked by the caller, mvin_abi_train.hip)
 hipError_t launch_select_negatives(const float* scores, const int64_t* items, const float* valid, const int64_t* group_key,
                                    int64_t n_groups, int Gp, int n_neg, int shortlist, uint64_t seed, uint64_t round,
                                    int64_t* out_items, float* out_valid, float* out_scores, int64_t* counts, hipStream_t st) {

@@ -1043,7 +1043,7 @@ class MVIN(object):
         if ws is None:        # reused across calls of the same batch size ON THE SAME STREAM (which orders the reuse)
             f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
             # grouped key addressing needs no [B, nR, D] item projection; its sort workspace instead
-            gws = torch.empty(2 * uts.shape[0] + 4 * B + 3, dtype=torch.int32, device=self.device) if grouped else None
+            gws = torch.empty(ops.score_group_ws_elems(uts.shape[0], B), dtype=torch.int32, device=self.device) if grouped else None
             ows = None                    # (the item-order workspace: allocated when first wanted, below)
             ws = self._native_l2_ws[wkey] = (None if grouped else f(B, self.n_relation, D), f(B, n_o * D),
                                              torch.empty(B, dtype=torch.int32, device=self.device), f(B, D), f(B, D), gws, ows)

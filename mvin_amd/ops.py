@@ -1432,6 +1432,19 @@ def key_addressing_grouped_supported(D, P, Nm, nR):
     return bool(_lib.load().mvin_key_addressing_grouped_supported(D, P, Nm, nR))
 
 
+def group_sort_ws_elems(n_user, B):
+    """int32 words of mvin_group_pairs_by_user's workspace: counters [n_user] | offsets [n_user] | per-pair ranks [B]
+    (GroupWs::sort_elems, csrc/mvin_workspaces.h)."""
+    return 2 * n_user + B
+
+
+def score_group_ws_elems(n_user, B):
+    """int32 words of mvin_score_l2_args.group_ws, the rule include/mvin_hip.h documents (GroupWs::elems, csrc/mvin_workspaces.h):
+    the sort's workspace, then seg_user [B] | seg_ptr [B + 2] | nseg [1] | pair_index [B].  The library exports no function for
+    it, so this is the one place on the Python side that states it."""
+    return group_sort_ws_elems(n_user, B) + B + (B + 2) + 1 + B
+
+
 def group_pairs_by_user(users, n_user=None):
     """Segments of a batch in user order, built on the device with static shapes (no host sync, graph-capturable):
     returns (seg_user [B] int32, seg_ptr [B+2] int32, nseg [1] int32, pair_index [B] int32); only the first
@@ -1440,7 +1453,7 @@ def group_pairs_by_user(users, n_user=None):
     B = users.shape[0]
     if n_user is not None and users.is_cuda and users.dtype in (torch.int64, I32) and users.is_contiguous():
         dev = users.device
-        ws = torch.empty(2 * n_user + B, dtype=I32, device=dev)      # counters | offsets | per-pair ranks
+        ws = torch.empty(group_sort_ws_elems(n_user, B), dtype=I32, device=dev)
         seg_user = torch.empty(B, dtype=I32, device=dev)
         seg_ptr = torch.empty(B + 2, dtype=I32, device=dev)
         nseg = torch.empty(1, dtype=I32, device=dev)

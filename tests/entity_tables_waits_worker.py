@@ -81,7 +81,9 @@ def run_case(name):
     buf, ws = _poisoned(n3)
     ops.fold_tables(E, enc_e, enc_r, t0, m[0], b[0], m[1], b[1], m[2], b[2], m[3], b[3], Wmix, b[4], m[4], K, nR, out=ws)
     torch.cuda.synchronize()
-    Wstack = ws[6 * tab:6 * tab + 4 * D * D].view(4, D, D).clone()
+    # the parameter block sits behind everything that grows with n_entity (the tables and aggregates); Wstack [4][D][D] heads it
+    blk = (lib.mvin_fold_tables_elems(2, D) - lib.mvin_fold_tables_elems(1, D)) * nE
+    Wstack = ws[blk:blk + 4 * D * D].view(4, D, D).clone()
     fold = ws[:4 * tab].view(4, nE, D)
     _assert_tables(fold, E, list(Wstack), f"{name}: folded tables")
     assert bool(torch.isfinite(ws[4 * tab:]).all()), f"{name}: aggregates and parameter block"
