@@ -900,6 +900,46 @@ MVIN_API int mvin_rank_segments(const float* scores, int64_t total, const int64_
                                 int64_t n_q, int64_t max_len, int form, int32_t* out_counts /* [n_q,3] */,
                                 float* out_vals /* [n_q] */, int32_t* out_eligible /* [n_seg] */, int64_t* status, void* stream);
 
+/* ---- per-user candidate lists: diversity-aware reranking, greedy maximal marginal relevance (MMR) --
+ * mvin_mmr_segments: segments, `ids`, the exclusion CSR, `max_len`, `form` and `status` mean exactly what they mean for
+ * mvin_topk_segments, with two differences: `ids` is required, an entry's id being its row in the feature table `feat` (f32,
+ * n_rows rows of D floats, row r at feat + r * ld; never written); and an entry is also ineligible when its id is >= n_rows, so
+ * no row outside the table is ever read.
+ * Similarity: sim(c, j) = dot(feat[id_c], feat[id_j]), times row_scale[id_c] * row_scale[id_j] when `row_scale` ([n_rows] f32)
+ * is given.  mvin_row_inv_norms writes out[r] = 1 / max(||feat[r]||, eps) (the sum of squares and the root in f64, rounded to
+ * f32 once), which makes the similarity a cosine.
+ * Rule, for step t = 0 .. k-1 over the eligible entries not yet picked: p_c = 0 at t = 0, otherwise the maximum of sim(c, j)
+ * over the picks j so far (a later similarity replaces the maximum only when it compares greater);
+ * v_c = lam * s_c - (1 - lam) * p_c in f32 (1 - lam, both products and the difference each rounded to f32, nothing fused); the
+ * pick is the largest v_c as mvin_topk_rows orders scores (-0.0 equals +0.0, every NaN is equal and below -inf), equal values
+ * going to the lower position.
+ * Outputs, [n_seg, k] each, slot t of a segment: out_pos / out_vals / out_ids = the pick's position, the input bits of its
+ * score and its id; out_mmr = v at the pick; out_pen = p at the pick; out_simsum = the sum of sim to all earlier picks, added in
+ * pick order (0 at t = 0).  out_mmr, out_pen and out_simsum may each be NULL.  A segment short of k eligible entries ends in
+ * position -1, id -1, value -inf and 0 in the three f32 outputs.  A segment longer than max_len, or whose pointers do not lie
+ * in [0, total] in order, is not read: its slots are that padding and `status` (int64 [2], ACCUMULATED) counts it in [0] and
+ * its k slots in [1].
+ * Properties: with lam == 1 and a finite table, positions, values and ids are mvin_topk_segments' bit for bit.  The picks of a
+ * segment are always distinct eligible positions, whatever the table holds; with inf or NaN in it the values are unspecified
+ * but no access is out of range.  On inputs where every product and sum is exact in f32, every output is independent of form,
+ * launch shape and max_len; elsewhere a dot product's summation order is the kernel's (a launch is deterministic).
+ * `form`: 0 = automatic, 1 = wave form (a segment and its per-entry state in the registers of a lane group, max_len <=
+ * mvin_segments_wave_cap()), 2 = block form (one workgroup per segment, the state in LDS).
+ * Limits: 1 <= k <= 1024; max_len <= mvin_mmr_max_len(); 4 <= D <= 256 with D % 4 == 0; ld >= D with ld % 4 == 0; feat 16-byte
+ * aligned; 0 <= n_rows < 2^31; lam finite and in [0, 1]; eps finite and > 0; an f32 table only.
+ * Errors (< 0, nothing launched): -2 for bad sizes (those limits, n_seg < 0 or >= 2^31, total < 0, max_len < 0, form outside
+ * 0..2), bad lam or eps, or form 1 above mvin_segments_wave_cap(); -1 for null required pointers (scores with total > 0,
+ * seg_ptr, ids, feat with n_rows > 0, out_pos / out_vals / out_ids, status, out) or exactly one of excl_ptr / excl_ids.
+ * n_seg == 0 (n_rows == 0 for the norms) launches nothing.  No workspace. */
+MVIN_API int mvin_mmr_max_len(void);                                            /* the longest segment taken: 4096 */
+MVIN_API int mvin_row_inv_norms(const float* feat, int64_t n_rows, int D, int64_t ld, float eps, float* out /* [n_rows] */,
+                                void* stream);
+MVIN_API int mvin_mmr_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                               const int64_t* excl_ptr, const int32_t* excl_ids, const float* feat, int64_t n_rows, int D,
+                               int64_t ld, const float* row_scale /* [n_rows] or NULL */, float lam, int k, int64_t max_len,
+                               int form, int32_t* out_pos, float* out_vals, int32_t* out_ids, float* out_mmr, float* out_pen,
+                               float* out_simsum, int64_t* status, void* stream);
+
 /* ---- CTR metrics: exact integer counts behind the reference's CTR evaluation (util.py:44-56: roc_auc_score, accuracy and
  * f1_score of every batch) for many segments at once --
  * mvin_ctr_counts: segment s is scores[s*ld .. s*ld+seg_len) (f32) with labels[s*ld .. s*ld+seg_len) (int32, 0 or 1); neither is

@@ -100,6 +100,11 @@ SIGNATURES = {
                            + [C.c_void_p] * 5),
     "mvin_rank_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int]
                            + [C.c_void_p] * 5),
+    "mvin_mmr_max_len": (C.c_int, []),
+    "mvin_row_inv_norms": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    "mvin_mmr_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+                          + [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_int64, C.c_int]
+                          + [C.c_void_p] * 8),
     "mvin_kg_explore_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_kg_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
     "mvin_kg_explore": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,

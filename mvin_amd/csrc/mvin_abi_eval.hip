@@ -103,6 +103,45 @@ int mvin_rank_segments(const float* scores, int64_t total, const int64_t* seg_pt
                       who);
 }
 
+int mvin_mmr_max_len(void) { return mvin::mmr_max_len(); }
+
+// what mvin_row_inv_norms and mvin_mmr_segments check alike about the feature table
+static int mmr_bad_table(const char* who, const float* feat, int64_t n_rows, int D, int64_t ld) {
+    if (n_rows < 0 || n_rows >= (int64_t(1) << 31) || D < 4 || D > 256 || (D & 3) != 0 || ld < D || (ld & 3) != 0)
+        return fail(-2, "%s: n_rows=%lld D=%d ld=%lld (0 <= n_rows < 2^31; D a multiple of 4, 4..256; ld >= D, a multiple of 4)", who,
+                    (long long)n_rows, D, (long long)ld);
+    if (n_rows > 0 && !feat) return fail(-1, "%s: null feat", who);
+    if (reinterpret_cast<uintptr_t>(feat) & 15) return fail(-2, "%s: feat is not 16-byte aligned", who);
+    return 0;
+}
+
+int mvin_row_inv_norms(const float* feat, int64_t n_rows, int D, int64_t ld, float eps, float* out, void* stream) {
+    const char* who = "mvin_row_inv_norms";
+    if (const int rc = mmr_bad_table(who, feat, n_rows, D, ld)) return rc;
+    if (!(eps > 0.f) || eps > 3.0e38f) return fail(-2, "%s: eps=%g (finite, > 0)", who, (double)eps);
+    if (n_rows > 0 && !out) return fail(-1, "%s: null out", who);
+    return hip_result(mvin::launch_row_inv_norms(feat, n_rows, D, ld, eps, out, (hipStream_t)stream), who);
+}
+
+int mvin_mmr_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                      const int64_t* excl_ptr, const int32_t* excl_ids, const float* feat, int64_t n_rows, int D, int64_t ld,
+                      const float* row_scale, float lam, int k, int64_t max_len, int form, int32_t* out_pos, float* out_vals,
+                      int32_t* out_ids, float* out_mmr, float* out_pen, float* out_simsum, int64_t* status, void* stream) {
+    const char* who = "mvin_mmr_segments";
+    if (!mvin::topk_rows_supported(k)) return fail(-2, "%s: k=%d (1 <= k <= 1024)", who, k);
+    if (!(lam >= 0.f && lam <= 1.f)) return fail(-2, "%s: lam=%g (finite, in [0, 1])", who, (double)lam);
+    if (max_len > mvin::mmr_max_len())
+        return fail(-2, "%s: max_len=%lld (segments of at most %d entries)", who, (long long)max_len, mvin::mmr_max_len());
+    if (const int rc = segments_bad_args(who, scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, max_len, form, status)) return rc;
+    if (const int rc = mmr_bad_table(who, feat, n_rows, D, ld)) return rc;
+    if (!ids || !out_pos || !out_vals || !out_ids)
+        return fail(-1, "%s: null ids / out_pos / out_vals / out_ids (an entry's id is its row in feat)", who);
+    return hip_result(mvin::launch_mmr_segments(scores, total, seg_ptr, n_seg, ids, excl_ptr, excl_ids, feat, n_rows, D, ld, row_scale,
+                                                lam, k, max_len, form, out_pos, out_vals, out_ids, out_mmr, out_pen, out_simsum, status,
+                                                (hipStream_t)stream),
+                      who);
+}
+
 static bool kg_bad_sizes(int64_t n_entity, int64_t M) {
     return n_entity < 0 || n_entity > (int64_t)0x7FFFFFFF || M < 0 || M > (int64_t)0x7FFFFFFF;
 }

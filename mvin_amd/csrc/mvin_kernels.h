@@ -474,6 +474,12 @@ hipError_t launch_rank_segments(const float* scores, int64_t total, const int64_
                                 const int64_t* excl_ptr, const int32_t* excl_ids, const int64_t* q_ptr, const int32_t* q_pos,
                                 int64_t n_q, int64_t max_len, int form, int32_t* out_counts, float* out_vals, int32_t* out_eligible,
                                 int64_t* status, hipStream_t st);
+int mmr_max_len();                                              // greedy MMR reranking inside CSR segments (mvin_mmr.hip)
+hipError_t launch_row_inv_norms(const float* feat, int64_t n_rows, int D, int64_t ld, float eps, float* out, hipStream_t st);
+hipError_t launch_mmr_segments(const float* scores, int64_t total, const int64_t* seg_ptr, int64_t n_seg, const int32_t* ids,
+                               const int64_t* excl_ptr, const int32_t* excl_ids, const float* feat, int64_t n_rows, int D, int64_t ld,
+                               const float* row_scale, float lam, int k, int64_t max_len, int form, int32_t* out_pos, float* out_vals,
+                               int32_t* out_ids, float* out_mmr, float* out_pen, float* out_simsum, int64_t* status, hipStream_t st);
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);

@@ -288,6 +288,56 @@ class DeviceFeeder(object):
                               out=(out[0][s0:s1], out[1][s0:s1], out[2][s0:s1], out[3]))
         return out[2].long(), out[1], out[0]
 
+    def diversify_lists(self, users, lists, k, lam=0.5, features=None, cosine=True, exclude=None, max_pairs=524288):
+        """``recommend_lists`` with a trade-off between relevance and redundancy inside the returned list: greedy maximal marginal
+        relevance (ops.mmr_segments).  Slot t of a user's list is the eligible item not taken yet with the largest
+        ``lam * score - (1 - lam) * (largest similarity to an item already taken)``; ``lam=1.0`` is ``recommend_lists`` bit for
+        bit, ``lam=0.0`` ignores the scores after the first pick.  Similarity is the dot product of two rows of ``features`` (an
+        f32 [n_rows, D] device table indexed by item id, D a multiple of 4 in 4..256; None = ``model.entity_emb_matrix``, where
+        the items are the low entity ids; a bf16 table raises ValueError), a cosine with ``cosine=True`` (the inverse row norms
+        are computed once per call on the device, ops.row_inv_norms).  ``lists``, ``exclude`` and ``max_pairs`` as in
+        ``recommend_lists``, scored and chunked the same way; an item id beyond the table is never eligible; a list longer than
+        ops.mmr_max_len() raises ValueError.  Returns ``(items int64 [U, k], scores f32 [U, k], positions int32 [U, k], penalties
+        f32 [U, k], simsums f32 [U, k])`` on the device: per slot the item, its score, its place in the user's list, the
+        similarity penalty it was taken at (0 in slot 0) and the sum of its similarities to the slots before it -- a list's
+        mean pairwise similarity is ``simsums.sum() / (m (m - 1) / 2)`` over its m picks.  A list with fewer than ``k`` eligible
+        items ends in item -1, score -inf, position -1 and zeros.  Nothing is copied back."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        k, max_pairs = int(k), int(max_pairs)
+        if max_pairs < 1:
+            raise ValueError(f"max_pairs={max_pairs}")
+        feat = self.model.entity_emb_matrix if features is None else features
+        if not torch.is_tensor(feat) or feat.dtype != torch.float32 or feat.dim() != 2:
+            raise ValueError(f"diversify_lists: features must be an f32 [n_rows, D] table, got "
+                             f"{feat.dtype if torch.is_tensor(feat) else type(feat).__name__} (a bf16 table is not taken)")
+        if isinstance(exclude, dict):
+            if torch.is_tensor(users) and users.is_cuda:
+                raise ValueError("diversify_lists: an exclusion record needs host users (or pass feeder.exclusion_csr(users, record))")
+            exclude = self.exclusion_csr(users, exclude)
+        u = _dev_ids(users, dev)
+        U = u.shape[0]
+        ptr, items = _lists_csr(lists, U, dev)
+        lens = np.diff(ptr)
+        if lens.size and int(lens.max()) > ops.mmr_max_len():
+            i = int(np.argmax(lens > ops.mmr_max_len()))
+            raise ValueError(f"diversify_lists: the list of user {int(u[i])} (row {i}) has {int(lens[i])} entries, "
+                             f"more than ops.mmr_max_len() = {ops.mmr_max_len()}")
+        feat = feat.to(dev)
+        row_scale = ops.row_inv_norms(feat) if cosine else None
+        flat = self._score_lists(u, ptr, items.clamp(min=0), max_pairs)      # padding is scored as item 0 and never eligible
+        ids = items.clamp(min=-1, max=(1 << 31) - 1).to(torch.int32)         # an id int32 cannot hold is beyond every table
+        seg_ptr = torch.from_numpy(ptr).to(dev)
+        pos, vals, oid, pen, simsum = (torch.empty((U, k), dtype=dt, device=dev)
+                                       for dt in (torch.int32, torch.float32, torch.int32, torch.float32, torch.float32))
+        status = torch.zeros(2, dtype=torch.int64, device=dev)
+        for s0, s1, longest in _segment_chunks(ptr, max_pairs):
+            ops.mmr_segments(flat, seg_ptr[s0:s1 + 1], ids, feat, k, lam, row_scale=row_scale,
+                             excl=None if exclude is None else (exclude[0][s0:s1 + 1], exclude[1]), max_len=longest,
+                             out=(pos[s0:s1], vals[s0:s1], oid[s0:s1], None, pen[s0:s1], simsum[s0:s1], status))
+        return oid.long(), vals, pos, pen, simsum
+
     def rank_lists(self, users, lists, queries, exclude=None, max_pairs=524288):
         """Where named entries of every user's OWN candidate list land in the user's ranking of that list: the device tensors
         ``(q_ptr int64 [U+1], q_pos int32 [Q], counts int32 [Q, 3], vals f32 [Q], eligible int32 [U])`` of ``rank_positives``,
@@ -1217,6 +1267,64 @@ def topk_eval_batched(feeder, user_list, train_record, eval_record, test_record,
             _rank_metrics(row[row >= 0].tolist(), ref[user], k_list, precision_list, recall_list, ndcg_list)
     return ([float(np.mean(precision_list[k])) for k in k_list], [float(np.mean(recall_list[k])) for k in k_list],
             [float(np.mean(ndcg_list[k])) for k in k_list], None, None)
+
+
+def diversity_eval(feeder, users, lists, truth_record, k, lams=(1.0, 0.7, 0.5, 0.3), exclude=None, n_item=None, features=None,
+                   cosine=True, max_pairs=524288):
+    """What the relevance / redundancy trade-off of DeviceFeeder.diversify_lists costs and buys on given candidate lists: ONE
+    ``diversify_lists`` call and ONE copy back (items, penalties and similarity sums packed into one int32 tensor) per ``lam``
+    of ``lams``, the rest in float64 on the host.  ``users`` on the host; ``lists``, ``exclude``, ``features``, ``cosine`` and
+    ``max_pairs`` as in ``diversify_lists``; ``truth_record``: a get_user_record dict of held-out items.  Returns one dict per
+    ``lam``, in order:
+      lam; recall, ndcg -- recall_at_k and ndcg_at_k (hits in the returned order) at ``k``, means over the ``n_users`` users
+      with a non-empty ``truth_record`` entry (0.0 without such a user);
+      ild -- intra-list diversity, 1 - (sum of a list's simsums) / (m (m - 1) / 2) over its m picks, the mean over the
+      ``n_lists`` lists with m >= 2 (NaN without one);
+      coverage -- the distinct items over all returned lists / ``n_item`` (None: the rows of the feature table);
+      penalty -- the mean penalty over the filled slots after each list's first (NaN without one);
+      items -- the returned lists, int64 [U, k] on the host (-1 = padding): the ``lam = 1.0`` row carries ``recommend_lists``'."""
+    import torch
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"diversity_eval: k={k}")
+    lams = [float(x) for x in lams]
+    if not lams or any(not 0.0 <= x <= 1.0 for x in lams):
+        raise ValueError(f"diversity_eval: lams={lams}: expected at least one value, each in [0, 1]")
+    if not isinstance(truth_record, dict):
+        raise ValueError("diversity_eval: truth_record must be a dict of user -> held-out items")
+    if torch.is_tensor(users) and users.is_cuda:
+        raise ValueError("diversity_eval: users must be on the host (they index truth_record)")
+    users = np.asarray(users.numpy() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
+    U = users.size
+    if n_item is None:
+        n_item = int((feeder.model.entity_emb_matrix if features is None else features).shape[0])
+    if int(n_item) < 1:
+        raise ValueError(f"diversity_eval: n_item={n_item}")
+    rows = []
+    for lam in lams:
+        items, _, _, pen, simsum = feeder.diversify_lists(users, lists, k, lam=lam, features=features, cosine=cosine, exclude=exclude,
+                                                          max_pairs=max_pairs)
+        packed = torch.cat([items.to(torch.int32).reshape(-1), pen.reshape(-1).view(torch.int32),
+                            simsum.reshape(-1).view(torch.int32)]).cpu().numpy()
+        n = U * k
+        it = packed[:n].reshape(U, k).astype(np.int64)
+        pn = packed[n:2 * n].view(np.float32).reshape(U, k).astype(np.float64)
+        ss = packed[2 * n:].view(np.float32).reshape(U, k).astype(np.float64)
+        recall, ndcg, ild, pens = [], [], [], []
+        for i, user in enumerate(users):
+            m = int((it[i] >= 0).sum())
+            ranked = it[i][:m].tolist()
+            truth = truth_record.get(int(user))
+            if truth:
+                recall.append(recall_at_k(ranked, truth, k))
+                ndcg.append(ndcg_at_k([1 if x in truth else 0 for x in ranked], k))
+            if m >= 2:
+                ild.append(1.0 - float(ss[i][:m].sum()) / (m * (m - 1) / 2.0))
+                pens.extend(pn[i][1:m].tolist())
+        rows.append(dict(lam=lam, recall=float(np.mean(recall)) if recall else 0.0, ndcg=float(np.mean(ndcg)) if ndcg else 0.0,
+                         ild=float(np.mean(ild)) if ild else float("nan"), coverage=len(set(it[it >= 0].tolist())) / float(n_item),
+                         penalty=float(np.mean(pens)) if pens else float("nan"), n_users=len(recall), n_lists=len(ild), items=it))
+    return rows
 
 
 def _ranked_metrics(feeder, users, positives, exclude, candidates, k_list, ndcg_window, max_pairs, auc=True):

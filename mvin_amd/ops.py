@@ -1008,6 +1008,99 @@ def rank_segments(scores, seg_ptr, queries, ids=None, excl=None, max_len=None, f
     return counts, vals, eligible, status
 
 
+def mmr_max_len():
+    """mvin_mmr_max_len: the longest segment mmr_segments takes."""
+    return int(_lib.load().mvin_mmr_max_len())
+
+
+def _mmr_table(feat, name):
+    """A feature table checked: (n_rows, D, ld) of an f32 [n_rows, D] tensor with dense rows, rows ``ld`` floats apart."""
+    if not isinstance(feat, torch.Tensor) or feat.dim() != 2:
+        raise ValueError(f"{name}: expected a [n_rows, D] tensor")
+    if feat.dtype != F32:
+        raise ValueError(f"{name}: expected an f32 table, got {feat.dtype} (a bf16 table is not taken)")
+    n_rows, D = feat.shape
+    if D < 4 or D > 256 or D % 4:
+        raise ValueError(f"{name}: D={D}: expected a multiple of 4 in 4..256")
+    if not feat.is_cuda:
+        raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    ld = feat.stride(0) if n_rows > 1 else D
+    if feat.stride(1) != 1 or ld < D or ld % 4 or feat.data_ptr() % 16:
+        raise ValueError(f"{name}: rows must be dense, a multiple of 4 floats apart and 16-byte aligned")
+    return n_rows, D, ld
+
+
+def row_inv_norms(feat, eps=1e-12, out=None):
+    """mvin_row_inv_norms: ``1 / max(||feat[r]||, eps)`` per row of an f32 table [n_rows, D] (rows may be strided), f32 [n_rows]:
+    the ``row_scale`` that makes mmr_segments' similarity a cosine.  The sum of squares and the root are taken in f64 and
+    rounded once.  Enqueues only."""
+    lib = _lib.load()
+    eps = float(eps)
+    if not (0.0 < eps < 3.0e38):
+        raise ValueError(f"eps={eps}: expected a finite value > 0")
+    n_rows, D, ld = _mmr_table(feat, "feat")
+    if out is None:
+        out = torch.empty((n_rows,), dtype=F32, device=feat.device)
+    _chk(out, F32, "out")
+    if tuple(out.shape) != (n_rows,):
+        raise ValueError(f"out: expected [{n_rows}]")
+    if n_rows:
+        _lib.check(lib.mvin_row_inv_norms(_p(feat), n_rows, D, ld, eps, _p(out), _stream()), "mvin_row_inv_norms")
+    return out
+
+
+def mmr_segments(scores, seg_ptr, ids, feat, k, lam, row_scale=None, excl=None, max_len=None, form=None, out=None):
+    """mvin_mmr_segments: greedy maximal-marginal-relevance reranking of every segment ``scores[seg_ptr[s]:seg_ptr[s+1]]`` --
+    step t takes, among the eligible entries not taken yet, the largest ``lam * score - (1 - lam) * (largest similarity to
+    anything already taken)`` (f32; the first step has no penalty; topk_segments' order, equal values to the lower position).
+    ``scores``, ``seg_ptr``, ``excl``, ``max_len`` and ``form`` are topk_segments' (``max_len=None`` reads the bound from
+    ``seg_ptr``: ONE synchronisation; with ``max_len`` passed the call only enqueues); ``ids`` int32 [T] is required: an entry's
+    id is its row in ``feat`` (f32 [n_rows, D], D a multiple of 4 in 4..256), a negative id is padding and an id >= n_rows is
+    ineligible too.  Similarity = the dot product of the two rows, times ``row_scale`` (f32 [n_rows]; ``row_inv_norms(feat)``
+    makes it a cosine) of both when given.  LIMITS: 0 <= lam <= 1, 1 <= k <= 1024, segments of at most mmr_max_len() entries.
+    Returns ``(pos int32, vals f32, ids int32, mmr f32, pen f32, simsum f32, status int64 [2])``, [n_seg, k] each (``out``: the
+    same seven to write into; status is accumulated): per slot the pick's position, the input bits of its score, its id, its
+    marginal value, its penalty, and the sum of its similarities to the earlier picks.  A segment short of k eligible entries
+    ends in position -1, id -1, value -inf and zeros; a segment over ``max_len`` is all padding and counted in status.  With
+    lam = 1 the first three are topk_segments' bit for bit."""
+    k, lam = int(k), float(lam)
+    if not 1 <= k <= 1024:
+        raise ValueError(f"k={k}: mvin_mmr_segments takes 1 <= k <= 1024")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lam={lam}: expected a value in [0, 1]")
+    if ids is None:
+        raise ValueError("mmr_segments: ids is required (an entry's id is its row in feat)")
+    n_rows, D, ld = _mmr_table(feat, "feat")
+    lib = _lib.load()
+    scores, seg_ptr, n_seg, ids, eptr, eids_p, max_len, form = _segments_common(scores, seg_ptr, ids, excl, max_len, form,
+                                                                                 "mmr_segments")
+    if max_len > mmr_max_len():
+        raise ValueError(f"max_len={max_len}: mvin_mmr_segments takes segments of at most {mmr_max_len()} entries")
+    if row_scale is not None:
+        _chk(row_scale, F32, "row_scale")
+        if tuple(row_scale.shape) != (n_rows,):
+            raise ValueError(f"row_scale: expected [{n_rows}]")
+    dev = scores.device
+    if out is None:
+        out = tuple(torch.empty((n_seg, k), dtype=dt, device=dev) for dt in (I32, F32, I32, F32, F32, F32)) \
+            + (torch.zeros(2, dtype=torch.int64, device=dev),)
+    if len(out) != 7:
+        raise ValueError("out: expected (pos, vals, ids, mmr, pen, simsum, status)")
+    for t, dt, name in zip(out, (I32, F32, I32, F32, F32, F32, torch.int64), ("pos", "vals", "ids", "mmr", "pen", "simsum", "status")):
+        _chk(t, dt, f"out {name}")
+    if any(t is None or tuple(t.shape) != (n_seg, k) for t in out[:3]) or out[6] is None or out[6].numel() != 2 \
+            or any(t is not None and tuple(t.shape) != (n_seg, k) for t in out[3:6]):
+        raise ValueError(f"out: expected pos / vals / ids [{n_seg}, {k}], mmr / pen / simsum [{n_seg}, {k}] or None, and status [2]")
+    T = scores.numel()
+    anyp = _p(seg_ptr)                          # an empty array: any valid pointer, nothing is read or written through it
+    opt = lambda t: None if t is None else (_p(t) if n_seg else anyp)      # noqa: E731
+    _lib.check(lib.mvin_mmr_segments(_p(scores) if T else None, T, _p(seg_ptr), n_seg, _p(ids) if T else anyp, _p(eptr), eids_p,
+                                     _p(feat) if n_rows else None, n_rows, D, ld, _p(row_scale) if n_rows else None, lam, k,
+                                     max_len, form, opt(out[0]), opt(out[1]), opt(out[2]), opt(out[3]), opt(out[4]), opt(out[5]),
+                                     _p(out[6]), _stream()), "mvin_mmr_segments")
+    return tuple(out)
+
+
 def _score_image_host(vals):
     """mvin_score_image.h on the host: uint32 images of f32 scores (-0.0 = +0.0, every NaN = 0, below image(-inf))."""
     import numpy as np
