@@ -33,7 +33,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import l2_plan, ops
+from . import l2_plan, ops, route_plan
 from .aggregators import SumAggregator_urh_matrix
 from .params import aggregator_keys, init_params
 
@@ -76,11 +76,6 @@ class _SmallOut(object):
         return self._buf[n:n + self._B]
 
 
-def _lib_flash_elems(m):
-    from . import _lib
-    return _lib.load().mvin_key_addressing_flash_tables_elems(m.n_entity, m.n_relation, m.dim, m.p_hop, 1 if m.args.PS_O_ft else 0)
-
-
 class MVIN(object):
     def __init__(self, args, n_user, n_entity, n_relation, adj_entity, adj_relation,
                  params=None, device=None, seed=0, fused=None, table_dtype="f32", hoist=False):
@@ -101,6 +96,7 @@ class MVIN(object):
         self.hoist = hoist
         self.dedup = None            # None: MVIN_L2_ENC / auto; True / False: force the encoded / the plain adjacency
         self._l2_static, self._l2_memo = None, {}             # see _l2_shape_caps, _l2_plan
+        self._route_static, self._route_memo = None, {}       # see _route_inputs, _route
         self._hoisted = None
         self._table_token = None     # see _hoist_key
         self._parse_args(args, adj_entity, adj_relation)
@@ -335,26 +331,24 @@ class MVIN(object):
         # folded-tail form of the native call (_fold_for): None = whenever the aggregates form is taken (MVIN_L2_FOLD=0 / 1 overrides)
         self.fold = {"0": False, "1": True}.get(os.environ.get("MVIN_L2_FOLD", ""), None)
         self._fold_ws = {}                   # per stream: workspace of mvin_fold_tables_elems floats, rewritten by every call
-        # gathered form of the grouped key addressing (mvin_key_addressing_grouped_er_fwd, _ka_er_for): on request only
+        # schedule, feed and key-addressing form of a call: mvin_amd/route_plan.py (thresholds and measurements: its THRESHOLDS)
+        # gathered form of the grouped key addressing (mvin_key_addressing_grouped_er_fwd): on request only (MVIN_KA_ER=1)
         self.ka_er = os.environ.get("MVIN_KA_ER", "0") == "1"
         self._ka_er_ws = {}                  # per stream: workspace of mvin_project_relations_elems floats, rewritten by every call
-        # flash form of the grouped key addressing + user MLP (mvin_key_addressing_flash_fwd, _ka_flash_for): None = automatic
-        # (MVIN_KA_FLASH=0 / 1 overrides), True / False
+        # flash form of the grouped key addressing + user MLP (mvin_key_addressing_flash_fwd): None = automatic (MVIN_KA_FLASH=0 / 1
+        # overrides), True / False
         self.ka_flash = {"0": False, "1": True}.get(os.environ.get("MVIN_KA_FLASH", ""), None)
         self._ka_flash_ws = {}               # per stream: workspace of mvin_key_addressing_flash_tables_elems floats, rewritten by every call
         # parents of the projected-tables launch in item order (_item_order_for): None = by batch size (MVIN_ITEM_ORDER=0 / 1 overrides)
         self.item_order = {"0": False, "1": True}.get(os.environ.get("MVIN_ITEM_ORDER", ""), None)
-        self._distinct_hint = None           # forward_device's distinct_users of the call at hand
-        self.group_min_pairs_per_user = 4    # forward_users: batch size / n_user above which pairs are grouped by user
-        self.native_l2_max_batch = 65536     # above this the pass is kernel-bound: the Python schedule costs nothing
-        # up to this many pairs the whole pass is ONE kernel launch (mvin_score_small_fwd: the reference's own batch sizes,
-        # 512 / 1024 per sess.run); beyond it the multi-launch schedule is the faster one (measured: 58 vs 60 us at 1 024 pairs,
-        # 112 vs 66 us at 2 048: a workgroup walks its pairs' dependent-load chain alone).  The entry point
-        # itself takes any batch (tests drive it to 16 384).  0 or MVIN_SMALL=0 turns it off; MVIN_SMALL_MAX overrides
-        self.small_max_batch = 0 if os.environ.get("MVIN_SMALL", "1") == "0" else int(os.environ.get("MVIN_SMALL_MAX", "1024"))
+        self._distinct_hint = None           # forward_device's distinct_users of the last call: the default of the _ka_flash_for view
+        th = route_plan.THRESHOLDS
+        self.group_min_pairs_per_user = th.group_min_pairs_per_user      # batch size / users above which pairs are grouped by user
+        self.native_l2_max_batch = th.native_l2_max_batch
+        # pairs up to which the whole pass is ONE kernel launch: 0 or MVIN_SMALL=0 turns it off; MVIN_SMALL_MAX overrides
+        self.small_max_batch = 0 if os.environ.get("MVIN_SMALL", "1") == "0" else int(os.environ.get("MVIN_SMALL_MAX", th.small_max_batch))
         self.small_group = 0                 # pairs per workgroup of that launch (0: chosen by the library)
         self._small_state = None
-        self._small_static = None
         # Device-resident feeds (forward_device / forward_users): ids are NOT validated per batch by default (it costs a
         # host sync; the kernels clamp entity / user / relation ids into their tables instead of reading out of bounds).
         # True (or MVIN_CHECK_IDS=1): every batch is checked and raises IndexError like the host-feed path and like
@@ -367,34 +361,126 @@ class MVIN(object):
         self.static_user_records = None
         self._uts_records = None
 
-    USER_RECORDS_MAX_BYTES = 8 << 30
-    FLASH_TABLES_MAX_BYTES = 4 << 30
+    # ------------------------------------------------------------------ schedule, feed, key-addressing form (mvin_amd/route_plan.py)
+    # thresholds: route_plan.THRESHOLDS, each with its measurement; the two byte caps stay settable (class or model), read through the table
+    USER_RECORDS_MAX_BYTES = route_plan.THRESHOLDS.user_records_max_bytes
+    FLASH_TABLES_MAX_BYTES = route_plan.THRESHOLDS.flash_tables_max_bytes
 
-    def user_records(self, uts):
-        """The static per-user records of a device-resident user_triplet_set, or None when the shape / table type has no
-        kernel over them.  Cached per tensor (identity + version counter), like the one-time id check."""
-        if self.static_user_records is False or os.environ.get("MVIN_KA_STATIC", "1") == "0" or self.p_hop < 1:
-            return None
-        if not (uts.is_cuda and uts.dtype == torch.int32 and uts.is_contiguous()):
-            return None
-        bf = self.entity_emb_matrix.dtype == torch.bfloat16
-        if not (ops.user_records_supported(self.dim, self.p_hop, self.n_memory, self.n_relation, bf)
-                or (not bf and ops.key_addressing_flash_supported(self.dim, self.p_hop, self.n_memory, self.n_relation, self.n_entity))):
-            return None
+    def _route_shape_caps(self):
+        """(RouteShape, RouteCaps): the shape and the library's capability answers, gathered once per (table, adjacency size, fused, hoist)."""
+        E = self.entity_emb_matrix
+        key = (E.dtype, E.numel(), self.adj_entity.numel(), self.fused, self.hoist, self.n_entity, self.n_relation)
+        c = self._route_static
+        if c is None or c[0] != key:
+            a, D, K, P, Nm, nE, nR = self.args, self.dim, self.n_neighbor, self.p_hop, self.n_memory, int(self.n_entity), int(self.n_relation)
+            f32, set_ = E.dtype == torch.float32, 1 if a.PS_O_ft else 0
+            sh = route_plan.RouteShape(bool(a.wide_deep), bool(a.PS_only), bool(a.HO_only), bool(a.User_orient_kg_eh), bool(a.PS_O_ft), D, K,
+                                       self.h_hop, self.n_mix_hop, P, Nm, nR, nE, f32, E.numel() * E.element_size(),
+                                       self.adj_entity.numel() * self.adj_entity.element_size(), bool(self.fused), bool(self.hoist))
+            caps = route_plan.RouteCaps(
+                score_small=ops.score_small_supported(D, K, P, Nm, nR), l2_tail=ops.l2_tail_supported(D),
+                gather_attn_l2=ops.gather_attn_l2_supported(D, K), key_addressing=ops.key_addressing_supported(Nm, D),
+                key_addressing_grouped=ops.key_addressing_grouped_supported(D, P, Nm, nR),
+                user_records=ops.user_records_supported(D, P, Nm, nR, E.dtype == torch.bfloat16),
+                key_addressing_flash=ops.key_addressing_flash_supported(D, P, Nm, nR, nE),
+                key_addressing_grouped_er=ops.key_addressing_grouped_er_supported(D, P, Nm, nR, nE, bool(set_)),
+                flash_tables_elems=int(ops._lib.load().mvin_key_addressing_flash_tables_elems(nE, nR, D, P, set_)),
+                user_records_words=ops.user_records_len(P, Nm, nR))
+            c = self._route_static = (key, sh, caps)
+        return c[1], c[2]
+
+    def _route_inputs(self):
+        """(shape, capabilities, overrides, thresholds) as route_plan takes them."""
+        sh, caps = self._route_shape_caps()
+        ov = route_plan.RouteOverrides(self.ka_flash, self.ka_er, self.static_user_records, os.environ.get("MVIN_KA_STATIC", "1"),
+                                       self.validate_device_ids, self._profile is not None, self.small_max_batch, self.native_l2_max_batch,
+                                       self.group_min_pairs_per_user)
+        th = route_plan.THRESHOLDS._replace(user_records_max_bytes=self.USER_RECORDS_MAX_BYTES, flash_tables_max_bytes=self.FLASH_TABLES_MAX_BYTES)
+        return sh, caps, ov, th
+
+    def _route(self, user, item, mem_h, mem_r, mem_t, uts, want_probs, distinct_users):
+        """The route of this call (route_plan.plan), remembered per everything it reads, as raw attributes (as _l2_plan)."""
+        B, E, P = item.shape[0], self.entity_emb_matrix, self.p_hop
+        if uts is not None:
+            fk = (uts.dtype, uts.is_contiguous(), uts.shape, self._records_cached(uts) is not None)
+        elif mem_h is None:
+            fk = "none"
+        elif mem_h[0].dim() == 1:
+            fk = "shared"
+        else:           # per-pair lists: the first p_hop of each are int32, contiguous, [B, Nm]
+            fk, shape, i32 = len(mem_h) >= P and len(mem_r) >= P and len(mem_t) >= P, (B, self.n_memory), torch.int32
+            for lst in (mem_h, mem_r, mem_t):
+                for m_ in lst[:P]:
+                    if m_.dtype != i32 or m_.shape != shape or not m_.is_contiguous():
+                        fk = False
+        key = (fk, B, item.dtype, user.dtype, user.numel(), want_probs, distinct_users, self._profile is None, self.fused, self.hoist,
+               self.ka_flash, self.ka_er, self.static_user_records, os.environ.get("MVIN_KA_STATIC"), self.small_max_batch,
+               self.native_l2_max_batch, self.group_min_pairs_per_user, self.USER_RECORDS_MAX_BYTES, self.FLASH_TABLES_MAX_BYTES,
+               E.dtype, E.numel(), self._generation)
+        route = self._route_memo.get(key)
+        if route is None:
+            if len(self._route_memo) >= 64:
+                self._route_memo.clear()
+            sh, caps, ov, th = self._route_inputs()
+            kind, i32, cont, shape, n_user, rec_ok = fk if isinstance(fk, str) else "pairs", fk is True, fk is True, fk is True, 0, False
+            if uts is not None:
+                kind, i32, cont, n_user = "uts", uts.dtype == torch.int32, uts.is_contiguous(), int(uts.shape[0])
+                shape = uts.dim() == 4 and uts.shape[1] == max(1, P) and uts.shape[3] == self.n_memory
+                rec_ok = uts.is_cuda and self._records_ok(uts, caps)
+            fd = route_plan.Feed(kind, B, item.dtype == torch.int64, user.dtype == torch.int64, user.dtype == torch.int32, user.numel(),
+                                 i32, cont, shape, n_user, distinct_users, bool(want_probs), rec_ok)
+            route = self._route_memo[key] = route_plan.plan(sh, caps, ov, th, fd)
+        return route
+
+    def _records_cached(self, uts):
         c = self._uts_records
-        if c is not None and c[0]() is uts and c[1] == uts._version and c[2] == (self.n_entity, self.n_relation):
-            return c[3]
-        if c is not None and c[0]() is None:
+        return c[3] if (c is not None and c[0]() is uts and c[1] == uts._version and c[2] == (self.n_entity, self.n_relation)) else None
+
+    def _records_ok(self, uts, caps):        # the records exist, or may be built: the byte cap (a capture that is open raises in _records)
+        return self._records_cached(uts) is not None or uts.shape[0] * caps.user_records_words * 4 <= self.USER_RECORDS_MAX_BYTES
+
+    def _records(self, uts):
+        """The static per-user records of ``uts``: cached per tensor (identity + version counter, like the one-time id check), else built."""
+        rec = self._records_cached(uts)
+        if rec is not None:
+            return rec
+        if self._uts_records is not None and self._uts_records[0]() is None:
             self._uts_records = None     # the tensor the records were built from is gone: free them (up to 8 GiB)
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("the static per-user records of this user_triplet_set are not built yet: call "
                                "model.prepare(user_triplet_set) before capturing a graph")
-        words = ops.user_records_len(self.p_hop, self.n_memory, self.n_relation)
-        if uts.shape[0] * words * 4 > self.USER_RECORDS_MAX_BYTES:
-            return None
         rec = ops.build_user_records(uts, self.p_hop, self.n_relation, self.n_entity)
         self._uts_records = (weakref.ref(uts), uts._version, (self.n_entity, self.n_relation), rec)
         return rec
+
+    # the plan's rules one by one, as bench.py, __graft_entry__.py and the tests read them
+    def user_records(self, uts):
+        """The static per-user records of a device-resident user_triplet_set, or None when no kernel of this shape / table type reads them."""
+        sh, caps, ov, _ = self._route_inputs()
+        ok = uts.is_cuda and uts.dtype == torch.int32 and uts.is_contiguous()
+        return self._records(uts) if route_plan.wants_records(sh, caps, ov, ok, ok and self._records_ok(uts, caps)) else None
+
+    def _small_static_ok(self):
+        sh, caps, _, th = self._route_inputs()
+        return route_plan.small_static_ok(sh, caps, th)
+
+    def _small_ok(self, item, memories_h, want_probs):
+        """``memories_h`` None = the users feed."""
+        sh, caps, ov, th = self._route_inputs()
+        return route_plan.small_ok(sh, caps, ov, th, item.shape[0], item.dtype == torch.int64, memories_h is None or memories_h[0].dim() == 2, want_probs)
+
+    def _native_l2_ok(self, item, memories_h, want_probs, cap=True):
+        sh, caps, ov, _ = self._route_inputs()
+        return route_plan.native_ok(sh, caps, ov, item.shape[0], item.dtype == torch.int64, memories_h is None or memories_h[0].dim() == 2, want_probs, cap)
+
+    def _ka_er_for(self, uts, records):
+        sh, caps, ov, _ = self._route_inputs()
+        return route_plan.gathered_er(sh, caps, ov, records is not None)
+
+    def _ka_flash_for(self, uts, records, B):
+        """(the distinct-users hint: that of the last forward)"""
+        sh, caps, ov, th = self._route_inputs()
+        return route_plan.flash(sh, caps, ov, th, records is not None, B, uts.shape[0], self._distinct_hint)
 
     def prepare(self, user_triplet_set=None):
         """Build, eagerly and on the current stream, everything the forward would otherwise build on first use: the
@@ -503,9 +589,9 @@ class MVIN(object):
         """tf.nn.embedding_lookup of [B] ids -> [B, D]."""
         return ops.linear([table], None, table.shape[-1], ids=[ids32])
 
-    def _key_addressing(self, user32, item32, mem_h, mem_r, mem_t, uts=None):
+    def _key_addressing(self, user32, item32, mem_h, mem_r, mem_t, uts=None, ripple=False):
         """model.py:161-240 -> user_o [B,D].  ``uts``: the ripple sets of pair b are user_triplet_set[user32[b]], indexed inside
-        the kernel (mvin_key_addressing_users_fwd) instead of per-pair arrays."""
+        the kernel (mvin_key_addressing_users_fwd) instead of per-pair arrays; ``ripple``: one ops.ripple_attn launch per read."""
         a, D, P = self.args, self.dim, self.p_hop
         B = item32.shape[0]
         nR = self.n_relation
@@ -520,7 +606,7 @@ class MVIN(object):
                        out=V, ldo=nR * D, nz=nR, w_zstride=D * D, out_zstride=D)
         if uts is not None:
             ops.key_addressing_users(self.entity_emb_matrix, V, w_h, uts, user32, P, o_cat, n_o * D, nR)
-        elif self.fused and ops.key_addressing_supported(self.n_memory, D):
+        elif not ripple:
             ops.key_addressing(self.entity_emb_matrix, V, w_h, mem_h, mem_r, mem_t, P, o_cat, n_o * D, nR)
         else:
             slot = 0
@@ -854,39 +940,6 @@ class MVIN(object):
                                    uts=user_triplet_set, distinct_users=distinct_users)
 
     # ------------------------------------------------------------------ native whole-pass schedule
-    def _native_l2_ok(self, item, memories_h, want_probs, cap=True):
-        """The pass can be enqueued by ONE native call (mvin_score_l2_fwd): default wiring, depth-2 trees.
-        ``memories_h`` None = the users feed (user_triplet_set + user ids)."""
-        a = self.args
-        return (self.fused is not False and not want_probs and not self.hoist and self._profile is None
-                and a.wide_deep and not a.PS_only and not a.HO_only and a.User_orient_kg_eh
-                and self.n_mix_hop == 1 and self.h_hop == 2 and self.p_hop >= 1
-                and item.dtype == torch.int64 and (memories_h is None or memories_h[0].dim() == 2)
-                and ops.l2_tail_supported(self.dim) and ops.gather_attn_l2_supported(self.dim, self.n_neighbor)
-                and ops.key_addressing_supported(self.n_memory, self.dim)
-                and (not cap or item.shape[0] <= self.native_l2_max_batch))
-
-    def _small_static_ok(self):
-        """Everything about ``_small_ok`` that does not depend on the batch, cached per parameter generation (the check
-        runs on every call of a path whose whole GPU time is ~20 us)."""
-        key = (self._generation, self.fused, bool(self.hoist), self.entity_emb_matrix.data_ptr())
-        c = self._small_static
-        if c is None or c[0] != key:
-            a = self.args
-            ok = (self.fused is not False and not self.hoist and a.wide_deep and not a.PS_only and not a.HO_only
-                  and a.User_orient_kg_eh and self.n_mix_hop == 1 and self.h_hop in (1, 2) and 1 <= self.p_hop <= 4
-                  and self.entity_emb_matrix.dtype == torch.float32
-                  and self.entity_emb_matrix.numel() * 4 < (1 << 32) - 4096 and self.adj_entity.numel() * 4 < (1 << 32) - 4096
-                  and ops.score_small_supported(self.dim, self.n_neighbor, self.p_hop, self.n_memory, self.n_relation))
-            c = self._small_static = (key, bool(ok))
-        return c[1]
-
-    def _small_ok(self, item, memories_h, want_probs):
-        """The pass can be ONE kernel launch (mvin_score_small_fwd): default wiring, depth-2 trees, fp32 table below 4 GiB,
-        at most ``small_max_batch`` pairs.  ``memories_h`` None = the users feed."""
-        return (item.shape[0] <= self.small_max_batch and not want_probs and self._profile is None
-                and item.dtype == torch.int64 and (memories_h is None or memories_h[0].dim() == 2) and self._small_static_ok())
-
     def _score_args_static(self, depth=None):
         """The static half of ScoreL2Args -- adjacency, KGE, MLPs, projections, aggregators, mix, shape words -- and the tensors whose
         addresses it holds (kept alive with the block; rebinding a parameter attribute needs invalidate(), as for the cached relation
@@ -963,37 +1016,10 @@ class MVIN(object):
             _lib.check(rc, "mvin_score_small_fwd")
         return _SmallOut(out, B, D)
 
-    def _ka_er_for(self, uts, records):
-        """Gathered form of the grouped key addressing for this call?  OFF unless asked for (``self.ka_er = True`` / MVIN_KA_ER=1):
-        measured at C3 the kernel over the records goes 0.94 -> 0.74 ms, the table R_KGE[r] . E[e] (245 MB, rebuilt per call) costs
-        0.11 ms, and with two scoring streams its writes compete with the other stream's kernels -- 2.74 -> 2.67 ms per step on
-        one stream, 197.0 -> 197.6 M pairs/s on two."""
-        if not self.ka_er or records is None or self.entity_emb_matrix.dtype != torch.float32 or self.p_hop < 1:
-            return False
-        return bool(ops.key_addressing_grouped_er_supported(self.dim, self.p_hop, self.n_memory, self.n_relation, self.n_entity,
-                                                            bool(self.args.PS_O_ft)))
-
-    def _ka_flash_for(self, uts, records, B):
-        """Flash form of the grouped key addressing + user MLP (mvin_key_addressing_flash_fwd) for a batch of B pairs?  Its per-call
-        tables cost ~(nR + P + 1) n_entity rows of work whatever the batch (0.15 ms at BASELINE C3, where the kernel then takes 0.52
-        ms against 0.89 + 0.15 for the kernel over the records + the MLP launch; amazon-book's 39 relations make it a 1.1 GB table):
-        automatic when the users the batch can hold reference at least as many ripple rows as the table has -- users x P x Nm >=
-        nR x n_entity.  ``self.ka_flash`` True / False (MVIN_KA_FLASH=1 / 0) forces it."""
-        if (records is None or self.ka_flash is False or self.entity_emb_matrix.dtype != torch.float32 or self.p_hop < 1
-                or not ops.key_addressing_flash_supported(self.dim, self.p_hop, self.n_memory, self.n_relation, self.n_entity)):
-            return False
-        if self.ka_flash:
-            return True
-        users = min(int(B), int(uts.shape[0]), int(self._distinct_hint or uts.shape[0]))
-        # (and never a workspace beyond FLASH_TABLES_MAX_BYTES per stream on its own initiative: nR = 100 relations over 10^6
-        #  entities would be a 27 GB table)
-        if _lib_flash_elems(self) * 4 > self.FLASH_TABLES_MAX_BYTES:
-            return False
-        return users * self.p_hop * self.n_memory >= self.n_relation * self.n_entity
-
-    def _score_l2_native(self, item, mem_h, mem_r, mem_t, uts=None, users=None, grouped=False):
+    def _score_l2_native(self, item, mem_h, mem_r, mem_t, uts=None, users=None, grouped=False, ka="per_pair", records=False):
         """model.py:125-159 through mvin_score_l2_fwd.  The argument block (every weight pointer) is built once and
-        kept until a parameter tensor is replaced; per call only the batch pointers change."""
+        kept until a parameter tensor is replaced; per call only the batch pointers change.  ``grouped`` / ``ka`` / ``records``: the
+        route's decision (pairs grouped by user, its key-addressing form, the static records go along)."""
         from . import _lib
         import ctypes as C
         a, D, P, B = self.args, self.dim, self.p_hop, item.shape[0]
@@ -1017,15 +1043,15 @@ class MVIN(object):
         form = plan.form
         enc = self.encoded_adjacency() if plan.adjacency == "encoded" else None
         s.enc_entity, s.enc_relation = (ptr(enc[0]), ptr(enc[1])) if enc is not None else (None, None)
-        rec = self.user_records(uts) if grouped else None
+        rec = self._records(uts) if records else None
         s.user_records = ptr(rec)
         st["live"] = (self.entity_emb_matrix, t0, t1, enc, rec)
         s.ka_er = s.ka_flash = None
         stream = torch.cuda.current_stream()
         cs, lib = stream.cuda_stream, _lib.load()
-        if grouped and self._ka_flash_for(uts, rec, B):    # flash form: its tables are rebuilt by every call
-            s.ka_flash = self._stream_ws(self._ka_flash_ws, _lib_flash_elems(self), stream=cs).data_ptr()
-        elif grouped and self._ka_er_for(uts, rec):        # gathered U rows: the table is rebuilt by every call
+        if ka == "flash":            # its tables are rebuilt by every call
+            s.ka_flash = self._stream_ws(self._ka_flash_ws, self._route_shape_caps()[1].flash_tables_elems, stream=cs).data_ptr()
+        elif ka == "gathered_er":    # gathered U rows: the table is rebuilt by every call
             s.ka_er = self._stream_ws(self._ka_er_ws, lib.mvin_project_relations_elems(self.n_entity, self.n_relation, D), stream=cs).data_ptr()
         n_o = P + (1 if a.PS_O_ft else 0)
         # projected tables: E.W1 | E.W1.A0 | E.W2.A0 is rebuilt by every call from the current parameters (~n_entity rows of work against
@@ -1071,21 +1097,22 @@ class MVIN(object):
         return SimpleNamespace(scores=scores, scores_normalized=sig, user_o=user_o, item_embeddings=item_emb,
                                importance_list=[])
 
-    def _key_addressing_grouped(self, user, item, uts):
-        """model.py:161-240 with the pairs grouped by user (mvin_key_addressing_grouped_fwd) -> user_o [B,D]."""
+    def _key_addressing_grouped(self, user, item, uts, form, records):
+        """model.py:161-240 with the pairs grouped by user (mvin_key_addressing_grouped_fwd) -> user_o [B,D].  ``form``: the route's
+        key-addressing form (route_plan.GROUPED_FORMS); ``records``: the call wants the static per-user records."""
         a, D, P = self.args, self.dim, self.p_hop
         n_o = P + 1 if a.PS_O_ft else P
         o_cat = torch.empty((item.shape[0], n_o * D), dtype=torch.float32, device=self.device)
         w_h = self.h_emb_item_mlp_matrix.view(-1) if a.PS_O_ft else None
         groups = ops.group_pairs_by_user(user, n_user=uts.shape[0])
-        rec = self.user_records(uts)
-        if self._ka_flash_for(uts, rec, item.shape[0]):
+        rec = self._records(uts) if records else None
+        if form == "flash":
             kp = getattr(self, "_ka_profile", None)      # bench.py: HIP events around the table build and the kernel
             if kp is not None:
                 evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 evs[0].record()
             tabs = ops.key_addressing_flash_prepare(self.entity_emb_matrix, self.relation_emb_KGE_matrix, w_h, self.user_mlp_matrix, P,
-                                                    out=self._stream_ws(self._ka_flash_ws, _lib_flash_elems(self)))
+                                                    out=self._stream_ws(self._ka_flash_ws, self._route_shape_caps()[1].flash_tables_elems))
             if kp is not None:
                 evs[1].record()
             uo = ops.key_addressing_flash(self.entity_emb_matrix, tabs, rec, groups, item, P, self.n_memory, self.n_relation,
@@ -1094,33 +1121,10 @@ class MVIN(object):
                 evs[2].record()
                 kp.append(evs)
             return uo
-        if not ops.user_records_supported(self.dim, P, self.n_memory, self.n_relation, self.entity_emb_matrix.dtype == torch.bfloat16):
-            rec = None                                   # (records built for the flash form's sake on a shape the records kernel does not take)
-        er = ops.project_relations(self.entity_emb_matrix, self.relation_emb_KGE_matrix, w_h) if self._ka_er_for(uts, rec) else None
+        er = ops.project_relations(self.entity_emb_matrix, self.relation_emb_KGE_matrix, w_h) if form == "gathered_er" else None
         ops.key_addressing_grouped(self.entity_emb_matrix, self.relation_emb_KGE_matrix, w_h, uts, groups, item, P,
-                                   o_cat, n_o * D, self.n_relation, records=rec, er=er)
+                                   o_cat, n_o * D, self.n_relation, records=rec if form in route_plan.RECORD_FORMS else None, er=er)
         return ops.linear([o_cat], self.user_mlp_matrix, D, bias=self.user_mlp_bias)
-
-    def _forward_small(self, users, items, mem_h, mem_r, mem_t, uts):
-        """The short way into the single-launch pass (the checks of forward_device that matter for it, nothing else): None
-        when the call is not its case."""
-        if not self._small_ok(items, mem_h, False):
-            return None
-        P, B = self.p_hop, items.shape[0]
-        if uts is not None:
-            self._check_uts(uts)
-            if (uts.dtype == torch.int32 and uts.is_contiguous() and uts.shape[1] == P and uts.shape[3] == self.n_memory
-                    and users.dtype == torch.int64 and users.dim() == 1 and users.shape[0] == B and users.is_contiguous()):
-                return self._score_small_native(items, None, None, None, uts=uts, users=users)
-            return None
-        if mem_h is None or len(mem_h) < P or len(mem_r) < P or len(mem_t) < P:
-            return None
-        Nm = self.n_memory
-        for lst in (mem_h, mem_r, mem_t):
-            for m_ in lst[:P]:
-                if m_.dtype != torch.int32 or m_.dim() != 2 or m_.shape[0] != B or m_.shape[1] != Nm or not m_.is_contiguous():
-                    return None
-        return self._score_small_native(items, mem_h, mem_r, mem_t)
 
     def forward_device(self, user_indices, item_indices, memories_h, memories_r, memories_t,
                        want_probs=False, uts=None, distinct_users=None):
@@ -1128,22 +1132,17 @@ class MVIN(object):
         [B, n_memory] per hop).  Returns a namespace of device tensors.
         Shared-user form: ripple sets given as ONE [n_memory] list per hop (and ``user_indices`` a
         single id or [B]) score one user against ``item_indices`` -- see ``_key_addressing_shared``.
-        ``uts`` (instead of the memories): see ``forward_users``."""
+        ``uts`` (instead of the memories): see ``forward_users``.  Which schedule, feed and key-addressing form the call
+        takes: ``_route`` (mvin_amd/route_plan.py)."""
         a = self.args
         if not item_indices.is_cuda:
             raise RuntimeError("forward_device needs device-resident inputs (no CPU path)")
-        if (self.small_max_batch and not want_probs and not self.validate_device_ids and item_indices.dim() == 1
-                and item_indices.shape[0] <= self.small_max_batch and item_indices.is_contiguous()):
-            out = self._forward_small(user_indices, item_indices, memories_h, memories_r, memories_t, uts)
-            if out is not None:
-                return out
         self._distinct_hint = distinct_users
         item32 = item_indices.contiguous()   # int64 (reference dtype) or int32: kernels take both
         user32 = user_indices.contiguous()
-        need_ps = a.PS_only or (not a.HO_only) or a.User_orient_kg_eh
-        grouped = False
         if uts is not None:
             self._check_uts(uts)
+            memories_h = memories_r = memories_t = None
         if self.validate_device_ids:
             self._check_device_ids(item32, self.n_entity, "item_indices")
             self._check_device_ids(user32, uts.shape[0] if uts is not None else self.n_user, "user_indices")
@@ -1151,65 +1150,44 @@ class MVIN(object):
                                    (memories_t, self.n_entity, "memories_t")):
                 for m_ in (lst or ()):
                     self._check_device_ids(m_, lim, what)
-        if uts is not None:
-            if user32.numel() == 1 and item32.shape[0] > 1:
-                user32 = user32.reshape(1).expand(item32.shape[0]).contiguous()
-            # grouping pays when users repeat inside the batch (a user's rows are staged once per segment); with
-            # about one pair per user the per-pair kernel is the faster one (measured: amazon-shaped, 32 768 pairs
-            # of 70 585 users: 15.5 M vs 10.1 M pairs/s).  Static rule, no device sync: pairs per user >= 4.
-            grouped = (need_ps and self.fused is not False and uts.dtype == torch.int32 and uts.is_contiguous()
-                       and item32.shape[0] >= self.group_min_pairs_per_user * min(uts.shape[0], int(distinct_users or uts.shape[0]))
-                       and ops.key_addressing_grouped_supported(self.dim, self.p_hop, self.n_memory, self.n_relation))
-            feed_ok = (need_ps and uts.dtype == torch.int32 and uts.is_contiguous() and uts.dim() == 4
-                       and uts.shape[1] == self.p_hop and uts.shape[3] == self.n_memory and user32.dtype == torch.int64
-                       and user32.shape[0] == item32.shape[0])
-            if feed_ok and self._small_ok(item32, None, want_probs):
-                return self._score_small_native(item32, None, None, None, uts=uts, users=user32)     # ONE launch
-            if (feed_ok and self._native_l2_ok(item32, None, want_probs, cap=not grouped)):
-                # one native call; key addressing indexes user_triplet_set by users[b] itself, or -- grouped -- sorts the
-                # batch by user on the device first (any batch size: the host issues ONE call per step instead of seven)
-                return self._score_l2_native(item32, None, None, None, uts=uts, users=user32, grouped=grouped)
-            users_kernel = (need_ps and not grouped and self.fused is not False and uts.dtype == torch.int32 and uts.is_contiguous()
-                            and uts.dim() == 4 and uts.shape[1] == max(1, self.p_hop) and uts.shape[3] == self.n_memory
-                            and user32.shape[0] == item32.shape[0] and user32.dtype in (torch.int64, torch.int32)
-                            and ops.key_addressing_supported(self.n_memory, self.dim))
-            if need_ps and not grouped and not users_kernel:     # any other wiring: assemble the per-pair feeds on the device
-                sel = uts[user32.long()]
-                P_ = sel.shape[1]
-                memories_h = [sel[:, i, 0].contiguous() for i in range(P_)]
-                memories_r = [sel[:, i, 1].contiguous() for i in range(P_)]
-                memories_t = [sel[:, i, 2].contiguous() for i in range(P_)]
-        else:
-            users_kernel = False
-        shared = (not grouped) and memories_h is not None and memories_h[0].dim() == 1   # one user's sets for the batch
-        if not grouped and not shared and memories_h is not None \
-                and all(m_.dtype == torch.int32 and m_.is_contiguous() for lst in (memories_h, memories_r, memories_t)
-                        for m_ in lst[:self.p_hop]):
-            if self._small_ok(item32, memories_h, want_probs):
-                return self._score_small_native(item32, memories_h, memories_r, memories_t)          # ONE launch
-            if self._native_l2_ok(item32, memories_h, want_probs):
-                return self._score_l2_native(item32, memories_h, memories_r, memories_t)
-        if shared and user32.numel() == 1:
-            user32 = user32.reshape(1).expand(item32.shape[0]).contiguous()
-        if shared and (self.n_memory % 4 != 0 or self.n_memory > 256):
-            # outside the dense form (the [B, Nm] logits go through mvin_linear_fwd): replicate the sets
-            rep = lambda lst: [m_.reshape(1, -1).expand(item32.shape[0], -1).contiguous() for m_ in lst]
+        route = self._route(user32, item32, memories_h, memories_r, memories_t, uts, want_probs, distinct_users)
+        schedule, feed, ka = route.schedule, route.feed, route.key_addressing
+        B = item32.shape[0]
+        if route.broadcast_user:
+            user32 = user32.reshape(1).expand(B).contiguous()
+        if schedule == "small" and feed != "assembled":            # ONE launch
+            return (self._score_small_native(item32, None, None, None, uts=uts, users=user32) if feed == "users"
+                    else self._score_small_native(item32, memories_h, memories_r, memories_t))
+        if feed == "assembled":              # any other wiring: assemble the per-pair feeds on the device
+            sel = uts[user32.long()]
+            memories_h, memories_r, memories_t = ([sel[:, i, x].contiguous() for i in range(sel.shape[1])] for x in range(3))
+        elif feed == "pairs" and memories_h is not None and memories_h[0].dim() == 1:
+            # one shared list outside the dense form (the [B, Nm] logits go through mvin_linear_fwd): replicate the sets
+            rep = lambda lst: [m_.reshape(1, -1).expand(B, -1).contiguous() for m_ in lst]
             memories_h, memories_r, memories_t = rep(memories_h), rep(memories_r), rep(memories_t)
-            shared = False
-        if not need_ps:
+        if schedule == "small":
+            return self._score_small_native(item32, memories_h, memories_r, memories_t)
+        if schedule == "native":
+            # one native call; key addressing indexes user_triplet_set by users[b] itself, or -- grouped -- sorts the batch by user on
+            # the device first; else it reads the per-pair lists
+            if feed == "users":
+                return self._score_l2_native(item32, None, None, None, uts=uts, users=user32, grouped=ka in route_plan.GROUPED_FORMS,
+                                             ka=ka, records=route.records)
+            return self._score_l2_native(item32, memories_h, memories_r, memories_t)
+        if ka == "none":
             ps = None
-        elif grouped:
-            ps = self._key_addressing_grouped(user32, item32, uts)
-        elif users_kernel:
-            # the Python schedule of the users feed (batches above native_l2_max_batch, sharded tables): key addressing reads the
-            # lists of users[b] out of user_triplet_set itself -- it was a torch gather + three copies per step to assemble them
+        elif ka in route_plan.GROUPED_FORMS:
+            ps = self._key_addressing_grouped(user32, item32, uts, ka, route.records)
+        elif ka == "users_feed":
+            # key addressing reads the lists of users[b] out of user_triplet_set itself -- it was a torch gather + three copies per
+            # step to assemble them
             ps = self._key_addressing(user32, item32, None, None, None, uts=uts)
-        elif shared:
+        elif ka == "shared":
             ps = self._key_addressing_shared(item32, [m_.contiguous() for m_ in memories_h],
                                              [m_.contiguous() for m_ in memories_r],
                                              [m_.contiguous() for m_ in memories_t])
         else:
-            ps = self._key_addressing(user32, item32, memories_h, memories_r, memories_t)
+            ps = self._key_addressing(user32, item32, memories_h, memories_r, memories_t, ripple=ka == "ripple")
         importance = []
         if a.PS_only:  # :142-144
             user_o = ps
