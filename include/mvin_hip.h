@@ -940,6 +940,49 @@ MVIN_API int mvin_mmr_segments(const float* scores, int64_t total, const int64_t
                                int form, int32_t* out_pos, float* out_vals, int32_t* out_ids, float* out_mmr, float* out_pen,
                                float* out_simsum, int64_t* status, void* stream);
 
+/* ---- first-stage retrieval: inner-product scores of query vectors against table rows, dense or fused with top-K (an opt-in
+ * extension; the reference ranks the whole catalogue with the model) --
+ * `q` is f32 [nq, D], dense, 16-byte aligned; `feat`, n_rows, D and ld are the table of mvin_mmr_segments (f32 only, never
+ * written).  Column j of a call is table row cand_ids[j] (int32 [n]); with cand_ids NULL it is row col_offset + j, as in
+ * mvin_topk_rows.  A column whose row id is negative or >= n_rows is INELIGIBLE and its row is never read.
+ * score(i, j) = dot(q[i], feat[row_j]) in f32, times q_scale[i] when `q_scale` ([nq] f32) is given, then times row_scale[row_j]
+ * when `row_scale` ([n_rows] f32) is given, each product rounded to f32; mvin_row_inv_norms on both sides makes it a cosine.
+ * The dot product of a pair is accumulated on the matrix cores in one fixed order of d, so a score is a pure function of the
+ * two rows and the two scales: the same bits in both entry points, for every split count, tile position and nq.  A score that
+ * is a NaN is written as the quiet NaN 0x7FC00000 and a zero score as +0.0 (its bits are those of its image,
+ * csrc/mvin_score_image.h).
+ *  - mvin_mips_scores: out[i*ldo + j] = score(i, j) for every query and column; an ineligible column gets the quiet NaN.
+ *  - mvin_mips_topk: out_ids / out_vals [nq, k] receive each query's k best ELIGIBLE columns, the row id and the score: what
+ *    mvin_topk_rows returns on the dense scores of the eligible columns -- -0.0 equals +0.0, every NaN is equal and below -inf,
+ *    equal scores go to the lower column, row i's exclusion list excl_ids[excl_ptr[i] .. excl_ptr[i+1]) (ascending row ids;
+ *    both NULL = none) removes columns, a short row ends in id -1, value -inf.  No [nq, n] buffer exists at any point.
+ *    `splits`: 0 lets the library cut the columns into ranges for separate workgroups when the queries alone do not fill the
+ *    device, a positive value forces that many; the result does not depend on it.  `ws`: mvin_mips_topk_ws_bytes(nq, n, k,
+ *    splits) bytes, 8-byte aligned (0 bytes without splits: NULL is taken).
+ *    mvin_mips_topk_max_k() is the largest k of the fused form; mvin_mips_topk_supported(k, D) says whether a shape is taken;
+ *    a larger k (up to 1024) is served by mvin_mips_scores over column blocks and mvin_topk_rows with its carry.
+ *  - mvin_mean_rows_segments: out [n_seg, D]; out[s] = the mean of feat[ids[e]] over the entries e of segment
+ *    [seg_ptr[s], seg_ptr[s+1]) (seg_ptr [n_seg+1] int64, ids int32 [total]) whose id lies inside the table; each component is
+ *    summed in f64 in entry order, divided by the count in f64 and rounded to f32 once.  A segment without such an entry (or with
+ *    pointers outside [0, total]) gives a zero row.  No atomics: the bits do not depend on `group` (lanes per segment: 0 =
+ *    automatic, or 8 / 16 / 32 / 64) or on the grid.
+ * Errors (< 0, nothing launched, the reason in mvin_last_error()): -2 for sizes (nq, n outside 0 .. 2^31 - 1, the table limits
+ * of mvin_mmr_segments, k outside 1 .. 1024, splits outside 0 .. 4096, ldo < n, a misaligned pointer, an implicit id beyond
+ * int32, a bad group), -1 for null required pointers or exactly one of excl_ptr / excl_ids, -3 for a k the fused form does not
+ * take.  nq == 0 (n_seg == 0) launches nothing. */
+MVIN_API int mvin_mips_topk_max_k(void);
+MVIN_API int mvin_mips_topk_supported(int k, int D);
+MVIN_API int64_t mvin_mips_topk_ws_bytes(int64_t nq, int64_t n, int k, int splits);      /* < 0: invalid sizes */
+MVIN_API int mvin_mips_scores(const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld,
+                              const float* q_scale /* [nq] or NULL */, const float* row_scale /* [n_rows] or NULL */,
+                              const int32_t* cand_ids, int64_t col_offset, int64_t n, float* out, int64_t ldo, void* stream);
+MVIN_API int mvin_mips_topk(const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld,
+                            const float* q_scale /* [nq] or NULL */, const float* row_scale /* [n_rows] or NULL */,
+                            const int32_t* cand_ids, int64_t col_offset, int64_t n, const int64_t* excl_ptr, const int32_t* excl_ids,
+                            int k, int splits, void* ws, int32_t* out_ids, float* out_vals, void* stream);
+MVIN_API int mvin_mean_rows_segments(const float* feat, int64_t n_rows, int D, int64_t ld, const int64_t* seg_ptr, int64_t n_seg,
+                                     const int32_t* ids, int64_t total, int group, float* out /* [n_seg, D] */, void* stream);
+
 /* ---- CTR metrics: exact integer counts behind the reference's CTR evaluation (util.py:44-56: roc_auc_score, accuracy and
  * f1_score of every batch) for many segments at once --
  * mvin_ctr_counts: segment s is scores[s*ld .. s*ld+seg_len) (f32) with labels[s*ld .. s*ld+seg_len) (int32, 0 or 1); neither is

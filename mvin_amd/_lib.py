@@ -105,6 +105,15 @@ SIGNATURES = {
     "mvin_mmr_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
                           + [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_int64, C.c_int]
                           + [C.c_void_p] * 8),
+    "mvin_mips_topk_max_k": (C.c_int, []),
+    "mvin_mips_topk_supported": (C.c_int, [C.c_int, C.c_int]),
+    "mvin_mips_topk_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mvin_mips_scores": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64] + [C.c_void_p] * 3
+                         + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvin_mips_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64] + [C.c_void_p] * 3
+                       + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "mvin_mean_rows_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_int, C.c_void_p, C.c_void_p]),
     "mvin_kg_explore_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_kg_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
     "mvin_kg_explore": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,

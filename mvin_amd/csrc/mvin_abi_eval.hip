@@ -142,6 +142,80 @@ int mvin_mmr_segments(const float* scores, int64_t total, const int64_t* seg_ptr
                       who);
 }
 
+int mvin_mips_topk_max_k(void) { return mvin::mips_topk_max_k(); }
+
+int mvin_mips_topk_supported(int k, int D) { return mvin::mips_topk_supported(k, D) ? 1 : 0; }
+
+// what the two score entry points check alike: the queries, the table (mmr_bad_table), the scales' companions and the columns
+static int mips_bad_args(const char* who, const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld,
+                         const int32_t* cand_ids, int64_t col_offset, int64_t n) {
+    if (nq < 0 || nq >= (int64_t(1) << 31) || n < 0 || n >= (int64_t(1) << 31))
+        return fail(-2, "%s: nq=%lld n=%lld (0 <= nq, n < 2^31)", who, (long long)nq, (long long)n);
+    if (const int rc = mmr_bad_table(who, feat, n_rows, D, ld)) return rc;
+    if (nq > 0 && !q) return fail(-1, "%s: null q", who);
+    if (reinterpret_cast<uintptr_t>(q) & 15) return fail(-2, "%s: q is not 16-byte aligned", who);
+    if (!cand_ids && (col_offset < 0 || col_offset + n > (int64_t)0x7FFFFFFF))
+        return fail(-2, "%s: col_offset=%lld: implicit ids col_offset + j must be int32", who, (long long)col_offset);
+    return 0;
+}
+
+int mvin_mips_scores(const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld, const float* q_scale,
+                     const float* row_scale, const int32_t* cand_ids, int64_t col_offset, int64_t n, float* out, int64_t ldo,
+                     void* stream) {
+    const char* who = "mvin_mips_scores";
+    if (const int rc = mips_bad_args(who, q, nq, feat, n_rows, D, ld, cand_ids, col_offset, n)) return rc;
+    if (ldo < n) return fail(-2, "%s: ldo=%lld n=%lld (ldo >= n)", who, (long long)ldo, (long long)n);
+    if (((nq + 31) / 32) * ((n + 255) / 256) >= (int64_t(1) << 31))
+        return fail(-2, "%s: nq=%lld n=%lld: more than 2^31 tiles of 32 x 256 in one call", who, (long long)nq, (long long)n);
+    if (nq > 0 && n > 0 && !out) return fail(-1, "%s: null out", who);
+    return hip_result(mvin::launch_mips_scores(q, nq, feat, n_rows, D, ld, q_scale, row_scale, cand_ids, col_offset, n, out, ldo,
+                                               (hipStream_t)stream),
+                      who);
+}
+
+int64_t mvin_mips_topk_ws_bytes(int64_t nq, int64_t n, int k, int splits) {
+    if (nq < 0 || nq >= (int64_t(1) << 31) || n < 0 || n >= (int64_t(1) << 31) || k < 1 || k > 1024 || splits < 0 ||
+        splits > mvin::mips_max_splits())
+        return fail(-2, "mvin_mips_topk_ws_bytes: nq=%lld n=%lld k=%d splits=%d", (long long)nq, (long long)n, k, splits);
+    return mvin::mips_topk_ws_bytes(nq, n, k, splits);
+}
+
+int mvin_mips_topk(const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld, const float* q_scale,
+                   const float* row_scale, const int32_t* cand_ids, int64_t col_offset, int64_t n, const int64_t* excl_ptr,
+                   const int32_t* excl_ids, int k, int splits, void* ws, int32_t* out_ids, float* out_vals, void* stream) {
+    const char* who = "mvin_mips_topk";
+    if (k < 1 || k > 1024) return fail(-2, "%s: k=%d (1 <= k <= 1024)", who, k);
+    if (splits < 0 || splits > mvin::mips_max_splits())
+        return fail(-2, "%s: splits=%d (0 = automatic, 1 .. %d)", who, splits, mvin::mips_max_splits());
+    if (const int rc = mips_bad_args(who, q, nq, feat, n_rows, D, ld, cand_ids, col_offset, n)) return rc;
+    if (!mvin::mips_topk_supported(k, D))
+        return fail(-3, "%s: unsupported shape k=%d D=%d (the fused form takes k <= %d; compose mvin_mips_scores and mvin_topk_rows)", who,
+                    k, D, mvin::mips_topk_max_k());
+    const int S = mvin::mips_resolve_splits(nq, n, splits);
+    if (((nq + 31) / 32) * S >= (int64_t(1) << 31) || nq * (int64_t)S * k >= (int64_t(1) << 40))
+        return fail(-2, "%s: nq=%lld splits=%d k=%d: too many workgroups or partial results in one call", who, (long long)nq, S, k);
+    if ((excl_ptr == nullptr) != (excl_ids == nullptr)) return fail(-1, "%s: excl_ptr and excl_ids go together", who);
+    if (nq > 0 && (!out_ids || !out_vals)) return fail(-1, "%s: null out_ids / out_vals", who);
+    if (nq > 0 && S > 1 && !ws) return fail(-1, "%s: null ws (splits=%d needs mvin_mips_topk_ws_bytes)", who, S);
+    if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(-2, "%s: ws is not 8-byte aligned", who);
+    return hip_result(mvin::launch_mips_topk(q, nq, feat, n_rows, D, ld, q_scale, row_scale, cand_ids, col_offset, n, excl_ptr, excl_ids,
+                                             k, splits, ws, out_ids, out_vals, (hipStream_t)stream),
+                      who);
+}
+
+int mvin_mean_rows_segments(const float* feat, int64_t n_rows, int D, int64_t ld, const int64_t* seg_ptr, int64_t n_seg,
+                            const int32_t* ids, int64_t total, int group, float* out, void* stream) {
+    const char* who = "mvin_mean_rows_segments";
+    if (n_seg < 0 || n_seg >= (int64_t(1) << 31) || total < 0)
+        return fail(-2, "%s: n_seg=%lld total=%lld", who, (long long)n_seg, (long long)total);
+    if (group != 0 && group != 8 && group != 16 && group != 32 && group != 64)
+        return fail(-2, "%s: group=%d (0 automatic, or 8 / 16 / 32 / 64 lanes per segment)", who, group);
+    if (const int rc = mmr_bad_table(who, feat, n_rows, D, ld)) return rc;
+    if (!seg_ptr || (total > 0 && !ids) || (n_seg > 0 && !out)) return fail(-1, "%s: null seg_ptr / ids / out", who);
+    return hip_result(mvin::launch_mean_rows_segments(feat, n_rows, D, ld, seg_ptr, n_seg, ids, total, group, out, (hipStream_t)stream),
+                      who);
+}
+
 static bool kg_bad_sizes(int64_t n_entity, int64_t M) {
     return n_entity < 0 || n_entity > (int64_t)0x7FFFFFFF || M < 0 || M > (int64_t)0x7FFFFFFF;
 }

@@ -480,6 +480,20 @@ hipError_t launch_mmr_segments(const float* scores, int64_t total, const int64_t
                                const int64_t* excl_ptr, const int32_t* excl_ids, const float* feat, int64_t n_rows, int D, int64_t ld,
                                const float* row_scale, float lam, int k, int64_t max_len, int form, int32_t* out_pos, float* out_vals,
                                int32_t* out_ids, float* out_mmr, float* out_pen, float* out_simsum, int64_t* status, hipStream_t st);
+int mips_topk_max_k();                                          // first-stage retrieval: inner-product scores and fused top-K (mvin_mips.hip)
+int mips_max_splits();
+bool mips_dim_ok(int D);
+bool mips_topk_supported(int k, int D);
+int mips_resolve_splits(int64_t nq, int64_t n, int splits);
+int64_t mips_topk_ws_bytes(int64_t nq, int64_t n, int k, int splits);
+hipError_t launch_mips_scores(const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld, const float* q_scale,
+                              const float* row_scale, const int32_t* cand_ids, int64_t col_offset, int64_t n, float* out, int64_t ldo,
+                              hipStream_t st);
+hipError_t launch_mips_topk(const float* q, int64_t nq, const float* feat, int64_t n_rows, int D, int64_t ld, const float* q_scale,
+                            const float* row_scale, const int32_t* cand_ids, int64_t col_offset, int64_t n, const int64_t* excl_ptr,
+                            const int32_t* excl_ids, int k, int splits, void* ws, int32_t* out_ids, float* out_vals, hipStream_t st);
+hipError_t launch_mean_rows_segments(const float* feat, int64_t n_rows, int D, int64_t ld, const int64_t* seg_ptr, int64_t n_seg,
+                                     const int32_t* ids, int64_t total, int group, float* out, hipStream_t st);
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);

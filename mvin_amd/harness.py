@@ -338,6 +338,114 @@ class DeviceFeeder(object):
                              out=(pos[s0:s1], vals[s0:s1], oid[s0:s1], None, pen[s0:s1], simsum[s0:s1], status))
         return oid.long(), vals, pos, pen, simsum
 
+    def _retrieval_table(self, name):
+        """The item rows retrieval scores against: ``model.entity_emb_matrix`` (the items are the low entity ids), f32 only."""
+        import torch
+        feat = self.model.entity_emb_matrix
+        if not torch.is_tensor(feat) or feat.dtype != torch.float32 or feat.dim() != 2:
+            raise ValueError(f"{name}: the entity table must be an f32 [n_rows, D] tensor, got "
+                             f"{feat.dtype if torch.is_tensor(feat) else type(feat).__name__} (a bf16 table is not taken)")
+        return feat.detach()
+
+    def user_queries(self, users, history):
+        """The default retrieval query of every user, f32 [U, D] on the device: the mean entity embedding of the user's
+        positive train items (ops.mean_rows_segments: summed in f64 in interaction order, rounded once, bit-reproducible).
+        ``history`` is a ``data_prep.history_csr`` pair (ptr int64 [n_user + 1], items int32) on the device; the means of all
+        its users are built and the rows of ``users`` taken.  A user without history gets a ZERO row: every item then scores
+        0 and ``retrieve`` returns the first eligible candidates in candidate order.  This query is a PROXY: MVIN's own user
+        vector depends on the item it is scored against, so nothing guarantees that the proxy keeps MVIN's top-k
+        (``retrieval_eval`` measures how much it keeps).  Enqueues only."""
+        from . import ops
+        if not isinstance(history, tuple) or len(history) != 2:
+            raise ValueError("user_queries: history must be a data_prep.history_csr pair (ptr, items)")
+        feat = self._retrieval_table("user_queries")
+        u = _dev_ids(users, self.model.device)
+        return ops.mean_rows_segments(feat, history[0], history[1])[u]
+
+    def retrieve(self, users, n_cand, candidates, queries=None, history=None, cosine=False, exclude=None, max_pairs=1 << 26):
+        """First-stage retrieval: every user's ``n_cand`` best candidates by inner product between a query vector and the items'
+        entity embeddings, ``(items int64 [U, n_cand], sims f32 [U, n_cand])`` on the device, best first, equal similarities in
+        the order of ``candidates``, rows short of ``n_cand`` eligible items ending in item -1, similarity -inf
+        (ops.mips_topk: the fused kernel for n_cand <= ops.mips_topk_max_k(), the composed form up to 1024).  ``queries``:
+        an f32 [U, D] device tensor of the caller's own tower; otherwise ``history`` (``user_queries``) is required.
+        ``cosine=True`` divides by both norms (ops.row_inv_norms).  ``candidates`` and ``exclude`` mean what they mean in
+        ``recommend``: a host list that is a contiguous id range takes the implicit-id path, ``exclude`` is a get_user_record
+        dict (``users`` then on the host) or an ``exclusion_csr`` pair.  A candidate id outside the entity table is never
+        returned.  ``max_pairs`` bounds the score buffer of the composed form.  Enqueues only."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        n_cand = int(n_cand)
+        if not 1 <= n_cand <= 1024:
+            raise ValueError(f"retrieve: n_cand={n_cand}: expected 1 .. 1024")
+        if int(max_pairs) < 1:
+            raise ValueError(f"max_pairs={max_pairs}")
+        if queries is None and history is None:
+            raise ValueError("retrieve: pass queries ([U, D] f32) or history (a data_prep.history_csr pair)")
+        if isinstance(exclude, dict):
+            if torch.is_tensor(users) and users.is_cuda:
+                raise ValueError("retrieve: an exclusion record needs host users (or pass feeder.exclusion_csr(users, record))")
+            exclude = self.exclusion_csr(users, exclude)
+        feat = self._retrieval_table("retrieve")
+        u = _dev_ids(users, dev)
+        U = u.shape[0]
+        if queries is None:
+            q = self.user_queries(u, history)
+        else:
+            if not torch.is_tensor(queries) or queries.dtype != torch.float32 or tuple(queries.shape) != (U, feat.shape[1]):
+                raise ValueError(f"retrieve: queries must be an f32 [{U}, {feat.shape[1]}] tensor")
+            q = queries.to(dev).contiguous()
+        cand_ids, base, N = _candidate_columns(candidates, dev)
+        q_scale = row_scale = None
+        if cosine:
+            row_scale = ops.row_inv_norms(feat)
+            q_scale = ops.row_inv_norms(q) if U else None
+        ids, sims = ops.mips_topk(q, feat, n_cand, cand_ids=cand_ids, col_offset=base, n=None if cand_ids is not None else N,
+                                  q_scale=q_scale, row_scale=row_scale, excl=exclude, max_scores=int(max_pairs))
+        return ids.long(), sims
+
+    def recommend_two_stage(self, users, k, n_cand, candidates, queries=None, history=None, cosine=False, exclude=None,
+                            max_pairs=524288):
+        """``retrieve`` followed by ``recommend_lists`` on the retrieved lists: the model scores ``n_cand`` items per user, not
+        the catalogue.  Arguments as in ``retrieve`` (``max_pairs`` is ``recommend_lists``'); the -1 padding of a short
+        retrieved list is ``recommend_lists``' padding.  Returns what ``recommend_lists`` returns, ``positions`` being places
+        in the user's retrieved list.  With ``n_cand`` at least the user's eligible candidates the item set is ``recommend``'s.
+        Nothing is copied back."""
+        k, n_cand = int(k), int(n_cand)
+        items, _ = self.retrieve(users, n_cand, candidates, queries=queries, history=history, cosine=cosine, exclude=exclude)
+        U = items.shape[0]
+        ptr = np.arange(U + 1, dtype=np.int64) * n_cand
+        return self.recommend_lists(users, (ptr, items.reshape(-1)), k, max_pairs=max_pairs)
+
+    def similar_items(self, items, k, candidates, cosine=True):
+        """Item-to-item neighbours: for every item of ``items`` (rows of the entity table) the ``k`` candidates whose entity
+        embedding has the largest cosine (``cosine=False``: inner product) with the item's own, the item itself excluded
+        through a one-id exclusion row: ``(neighbours int64 [n, k], sims f32 [n, k])`` on the device.  ``candidates`` as in
+        ``recommend``.  Enqueues only."""
+        import torch
+        from . import ops
+        dev = self.model.device
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError(f"similar_items: k={k}: expected 1 .. 1024")
+        feat = self._retrieval_table("similar_items")
+        if not torch.is_tensor(items):
+            arr = np.asarray(items, dtype=np.int64).reshape(-1)
+            if arr.size and (arr.min() < 0 or arr.max() >= feat.shape[0]):
+                raise ValueError(f"similar_items: item ids must be rows of the entity table (0 .. {feat.shape[0] - 1})")
+        it = _dev_ids(items, dev)
+        n = it.shape[0]
+        q = feat[it.clamp(0, max(feat.shape[0] - 1, 0))].contiguous()
+        excl = (torch.arange(n + 1, dtype=torch.int64, device=dev), it.to(torch.int32))
+        cand_ids, base, N = _candidate_columns(candidates, dev)
+        q_scale = row_scale = None
+        if cosine:
+            row_scale = ops.row_inv_norms(feat)
+            q_scale = row_scale[it.clamp(0, max(feat.shape[0] - 1, 0))].contiguous()
+        ids, sims = ops.mips_topk(q, feat, k, cand_ids=cand_ids, col_offset=base, n=None if cand_ids is not None else N,
+                                  q_scale=q_scale, row_scale=row_scale, excl=excl)
+        return ids.long(), sims
+
     def rank_lists(self, users, lists, queries, exclude=None, max_pairs=524288):
         """Where named entries of every user's OWN candidate list land in the user's ranking of that list: the device tensors
         ``(q_ptr int64 [U+1], q_pos int32 [Q], counts int32 [Q, 3], vals f32 [Q], eligible int32 [U])`` of ``rank_positives``,
@@ -567,6 +675,23 @@ def _candidate_ids(candidates, dev):
     contiguous = bool(N and arr[0] >= 0 and arr[-1] < (1 << 31) - 1 and np.array_equal(arr, np.arange(arr[0], arr[0] + N)))
     cand = torch.from_numpy(arr).to(dev)
     return cand, None if contiguous else cand.to(torch.int32), int(arr[0]) if contiguous else 0
+
+
+def _candidate_columns(candidates, dev):
+    """(int32 ids per column on the device or None, first id, N) for the retrieval calls: ``_candidate_ids`` without the int64
+    copy of the list on the device, which retrieval never reads; a ``range`` of step 1 is not even expanded on the host."""
+    import torch
+    if isinstance(candidates, range) and candidates.step == 1 and (len(candidates) == 0 or
+                                                                   (candidates.start >= 0 and candidates.stop < (1 << 31))):
+        return None, candidates.start if len(candidates) else 0, len(candidates)
+    if torch.is_tensor(candidates):
+        cand = candidates.to(dev).reshape(-1)
+        return cand.clamp(-1, (1 << 31) - 1).to(torch.int32), 0, cand.shape[0]      # an id int32 cannot hold is beyond every table
+    arr = np.asarray(candidates, dtype=np.int64).reshape(-1)
+    N = arr.shape[0]
+    if N and arr[0] >= 0 and arr[-1] < (1 << 31) - 1 and arr[-1] - arr[0] == N - 1 and np.array_equal(arr, np.arange(arr[0], arr[0] + N)):
+        return None, int(arr[0]), N
+    return torch.from_numpy(np.clip(arr, -1, (1 << 31) - 1).astype(np.int32)).to(dev), 0, N
 
 
 def _dev_ids(x, dev):
@@ -1324,6 +1449,61 @@ def diversity_eval(feeder, users, lists, truth_record, k, lams=(1.0, 0.7, 0.5, 0
         rows.append(dict(lam=lam, recall=float(np.mean(recall)) if recall else 0.0, ndcg=float(np.mean(ndcg)) if ndcg else 0.0,
                          ild=float(np.mean(ild)) if ild else float("nan"), coverage=len(set(it[it >= 0].tolist())) / float(n_item),
                          penalty=float(np.mean(pens)) if pens else float("nan"), n_users=len(recall), n_lists=len(ild), items=it))
+    return rows
+
+
+def retrieval_eval(feeder, users, train_record, truth_record, candidates, n_cand_list, k, history, full_users=0, cosine=False,
+                   max_pairs=524288):
+    """What first-stage retrieval with the history-mean query (DeviceFeeder.user_queries, a PROXY for MVIN's item-dependent
+    user vector) keeps of the model's ranking: for every ``n_cand`` of ``n_cand_list`` ONE ``retrieve`` (the user's
+    ``train_record`` items excluded), ONE ``recommend_lists`` over the retrieved lists and ONE copy back (both id matrices
+    packed into one int32 tensor), the rest in float64 on the host.  ``users`` on the host; only those with a non-empty
+    ``truth_record`` entry (a get_user_record dict of held-out items) are taken.  Returns one dict per ``n_cand``, in order:
+      n_cand; candidate_recall -- the share of a user's held-out items that reach the retrieved list, the mean over users;
+      recall, ndcg -- recall_at_k and ndcg_at_k (hits in the returned order) at ``k`` of the two-stage result, means over users;
+      overlap -- with ``full_users`` > 0: |two-stage top-k intersect ``recommend``'s top-k| / |``recommend``'s top-k| over
+      the first ``full_users`` users (``recommend`` over all candidates runs once, one more copy back), else None;
+      n_users; items -- the two-stage lists, int64 [U, k] on the host (-1 = padding)."""
+    import torch
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"retrieval_eval: k={k}")
+    n_cand_list = [int(x) for x in n_cand_list]
+    if not n_cand_list or any(not 1 <= x <= 1024 for x in n_cand_list):
+        raise ValueError(f"retrieval_eval: n_cand_list={n_cand_list}: expected at least one value, each in 1 .. 1024")
+    if not isinstance(truth_record, dict) or not isinstance(train_record, dict):
+        raise ValueError("retrieval_eval: train_record and truth_record must be dicts of user -> items")
+    if torch.is_tensor(users) and users.is_cuda:
+        raise ValueError("retrieval_eval: users must be on the host (they index the records)")
+    users = [int(x) for x in np.asarray(users.numpy() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
+             if truth_record.get(int(x))]
+    U, F = len(users), min(int(full_users), len(users))
+    excl = feeder.exclusion_csr(users, train_record)
+    full = None
+    if F > 0:
+        full_ids, _ = feeder.recommend(users[:F], k, candidates, exclude=(excl[0][:F + 1], excl[1]))
+        full = full_ids.to(torch.int32).cpu().numpy().reshape(F, k)
+    rows = []
+    for n_cand in n_cand_list:
+        cand, _ = feeder.retrieve(users, n_cand, candidates, history=history, cosine=cosine, exclude=excl)
+        ptr = np.arange(U + 1, dtype=np.int64) * n_cand
+        top, _, _ = feeder.recommend_lists(users, (ptr, cand.reshape(-1)), k, max_pairs=max_pairs)
+        packed = torch.cat([cand.to(torch.int32).reshape(-1), top.to(torch.int32).reshape(-1)]).cpu().numpy()
+        cd = packed[:U * n_cand].reshape(U, n_cand).astype(np.int64)
+        it = packed[U * n_cand:].reshape(U, k).astype(np.int64)
+        cr, recall, ndcg, overlap = [], [], [], []
+        for i, user in enumerate(users):
+            truth = set(int(x) for x in truth_record[user])
+            ranked = [int(x) for x in it[i] if x >= 0]
+            cr.append(len(truth & set(int(x) for x in cd[i] if x >= 0)) / float(len(truth)))
+            recall.append(recall_at_k(ranked, truth, k))
+            ndcg.append(ndcg_at_k([1 if x in truth else 0 for x in ranked], k))
+            if i < F:
+                ref = set(int(x) for x in full[i] if x >= 0)
+                overlap.append(len(ref & set(ranked)) / float(len(ref)) if ref else 1.0)
+        rows.append(dict(n_cand=n_cand, candidate_recall=float(np.mean(cr)) if cr else 0.0,
+                         recall=float(np.mean(recall)) if recall else 0.0, ndcg=float(np.mean(ndcg)) if ndcg else 0.0,
+                         overlap=float(np.mean(overlap)) if overlap else None, n_users=U, items=it))
     return rows
 
 

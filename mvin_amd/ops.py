@@ -1101,6 +1101,187 @@ def mmr_segments(scores, seg_ptr, ids, feat, k, lam, row_scale=None, excl=None, 
     return tuple(out)
 
 
+def mips_topk_max_k():
+    """mvin_mips_topk_max_k: the largest k the fused retrieval kernel takes."""
+    return int(_lib.load().mvin_mips_topk_max_k())
+
+
+def mips_topk_supported(k, D):
+    return bool(_lib.load().mvin_mips_topk_supported(int(k), int(D)))
+
+
+# Below this many queries form=None takes the composed form.  0: the fused form wherever it is supported.  Set by
+# scripts/bench_retrieve.py on the MI355X (48 091 rows, D 64, k 200; DESIGN.md section 5): fused 0.41 ms against composed
+# 0.43 ms at 250 queries (level: 4 %, the spreads 1 % wide) and 7.9 ms against 11.3 ms at 23 553 -- the fused form lost at
+# neither end, so no range goes to the composed form.  Other D, k and n have not been measured.
+MIPS_FUSED_MIN_QUERIES = 0
+
+
+def _mips_common(q, feat, cand_ids, col_offset, n, q_scale, row_scale, name):
+    """The arguments mips_scores and mips_topk share, checked: (nq, n_rows, D, ld, n, col_offset)."""
+    n_rows, D, ld = _mmr_table(feat, "feat")
+    if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.shape[1] != D:
+        raise ValueError(f"q: expected a [nq, {D}] tensor")
+    if q.dtype != F32:
+        raise TypeError(f"q: expected {F32}, got {q.dtype}")
+    _chk(q, F32, "q")
+    if q.data_ptr() % 16:
+        raise ValueError("q: rows must be 16-byte aligned")
+    nq = q.shape[0]
+    col_offset = int(col_offset)
+    if cand_ids is not None:
+        _chk(cand_ids, I32, "cand_ids")
+        if cand_ids.dim() != 1 or (n is not None and int(n) != cand_ids.numel()):
+            raise ValueError(f"cand_ids: expected a 1-d tensor of n={n} ids" if n is not None else "cand_ids: expected a 1-d tensor")
+        n = cand_ids.numel()
+    else:
+        if col_offset < 0:
+            raise ValueError(f"col_offset={col_offset}: expected >= 0")
+        n = max(0, n_rows - col_offset) if n is None else int(n)
+        if n < 0 or col_offset + n > 0x7FFFFFFF:
+            raise ValueError(f"{name}: n={n} col_offset={col_offset}: implicit ids col_offset + j must be int32")
+    for t, size, tname in ((q_scale, nq, "q_scale"), (row_scale, n_rows, "row_scale")):
+        if t is not None:
+            _chk(t, F32, tname)
+            if tuple(t.shape) != (size,):
+                raise ValueError(f"{tname}: expected [{size}]")
+    return nq, n_rows, D, ld, n, col_offset
+
+
+def mips_scores(q, feat, cand_ids=None, col_offset=0, n=None, q_scale=None, row_scale=None, out=None):
+    """mvin_mips_scores: ``out[i, j] = dot(q[i], feat[row_j])`` (f32 on the matrix cores, one fixed order of d), times
+    ``q_scale[i]`` and then ``row_scale[row_j]`` when given.  ``q`` f32 [nq, D]; ``feat`` the f32 table of mmr_segments (rows may
+    be strided; a bf16 table is refused); column j is table row ``cand_ids[j]`` (int32 [n]) or ``col_offset + j`` (``n`` columns,
+    default: to the end of the table).  A column whose row id is negative or outside the table gets a quiet NaN.  ``out``: f32
+    [nq, n], rows may be strided.  Enqueues only."""
+    lib = _lib.load()
+    nq, n_rows, D, ld, n, col_offset = _mips_common(q, feat, cand_ids, col_offset, n, q_scale, row_scale, "mips_scores")
+    if out is None:
+        out = torch.empty((nq, n), dtype=F32, device=q.device)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != F32:
+        raise TypeError(f"out: expected a CUDA/ROCm {F32} tensor")
+    if tuple(out.shape) != (nq, n) or (n > 1 and out.stride(1) != 1) or (nq > 1 and out.stride(0) < n):
+        raise ValueError(f"out: expected [{nq}, {n}] with dense rows")
+    ldo = out.stride(0) if nq > 1 else n
+    if nq and n:
+        _lib.check(lib.mvin_mips_scores(_p(q), nq, _p(feat) if n_rows else None, n_rows, D, ld, _p(q_scale), _p(row_scale),
+                                        _p(cand_ids), col_offset, n, _p(out), ldo, _stream()), "mvin_mips_scores")
+    return out
+
+
+def _mips_composed(q, feat, k, cand_ids, col_offset, n, n_rows, q_scale, row_scale, excl, max_scores, out):
+    """mips_topk's composed form: column blocks of mips_scores into a bounded buffer, topk_rows with its carry."""
+    nq, dev = q.shape[0], q.device
+    sentinel = 0x7FFFFFFF                       # never a table row (n_rows < 2^31): stands for every ineligible column
+    if cand_ids is None:
+        n = min(n, max(0, n_rows - col_offset))     # the ineligible columns are the tail
+    else:
+        # an ineligible column holds a NaN in the dense scores, which topk_rows would rank: give those columns one id and
+        # put that id at the end of every exclusion row
+        tk_ids = torch.where((cand_ids < 0) | (cand_ids >= n_rows), torch.full_like(cand_ids, sentinel), cand_ids)
+        ar = torch.arange(nq + 1, dtype=torch.int64, device=dev)
+        if excl is None:
+            excl = (ar, torch.full((nq,), sentinel, dtype=I32, device=dev))
+        else:
+            ptr, ids = excl
+            E = ids.numel()
+            ids2 = torch.full((E + nq,), sentinel, dtype=I32, device=dev)
+            if E:
+                rows_of = torch.repeat_interleave(ar[:nq], ptr[1:] - ptr[:-1], output_size=E)
+                ids2[torch.arange(E, dtype=torch.int64, device=dev) + rows_of] = ids
+            excl = (ptr + ar, ids2)
+    blk = max(256, (int(max_scores) // max(nq, 1)) // 256 * 256)
+    buf = torch.empty((nq, min(blk, max(n, 1))), dtype=F32, device=dev)
+    carry = None
+    for b in range(0, max(n, 1), blk):
+        w = max(0, min(blk, n - b))
+        view = buf[:, :w]
+        if cand_ids is None:
+            mips_scores(q, feat, None, col_offset + b, w, q_scale, row_scale, out=view)
+            carry = topk_rows(view, k, None, col_offset + b, excl, carry, out=out if carry is None else carry)
+        else:
+            mips_scores(q, feat, cand_ids[b:b + w], 0, None, q_scale, row_scale, out=view)
+            carry = topk_rows(view, k, tk_ids[b:b + w], 0, excl, carry, out=out if carry is None else carry)
+    return carry
+
+
+def mips_topk(q, feat, k, cand_ids=None, col_offset=0, n=None, q_scale=None, row_scale=None, excl=None, form=None, splits=0,
+              max_scores=1 << 26, out=None):
+    """mvin_mips_topk: each query's ``k`` best ELIGIBLE columns of mips_scores(q, feat, ...) -- ``(ids int32 [nq, k], vals f32
+    [nq, k])``, the table row and the score, higher first, in topk_rows' order (-0.0 equals +0.0, NaN below -inf, equal scores to
+    the lower column), a short row padded with id -1, value -inf.  A column is ineligible when its row id is negative, outside
+    the table, or in the query's exclusion row (``excl``: topk_rows' CSR).  ``form="fused"`` selects while it multiplies (no
+    [nq, n] buffer; k <= mips_topk_max_k(); ``splits`` > 0 forces the number of column ranges, 0 chooses); ``form="composed"``
+    runs column blocks of mips_scores into a buffer of at most ``max_scores`` floats and topk_rows with its carry (k <= 1024);
+    ``None`` takes the fused form where it is supported.  Both forms return the same bits.  Enqueues only."""
+    lib = _lib.load()
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError(f"k={k}: mvin_mips_topk takes 1 <= k <= 1024")
+    if form not in (None, "fused", "composed"):
+        raise ValueError(f"form={form!r}: expected None, 'fused' or 'composed'")
+    splits = int(splits)
+    if not 0 <= splits <= 4096:
+        raise ValueError(f"splits={splits}: expected 0 (automatic) or 1 .. 4096")
+    nq, n_rows, D, ld, n, col_offset = _mips_common(q, feat, cand_ids, col_offset, n, q_scale, row_scale, "mips_topk")
+    if excl is not None:
+        ptr, ids = excl
+        _chk(ptr, torch.int64, "excl ptr")
+        _chk(ids, I32, "excl ids")
+        if ptr.numel() != nq + 1:
+            raise ValueError(f"excl ptr: {ptr.numel()} entries for {nq} rows")
+    if form is None:
+        form = "fused" if mips_topk_supported(k, D) and nq >= MIPS_FUSED_MIN_QUERIES else "composed"
+    if form == "fused" and not mips_topk_supported(k, D):
+        raise ValueError(f"k={k}: the fused form takes k <= {mips_topk_max_k()} (form='composed' takes k <= 1024)")
+    dev = q.device
+    if out is None:
+        out = (torch.empty((nq, k), dtype=I32, device=dev), torch.empty((nq, k), dtype=F32, device=dev))
+    oid, oval = out
+    _chk(oid, I32, "out ids")
+    _chk(oval, F32, "out vals")
+    if tuple(oid.shape) != (nq, k) or tuple(oval.shape) != (nq, k):
+        raise ValueError(f"out: expected [{nq}, {k}]")
+    if nq == 0:
+        return oid, oval
+    if form == "composed":
+        return _mips_composed(q, feat, k, cand_ids, col_offset, n, n_rows, q_scale, row_scale, excl, max_scores, (oid, oval))
+    nws = lib.mvin_mips_topk_ws_bytes(nq, n, k, splits)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    eptr = eids = None
+    if excl is not None:
+        eptr, eids = _p(excl[0]), _p(excl[1]) if excl[1].numel() else _p(excl[0])
+    _lib.check(lib.mvin_mips_topk(_p(q), nq, _p(feat) if n_rows else None, n_rows, D, ld, _p(q_scale), _p(row_scale), _p(cand_ids),
+                                  col_offset, n, eptr, eids, k, splits, _p(ws), _p(oid), _p(oval), _stream()), "mvin_mips_topk")
+    return oid, oval
+
+
+def mean_rows_segments(feat, ptr, ids, out=None, group=0):
+    """mvin_mean_rows_segments: ``out[s]`` = the mean of ``feat[ids[e]]`` over the entries of CSR segment ``s`` (``ptr`` int64
+    [n_seg + 1], ``ids`` int32) whose id lies inside the table: each component summed in f64 in entry order, divided by the count
+    and rounded to f32 once; a segment without such an entry gives a zero row.  No atomics, so the bits are reproducible and
+    independent of ``group`` (lanes per segment: 0 automatic, 8 / 16 / 32 / 64).  Returns f32 [n_seg, D].  Enqueues only."""
+    lib = _lib.load()
+    n_rows, D, ld = _mmr_table(feat, "feat")
+    _chk(ptr, torch.int64, "ptr")
+    _chk(ids, I32, "ids")
+    if ptr.dim() != 1 or ptr.numel() < 1 or ids.dim() != 1:
+        raise ValueError("ptr / ids: expected a CSR pair (ptr int64 [n_seg + 1], ids int32 [total])")
+    if group not in (0, 8, 16, 32, 64):
+        raise ValueError(f"group={group}: expected 0 (automatic), 8, 16, 32 or 64")
+    n_seg = ptr.numel() - 1
+    if out is None:
+        out = torch.empty((n_seg, D), dtype=F32, device=feat.device)
+    _chk(out, F32, "out")
+    if tuple(out.shape) != (n_seg, D):
+        raise ValueError(f"out: expected [{n_seg}, {D}]")
+    if n_seg:
+        _lib.check(lib.mvin_mean_rows_segments(_p(feat) if n_rows else None, n_rows, D, ld, _p(ptr), n_seg,
+                                               _p(ids) if ids.numel() else _p(ptr), ids.numel(), int(group), _p(out), _stream()),
+                   "mvin_mean_rows_segments")
+    return out
+
+
 def _score_image_host(vals):
     """mvin_score_image.h on the host: uint32 images of f32 scores (-0.0 = +0.0, every NaN = 0, below image(-inf))."""
     import numpy as np
