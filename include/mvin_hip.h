@@ -293,7 +293,9 @@ MVIN_API int mvin_score_l2_folded_fwd(const float* ws, const int32_t* enc_entity
  * probs, adjacency and outputs below 2 GiB), 3 = the wave-per-parent kernel for D = 16, K in {4, 8, 16} (the
  * reference's shipped settings: no workgroup phases at all; no probs, table below 4 GiB), 4 = the wave-per-parent
  * kernel for D = 32, K in {8, 16} (BASELINE config C2; same conditions; it takes these shapes ahead of the pipeline).
- * n_parents = B * parents_per_pair.  For tests and benchmarks.  The query takes no nR: it answers for relation tables that fit
+ * n_parents = B * parents_per_pair.  For tests and benchmarks.  The answer is the library's one dispatch (plan_l2_kernel,
+ * csrc/mvin_l2_kernel_plan.h) asked about a plain, unprojected call whose relation count is NOT KNOWN -- a deliberate argument of
+ * the query, not an omission: it answers for relation tables that fit
  * the wave-per-parent kernels' LDS (two logit tables of nR floats beside the waves' tiles in 64 KiB: a few thousand relations).
  * With more, the launcher gives a call answered 4 to the role-split pipeline (D = 32, K = 16) or the symmetric kernel
  * (D = 32, K = 8); an answer of 3 always holds (the D = 16 kernel's LDS takes the entry points' limit of 4096 relations). */

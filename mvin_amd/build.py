@@ -22,7 +22,7 @@ SOURCES = ["mvin_kernels.hip", "mvin_fused.hip", "mvin_fused_split.hip", "mvin_f
            # the extern "C" boundary, one translation unit per section of include/mvin_hip.h
            "mvin_abi_basic.hip", "mvin_abi_levels.hip", "mvin_abi_keyaddr.hip", "mvin_abi_score.hip", "mvin_abi_eval.hip", "mvin_abi_train.hip"]
 HEADERS = ["mvin_common.h", "mvin_kernels.h", "mvin_launch.h", "mvin_fused_agg.h", "mvin_score_image.h", "mvin_ctr_bodies.h", "mvin_row_select.h", "mvin_rnd.h", "mvin_explain_mass.h",
-           "mvin_workspaces.h", "mvin_score_plan.h", "mvin_abi_util.h", "mvin_entity_tables_plan.h"]
+           "mvin_workspaces.h", "mvin_score_plan.h", "mvin_abi_util.h", "mvin_entity_tables_plan.h", "mvin_l2_kernel_plan.h"]
 VERSION_SCRIPT = os.path.join(CSRC, "libmvin_hip.map")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared", f"--offload-arch={ARCH}"]

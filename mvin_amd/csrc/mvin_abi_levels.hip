@@ -1,70 +1,12 @@
 // extern "C" boundary, the two deepest levels: the fused level-2 kernels over the entity table, over projected tables and over
-// per-entity aggregates, the folded-tail forms, and the tail.  First the predicates and bodies that mvin_score_l2_fwd
-// (mvin_abi_score.hip) shares with the entry points here (declared in mvin_abi_util.h), then the entry points.
+// per-entity aggregates, the folded-tail forms, and the tail.  First the bodies that mvin_score_l2_fwd (mvin_abi_score.hip) shares
+// with the entry points here (declared in mvin_abi_util.h), then the entry points.  Which kernel takes a call and whether a form
+// applies to a set of tables: mvin_l2_kernel_plan.h.
 #include "mvin_abi_util.h"
 #include "mvin_fused_agg.h"
 
 namespace mvin {
 namespace abi {
-
-// does mvin_gather_attn_l2_prj_fwd run for these tables?  (the plain-adjacency form exists in the wave-per-parent kernel only)
-bool prj_applies(int D, int K, bool encoded, int n_entity, int nR, int64_t n_parents) {
-    if (n_entity <= 0 || nR <= 0 || nR > 4096 || !mvin::fused_l2_supported(D, K)) return false;
-    mvin::FusedL2Args f{};
-    f.K = K;
-    f.nR = nR;
-    f.P = n_parents > 0 ? n_parents : 1;
-    f.prj = 1;
-    f.parents_per_pair = 1;
-    f.max_id = (unsigned)(n_entity - 1);
-    static const int32_t present = 0;
-    f.adj_r = &present;                       // (only tested for presence)
-    f.table_bytes = (uint64_t)n_entity * (uint64_t)D * 4;
-    f.adj_bytes = (uint64_t)n_entity * (uint64_t)K * 4;
-    if (f.table_bytes >= (1ull << 30)) return false;
-    if (encoded) return mvin::fused_packed_supported(D, K) && mvin::fused_packed_applies(f, D);
-    return mvin::fused_d32_applies(f, D);
-}
-
-// does the per-entity aggregates form run for these tables?
-bool agg_applies(int D, int K, int n_entity, int nR, int64_t n_parents) {
-    if (n_entity <= 0 || nR <= 0 || nR > 4096 || !mvin::fused_agg_supported(D, K)) return false;
-    static const char* e = getenv("MVIN_L2_AGG");
-    if (e && e[0] == '0') return false;                   // A/B: the kernels over the projected tables themselves
-    mvin::FusedL2Args f{};
-    f.K = K;
-    f.nR = nR;
-    f.P = n_parents > 0 ? n_parents : 1;
-    f.prj = 1;
-    f.parents_per_pair = 1;
-    f.max_id = (unsigned)(n_entity - 1);
-    static const int32_t present = 0;
-    f.adj_r = &present;                       // (only tested for presence)
-    f.table_bytes = (uint64_t)n_entity * (uint64_t)D * 4;
-    f.adj_bytes = (uint64_t)n_entity * (uint64_t)K * 4;
-    return mvin::fused_agg_applies(f, D);
-}
-
-// does the folded-tail form run for these tables?  (dim 64 like the aggregates form, and dim 32)
-bool fold_applies(int D, int K, int n_entity, int nR, int64_t B) {
-    if (D == 64) return agg_applies(D, K, n_entity, nR, B);
-    static const char* e = getenv("MVIN_L2_AGG");
-    if (e && e[0] == '0') return false;
-    if (n_entity <= 0 || nR <= 0 || nR > 4096 || !mvin::fused_fold_supported(D, K)) return false;
-    const uint64_t tb = (uint64_t)n_entity * (uint64_t)D * 4, ab = (uint64_t)n_entity * (uint64_t)K * 4;
-    return tb < (1ull << 30) && ab < (1ull << 31) && n_entity <= (1 << 24) && (B <= 0 || (uint64_t)B * D * 4 < (1ull << 31)) &&
-           mvin::fused_fold_lds_bytes(D, nR, K) <= 48 * 1024;
-}
-
-// the folded tail with every pair gathering its own rows (no per-entity sums): dim 64, K in {16, 32}
-bool fold_gather_applies(int D, int K, int n_entity, int nR, int64_t B) {
-    if (D != 64 || (K != 16 && K != 32) || n_entity <= 0 || nR <= 0 || nR > 4096) return false;
-    static const char* e = getenv("MVIN_L2_FOLD_GATHER");
-    if (e && e[0] == '0') return false;                   // A/B: wave-per-parent kernel + mvin_l2_tail_fwd
-    const uint64_t tb = (uint64_t)n_entity * (uint64_t)D * 4, ab = (uint64_t)n_entity * (uint64_t)K * 4;
-    return tb < (1ull << 30) && ab < (1ull << 31) && n_entity <= (1 << 24) && (B <= 0 || (uint64_t)B * D * 4 < (1ull << 31)) &&
-           mvin::fused_wppfold_lds_bytes(nR, K) <= 48 * 1024;
-}
 
 // pid_stride 2: parent_ids points at an int64 [P] array whose low words are read (the item ids of the reference's
 // placeholder, model.py:50) -- mvin_score_l2_fwd's depth-2 pass then needs no id-conversion launch
@@ -74,21 +16,29 @@ int gather_attn_l2_impl(const void* table, const int32_t* adj_entity, const int3
                         float* nagg1, float* probs_parent, float* probs_child, int table_bf16, void* stream, bool encoded, bool prj,
                         const int32_t* order, const float* agg) {
     const char* who = prj ? "mvin_gather_attn_l2_prj_fwd" : encoded ? "mvin_gather_attn_l2_enc_fwd" : "mvin_gather_attn_l2_fwd";
-    if (prj && (table_bf16 || !W1 || !W2 || !q))
-        return fail(-1, "%s: projected tables are fp32 and go with the queries", who);
-    if (encoded && !mvin::fused_packed_supported(D, K))
-        return fail(-3, "%s: unsupported shape D=%d K=%d (D in {32,64,128}, K in {16,32,64,128})", who, D, K);
-    if (!mvin::fused_l2_supported(D, K))
-        return fail(-3, "%s: unsupported shape D=%d K=%d (D in {16,32,64,128}, K power of two in [4,256])",
-                    who, D, K);
+    // ---- the call in values, and the plan: the kernel, or the refusal (mvin_l2_kernel_plan.h) ----
+    mvin::L2Call c{};
+    c.D = D, c.K = K, c.nR = nR, c.n_entity = n_entity, c.parents = (int64_t)B * parents_per_pair, c.parents_per_pair = parents_per_pair;
+    c.table_bf16 = table_bf16 != 0, c.encoded = encoded, c.prj = prj, c.agg = agg != nullptr, c.has_relations = adj_relation != nullptr;
+    c.want_probs = probs_parent || probs_child, c.has_projection = W1 && W2 && q, c.has_order = order != nullptr;
+    const mvin::L2KernelPlan plan = mvin::plan_l2_kernel(c, mvin::l2_switches());
+    const auto refuse = [&] {
+        switch (plan.refusal) {
+            case mvin::L2Refusal::EncodedShape:
+            case mvin::L2Refusal::Shape: return fail(plan.code(), plan.message(), who, D, K);
+            case mvin::L2Refusal::BadSizes: return fail(plan.code(), plan.message(), who, B, parents_per_pair, n_entity, nR);
+            default: return fail(plan.code(), plan.message(), who);
+        }
+    };
+    // ---- validate: the form and the shape, the pointers, then the sizes and the limits ----
+    if (plan.refused_before_pointers()) return refuse();
     if (!table || !adj_entity || !parent_ids || !A0 || !nagg0 || !nagg1) return fail(-1, "%s: null pointer", who);
     if ((t0 || t1) && !adj_relation) return fail(-1, "%s: attention needs adj_relation", who);
     if ((W1 == nullptr) != (W2 == nullptr)) return fail(-1, "%s: W1 and W2 must be given together", who);
     if (W1 && !q) return fail(-1, "%s: projection needs the query vectors q", who);
     if ((probs_parent || probs_child) && !t0) return fail(-2, "%s: probs requested without t0", who);
-    if (B <= 0 || parents_per_pair <= 0 || n_entity <= 0 || nR <= 0 || nR > 4096)
-        return fail(-2, "%s: bad sizes B=%d parents_per_pair=%d n_entity=%d nR=%d", who, B, parents_per_pair,
-                    n_entity, nR);
+    if (plan.refused()) return refuse();
+    // ---- the kernel arguments, once ----
     mvin::FusedL2Args f{};
     f.table = table;
     f.adj_e = adj_entity;
@@ -107,61 +57,43 @@ int gather_attn_l2_impl(const void* table, const int32_t* adj_entity, const int3
     f.nagg1 = nagg1;
     f.probs_parent = probs_parent;
     f.probs_child = probs_child;
-    f.P = (int64_t)B * parents_per_pair;
-    f.table_bytes = (uint64_t)n_entity * (uint64_t)D * (table_bf16 ? 2 : 4);
-    f.adj_bytes = (uint64_t)n_entity * (uint64_t)K * 4;
+    f.P = c.parents;
+    f.table_bytes = c.table_bytes();
+    f.adj_bytes = c.adj_bytes();
     f.parents_per_pair = parents_per_pair;
     f.K = K;
     f.nR = nR;
     f.pid_stride = pid_stride;
-    f.max_id = (unsigned)(n_entity - 1);
+    f.max_id = c.max_id();
     f.prj = prj ? 1 : 0;
-    int l = 0;
-    if (agg) {                   // per-entity aggregates in place of the tables (mvin_gather_attn_l2_agg_fwd)
-        f.agg = const_cast<float*>(agg);
-        f.order = order;
-        if (!(prj && encoded && mvin::fused_agg_applies(f, D) && (!order || parents_per_pair == 1)))
-            return fail(-3, "mvin_gather_attn_l2_agg_fwd: D = 64, K in {16, 32, 64}, n_entity <= 2^24, tables < 1 GiB, adjacency and outputs < 2 GiB "
-                            "(a parent order: one parent per pair)");
-        return hip_result(mvin::launch_gather_attn_l2_agg(f, (hipStream_t)stream), "mvin_gather_attn_l2_agg_fwd");
-    }
-    if (order) {
-        if (!(prj && encoded && parents_per_pair == 1))
-            return fail(-3, "%s: a parent order goes with projected tables, an encoded adjacency and one parent per pair", who);
-        // only the wave-per-parent kernel takes it; where that kernel does not apply the order is not passed on, as in mvin_score_l2_fwd
-        // (results do not depend on it)
-        if (mvin::fused_wpp_applies(f, D)) f.order = order;
-    }
-    while ((4 << l) < K) ++l;
-    f.lpn_log2 = l;
-    {
+    f.agg = const_cast<float*>(agg);
+    f.order = plan.pass_order ? order : nullptr;
+    if (plan.kernel != mvin::L2Kernel::Agg) {
+        int l = 0;
+        while ((4 << l) < K) ++l;
+        f.lpn_log2 = l;
         static const char* dbg = getenv("MVIN_SPLIT_DBG");
         f.dbg = dbg ? atoi(dbg) : 0;
     }
-    if (prj && !encoded) {       // plain adjacency: only the wave-per-parent kernel (D = 32, K <= 16) has a projected-tables form
-        if (!mvin::fused_d32_applies(f, D)) return fail(-3, "%s: the projected-tables form over a plain adjacency exists for D = 32, K in {8, 16}", who);
-        return hip_result(mvin::launch_gather_attn_l2_d32(f, 0, (hipStream_t)stream, false), who);
+    // ---- launch ----
+    const hipStream_t st = (hipStream_t)stream;
+    switch (plan.kernel) {
+        case mvin::L2Kernel::Agg: return hip_result(mvin::launch_gather_attn_l2_agg(f, st), "mvin_gather_attn_l2_agg_fwd");
+        case mvin::L2Kernel::D32: return hip_result(mvin::launch_gather_attn_l2_d32(f, table_bf16, st, plan.d32_enc), who);
+        case mvin::L2Kernel::Wpp: return hip_result(mvin::launch_gather_attn_l2_wpp(f, st), who);
+        case mvin::L2Kernel::Packed: return hip_result(mvin::launch_gather_attn_l2_packed(f, D, table_bf16, st), who);
+        case mvin::L2Kernel::Split: return hip_result(mvin::launch_gather_attn_l2_split(f, D, table_bf16, st), who);
+        case mvin::L2Kernel::D16: return hip_result(mvin::launch_gather_attn_l2_d16(f, table_bf16, st), who);
+        case mvin::L2Kernel::Symmetric: return hip_result(mvin::launch_gather_attn_l2(f, D, table_bf16, st), who);
     }
-    if (encoded) {
-        if (!adj_relation) return fail(-1, "%s: null enc_relation", who);
-        if (!mvin::fused_packed_applies(f, D))
-            return fail(-3, "%s: tables too large (n_entity <= 2^24, table < 4 GiB, adjacency and outputs < 2 GiB)", who);
-        // D = 32, K <= 16 (BASELINE C2): the wave-per-parent kernel reads the encoding too (MVIN_L2_D32ENC=0: the packed-tile kernel, A/B)
-        static const bool d32enc_off = getenv("MVIN_L2_D32ENC") && atoi(getenv("MVIN_L2_D32ENC")) == 0;
-        if (!d32enc_off && mvin::fused_d32_applies(f, D))
-            return hip_result(mvin::launch_gather_attn_l2_d32(f, table_bf16, (hipStream_t)stream, true), who);
-        // dim 64 over projected tables: the wave-per-parent kernel (MVIN_L2_WPP=0: the packed-tile kernel, A/B)
-        if (prj && mvin::fused_wpp_applies(f, D)) return hip_result(mvin::launch_gather_attn_l2_wpp(f, (hipStream_t)stream), who);
-        return hip_result(mvin::launch_gather_attn_l2_packed(f, D, table_bf16, (hipStream_t)stream), who);
-    }
-    return hip_result(mvin::launch_gather_attn_l2(f, D, table_bf16, (hipStream_t)stream), who);
+    return fail(-3, "%s: no kernel", who);
 }
 
 int fold_tables_check(const char* who, const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* W0,
                       const float* W1, const float* W2, const float* A0, const float* Wmix, const float* A1, int aggregates, int K, int D,
                       int n_entity, int nR, const float* ws) {
     if (!entity_emb || !enc_entity || !enc_relation || !W0 || !W1 || !W2 || !A0 || !Wmix || !A1 || !ws) return fail(-1, "%s: null pointer", who);
-    if (!(aggregates ? fold_applies(D, K, n_entity, nR, 1) : fold_gather_applies(D, K, n_entity, nR, 1)))
+    if (!(aggregates ? fold_applies(D, K, n_entity, nR, 1, l2_switches()) : fold_gather_applies(D, K, n_entity, nR, 1, l2_switches())))
         return fail(-3, "%s: D = 64 with K in {16, 32, 64} or D = 32 with K in {16, 32}; n_entity <= 2^24, tables < 1 GiB, adjacency < 2 GiB, nR <= 4096 "
                         "(D=%d K=%d n_entity=%d nR=%d)", who, D, K, n_entity, nR);
     return 0;
@@ -256,18 +188,19 @@ int mvin_gather_attn_l2_variant(int D, int K, int64_t n_parents, int n_entity, i
     return mvin_gather_attn_l2_variant_ex(D, K, n_parents, n_entity, want_probs, 0);
 }
 
+// a plain, unprojected call whose relation count is not known (L2Call::nR_unknown): no LDS bound applies (include/mvin_hip.h)
 int mvin_gather_attn_l2_variant_ex(int D, int K, int64_t n_parents, int n_entity, int want_probs, int table_bf16) {
-    if (!mvin::fused_l2_supported(D, K)) return 0;
-    mvin::FusedL2Args f{};
-    f.K = K;
-    f.P = n_parents;
-    f.adj_bytes = (uint64_t)n_entity * (uint64_t)K * 4;
-    float probe = 0.f;
-    if (want_probs) f.probs_parent = f.probs_child = &probe;     // only tested for presence
-    f.table_bytes = (uint64_t)n_entity * (uint64_t)D * (table_bf16 ? 2 : 4);
-    if (mvin::fused_d32_applies(f, D)) return 4;
-    if (mvin::fused_l2_split_in_use() && mvin::fused_split_applies(f, D)) return 2;
-    return mvin::fused_d16_applies(f, D) ? 3 : 1;
+    mvin::L2Call c{};
+    c.D = D, c.K = K, c.nR_unknown = true, c.n_entity = n_entity, c.parents = n_parents, c.parents_per_pair = 1;
+    c.table_bf16 = table_bf16 != 0, c.want_probs = want_probs != 0;
+    const mvin::L2KernelPlan plan = mvin::plan_l2_kernel(c, mvin::l2_switches());
+    if (plan.refused()) return 0;
+    switch (plan.kernel) {
+        case mvin::L2Kernel::Split: return 2;
+        case mvin::L2Kernel::D16: return 3;
+        case mvin::L2Kernel::D32: return 4;
+        default: return 1;
+    }
 }
 
 int mvin_gather_attn_l2_enc_supported(int D, int K) { return mvin::fused_packed_supported(D, K) ? 1 : 0; }
@@ -314,7 +247,7 @@ int mvin_project_tables(const float* entity_emb, const float* W1, const float* W
 }
 
 int mvin_gather_attn_l2_prj_supported(int D, int K, int adjacency_encoded, int n_entity, int nR) {
-    return prj_applies(D, K, adjacency_encoded != 0, n_entity, nR, 1) ? 1 : 0;
+    return mvin::prj_applies(D, K, adjacency_encoded != 0, n_entity, nR, 1, mvin::l2_switches()) ? 1 : 0;
 }
 
 int mvin_gather_attn_l2_prj_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, int adjacency_encoded,
@@ -338,7 +271,9 @@ int mvin_gather_attn_l2_prj_ordered_fwd(const float* ws, const int32_t* enc_enti
                                K, D, n_entity, nR, nagg0, nagg1, nullptr, nullptr, 0, stream, adjacency_encoded != 0, true, order);
 }
 
-int mvin_gather_attn_l2_agg_supported(int D, int K, int n_entity, int nR) { return agg_applies(D, K, n_entity, nR, 1) ? 1 : 0; }
+int mvin_gather_attn_l2_agg_supported(int D, int K, int n_entity, int nR) {
+    return mvin::agg_applies(D, K, n_entity, nR, 1, mvin::l2_switches()) ? 1 : 0;
+}
 
 size_t mvin_entity_aggregates_elems(int n_entity, int D) { return n_entity > 0 && D > 0 ? mvin::AggWs(n_entity, D).elems() : 0; }
 
@@ -346,7 +281,7 @@ int mvin_entity_aggregates(const float* ws, const int32_t* enc_entity, const int
                            int n_entity, int nR, float* agg, void* stream) {
     const char* who = "mvin_entity_aggregates";
     if (!ws || !enc_entity || !enc_relation || !agg) return fail(-1, "%s: null pointer", who);
-    if (!agg_applies(D, K, n_entity, nR, 1))
+    if (!mvin::agg_applies(D, K, n_entity, nR, 1, mvin::l2_switches()))
         return fail(-3, "%s: D = 64, K in {16, 32, 64}, n_entity <= 2^24, tables < 1 GiB, adjacency < 2 GiB, nR <= 4096 (D=%d K=%d n_entity=%d nR=%d)",
                     who, D, K, n_entity, nR);
     mvin::EntityAggArgs f{};
@@ -383,7 +318,9 @@ int mvin_gather_attn_l2_agg_fwd(const float* ws, const float* agg, const int32_t
 // ---- folded-tail form: tables TA1 | TA2 | T0A | M0, aggregates H0 | G, parameter block (FoldWs, mvin_workspaces.h) ----
 size_t mvin_fold_tables_elems(int n_entity, int D) { return n_entity > 0 && D > 0 ? mvin::FoldWs(n_entity, D).elems() : 0; }
 
-int mvin_score_l2_folded_supported(int D, int K, int n_entity, int nR) { return fold_applies(D, K, n_entity, nR, 1) ? 1 : 0; }
+int mvin_score_l2_folded_supported(int D, int K, int n_entity, int nR) {
+    return mvin::fold_applies(D, K, n_entity, nR, 1, mvin::l2_switches()) ? 1 : 0;
+}
 
 int mvin_fold_tables(const float* entity_emb, const int32_t* enc_entity, const int32_t* enc_relation, const float* t0, const float* W0,
                      const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0, const float* a0,
@@ -408,12 +345,11 @@ int mvin_score_l2_folded_fwd(const float* ws, const int32_t* enc_entity, const i
     if (!ws || !enc_entity || !enc_relation || !q || !user_o || !A1 || !Wmix || !scores) return fail(-1, "%s: null pointer", who);
     if ((items_i64 == nullptr) == (items_i32 == nullptr)) return fail(-1, "%s: exactly one of items_i64 / items_i32", who);
     if (B <= 0 || B >= (int64_t(1) << 31)) return fail(-2, "%s: B=%lld", who, (long long)B);
-    if (!fold_applies(D, K, n_entity, nR, B)) return fail(-3, "%s: unsupported shape / sizes D=%d K=%d n_entity=%d nR=%d B=%lld", who, D, K, n_entity, nR, (long long)B);
+    if (!mvin::fold_applies(D, K, n_entity, nR, B, mvin::l2_switches())) return fail(-3, "%s: unsupported shape / sizes D=%d K=%d n_entity=%d nR=%d B=%lld", who, D, K, n_entity, nR, (long long)B);
     const mvin::FoldWs L(n_entity, D);
     const float* blk = ws + L.block();
     const float *bv = blk + L.blk.bv(), *bq = blk + L.blk.bq(), *bm = blk + L.blk.bm();
-    static const bool two = getenv("MVIN_L2_FOLD_TWO") && atoi(getenv("MVIN_L2_FOLD_TWO")) != 0;
-    if (!two || D != 64)                      // ONE launch: pair kernel and tail on the same batches of 16 pairs (out0 / z2 stay unused)
+    if (!mvin::l2_switches().fold_two || D != 64)                      // ONE launch: pair kernel and tail on the same batches of 16 pairs (out0 / z2 stay unused)
     {       // (the regrouped copies Wperm of the six blocks -- of the CURRENT A1 / Wmix too: mvin_fold_tables wrote them)
         const mvin::FoldBlock& W = L.blk;       // Wperm: Wq | Wv | Wqm | A1 | Wm1 | Wm2
         return hip_result(mvin::launch_score_l2_folded(ws + L.H0(), ws + L.M0(), enc_entity, enc_relation,
@@ -472,7 +408,9 @@ int mvin_score_l2_folded_fwd(const float* ws, const int32_t* enc_entity, const i
     return hip_result(mvin::launch_l2_tail_fold(t, (hipStream_t)stream), who);
 }
 
-int mvin_score_l2_folded_gather_supported(int D, int K, int n_entity, int nR) { return fold_gather_applies(D, K, n_entity, nR, 1) ? 1 : 0; }
+int mvin_score_l2_folded_gather_supported(int D, int K, int n_entity, int nR) {
+    return mvin::fold_gather_applies(D, K, n_entity, nR, 1, mvin::l2_switches()) ? 1 : 0;
+}
 
 int mvin_score_l2_folded_gather_fwd(const float* ws, const int32_t* enc_entity, const int32_t* enc_relation, const int64_t* items_i64,
                                     const int32_t* items_i32, const int32_t* order, const float* t0, const float* t1, const float* q,
@@ -482,7 +420,7 @@ int mvin_score_l2_folded_gather_fwd(const float* ws, const int32_t* enc_entity, 
     if (!ws || !enc_entity || !enc_relation || !q || !user_o || !A1 || !Wmix || !scores) return fail(-1, "%s: null pointer", who);
     if ((items_i64 == nullptr) == (items_i32 == nullptr)) return fail(-1, "%s: exactly one of items_i64 / items_i32", who);
     if (B <= 0 || B >= (int64_t(1) << 31)) return fail(-2, "%s: B=%lld", who, (long long)B);
-    if (!fold_gather_applies(D, K, n_entity, nR, B))
+    if (!mvin::fold_gather_applies(D, K, n_entity, nR, B, mvin::l2_switches()))
         return fail(-3, "%s: D = 64, K in {16, 32}; n_entity <= 2^24, tables < 1 GiB, adjacency < 2 GiB (D=%d K=%d n_entity=%d nR=%d B=%lld)", who, D, K,
                     n_entity, nR, (long long)B);
     const mvin::FoldWs L(n_entity, D);

@@ -25,18 +25,15 @@ mvin::ScoreInputs score_inputs(const mvin_score_l2_args* a) {
     mvin::ScoreCaps& c = in.caps;
     c.flash = mvin::key_addr_flash_supported(D, in.P, in.Nm, nR, nE);
     c.er = mvin_key_addressing_grouped_er_supported(D, in.P, in.Nm, nR, nE, in.has_set) != 0;
-    c.fold = fold_applies(D, K, nE, nR, in.B);
-    c.fold_gather = fold_gather_applies(D, K, nE, nR, in.B);
+    const mvin::L2Switches& sw = mvin::l2_switches();
+    c.fold = mvin::fold_applies(D, K, nE, nR, in.B, sw);
+    c.fold_gather = mvin::fold_gather_applies(D, K, nE, nR, in.B, sw);
     c.packed = mvin::fused_packed_supported(D, K);
     c.d32 = mvin::fused_d32_supported(D, K);       // the wave-per-parent kernel: projected tables over either adjacency
-    c.prj = prj_applies(D, K, in.encoded(), nE, nR, in.B);
-    c.agg = agg_applies(D, K, nE, nR, in.B);
-    // the wave-per-parent kernel of dim 64 takes the tables form's launch, and with it an item order, when fused_wpp_applies
-    mvin::FusedL2Args f{};
-    f.prj = 1, f.K = K, f.nR = nR, f.P = in.B, f.parents_per_pair = 1, f.max_id = (unsigned)(nE - 1);
-    f.table_bytes = (uint64_t)nE * D * 4, f.adj_bytes = (uint64_t)nE * K * 4;
-    f.adj_r = a->enc_relation, f.W1 = a->W1, f.W2 = a->W2, f.q = a->user_o;
-    c.wpp = mvin::fused_wpp_supported(D, K) && nR <= 4096 && mvin::fused_wpp_applies(f, D);
+    c.prj = mvin::prj_applies(D, K, in.encoded(), nE, nR, in.B, sw);
+    c.agg = mvin::agg_applies(D, K, nE, nR, in.B, sw);
+    // the wave-per-parent kernel of dim 64 takes the tables form's launch, and with it an item order
+    c.wpp = mvin::wpp_applies(D, K, nE, nR, in.B, a->enc_relation != nullptr, a->W1 != nullptr, a->W2 != nullptr, sw);
     // MVIN_ITEM_ROWS=0 (read once per process): whole tables from the same binary
     static const bool item_rows_on = !(getenv("MVIN_ITEM_ROWS") && atoi(getenv("MVIN_ITEM_ROWS")) == 0);
     c.item_rows = item_rows_on;

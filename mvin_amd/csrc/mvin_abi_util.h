@@ -43,12 +43,7 @@ struct EntityTableList {
 int build_entity_tables(const char* who, const float* E, int n_entity, const float* relation_kge, int nR, float* er, const float* user_mlp_W,
                         int n_o, float* tw, const float* fold_blk, float* fold_tabs, void* stream);
 
-// ---- mvin_abi_levels.hip: the predicates of the deepest-levels forms, and the bodies behind their entry points ----
-bool prj_applies(int D, int K, bool encoded, int n_entity, int nR, int64_t n_parents);
-bool agg_applies(int D, int K, int n_entity, int nR, int64_t n_parents);
-bool fold_applies(int D, int K, int n_entity, int nR, int64_t B);
-bool fold_gather_applies(int D, int K, int n_entity, int nR, int64_t B);
-
+// ---- mvin_abi_levels.hip: the bodies behind the entry points of the deepest-levels forms (their predicates: mvin_l2_kernel_plan.h) ----
 // pid_stride 2: parent_ids points at an int64 [P] array whose low words are read (the item ids of the reference's
 // placeholder, model.py:50) -- mvin_score_l2_fwd's depth-2 pass then needs no id-conversion launch
 int gather_attn_l2_impl(const void* table, const int32_t* adj_entity, const int32_t* adj_relation, const int32_t* parent_ids, int pid_stride,

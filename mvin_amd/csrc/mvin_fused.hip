@@ -569,7 +569,7 @@ static hipError_t launch_l2(const FusedL2Args& a, hipStream_t st) {
 // which is the faster one there (K=64: 3.9 vs 6.2 ms).
 template <int D, int NW, bool BF, int TMV>
 static hipError_t launch_l2_pick(const FusedL2Args& a, hipStream_t st) {
-    static const bool nopipe = getenv("MVIN_L2_NOPIPE") != nullptr;
+    const bool nopipe = l2_switches().nopipe;
     constexpr bool GPC = (TMV == 16) || D >= 32;
     const int kit = ((TMV / NW) * (a.K / 4) + 63) / 64;
     if (!nopipe && kit <= 1) return launch_l2<D, NW, 1, BF, TMV, GPC>(a, st);
@@ -586,29 +586,9 @@ static hipError_t launch_l2_small(const FusedL2Args& a, hipStream_t st) {
     return launch_l2_pick<D, D / 16, BF, 16>(a, st);
 }
 
-bool fused_l2_supported(int D, int K) {
-    const bool dok = D == 16 || D == 32 || D == 64 || D == 128;
-    const bool kok = K >= 4 && K <= 256 && (K & (K - 1)) == 0;
-    return dok && kok;
-}
-
-bool fused_l2_split_in_use() {
-    static const char* split_env = getenv("MVIN_L2_SPLIT");
-    static const bool use_split = !(split_env && split_env[0] == '0');
-    return use_split;
-}
-
+// the symmetric kernel's template ladder (which kernel of the family takes a call: plan_l2_kernel, mvin_l2_kernel_plan.h)
 hipError_t launch_gather_attn_l2(const FusedL2Args& a, int D, int table_bf16, hipStream_t st) {
-    // D >= 32, K in {16 (D = 32), 32, 64, 128}: the role-split pipeline (gather waves + dense waves);
-    // MVIN_L2_SPLIT=0 keeps the symmetric kernel below for A/B measurements
-    // D = 32, K <= 16 (BASELINE config C2): one wave per parent -- tiles of 16 x 16 rows are too small for the pipeline's
-    // per-step costs (MVIN_L2_D32=0: A/B)
-    if (fused_d32_applies(a, D)) return launch_gather_attn_l2_d32(a, table_bf16, st);
-    if (fused_l2_split_in_use() && fused_split_applies(a, D)) return launch_gather_attn_l2_split(a, D, table_bf16, st);
-    // D = 16, K <= 16 (the reference's shipped settings): one wave per parent, no workgroup phases
-    if (fused_d16_applies(a, D)) return launch_gather_attn_l2_d16(a, table_bf16, st);
-    static const bool no_small = getenv("MVIN_L2_NOSMALL") != nullptr;
-    const bool small = a.K <= 16 && !no_small;
+    const bool small = a.K <= 16 && !l2_switches().nosmall;
     if (table_bf16) {
         switch (D) {
             case 16: return small ? launch_l2_small<16, true>(a, st) : launch_l2_pick<16, 4, true, 32>(a, st);

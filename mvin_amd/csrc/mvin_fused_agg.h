@@ -12,14 +12,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kAggWaves = 4;
-constexpr int kAggUvLd = 132;         // floats per parent of the u1 | v block in LDS (128 + 4: sixteen lanes, sixteen bank groups)
-constexpr int kAggPad = 4;            // list entries of padding behind a group's K slots (the half round issued ahead of the last one)
+// (kAggWaves, kAggUvLd, kAggPad, agg_list_words, fused_agg_lds_words / _bytes, kA32Ld, a32_list_words: mvin_l2_kernel_plan.h)
 constexpr unsigned kAggOob = 0xFFFFFFF0u;       // a byte offset beyond every buffer: the load returns zeros, no memory access
 constexpr unsigned kAggPadRow = 0xFFFFFE00u;    // ... that stays beyond them (and below 2^32) with a lane's column offset added
-constexpr int agg_list_words(int K) { return 4 * 2 * (K + kAggPad); }      // per wave: 4 groups x (K + padding) x (offset, weight)
-constexpr size_t fused_agg_lds_words(int nR, int K) { return (size_t)((nR + 3) & ~3) + (size_t)kAggWaves * (16 * kAggUvLd + agg_list_words(K)); }
-size_t fused_agg_lds_bytes(int nR, int K);
 
 __device__ __forceinline__ int agg_xor16_imax(int v) {
     const auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
@@ -148,6 +143,5 @@ struct FoldArgs {
 hipError_t launch_entity_aggregates_d32(const EntityAggArgs& a, hipStream_t st);      // mvin_fused_agg32.hip
 hipError_t launch_score_l2_folded_d32(const FoldArgs& f, hipStream_t st);
 hipError_t launch_score_l2_folded_gather(const FoldArgs& f, hipStream_t st);           // mvin_fused_wpp_fold.hip
-size_t fused_wppfold_lds_bytes(int nR, int K);
 
 }  // namespace mvin

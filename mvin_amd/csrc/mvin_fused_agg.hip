@@ -794,7 +794,6 @@ static hipError_t launch_fold_k(const FoldArgs& a, hipStream_t st) {
     static const int grid_cap = getenv("MVIN_FOLD_GRID") ? atoi(getenv("MVIN_FOLD_GRID")) : 0;
     static const int wgs = getenv("MVIN_FOLD_WGS") ? atoi(getenv("MVIN_FOLD_WGS")) : 0;
     using Kern = void (*)(FoldArgs);
-    constexpr size_t kLdsNoOptIn = 48 * 1024;            // dynamic LDS above it needs a function attribute
     constexpr bool kTwoLists = fused_agg_lds_words(0, K) * sizeof(float) + (size_t)kAggWaves * agg_list_words(K) * sizeof(float) <= kLdsNoOptIn;
     auto kernel_of = [&](int mode) -> Kern {
         if (trace) {
@@ -863,20 +862,6 @@ hipError_t launch_score_l2_folded(const float* agg, const float* M0, const int32
         case 64: return launch_fold_k<64>(f, st);
         default: return hipErrorInvalidValue;
     }
-}
-
-bool fused_agg_supported(int D, int K) { return D == 64 && (K == 16 || K == 32 || K == 64); }
-bool fused_fold_supported(int D, int K) { return fused_agg_supported(D, K) || (D == 32 && (K == 16 || K == 32)); }
-size_t fused_fold_d32_lds_bytes(int nR, int K);
-size_t fused_fold_lds_bytes(int D, int nR, int K) { return D == 32 ? fused_fold_d32_lds_bytes(nR, K) : fused_agg_lds_bytes(nR, K); }
-
-size_t fused_agg_lds_bytes(int nR, int K) { return fused_agg_lds_words(nR, K) * sizeof(float); }
-
-// the projected-tables form over the ENCODED adjacency with every buffer addressable by 32-bit byte offsets, aggregates given
-bool fused_agg_applies(const FusedL2Args& a, int D) {
-    return a.prj && fused_agg_supported(D, a.K) && !a.probs_parent && !a.probs_child && a.adj_r && a.adj_bytes > 0 &&
-           a.adj_bytes < (1ull << 31) && a.table_bytes > 0 && a.table_bytes < (1ull << 30) && (uint64_t)a.P * D * 4 < (1ull << 31) &&
-           a.max_id < (1u << 24) && a.nR > 0 && fused_agg_lds_bytes(a.nR, a.K) <= 48 * 1024;      // (dynamic LDS above 48 KB needs a function attribute: such relation counts keep the other kernels)
 }
 
 template <int K>

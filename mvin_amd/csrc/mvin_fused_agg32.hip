@@ -8,8 +8,7 @@
 
 namespace mvin {
 
-constexpr int kA32Ld = 68;            // floats per pair of the t | v block in LDS (64 + 4)
-constexpr int a32_list_words(int K) { return 8 * 2 * (K + kAggPad); }      // per wave: 8 groups x (K + padding) x (offset, weight)
+// (kA32Ld, a32_list_words and fused_fold_d32_lds_bytes: mvin_l2_kernel_plan.h)
 
 // max over the eight 8-lane groups of a value that is uniform inside each
 __device__ __forceinline__ int a32_groups_imax(int v) {
@@ -327,10 +326,6 @@ __global__ __launch_bounds__(kAggWaves * 64, 3) void score_l2_folded_d32_kernel(
     };
     if (fast) run(std::true_type{});
     else run(std::false_type{});
-}
-
-size_t fused_fold_d32_lds_bytes(int nR, int K) {
-    return ((size_t)((nR + 3) & ~3) + (size_t)kAggWaves * (16 * kA32Ld + a32_list_words(K))) * sizeof(float);
 }
 
 template <int K>

@@ -28,12 +28,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kD16 = 16;
-constexpr int kD16Ld = 20;                                   // LDS row stride (floats): 16-byte aligned rows
-constexpr int kD16WaveWords = 3 * 16 * kD16Ld + 32;         // sA1 | sA2 | sZ | sP0 | sP1 per wave
-constexpr int kD16Waves = 4;
-
-size_t fused_d16_lds_bytes(int nR) { return (size_t)(2 * ((nR + 3) & ~3) + kD16Waves * kD16WaveWords) * 4; }
+// (kD16, kD16Ld, kD16WaveWords, kD16Waves and fused_d16_lds_bytes: mvin_l2_kernel_plan.h)
 
 // The kernel is VALU-ISSUE-bound (~520 instructions per parent and wave, 4 cycles each, against 12 MFMAs and ~6 wave-loads;
 // a software pipeline of the id chain across a wave's parents changed nothing: 0.395 ms either way).  So the softmax
@@ -283,17 +278,6 @@ __global__ __launch_bounds__(kD16Waves * 64) void gather_attn_l2_d16_kernel(Fuse
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
         __builtin_amdgcn_wave_barrier();
     }
-}
-
-bool fused_d16_supported(int D, int K) { return D == 16 && (K == 4 || K == 8 || K == 16); }
-
-// ... and for these arguments: no attention outputs requested, every buffer addressable with 32-bit byte offsets
-bool fused_d16_applies(const FusedL2Args& a, int D) {
-    static const char* e = getenv("MVIN_L2_D16");
-    if (e && e[0] == '0') return false;                  // A/B: keep gather_attn_l2_kernel
-    return fused_d16_supported(D, a.K) && !a.probs_parent && !a.probs_child && a.adj_bytes > 0 && a.adj_bytes < (1ull << 31) &&
-           a.table_bytes > 0 && a.table_bytes < (1ull << 32) && (uint64_t)a.P * D * 4 < (1ull << 31) &&
-           fused_d16_lds_bytes(a.nR) <= 64 * 1024;          // (default dynamic-LDS limit)
 }
 
 template <int K, bool BF>

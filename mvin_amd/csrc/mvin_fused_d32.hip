@@ -27,15 +27,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kD32 = 32;
-constexpr int kD32Ld = 36;                                   // LDS row stride (floats): 16-byte aligned rows, 16 rows -> 16 bank groups
-constexpr int kD32Waves = 4;
-constexpr int d32_wave_words(int K) { return 2 * 16 * kD32Ld + 32 + 2 * 16 * K + 96; }      // sA1 | sA2 (= sZ) | sP0 | sP1 | sY | sWt | sQ | sUV (PRJ)
-constexpr int kD32WeightWords = 3 * kD32 * kD32;             // W1 | W2 | A0, shared by the workgroup
-
-size_t fused_d32_lds_bytes(int nR, int K) {
-    return (size_t)(2 * ((nR + 3) & ~3) + kD32WeightWords + kD32Waves * d32_wave_words(K)) * 4;
-}
+// (kD32, kD32Ld, kD32Waves, d32_wave_words, kD32WeightWords and fused_d32_lds_bytes: mvin_l2_kernel_plan.h)
 
 // exp for softmax arguments (x = logit - max <= 0): the library's argument reduction without its range selects
 __device__ __forceinline__ float d32_exp(float x) {
@@ -446,17 +438,6 @@ __global__ __launch_bounds__(kD32Waves * 64, 4) void gather_attn_l2_d32_kernel(F
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
         __builtin_amdgcn_wave_barrier();
     }
-}
-
-bool fused_d32_supported(int D, int K) { return D == 32 && (K == 8 || K == 16); }
-
-// ... and for these arguments: no attention outputs requested, every buffer addressable with 32-bit byte offsets
-bool fused_d32_applies(const FusedL2Args& a, int D) {
-    static const char* e = getenv("MVIN_L2_D32");
-    if (e && e[0] == '0') return false;                  // A/B: the role-split / symmetric kernel
-    return fused_d32_supported(D, a.K) && !a.probs_parent && !a.probs_child && a.adj_bytes > 0 && a.adj_bytes < (1ull << 31) &&
-           a.table_bytes > 0 && a.table_bytes < (a.prj ? (1ull << 30) : (1ull << 32) - 4096) && (uint64_t)a.P * D * 4 < (1ull << 31) &&
-           fused_d32_lds_bytes(a.nR, a.K) <= 64 * 1024;     // (default dynamic-LDS limit; larger relation tables keep the pipeline)
 }
 
 template <int K, bool BF, bool ENC, bool PRJ = false>

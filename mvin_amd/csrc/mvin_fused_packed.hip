@@ -1074,19 +1074,6 @@ hipError_t launch_prj_prepare(const float* W1, const float* W2, const float* b1,
     return hipGetLastError();
 }
 
-bool fused_packed_supported(int D, int K) {
-    return (D == 32 || D == 64 || D == 128) && (K == 16 || K == 32 || K == 64 || K == 128);
-}
-
-// ... and for these arguments: no attention outputs (they are per slot: the plain adjacency), tables addressable with
-// 32-bit byte offsets, output rows indexable with an int
-bool fused_packed_applies(const FusedL2Args& a, int D) {
-    return fused_packed_supported(D, a.K) && !a.probs_parent && !a.probs_child && a.adj_r && a.adj_bytes > 0 &&
-           a.adj_bytes < (1ull << 31) && (uint64_t)a.P * D * 4 < (1ull << 31) && a.table_bytes < (a.prj ? (1ull << 30) : (1ull << 32)) &&
-           a.max_id < (1u << 24) &&
-           (uint64_t)a.P / (uint64_t)a.parents_per_pair * D * 4 < (a.prj ? (1ull << 30) : (1ull << 31));
-}
-
 template <int D, bool BF>
 static hipError_t launch_packed_k(const FusedL2Args& a, hipStream_t st) {
     if constexpr (!BF) {

@@ -580,18 +580,6 @@ static hipError_t launch_split(const FusedL2Args& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-bool fused_split_supported(int D, int K) {
-    if (D == 32) return K == 16 || K == 32 || K == 64 || K == 128;
-    return (D == 64 || D == 128) && (K == 32 || K == 64 || K == 128);
-}
-
-// ... and for these arguments: no attention outputs requested (eval_case_study keeps the symmetric kernel),
-// adjacency tables and output rows addressable with 32-bit byte offsets
-bool fused_split_applies(const FusedL2Args& a, int D) {
-    return fused_split_supported(D, a.K) && !a.probs_parent && !a.probs_child && a.adj_bytes > 0 &&
-           a.adj_bytes < (1ull << 31) && (uint64_t)a.P * D * 4 < (1ull << 31);
-}
-
 // rows in flight per lane in the gather loop: 16 (the unroller's batches) everywhere, except at D = 128 on a bf16 table
 // (168-VGPR budget, one workgroup per CU, so only 4 gather waves feed the texture path): two register batches of 8 in
 // rotation for K >= 64 (UNR = 48; C5, K = 128: 10.9 -> 13.3 TB/s; K = 64: 9.2 -> 10.5).  The same rotation spills in the 128-VGPR kernels (C3 / C4: 5-10x slower)

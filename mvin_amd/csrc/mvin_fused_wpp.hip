@@ -31,10 +31,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kWppWaves = 4;
-constexpr int kWppUvLd = 132;         // floats per parent of the u1 | v block in LDS (128 + 4: sixteen lanes, sixteen bank groups)
-constexpr int kWppRound = 4;          // list entries of padding behind a group's K slots (the half round issued ahead of the last one)
-constexpr int wpp_list_words(int K) { return 4 * 2 * (K + kWppRound); }      // per wave: 4 groups x (K + a round of padding) x (offset, weight)
+// (kWppWaves, kWppUvLd, kWppRound, wpp_list_words and fused_wpp_lds_bytes: mvin_l2_kernel_plan.h)
 
 __device__ __forceinline__ float wpp_bperm(float v, int src_lane) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
@@ -370,21 +367,6 @@ __global__ __launch_bounds__(kWppWaves * 64, 3) void gather_attn_l2_wpp_kernel(F
     };
     if (fast) run(std::true_type{});
     else run(std::false_type{});
-}
-
-bool fused_wpp_supported(int D, int K) { return D == 64 && (K == 16 || K == 32); }
-
-size_t fused_wpp_lds_bytes(int nR, int K) {
-    return ((size_t)2 * ((nR + 3) & ~3) + (size_t)kWppWaves * (16 * kWppUvLd + wpp_list_words(K))) * sizeof(float);
-}
-
-// the projected-tables form over the ENCODED adjacency with every buffer addressable by 32-bit byte offsets
-bool fused_wpp_applies(const FusedL2Args& a, int D) {
-    static const char* e = getenv("MVIN_L2_WPP");
-    if (e && e[0] == '0') return false;                  // A/B: the packed-tile kernel
-    return a.prj && fused_wpp_supported(D, a.K) && !a.probs_parent && !a.probs_child && a.adj_r && a.adj_bytes > 0 &&
-           a.adj_bytes < (1ull << 31) && a.table_bytes > 0 && a.table_bytes < (1ull << 30) && (uint64_t)a.P * D * 4 < (1ull << 31) &&
-           a.max_id < (1u << 24) && a.W1 && a.W2 && a.q && fused_wpp_lds_bytes(a.nR, a.K) <= 48 * 1024;      // (dynamic LDS above 48 KB would need a function attribute)
 }
 
 template <int K>

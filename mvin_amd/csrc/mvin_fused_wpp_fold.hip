@@ -12,10 +12,7 @@
 
 namespace mvin {
 
-constexpr int kWppWaves = 4;
-constexpr int kWppUvLd = 132;
-constexpr int kWppRound = 4;
-constexpr int wpp_list_words(int K) { return 4 * 2 * (K + kWppRound); }
+// (the LDS layout is the wave-per-parent kernel's: kWppWaves, kWppUvLd, kWppRound, wpp_list_words, fused_wpp_lds_bytes of mvin_l2_kernel_plan.h)
 
 __device__ __forceinline__ float wppf_bperm(float v, int src_lane) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
@@ -402,14 +399,9 @@ __global__ __launch_bounds__(kWppWaves * 64, 4) void score_l2_wppfold_kernel(Fol
     else run(std::false_type{});
 }
 
-
-size_t fused_wppfold_lds_bytes(int nR, int K) {
-    return ((size_t)2 * ((nR + 3) & ~3) + (size_t)kWppWaves * (16 * kWppUvLd + wpp_list_words(K))) * sizeof(float);
-}
-
 template <int K>
 static hipError_t launch_wppfold_k(const FoldArgs& a, hipStream_t st) {
-    const size_t lds = fused_wppfold_lds_bytes(a.nR, K);
+    const size_t lds = fused_wpp_lds_bytes(a.nR, K);
     const int v = workgroups_per_cu(score_l2_wppfold_kernel<K>, kWppWaves * 64, lds, 3);
     const int64_t nbatch = (a.B + 15) >> 4;
     const int64_t want = (nbatch + kWppWaves - 1) / kWppWaves;

@@ -6,6 +6,7 @@
 #include "../../include/mvin_hip.h"
 #include "mvin_common.h"
 #include "mvin_launch.h"   // kNumCUs, persistent_grid, workgroups_per_cu, grant_lds
+#include "mvin_l2_kernel_plan.h"   // the level-2 kernels' shape sets, LDS sizes, limits, switches and dispatch order
 
 namespace mvin {
 
@@ -442,10 +443,7 @@ bool l2_tail_supported(int D);
 hipError_t launch_l2_tail(const TailArgs& a, int D, hipStream_t st);
 bool l2_tail_flash_applies(const TailArgs& a, int D);
 hipError_t launch_l2_tail_flash(const TailArgs& a, hipStream_t st);
-bool fused_l2_supported(int D, int K);
-hipError_t launch_gather_attn_l2(const FusedL2Args& a, int D, int table_bf16, hipStream_t st);
-bool fused_split_supported(int D, int K);      // role-split variant (mvin_fused_split.hip)
-bool fused_split_applies(const FusedL2Args& a, int D);
+hipError_t launch_gather_attn_l2(const FusedL2Args& a, int D, int table_bf16, hipStream_t st);      // the symmetric kernel (mvin_fused.hip)
 hipError_t launch_gather_probe_l2(const void* table, const int32_t* ids1, const int32_t* ids2, int64_t n_parents, int K,
                                   int D, int table_bf16, float* sums, hipStream_t st);   // mvin_probe.hip
 // (item_rows given: the device word *item_rows = 1 + the batch's largest item id, ids clamped as the folded score kernels clamp them,
@@ -457,8 +455,6 @@ hipError_t launch_group_pairs(const int64_t* u64, const int32_t* u32, int64_t B,
 // table are the only ones a pair's ITEM can address.  A memset of the word and one launch; no host synchronisation
 hipError_t launch_item_rows(const int32_t* items, int item_stride, int64_t B, unsigned max_id, int32_t* item_rows, hipStream_t st);
 hipError_t launch_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, hipStream_t st);   // mvin_bwd.hip
-bool fused_d32_supported(int D, int K);        // wave-per-parent variant for D = 32, K in {8, 16} (mvin_fused_d32.hip)
-bool fused_d32_applies(const FusedL2Args& a, int D);
 bool topk_rows_supported(int k);                               // row-wise top-K selection (mvin_topk.hip)
 hipError_t launch_topk_rows(const float* scores, int64_t rows, int64_t n, int64_t ld, const int32_t* cand_ids, int64_t col_offset,
                             const int64_t* excl_ptr, const int32_t* excl_ids, const int32_t* carry_ids, const float* carry_vals, int k,
@@ -556,13 +552,7 @@ hipError_t launch_kg_explore(const int64_t* eptr, const int32_t* edst, const int
                              int hops, void* ws, uint32_t* explored_bits, int64_t* out_counts, hipStream_t st);
 size_t order_ws_elems(int64_t B);                             // pairs in key order (mvin_order.hip)
 hipError_t launch_order_by_key(const int64_t* k64, const int32_t* k32, int64_t B, int32_t* ws, int32_t* order, hipStream_t st);
-bool fused_wpp_supported(int D, int K);                       // wave-per-parent kernel over projected tables, dim 64 (mvin_fused_wpp.hip)
-bool fused_wpp_applies(const FusedL2Args& a, int D);
-hipError_t launch_gather_attn_l2_wpp(const FusedL2Args& a, hipStream_t st);
-bool fused_agg_supported(int D, int K);                       // per-entity aggregates S0 | G of the projected tables, dim 64 (mvin_fused_agg.hip)
-bool fused_fold_supported(int D, int K);                      // folded-tail form: dim 64 (K 16 / 32 / 64) and dim 32 (K 16 / 32: mvin_fused_agg32.hip)
-size_t fused_fold_lds_bytes(int D, int nR, int K);
-bool fused_agg_applies(const FusedL2Args& a, int D);
+hipError_t launch_gather_attn_l2_wpp(const FusedL2Args& a, hipStream_t st);                       // wave-per-parent kernel over projected tables, dim 64 (mvin_fused_wpp.hip)
 hipError_t launch_entity_aggregates(const EntityAggArgs& a, hipStream_t st);
 hipError_t launch_fold_prepare(const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* A0,
                                const float* a0, const float* Wmix, const float* bmix, const float* A1, float c, int D, float* blk, hipStream_t st);   // mvin_fused_agg.hip
@@ -574,13 +564,9 @@ hipError_t launch_score_l2_folded(const float* agg, const float* M0, const int32
                                   hipStream_t st);                              // mvin_fused_agg.hip / mvin_fused_agg32.hip: the folded-tail form in one launch
 hipError_t launch_gather_attn_l2_agg(const FusedL2Args& a, hipStream_t st);     // a.agg, the encoding, a.t1, the query terms -> nagg0 / nagg1
 hipError_t launch_gather_attn_l2_d32(const FusedL2Args& a, int table_bf16, hipStream_t st, bool encoded = false);   // encoded: adj_e / adj_r = the duplicate-slot encoding
-bool fused_d16_supported(int D, int K);        // wave-per-parent variant for D = 16, K <= 16 (mvin_fused_d16.hip)
-bool fused_d16_applies(const FusedL2Args& a, int D);
-hipError_t launch_gather_attn_l2_d16(const FusedL2Args& a, int table_bf16, hipStream_t st);
-bool fused_l2_split_in_use();                   // false under MVIN_L2_SPLIT=0
-hipError_t launch_gather_attn_l2_split(const FusedL2Args& a, int D, int table_bf16, hipStream_t st);
+hipError_t launch_gather_attn_l2_d16(const FusedL2Args& a, int table_bf16, hipStream_t st);   // wave-per-parent variant for D = 16, K <= 16 (mvin_fused_d16.hip)
+hipError_t launch_gather_attn_l2_split(const FusedL2Args& a, int D, int table_bf16, hipStream_t st);   // role-split variant (mvin_fused_split.hip)
 hipError_t split_read_trace(long long* host_dst, size_t n);
-bool fused_packed_supported(int D, int K);
 bool key_addr_static_er_ok(int P, int Nm, int nR, int n_entity, bool has_set);
 hipError_t launch_transpose_blocks(const float* R, int nR, int D, float* RT, hipStream_t st);
 // the per-call entity tables of dim 64 in one launch (mvin_entity_tables.hip): out[e][:] = E[e][:] . W for every job
@@ -594,7 +580,6 @@ hipError_t launch_entity_tables(const float* E, int n_entity, const EntityTableJ
 hipError_t launch_entity_dot(const float* E, const float* w, int n, int D, float* out, hipStream_t st);
 hipError_t launch_prj_prepare(const float* W1, const float* W2, const float* b1, const float* b2, const float* A0, const float* a0,
                               float c, int D, float* blk, hipStream_t st);     // packed-tile variant over the duplicate-slot encoding (mvin_fused_packed.hip)
-bool fused_packed_applies(const FusedL2Args& a, int D);
 hipError_t pack_read_prof(long long* host_dst, size_t n);
 hipError_t launch_gather_attn_l2_packed(const FusedL2Args& a, int D, int table_bf16, hipStream_t st);
 hipError_t launch_encode_adjacency(const int32_t* adj_e, const int32_t* adj_r, int n_entity, int K, int32_t* cnt,

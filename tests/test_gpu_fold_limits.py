@@ -1,4 +1,4 @@
-"""The folded score forms AT the limits their _supported predicates promise (fold_applies / agg_applies / fold_gather_applies, mvin_abi_levels.hip):
+"""The folded score forms AT the limits their _supported predicates promise (fold_applies / agg_applies / fold_gather_applies, mvin_l2_kernel_plan.h):
 an entity table of 1 GiB - one row, an adjacency up to 1 GiB, B D 4 one row below 2^31 -- where the kernels' 32-bit buffer offsets, (int)
 casts of table bytes and unsigned query-row offsets come closest to wrapping.  Every case is its own test so that a failure names its form.
 

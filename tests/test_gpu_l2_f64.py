@@ -7,7 +7,9 @@ references are built once per shape (l2_cases.world / references), every test pr
 a case from passing vacuously (l2_cases.conditions: ReLU share, sharp rows, unit weights, every distinct-children count, probabilities
 summing to 1) are asserted on the float64 reference of EVERY case run here.
 
-ROUTES and the template instances they reach (kernel names as in the MEASURED lines):
+ROUTES and the template instances they reach (kernel names as in the MEASURED lines).  Which kernel takes a call is decided by
+plan_l2_kernel (mvin_amd/csrc/mvin_l2_kernel_plan.h: shape sets, limits, LDS budgets, switches, dispatch order); the symmetric
+kernel's template ladder is launch_gather_attn_l2 (mvin_fused.hip):
     sym       gather_attn_l2(want_probs=True), variant 1: mvin_fused.hip gather_attn_l2_kernel<D, NW, KIT, BF, TMV, GPC>, all four
               outputs.  launch_gather_attn_l2: K <= 16 -> launch_l2_small (TMV = 16, NW = D / 16, GPC = true), else launch_l2_pick
               (TMV = 32, NW = 4, 8 at D = 128, GPC = D >= 32); kit = ceil((TMV / NW) (K / 4) / 64); KIT = 1 if kit <= 1, 2 if kit == 2
@@ -19,16 +21,17 @@ ROUTES and the template instances they reach (kernel names as in the MEASURED li
               (D = 16: TMV / NW = 16 rows per wave at TMV = 16, so K = 16 has kit = 1; D = 128, NW = 8: 4 rows per wave, kit = 1 up to
               K = 64.)  Every (D, K) of the list x fp32 / bf16 runs here, so every instance launch_gather_attn_l2 can reach is hit; the
               KIT = 2 instances at D >= 64 and <D,NW,0,BF,16,1> are unreachable without MVIN_L2_NOPIPE / MVIN_L2_NOSMALL (out of scope).
-    split     gather_attn_l2 without probs, variant 2: mvin_fused_split.hip, every (D, K) of fused_split_supported x fp32 / bf16 (the
+    split     gather_attn_l2 without probs, variant 2: mvin_fused_split.hip, every (D, K) of fused_split_supported (mvin_l2_kernel_plan.h) x fp32 / bf16 (the
               UNR = 48 rotation is what D = 128 bf16 K >= 64 takes by default); (32, 16) only with nR = 4000 (shadowed by d32).
     d16       variant 3: mvin_fused_d16.hip <K, BF>, K in {4, 8, 16}.          d32   variant 4: mvin_fused_d32.hip <K, BF, false>, K in {8, 16}.
     packed    gather_attn_l2_enc: mvin_fused_packed.hip, 11 of the 12 (D, K) x fp32 / bf16, and (32, 16) with nR = 4000.
     d32enc    gather_attn_l2_enc at (32, 16): mvin_fused_d32.hip <16, BF, true>.  <8, BF, true> and <8, false, true, true> (the K = 8
-              ENC instances) are UNREACHABLE: every encoded entry point refuses K = 8 with -3 (fused_packed_supported), asserted here.
+              ENC instances) are UNREACHABLE: every encoded entry point refuses K = 8 with -3 (L2Refusal::EncodedShape: fused_packed_supported), asserted here.
     d32prj    gather_attn_l2_prj at (32, 16) encoded <16,false,true,true> and at (32, 8), (32, 16) plain <K,false,false,true>.
     wpp       gather_attn_l2_prj at (64, 16), (64, 32): mvin_fused_wpp.hip <K>.
-    packedprj gather_attn_l2_prj elsewhere, and at (64, 16), (64, 32) with nR = 4000 (past the 48 KiB of fused_wpp_applies).
-mvin_gather_attn_l2_variant takes no nR: with nR = 4000 it still answers 4 at (32, 16) while the launcher runs the pipeline (header).
+    packedprj gather_attn_l2_prj elsewhere, and at (64, 16), (64, 32) with nR = 4000 (past kLdsNoOptIn = 48 KiB in l2_wpp_fits).
+mvin_gather_attn_l2_variant asks plan_l2_kernel about a call whose nR is not known (a deliberate argument of the query): with nR = 4000
+it still answers 4 at (32, 16) while the plan of the call itself names the pipeline (include/mvin_hip.h).
 
 GRID LOOPS.  test_more_parents_than_one_pass_of_the_grid runs 131 089 parents: the largest persistent grid of the family is wpp's, 256
 CUs x at most 8 workgroups x 4 waves x batches of 16 parents = 131 072 parents per pass; d16 covers at most 2048 workgroups x 4 waves
@@ -123,7 +126,8 @@ def ops():
 
 
 def wpp_lds_limit_nr(K):
-    """First nR past the 48 KiB of fused_wpp_applies (mvin_fused_wpp.hip: 2 round_up(nR, 4) + 4 (16 x 132 + 4 x 2 (K + 4)) floats)."""
+    """First nR past the 48 KiB of l2_wpp_fits (mvin_l2_kernel_plan.h, fused_wpp_lds_bytes: 2 round_up(nR, 4) + 4 (16 x 132 + 4 x 2 (K + 4))
+    floats), stated here independently of the header."""
     per_workgroup = 4 * (16 * 132 + 4 * 2 * (K + 4))
     nR = 1
     while (2 * ((nR + 3) & ~3) + per_workgroup) * 4 <= 48 * 1024:
@@ -332,7 +336,7 @@ def test_no_encoded_entry_point_takes_fan_out_8(hip_lib):
 @pytest.mark.parametrize("route,dk,expect", [("enc", (32, 16), "packed"), ("prj", (64, 16), "packedprj"), ("prj", (64, 32), "packedprj"),
                                              ("plain", (32, 16), "split"), ("plain", (32, 8), "sym")], ids=lambda v: v if isinstance(v, str) else ids(v))
 def test_shadowed_instances_with_4000_relations(route, dk, expect, hip_lib):
-    """nR = 4000: past the 64 KiB of fused_d32_applies and the 48 KiB of fused_wpp_applies, so the same calls reach the packed-tile
+    """nR = 4000: past the 64 KiB of l2_d32_fits and the 48 KiB of l2_wpp_fits (mvin_l2_kernel_plan.h), so the same calls reach the packed-tile
     kernel at (32, 16), the projected packed-tile kernel at (64, 16) / (64, 32) and the pipeline at (32, 16), in process."""
     o = ops()
     assert wpp_lds_limit_nr(16) == 1601 and wpp_lds_limit_nr(32) < BIG_NR

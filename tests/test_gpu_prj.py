@@ -323,7 +323,7 @@ def test_attention_outputs_keep_the_unprojected_form(K, hip_lib):
 
 def test_forced_projection_falls_back_where_no_kernel_takes_it(hip_lib):
     """D = 32, K = 16 over the plain adjacency with a relation table too large for the wave-per-parent kernel's LDS
-    (fused_d32_applies false): a forced / automatic projected-tables form must fall back to the unprojected kernels, not raise."""
+    (l2_d32_fits of mvin_l2_kernel_plan.h false): a forced / automatic projected-tables form must fall back to the unprojected kernels, not raise."""
     nR = 4000
     args = make_args(**_shape(32, 16, B=21))
     case = synth.small_case(args, n_user=16, n_entity=900, n_relation=nR, seed=99, zero_rows=4, repeats=False)
@@ -345,7 +345,7 @@ def test_forced_projection_falls_back_where_no_kernel_takes_it(hip_lib):
 def _first_n_relation_past_the_wave_per_parent_lds(K):
     """mvin_fused_wpp.hip: a workgroup of the wave-per-parent kernel holds fused_wpp_lds_bytes(nR, K) = (2 round_up(nR, 4) + kWppWaves
     (16 kWppUvLd + wpp_list_words(K))) floats of LDS -- the two relation-logit tables and, per wave, sixteen u1 | v rows and the four
-    groups' (offset, weight) lists -- with kWppWaves = 4, kWppUvLd = 132, wpp_list_words(K) = 4 * 2 * (K + 4); fused_wpp_applies
+    groups' (offset, weight) lists -- with kWppWaves = 4, kWppUvLd = 132, wpp_list_words(K) = 4 * 2 * (K + 4) (mvin_l2_kernel_plan.h); l2_wpp_fits
     takes at most 48 KiB (dynamic LDS beyond it would need a function attribute)."""
     per_workgroup = 4 * (16 * 132 + 4 * 2 * (K + 4))
     nR = 1
