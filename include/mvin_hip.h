@@ -985,6 +985,35 @@ MVIN_API int mvin_mips_topk(const float* q, int64_t nq, const float* feat, int64
 MVIN_API int mvin_mean_rows_segments(const float* feat, int64_t n_rows, int D, int64_t ld, const int64_t* seg_ptr, int64_t n_seg,
                                      const int32_t* ids, int64_t total, int group, float* out /* [n_seg, D] */, void* stream);
 
+/* ---- resampled column sums: what bootstrap intervals and paired sign-flip tests of per-user metric values are made of (an
+ * opt-in extension; the reference reports bare means) --
+ * `vals` is f64 [n_rows, n_cols], rows `ld` doubles apart, never written: one row per user, one column per metric (NaN = the
+ * metric is undefined for that user).  The call writes sums f64 [n_rep, n_cols] and counts int32 [n_rep, n_cols] for the
+ * replicates r = first .. first + n_rep - 1.  THE RULE, for replicate r and column c:
+ *   64 partial sums p_0 .. p_63 start at +0.0 (f64) and 64 counts n_0 .. n_63 at 0.  For j = 0 .. n_rows - 1 ascending, with
+ *   l = j mod 64, a row i and a sign s follow from `mode`:
+ *     0 bootstrap:  i = (rnd32(seed, 7, r, 0, j) * n_rows) >> 32,  s = +1     (csrc/mvin_rnd.h: rnd_below on stream 7)
+ *     1 sign flip:  i = j,  s = -1 when bit 31 of rnd32(seed, 8, r, 0, j) is set, else +1           (stream 8)
+ *     2 observed:   i = j,  s = +1                                            (seed and r are ignored)
+ *   x = vals[i*ld + c]; a NaN is skipped (nothing added to sum or count); anything else, infinities included, does
+ *   p_l += s * x and n_l += 1.  Then for h = 32, 16, 8, 4, 2, 1:  p_l = p_l + p_{l+h} for l < h.
+ *   sums[(r - first)*n_cols + c] = p_0,  counts[(r - first)*n_cols + c] = the sum of the n_l.
+ * So ONE draw serves every column -- the columns of a call are resampled with the same rows, which is what makes a comparison
+ * of two columns paired -- and a column's bits depend on neither the other columns of the call, nor the split of replicates into
+ * calls (first, n_rep), nor max_groups or the launch shape, nor ld.  No floating-point atomics.  The observed sums (mode 2) come
+ * out in the summation order of the replicates, so |S_r| >= |S_obs| is an exact comparison.  A sum that is not a number (inf -
+ * inf) is some NaN; its sign and payload are not specified.
+ * `max_groups`: 0 = automatic, a positive value caps the workgroups of the launch.
+ * Limits: 0 <= n_rows < 2^31; 0 <= n_cols <= mvin_resample_max_cols() (16; split a wider table by columns, which the rule makes
+ * bit-neutral); n_cols <= ld < 2^31; 0 <= first < 2^62; 0 <= n_rep < 2^40.
+ * Errors (< 0, nothing launched): -2 for sizes outside those limits, a mode outside 0..2, max_groups < 0 or a misaligned
+ * pointer; -1 for null vals (with n_rows > 0) / sums / counts.  n_rows == 0 gives zero sums and counts; n_rep == 0 or
+ * n_cols == 0 launches nothing.  No workspace. */
+MVIN_API int mvin_resample_max_cols(void);
+MVIN_API int mvin_resample_sums(const double* vals, int64_t n_rows, int n_cols, int64_t ld, int mode, uint64_t seed, int64_t first,
+                                int64_t n_rep, int max_groups, double* sums /* [n_rep, n_cols] */,
+                                int32_t* counts /* [n_rep, n_cols] */, void* stream);
+
 /* ---- CTR metrics: exact integer counts behind the reference's CTR evaluation (util.py:44-56: roc_auc_score, accuracy and
  * f1_score of every batch) for many segments at once --
  * mvin_ctr_counts: segment s is scores[s*ld .. s*ld+seg_len) (f32) with labels[s*ld .. s*ld+seg_len) (int32, 0 or 1); neither is

@@ -114,6 +114,9 @@ SIGNATURES = {
                        + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "mvin_mean_rows_segments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                           C.c_int, C.c_void_p, C.c_void_p]),
+    "mvin_resample_max_cols": (C.c_int, []),
+    "mvin_resample_sums": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvin_kg_explore_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_kg_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
     "mvin_kg_explore": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,

@@ -216,6 +216,30 @@ int mvin_mean_rows_segments(const float* feat, int64_t n_rows, int D, int64_t ld
                       who);
 }
 
+int mvin_resample_max_cols(void) { return mvin::resample_max_cols(); }
+
+int mvin_resample_sums(const double* vals, int64_t n_rows, int n_cols, int64_t ld, int mode, uint64_t seed, int64_t first,
+                       int64_t n_rep, int max_groups, double* sums, int32_t* counts, void* stream) {
+    const char* who = "mvin_resample_sums";
+    if (n_rows < 0 || n_rows >= (int64_t(1) << 31) || n_cols < 0 || ld < n_cols || ld >= (int64_t(1) << 31))
+        return fail(-2, "%s: n_rows=%lld n_cols=%d ld=%lld (0 <= n_rows < 2^31; 0 <= n_cols <= ld < 2^31)", who, (long long)n_rows, n_cols,
+                    (long long)ld);
+    if (n_cols > mvin::resample_max_cols())
+        return fail(-2, "%s: n_cols=%d (at most %d columns per call; split wider tables by columns, the bits do not change)", who, n_cols,
+                    mvin::resample_max_cols());
+    if (mode < 0 || mode > 2) return fail(-2, "%s: mode=%d (0 bootstrap, 1 sign flip, 2 observed)", who, mode);
+    if (first < 0 || n_rep < 0 || first >= (int64_t(1) << 62) || n_rep >= (int64_t(1) << 40) || max_groups < 0)
+        return fail(-2, "%s: first=%lld n_rep=%lld max_groups=%d (0 <= first < 2^62, 0 <= n_rep < 2^40, max_groups >= 0)", who,
+                    (long long)first, (long long)n_rep, max_groups);
+    if ((n_rep > 0 && n_cols > 0 && (!sums || !counts)) || (n_rows > 0 && n_cols > 0 && !vals))
+        return fail(-1, "%s: null vals / sums / counts", who);
+    if ((reinterpret_cast<uintptr_t>(vals) & 7) || (reinterpret_cast<uintptr_t>(sums) & 7) || (reinterpret_cast<uintptr_t>(counts) & 3))
+        return fail(-2, "%s: vals / sums are not 8-byte aligned or counts is not 4-byte aligned", who);
+    return hip_result(mvin::launch_resample_sums(vals, n_rows, n_cols, ld, mode, seed, first, n_rep, max_groups, sums, counts,
+                                                 (hipStream_t)stream),
+                      who);
+}
+
 static bool kg_bad_sizes(int64_t n_entity, int64_t M) {
     return n_entity < 0 || n_entity > (int64_t)0x7FFFFFFF || M < 0 || M > (int64_t)0x7FFFFFFF;
 }

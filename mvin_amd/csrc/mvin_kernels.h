@@ -490,6 +490,9 @@ hipError_t launch_mips_topk(const float* q, int64_t nq, const float* feat, int64
                             const int32_t* excl_ids, int k, int splits, void* ws, int32_t* out_ids, float* out_vals, hipStream_t st);
 hipError_t launch_mean_rows_segments(const float* feat, int64_t n_rows, int D, int64_t ld, const int64_t* seg_ptr, int64_t n_seg,
                                      const int32_t* ids, int64_t total, int group, float* out, hipStream_t st);
+int resample_max_cols();                                        // resampled column sums of per-user metric values (mvin_resample.hip)
+hipError_t launch_resample_sums(const double* vals, int64_t n_rows, int n_cols, int64_t ld, int mode, uint64_t seed, int64_t first,
+                                int64_t n_rep, int max_groups, double* sums, int32_t* counts, hipStream_t st);
 int64_t ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);   // exact per-segment CTR counts (mvin_ctr_metrics.hip)
 hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, hipStream_t st);

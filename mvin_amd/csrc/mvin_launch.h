@@ -26,7 +26,8 @@ struct OccKey {
 // score kernel (the folded score kernel asks for its one- and its two-list form: 2), flash key addressing (1), and for the forms
 // without it the grouped wave or dense kernel (1) and the wave-per-parent kernel (1).  The default benchmark line produces 3
 // (both folded forms and flash key addressing); a training step's forward is such a model's.  32 keeps six such models, or three on two devices,
-// resident.  A full table overwrites its oldest entry; a lookup never answers for another key.
+// resident.  Beside a model, the metric resampler (mvin_resample.hip) adds at most 3: one per column count, whatever the mode.
+// A full table overwrites its oldest entry; a lookup never answers for another key.
 template <int N = 32>
 struct OccTable {
     OccKey key[N];

@@ -1,7 +1,9 @@
 // The draw function of the GPU samplers (mvin_prep.hip, mvin_negatives.hip, mvin_select_negatives.hip): every draw is a pure function of
 // (seed, stream, a, b, c) through a splitmix64 finaliser.  oracle/prep_ref.py restates it in Python integers.
 // Streams in use: 1 adjacency, 2 / 3 ripple sets, 4 negatives, 5 hard-negative selection (mvin_select_negatives.hip),
-// 6 weighted negatives (the alias draw of mvin_negatives.hip: two words per draw, c = 2j and 2j + 1).
+// 6 weighted negatives (the alias draw of mvin_negatives.hip: two words per draw, c = 2j and 2j + 1),
+// 7 bootstrap rows and 8 sign flips of the metric resampler (mvin_resample.hip: a = the replicate, b = 0, c = the position j;
+// tests/resample_oracle.py restates both in numpy).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

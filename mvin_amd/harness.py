@@ -1522,25 +1522,153 @@ def _ranked_metrics(feeder, users, positives, exclude, candidates, k_list, ndcg_
                                         vals=packed[3 * T:4 * T].view(np.float32) if auc else None, ndcg_window=ndcg_window)
 
 
-def rank_eval(feeder, users, train_record, truth_record, item_set, k_list, max_pairs=524288, ndcg_window=None):
+def rank_eval_per_user(feeder, users, train_record, truth_record, item_set, k_list, max_pairs=524288, ndcg_window=None):
+    """rank_eval's per-user values, kept: ``{"users": [...], "k_list": [...], metric: f64 [U, len(k_list)] for every metric of
+    ops.RANK_METRICS, "auc": f64 [U]}`` for the ``users`` present in ``truth_record``, in their order (NaN where a metric is not
+    defined for a user).  What metric_intervals and compare_rankings resample."""
+    from . import ops
+    users = [u for u in users if u in truth_record]
+    ks = [int(k) for k in k_list]
+    if not users:
+        per = {m: np.zeros((0, len(ks)), dtype=np.float64) for m in ops.RANK_METRICS}
+        per["auc"] = np.zeros(0, dtype=np.float64)
+    else:
+        per = dict(_ranked_metrics(feeder, users, truth_record, train_record, sorted(item_set), ks, ndcg_window, max_pairs))
+    per["users"], per["k_list"] = list(users), ks
+    return per
+
+
+def _per_user_table(per):
+    """The metric columns of a rank_eval_per_user dict side by side, f64 [U, 7 len(k) + 1]: metric-major, k-minor, auc last."""
+    from . import ops
+    nk = len(per["k_list"])
+    cols = [np.asarray(per[m], dtype=np.float64).reshape(-1, nk) for m in ops.RANK_METRICS]
+    return np.concatenate(cols + [np.asarray(per["auc"], dtype=np.float64).reshape(-1, 1)], axis=1)
+
+
+def _split_columns(flat, nk):
+    """A [7 nk + 1] vector back as {metric: list per k, "auc": float}."""
+    from . import ops
+    out = {m: [float(v) for v in flat[i * nk:(i + 1) * nk]] for i, m in enumerate(ops.RANK_METRICS)}
+    out["auc"] = float(flat[len(ops.RANK_METRICS) * nk])
+    return out
+
+
+def _copy_back(f64s, i32s):
+    """ONE copy to the host of some f64 and some int32 device tensors (packed as int32 words, the doubles first so that they
+    stay 8-byte aligned): two lists of numpy arrays of the tensors' shapes."""
+    import torch
+    packed = torch.cat([t.reshape(-1).view(torch.int32) for t in f64s] + [t.reshape(-1) for t in i32s]).cpu().numpy()
+    out, at = ([], []), 0
+    for t in f64s:
+        out[0].append(packed[at:at + 2 * t.numel()].view(np.float64).reshape(tuple(t.shape)))
+        at += 2 * t.numel()
+    for t in i32s:
+        out[1].append(packed[at:at + t.numel()].reshape(tuple(t.shape)))
+        at += t.numel()
+    return out
+
+
+def metric_intervals(per, level=0.95, n_rep=2000, seed=1, device="cuda"):
+    """Percentile bootstrap intervals (users resampled with replacement, ``n_rep`` replicates of ``seed``) of every metric of a
+    rank_eval_per_user dict: ONE upload of the f64 [U, 7 len(k) + 1] table, one "observed" and one "bootstrap" call of
+    ops.resample_sums (mvin_resample_sums), ONE copy back, ops.resample_summary on the host.  Returns ``{metric: {"mean", "se",
+    "lo", "hi"}}`` with a list per k (a float each for ``auc``) and ``n_users``.  ``mean`` is the column's sum in the kernel's
+    summation order over its count: rank_eval's mean up to the f64 summation order -- rank_eval's own mean stays the reported
+    number, this one only says where the interval sits.  All columns share one draw of users per replicate."""
+    import torch
+    from . import ops
+    nk = len(per["k_list"])
+    tab = _per_user_table(per)
+    U, M = tab.shape
+    t = torch.from_numpy(np.ascontiguousarray(tab)).to(device)
+    o_s, o_c = ops.resample_sums(t, 1, seed=seed, mode="observed")
+    b_s, b_c = ops.resample_sums(t, n_rep, seed=seed, mode="bootstrap")
+    R = int(n_rep)
+    (o_s, b_s), (o_c, b_c) = _copy_back([o_s, b_s], [o_c, b_c])
+    summ = ops.resample_summary(o_s.reshape(-1), o_c.reshape(-1), b_s, b_c, level=level)
+    parts = {key: _split_columns(summ[key], nk) for key in ("mean", "se", "lo", "hi")}
+    out = {m: {key: parts[key][m] for key in parts} for m in list(ops.RANK_METRICS) + ["auc"]}
+    out["n_users"] = U
+    return out
+
+
+def _add_intervals(out, per, ci, n_rep, ci_seed, device):
+    """rank_eval's ``ci`` and ``se`` entries from metric_intervals."""
+    from . import ops
+    iv = metric_intervals(per, level=ci, n_rep=n_rep, seed=ci_seed, device=device)
+    out["ci"] = {m: list(zip(iv[m]["lo"], iv[m]["hi"])) for m in ops.RANK_METRICS}
+    out["ci"]["auc"] = (iv["auc"]["lo"], iv["auc"]["hi"])
+    out["se"] = {m: iv[m]["se"] for m in ops.RANK_METRICS}
+    out["se"]["auc"] = iv["auc"]["se"]
+
+
+def rank_eval(feeder, users, train_record, truth_record, item_set, k_list, max_pairs=524288, ndcg_window=None, ci=None, n_rep=2000,
+              ci_seed=1):
     """Ranking metrics of the ``users`` present in ``truth_record`` from the exact ranks of their truth items among
     ``sorted(item_set)``, their ``train_record`` items excluded (DeviceFeeder.rank_positives, mvin_rank_positives): no top-K
     selection, so no bound on k, and one copy of a few ints per truth item comes back.  Returns a dict of means over those
     users: a list per k of ``k_list`` for precision, recall, hit_ratio, mrr, map, ndcg (window ``ndcg_window``, default
     max(k_list)) and ndcg_ideal as ops.rank_metrics_from_counts defines them, ``auc`` (the mean of the per-user AUC of truth
-    items against the other eligible candidates, over the users where it is defined) and ``n_users``."""
+    items against the other eligible candidates, over the users where it is defined) and ``n_users``.
+    ``ci`` (a level such as 0.95; None: the dict and the launches above, nothing more) adds ``"ci"``: metric -> a list of
+    ``(lo, hi)`` per k, and ``auc`` -> ``(lo, hi)``, the percentile bootstrap interval over users of metric_intervals (``n_rep``
+    replicates of ``ci_seed``), and ``"se"``: the bootstrap standard errors in the same layout."""
     import warnings
     from . import ops
-    users = [u for u in users if u in truth_record]
+    per = rank_eval_per_user(feeder, users, train_record, truth_record, item_set, k_list, max_pairs=max_pairs, ndcg_window=ndcg_window)
+    users = per["users"]
     out = {m: [float("nan")] * len(k_list) for m in ops.RANK_METRICS}
     out.update(auc=float("nan"), n_users=len(users))
     if not users:
         return out
-    per = _ranked_metrics(feeder, users, truth_record, train_record, sorted(item_set), k_list, ndcg_window, max_pairs)
     for m in ops.RANK_METRICS:
         out[m] = [float(np.mean(per[m][:, q].tolist())) for q in range(len(k_list))]
     defined = per["auc"][~np.isnan(per["auc"])]
     out["auc"] = float(np.mean(defined)) if defined.size else float("nan")
+    if ci is not None:
+        _add_intervals(out, per, ci, n_rep, ci_seed, feeder.model.device)
+    return out
+
+
+def compare_rankings(per_a, per_b, level=0.95, n_rep=10000, seed=1, device="cuda"):
+    """Paired comparison of two rank_eval_per_user dicts over the SAME users (equal ``users`` lists and ``k_list``, else
+    ValueError naming the first difference).  The difference columns d = a - b are formed on the host in f64 (NaN where either
+    is NaN), ONE table [a | b | d] is uploaded, and ops.resample_sums runs "observed", "bootstrap" and "signflip" over it: every
+    replicate resamples a, b and d with the same users.  Returns ``{metric: {...}, "auc": {...}, "n_users", "k_list", "n_rep"}``;
+    per metric, a list per k (a float each for ``auc``) of ``mean_a``, ``mean_b`` (over the users where each is defined),
+    ``diff`` (the mean of d over the users where both are), ``diff_lo`` / ``diff_hi`` (the percentile bootstrap interval of that
+    mean at ``level``), ``p`` (the two-sided sign-flip permutation p-value of sum d, ops.signflip_pvalue; NaN where d has no
+    defined user) and ``p_holm`` (Holm-adjusted over all metric x k cells of the call, auc included)."""
+    import torch
+    from . import ops
+    ua, ub = list(per_a["users"]), list(per_b["users"])
+    if len(ua) != len(ub):
+        raise ValueError(f"compare_rankings: {len(ua)} users against {len(ub)}: the two evaluations must cover the same users")
+    for i, (x, y) in enumerate(zip(ua, ub)):
+        if x != y:
+            raise ValueError(f"compare_rankings: users differ first at position {i}: {x} against {y}")
+    if list(per_a["k_list"]) != list(per_b["k_list"]):
+        raise ValueError(f"compare_rankings: k_list {list(per_a['k_list'])} against {list(per_b['k_list'])}")
+    nk = len(per_a["k_list"])
+    a, b = _per_user_table(per_a), _per_user_table(per_b)
+    U, M = a.shape
+    tab = np.ascontiguousarray(np.concatenate([a, b, a - b], axis=1))            # NaN - x = NaN
+    t = torch.from_numpy(tab).to(device)
+    R = int(n_rep)
+    o_s, o_c = ops.resample_sums(t, 1, seed=seed, mode="observed")
+    b_s, b_c = ops.resample_sums(t, R, seed=seed, mode="bootstrap")
+    f_s, _ = ops.resample_sums(t[:, 2 * M:], R, seed=seed, mode="signflip")
+    (o_s, b_s, f_s), (o_c, b_c) = _copy_back([o_s, b_s, f_s], [o_c, b_c])
+    o_s, o_c = o_s.reshape(-1), o_c.reshape(-1)
+    summ = ops.resample_summary(o_s, o_c, b_s, b_c, level=level)
+    p = ops.signflip_pvalue(o_s[2 * M:], f_s)
+    p = np.where(o_c[2 * M:] > 0, p, np.nan)
+    cells = dict(mean_a=summ["mean"][:M], mean_b=summ["mean"][M:2 * M], diff=summ["mean"][2 * M:], diff_lo=summ["lo"][2 * M:],
+                 diff_hi=summ["hi"][2 * M:], p=p, p_holm=ops.holm_adjust(p))
+    parts = {key: _split_columns(v, nk) for key, v in cells.items()}
+    out = {m: {key: parts[key][m] for key in parts} for m in list(ops.RANK_METRICS) + ["auc"]}
+    out.update(n_users=U, k_list=list(per_a["k_list"]), n_rep=R)
     return out
 
 
@@ -1559,17 +1687,36 @@ def topk_eval_ranked(feeder, user_list, train_record, eval_record, test_record, 
     return ([float(np.mean(x)) for x in p], [float(np.mean(x)) for x in r], [float(np.mean(x)) for x in n], None, None)
 
 
-def full_ranking_eval(feeder, train_data, split_data, n_item, k_list=(20, 40, 60, 80, 100), max_pairs=524288):
+def _full_ranking_protocol(train_data, split_data, users=None):
+    """(users, train_record, truth) of the all-ranking protocol; ``users``: keep only these (those with a label-1 row)."""
+    train_record = get_user_record(np.asarray(train_data), True)
+    truth = get_user_record(np.asarray(split_data), False)
+    truth = {int(u): v for u, v in truth.items()}
+    keep = sorted(truth) if users is None else sorted({int(u) for u in users} & set(truth))
+    return keep, {int(u): v for u, v in train_record.items()}, truth
+
+
+def full_ranking_eval(feeder, train_data, split_data, n_item, k_list=(20, 40, 60, 80, 100), max_pairs=524288, ci=None, n_rep=2000,
+                      ci_seed=1):
     """The all-ranking protocol of the KG-recommender papers (the reference's KGAT/utility/batch_test.py:test): EVERY user
     with a label-1 row in ``split_data`` against the whole catalogue ``range(n_item)``, the user's label-1 items of
     ``train_data`` masked, each metric averaged over those users.  Returns rank_eval's dict (ndcg over the window max(k_list),
-    as that protocol computes it, and the per-user AUC)."""
-    train_record = get_user_record(np.asarray(train_data), True)
-    truth = get_user_record(np.asarray(split_data), False)
-    users = sorted(int(u) for u in truth)
-    truth = {int(u): v for u, v in truth.items()}
-    return rank_eval(feeder, users, {int(u): v for u, v in train_record.items()}, truth, range(int(n_item)), list(k_list),
-                     max_pairs=max_pairs)
+    as that protocol computes it, and the per-user AUC; with ``ci`` its bootstrap intervals and standard errors)."""
+    users, train_record, truth = _full_ranking_protocol(train_data, split_data)
+    return rank_eval(feeder, users, train_record, truth, range(int(n_item)), list(k_list), max_pairs=max_pairs, ci=ci, n_rep=n_rep,
+                     ci_seed=ci_seed)
+
+
+def compare_models(feeder_a, feeder_b, train_data, split_data, n_item, k_list=(20, 40, 60, 80, 100), users=None, level=0.95,
+                   n_rep=10000, seed=1, max_pairs=524288):
+    """Is model A better than model B on this split?  full_ranking_eval's protocol for both feeders over the same users
+    (``users``: restrict it to these -- a sample keeps the two full-catalogue passes short), then compare_rankings on the two
+    sets of per-user values: per metric and k the two means, the mean difference with its paired bootstrap interval, the
+    sign-flip p-value and its Holm adjustment over every cell of the call."""
+    keep, train_record, truth = _full_ranking_protocol(train_data, split_data, users)
+    per = [rank_eval_per_user(f, keep, train_record, truth, range(int(n_item)), list(k_list), max_pairs=max_pairs)
+           for f in (feeder_a, feeder_b)]
+    return compare_rankings(per[0], per[1], level=level, n_rep=n_rep, seed=seed, device=feeder_a.model.device)
 
 
 def _sampled_summary(users, counts, vals, eligible, k_list):

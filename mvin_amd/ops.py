@@ -1282,6 +1282,145 @@ def mean_rows_segments(feat, ptr, ids, out=None, group=0):
     return out
 
 
+RESAMPLE_MODES = {"bootstrap": 0, "signflip": 1, "observed": 2}
+
+
+def resample_max_cols():
+    """mvin_resample_max_cols: the columns one mvin_resample_sums launch takes (resample_sums splits wider tables)."""
+    return int(_lib.load().mvin_resample_max_cols())
+
+
+def resample_sums(vals, n_rep, seed=1, mode="bootstrap", first=0, max_groups=0, out=None):
+    """mvin_resample_sums: resampled column sums of ``vals`` (f64 [n_rows, n_cols] on the device, dense rows that may be strided;
+    one row per user, NaN = undefined for that user) for the replicates ``first .. first + n_rep - 1`` of ``seed``.
+    ``mode``: "bootstrap" (n_rows rows drawn with replacement), "signflip" (every row kept, its sign flipped with probability
+    1/2) or "observed" (the plain column sums, in the replicates' summation order; seed and replicate are ignored).  ONE draw
+    serves every column, so the columns of a call are resampled with the same users.  Returns ``(sums f64 [n_rep, n_cols],
+    counts int32 [n_rep, n_cols])`` (``out``: the same two to write into): the sum and the number of the non-NaN cells a
+    replicate took per column.  The bits follow the rule in include/mvin_hip.h and depend on neither the other columns, nor
+    ``first`` / ``n_rep`` splitting, nor ``max_groups`` (0 automatic, else a cap on the workgroups), nor the row stride.  A table
+    wider than resample_max_cols() goes through one launch per block of columns (and one strided copy per block into the
+    outputs), which changes no bit.  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(vals, torch.Tensor) or vals.dim() != 2:
+        raise ValueError("vals: expected a [n_rows, n_cols] tensor")
+    if vals.dtype != torch.float64:
+        raise TypeError(f"vals: expected torch.float64, got {vals.dtype}")
+    if not vals.is_cuda:
+        raise _lib.MvinHipError("vals: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if mode not in RESAMPLE_MODES:
+        raise ValueError(f"mode={mode!r}: expected one of {sorted(RESAMPLE_MODES)}")
+    n_rep, first, max_groups, seed = int(n_rep), int(first), int(max_groups), int(seed)
+    if n_rep < 0 or first < 0 or max_groups < 0:
+        raise ValueError(f"n_rep={n_rep} first={first} max_groups={max_groups}: expected values >= 0")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed={seed}: expected an unsigned 64-bit value")
+    n_rows, n_cols = vals.shape
+    ld = vals.stride(0) if n_rows > 1 else max(n_cols, 1)
+    if n_rows and ((n_cols > 1 and vals.stride(1) != 1) or ld < n_cols):      # (the strides of an empty dimension say nothing)
+        raise ValueError("vals: rows must be dense (stride 1 along the columns, rows at least n_cols doubles apart)")
+    if n_rows >= 1 << 31:
+        raise ValueError(f"n_rows={n_rows}: mvin_resample_sums takes fewer than 2^31 rows")
+    dev = vals.device
+    if out is None:
+        out = (torch.empty((n_rep, n_cols), dtype=torch.float64, device=dev), torch.empty((n_rep, n_cols), dtype=I32, device=dev))
+    if len(out) != 2:
+        raise ValueError("out: expected (sums, counts)")
+    sums, counts = _chk(out[0], torch.float64, "out sums"), _chk(out[1], I32, "out counts")
+    if sums is None or counts is None or tuple(sums.shape) != (n_rep, n_cols) or tuple(counts.shape) != (n_rep, n_cols):
+        raise ValueError(f"out: expected sums f64 and counts int32 [{n_rep}, {n_cols}]")
+    if n_rep == 0 or n_cols == 0:
+        return sums, counts
+    cap = resample_max_cols()
+
+    def launch(c0, w, s, c):
+        _lib.check(lib.mvin_resample_sums(_p(vals, c0) if n_rows else None, n_rows, w, ld, RESAMPLE_MODES[mode], C.c_uint64(seed), first,
+                                          n_rep, max_groups, _p(s), _p(c), _stream()), "mvin_resample_sums")
+
+    if n_cols <= cap:
+        launch(0, n_cols, sums, counts)
+        return sums, counts
+    for c0 in range(0, n_cols, cap):
+        w = min(cap, n_cols - c0)
+        s = torch.empty((n_rep, w), dtype=torch.float64, device=dev)
+        c = torch.empty((n_rep, w), dtype=I32, device=dev)
+        launch(c0, w, s, c)
+        sums[:, c0:c0 + w].copy_(s)
+        counts[:, c0:c0 + w].copy_(c)
+    return sums, counts
+
+
+def resample_summary(obs_sums, obs_counts, sums, counts, level=0.95, num=None, den=None):
+    """Intervals from resample_sums' outputs, on the host, per column.  ``obs_sums`` / ``obs_counts`` [n_cols] (or [1, n_cols]):
+    the "observed" call; ``sums`` / ``counts`` [R, n_cols]: the bootstrap replicates.  The statistic of a column is its mean
+    sum / count -- or, with ``num`` and ``den`` (two equally long lists of column numbers), the ratio sum[num] / sum[den] of two
+    column sums (a per-interaction average or an impression-weighted mean under resampling of users).  Returns a dict of f64
+    arrays, one entry per column (per ratio): ``mean`` the observed statistic; ``se`` the sample standard deviation (ddof 1) of
+    the replicate statistics; ``lo`` / ``hi`` numpy.quantile of the finite replicate statistics at (1 - level) / 2 and
+    1 - (1 - level) / 2; ``degenerate`` (int64) the replicates left out because their count (their denominator) was zero.
+    NaN where nothing is defined (no finite replicate; ``se`` with fewer than two)."""
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level={level}: expected a value in (0, 1)")
+    if (num is None) != (den is None):
+        raise ValueError("num and den go together")
+    os_ = np.asarray(obs_sums, dtype=np.float64).reshape(-1)
+    oc = np.asarray(obs_counts).astype(np.float64).reshape(-1)
+    s = np.asarray(sums, dtype=np.float64)
+    c = np.asarray(counts).astype(np.float64)
+    if s.ndim != 2 or s.shape != c.shape or s.shape[1] != os_.size or oc.size != os_.size:
+        raise ValueError(f"expected sums / counts [R, n_cols] and observed [n_cols], got {s.shape}, {c.shape}, {os_.shape}, {oc.shape}")
+    if num is not None:
+        num, den = [int(i) for i in num], [int(i) for i in den]
+        if len(num) != len(den) or any(not 0 <= i < os_.size for i in num + den):
+            raise ValueError("num / den: expected two equally long lists of column numbers")
+        top_o, bot_o, top, bot = os_[num], os_[den], s[:, num], s[:, den]
+    else:
+        top_o, bot_o, top, bot = os_, oc, s, c
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(bot_o != 0, top_o / bot_o, np.nan)
+        stat = np.where(bot != 0, top / bot, np.nan)
+    n_stat = stat.shape[1]
+    out = dict(mean=mean, se=np.full(n_stat, np.nan), lo=np.full(n_stat, np.nan), hi=np.full(n_stat, np.nan),
+               degenerate=(bot == 0).sum(axis=0).astype(np.int64))
+    a = (1.0 - float(level)) / 2.0
+    for j in range(n_stat):
+        x = stat[:, j]
+        x = x[np.isfinite(x)]
+        if x.size:
+            out["lo"][j], out["hi"][j] = np.quantile(x, a), np.quantile(x, 1.0 - a)
+        if x.size > 1:
+            out["se"][j] = np.std(x, ddof=1)
+    return out
+
+
+def signflip_pvalue(obs_sum, sums):
+    """The two-sided sign-flip permutation p-value per column: ``(1 + #{r: |sums[r]| >= |obs_sum|}) / (R + 1)`` -- never 0.
+    ``obs_sum`` [n_cols] from the "observed" call and ``sums`` [R, n_cols] from the "signflip" call of resample_sums share one
+    summation order, so the comparison is exact and ties count.  NaN where the observed sum is NaN."""
+    o = np.asarray(obs_sum, dtype=np.float64).reshape(-1)
+    s = np.asarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[1] != o.size:
+        raise ValueError(f"expected sums [R, n_cols] and obs_sum [n_cols], got {s.shape} and {o.shape}")
+    with np.errstate(invalid="ignore"):
+        p = (1.0 + (np.abs(s) >= np.abs(o)[None, :]).sum(axis=0)) / (s.shape[0] + 1.0)
+    return np.where(np.isnan(o), np.nan, p)
+
+
+def holm_adjust(p):
+    """Holm's step-down adjustment of the p-values ``p`` (any shape; the same shape comes back): with the m non-NaN values sorted
+    ascending, adjusted_(i) = min(1, max_{j <= i} (m - j + 1) p_(j)).  NaNs pass through and are not counted in m."""
+    p = np.asarray(p, dtype=np.float64)
+    flat = p.reshape(-1)
+    out = np.full(flat.shape, np.nan)
+    idx = np.flatnonzero(~np.isnan(flat))
+    if idx.size:
+        order = idx[np.argsort(flat[idx], kind="stable")]
+        m = idx.size
+        adj = np.maximum.accumulate((m - np.arange(m)) * flat[order])
+        out[order] = np.minimum(1.0, adj)
+    return out.reshape(p.shape)
+
+
 def _score_image_host(vals):
     """mvin_score_image.h on the host: uint32 images of f32 scores (-0.0 = +0.0, every NaN = 0, below image(-inf))."""
     import numpy as np
