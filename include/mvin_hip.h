@@ -1035,6 +1035,46 @@ MVIN_API int64_t mvin_ctr_counts_ws_bytes(int64_t n_seg, int64_t seg_len);     /
 MVIN_API int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, void* ws,
                              int64_t* out, void* stream);
 
+/* ---- CTR significance: what DeLong's variance of the AUC and DeLong's paired test of two AUCs on the same rows are made of,
+ * as integers (an opt-in extension; the reference reports bare point estimates) --
+ * mvin_ctr_placements: scores [n] f32 and labels [n] int32 (one population; neither is written).  THE RULE:
+ *   row i is VALID when its score is finite and its label is 0 or 1; an invalid row gets place[i] = -1 and is in no class;
+ *   for a valid row, with image = the order-preserving image of the score mvin_ctr_counts compares (-0.0 equals +0.0,
+ *   denormals are distinct numbers),
+ *     place[i] = 2 * #{valid j: label_j != label_i, image_j < image_i} + #{valid j: label_j != label_i, image_j == image_i};
+ *   counts [4] = n_pos, n_neg (valid rows per class), u2 = the sum of place over the valid positives (twice the Mann-Whitney
+ *   U: with bad == 0 the first three are mvin_ctr_counts' n_pos, n_neg, u2 of the buffer), bad = the invalid rows.
+ * The sum of place over the valid negatives is 2 * n_pos * n_neg - u2.  Every number is an integer, independent of the launch
+ * shape and the same on every launch.  n <= MVIN_CTR_SEG_CAP: one workgroup, no workspace; longer n take a sequence of
+ * launches on `stream` through `ws` (mvin_ctr_placements_ws_bytes bytes, may be NULL when that is 0).
+ * Limit: 1 <= n < 2^31, so place < 2^32.
+ * Errors (< 0, nothing launched): -2 for n outside the limit; -1 for null scores / labels / place / counts, or a null ws that
+ * is needed.
+ *
+ * mvin_placement_moments: the exact sums and cross-products of K = n_models models' placements of the SAME n rows.
+ * place [K, n] int64, model a's row at place + a*ld; labels [n] int32; neither is written.  A row is USED when its label is 0
+ * or 1 and place[a][i] >= 0 for every model a; its class c is its label.
+ *   counts [3] = used rows of class 0, used rows of class 1, bad = the rows with label 0 / 1 that some model marked -1.  Rows
+ *     with any other label are skipped silently;
+ *   sums [2, K]:        sums[c][a] = sum place[a][i] over the used rows of class c;
+ *   cross [2, K, K, 2]: cross[c][a][b] = sum place[a][i] * place[b][i] over the used rows of class c, as a 96-bit integer in two
+ *     unsigned 64-bit words: [0] = sum (product & 0xFFFFFFFF), [1] = sum (product >> 32); the value is [0] + [1] * 2^32.  The
+ *     full symmetric matrix is written.
+ * The outputs are zeroed by the call.  With place < 2^32 and n < 2^31 each word stays below 2^63: nothing overflows, and the
+ * integer adds give the same bits in any order, so the result depends on neither `max_groups` (0 = automatic, a positive
+ * value caps the workgroups per model) nor the launch.  No workspace.
+ * Limits: 1 <= K <= mvin_placement_moments_max_models() (8); ld >= n; 0 <= n < 2^31; place values in [-1, 2^32).  A value
+ * outside that range in a used row is NOT detected: its low 32 bits are taken.
+ * Errors (< 0, nothing launched): -2 for sizes outside the limits or max_groups < 0; -1 for null cross / sums / counts, or null
+ * place / labels with n > 0.  n == 0 gives zeros. */
+MVIN_API int64_t mvin_ctr_placements_ws_bytes(int64_t n);                       /* < 0: invalid n */
+MVIN_API int mvin_ctr_placements(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* place /* [n] */,
+                                 int64_t* counts /* [4] */, void* stream);
+MVIN_API int mvin_placement_moments_max_models(void);
+MVIN_API int mvin_placement_moments(const int64_t* place /* [K, n], rows ld apart */, int64_t ld, int n_models,
+                                    const int32_t* labels, int64_t n, int max_groups, uint64_t* cross /* [2, K, K, 2] */,
+                                    int64_t* sums /* [2, K] */, int64_t* counts /* [3] */, void* stream);
+
 /* ---- CTR report: probabilistic quality of the scores (logloss, Brier, reliability bins), one Newton iteration of a Platt
  * fit, and the CTR counts of segments of their own lengths (per-user AUC).  An extension: the reference reports none of these --
  * mvin_ctr_calib: mvin_ctr_counts' layout (segment s is logits[s*ld .. s*ld+seg_len) with labels[...]; the gaps between rows

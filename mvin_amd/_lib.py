@@ -123,6 +123,10 @@ SIGNATURES = {
                                   C.c_int] + [C.c_void_p] * 4),
     "mvin_ctr_counts_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_ctr_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvin_ctr_placements_ws_bytes": (C.c_int64, [C.c_int64]),
+    "mvin_ctr_placements": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "mvin_placement_moments_max_models": (C.c_int, []),
+    "mvin_placement_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
     "mvin_ctr_calib_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_ctr_calib": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_double] * 4
                        + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),

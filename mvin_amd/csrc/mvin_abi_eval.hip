@@ -296,6 +296,35 @@ int mvin_ctr_counts(const float* scores, const int32_t* labels, int64_t n_seg, i
     return hip_result(mvin::launch_ctr_counts(scores, labels, n_seg, seg_len, ld, ws, out, (hipStream_t)stream), who);
 }
 
+int64_t mvin_ctr_placements_ws_bytes(int64_t n) {
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "mvin_ctr_placements_ws_bytes: n=%lld (1 <= n < 2^31)", (long long)n);
+    return mvin::ctr_placements_ws_bytes(n);
+}
+
+int mvin_ctr_placements(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* place, int64_t* counts,
+                        void* stream) {
+    const char* who = "mvin_ctr_placements";
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "%s: n=%lld (1 <= n < 2^31)", who, (long long)n);
+    if (!scores || !labels || !place || !counts) return fail(-1, "%s: null scores / labels / place / counts", who);
+    if (!ws && mvin::ctr_placements_ws_bytes(n) > 0)
+        return fail(-1, "%s: null ws (n=%lld needs mvin_ctr_placements_ws_bytes)", who, (long long)n);
+    return hip_result(mvin::launch_ctr_placements(scores, labels, n, ws, place, counts, (hipStream_t)stream), who);
+}
+
+int mvin_placement_moments_max_models(void) { return mvin::placement_moments_max_models(); }
+
+int mvin_placement_moments(const int64_t* place, int64_t ld, int n_models, const int32_t* labels, int64_t n, int max_groups,
+                           uint64_t* cross, int64_t* sums, int64_t* counts, void* stream) {
+    const char* who = "mvin_placement_moments";
+    if (n_models < 1 || n_models > mvin::placement_moments_max_models() || n < 0 || n >= (int64_t(1) << 31) || ld < n || max_groups < 0)
+        return fail(-2, "%s: n_models=%d n=%lld ld=%lld max_groups=%d (1 <= n_models <= %d; 0 <= n < 2^31; ld >= n; max_groups >= 0)", who,
+                    n_models, (long long)n, (long long)ld, max_groups, mvin::placement_moments_max_models());
+    if (!cross || !sums || !counts || (n > 0 && (!place || !labels)))
+        return fail(-1, "%s: null place / labels / cross / sums / counts", who);
+    return hip_result(mvin::launch_placement_moments(place, ld, n_models, labels, n, max_groups, cross, sums, counts, (hipStream_t)stream),
+                      who);
+}
+
 int64_t mvin_ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len) {
     if (ctr_bad_sizes(n_seg, seg_len)) return fail(-2, "mvin_ctr_calib_ws_bytes: n_seg=%lld seg_len=%lld", (long long)n_seg, (long long)seg_len);
     return mvin::ctr_calib_ws_bytes(n_seg, seg_len);

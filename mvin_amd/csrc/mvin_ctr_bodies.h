@@ -1,6 +1,7 @@
 // The bodies mvin_ctr_counts (mvin_ctr_metrics.hip) and mvin_ctr_counts_segments (mvin_ctr_segments.hip) share: one load and
 // count rule, one LDS sort of the negatives' images, one search, one workgroup sum -- so that "the same six integers" is the
-// same code.
+// same code.  mvin_ctr_placements (mvin_ctr_delong.hip) takes the sort, the search and the sum from here too, and adds the helpers
+// below them in which the class is a parameter.
 #pragma once
 #include "mvin_kernels.h"
 #include "mvin_score_image.h"
@@ -64,6 +65,48 @@ __device__ __forceinline__ void ctr_sort(unsigned* keys, int P) {
             __syncthreads();
         }
     }
+}
+
+// ---- what the placement kernels (mvin_ctr_delong.hip) add: the same sort and search, with the class a parameter ----
+
+// the class of a pair: 0 / 1 = its label when the score is finite, else -1 (in neither class: mvin_ctr_placements' VALID rule)
+__device__ __forceinline__ int ctr_valid_class(float s, int32_t l) {
+    const bool finite = (__float_as_uint(s) & 0x7F800000u) != 0x7F800000u;
+    return (finite && (l == 0 || l == 1)) ? (int)l : -1;
+}
+
+// pairs [0, len) into LDS keys[0, P): the images of the valid pairs of class `cls`, else the sentinel; counts those pairs into
+// n_cls and the invalid ones into n_bad
+template <int NT>
+__device__ __forceinline__ void ctr_load_class(const float* srow, const int32_t* lrow, int len, int P, int cls, unsigned* keys,
+                                               unsigned& n_cls, unsigned& n_bad) {
+    for (int i = threadIdx.x; i < P; i += NT) {
+        unsigned key = kCtrSentinel;
+        if (i < len) {
+            const float s = srow[i];
+            const int c = ctr_valid_class(s, lrow[i]);
+            n_cls += c == cls;
+            n_bad += c < 0;
+            if (c == cls) key = score_image(s);
+        }
+        keys[i] = key;
+    }
+}
+
+// 2 * #{i < n: k[i] < x} + #{i < n: k[i] == x} = lower_bound + upper_bound, k ascending (sentinels above every image may follow)
+template <typename T, typename P>
+__device__ __forceinline__ unsigned long long ctr_place(P k, T n, unsigned x) {
+    return (unsigned long long)ctr_rank<T>(k, n, x, false) + (unsigned long long)ctr_rank<T>(k, n, x, true);
+}
+
+// where key i of a row of T sorted runs of w keys goes when the runs are merged pairwise (ties: the first run's keys first)
+template <typename P>
+__device__ __forceinline__ int64_t ctr_merge_place(P s, int64_t T, int64_t w, int64_t i) {
+    const int64_t base = i / (2 * w) * (2 * w);
+    const int64_t b0 = min(base + w, T), bn = min(w, T - b0);
+    const unsigned x = s[i];
+    if (i < b0) return base + (i - base) + ctr_rank<int64_t>(s + b0, bn, x, false);
+    return base + (i - b0) + ctr_rank<int64_t>(s + base, w, x, true);
 }
 
 // workgroup sums of v[0..5] into red (LDS, >= 6 * NT / kWave u64, 8-byte aligned; free to overwrite); valid in threads 0..5

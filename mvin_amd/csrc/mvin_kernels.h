@@ -498,6 +498,12 @@ hipError_t launch_ctr_counts(const float* scores, const int32_t* labels, int64_t
                              int64_t* out, hipStream_t st);
 hipError_t launch_ctr_counts_segments(const float* scores, const int32_t* labels, int64_t total, const int64_t* seg_ptr, int64_t n_seg,
                                       float threshold, int64_t max_len, int form, int64_t* out, int64_t* status, hipStream_t st);
+int64_t ctr_placements_ws_bytes(int64_t n);                    // per-row placements and their exact moments (mvin_ctr_delong.hip)
+hipError_t launch_ctr_placements(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* place, int64_t* counts,
+                                 hipStream_t st);
+int placement_moments_max_models();
+hipError_t launch_placement_moments(const int64_t* place, int64_t ld, int K, const int32_t* labels, int64_t n, int max_groups,
+                                    uint64_t* cross, int64_t* sums, int64_t* counts, hipStream_t st);
 int64_t ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len);    // calibration sums and reliability bins (mvin_ctr_calib.hip)
 hipError_t launch_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b,
                             double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums,

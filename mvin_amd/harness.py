@@ -1224,7 +1224,7 @@ def fit_calibration(feeder, data, smooth=True, max_iter=50, tol=1e-10, max_pairs
     return Calibration(a, b, iterations, converged, float(before[0][0] / before[1]), float(after[0][0] / after[1]))
 
 
-def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288):
+def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288, ci=None):
     """The CTR report of a split as ONE population (an extension: the reference reports none of these but the per-batch means
     of auc / acc / f1).  The split is scored once (logits and sigmoid scores of the same forward calls); everything else is
     reductions over the resident buffers and one copy back per result tensor.  Returns a dict:
@@ -1238,7 +1238,12 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
         ops.gauc_from_counts).  LIMIT: a user with more than ops.CTR_SEG_CAP = 16 384 rows in the split raises ValueError.
     ``calibration``: a Calibration or an ``(a, b)`` pair with a > 0.  The calibration numbers are then those of
     p = sigmoid(a z + b), and ``acc`` / ``f1`` those of the prediction z >= float32(-b / a), i.e. a z + b >= 0; ``auc`` and
-    ``gauc`` do not change under an increasing map."""
+    ``gauc`` do not change under an increasing map.
+    ``ci`` (a level such as 0.95; None: the dict and the launches above, nothing more) adds ``"auc_se"`` and ``"auc_ci": (lo,
+    hi)``: DeLong's standard error of ``auc`` and the Wald interval around it (ops.delong_interval), from ONE
+    mvin_ctr_placements launch and ONE mvin_placement_moments launch on the sigmoid scores ``auc`` is counted on.  The rows are
+    treated as independent draws; a user's rows are correlated, so the interval is on the narrow side.  A split with fewer than
+    two rows of a class raises ValueError.  (User-clustered variants and intervals for f1 / ece / gauc are not built.)"""
     import torch
     from . import ops
     cols = np.asarray(data)
@@ -1275,10 +1280,18 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
         od = torch.from_numpy(order).to(dev)
         ucounts, _ = ops.ctr_counts_segments(logits.index_select(0, od), labels.index_select(0, od),
                                              torch.from_numpy(seg_ptr).to(dev), threshold=0.0, max_len=int(rows.max()))
+    moments = None
+    if ci is not None:
+        place, _ = ops.ctr_placements(scores, labels)
+        moments = ops.placement_moments(place.view(1, n), labels)
     counts = counts.cpu().numpy()
     auc, acc, f1 = ops.ctr_metrics_from_counts(counts)
     cal = ops.ctr_calibration_from_sums(sums.cpu().numpy(), valid.cpu().numpy(), bins.cpu().numpy())
     rep = {"auc": float(auc[0]), "acc": float(acc[0]), "f1": float(f1[0])}
+    if moments is not None:
+        dl = ops.delong_from_moments(*(t.cpu().numpy() for t in moments))
+        se, lo, hi = ops.delong_interval(rep["auc"], dl["cov"][0, 0], ci)
+        rep["auc_se"], rep["auc_ci"] = se, (lo, hi)
     if cut is not None:
         cut = cut.cpu().numpy()[0]
         c2 = counts.copy()
@@ -1297,6 +1310,114 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
 
 
 _ctr_report = ctr_report                                        # train() takes an option of the same name
+
+CTR_ROW_METRICS = ("logloss", "brier", "acc")
+
+
+def ctr_row_table(logits, labels):
+    """The per-row values compare_ctr resamples, f64 [n, 3] (``CTR_ROW_METRICS``) on the tensors' device, from f32 ``logits`` z
+    and 0 / 1 ``labels`` y by elementwise torch operations in float64: ``max(z, 0) - y z + log1p(exp(-|z|))`` (the logloss of
+    sigmoid(z)), ``(sigmoid(z) - y)^2`` and ``(z >= 0) == y`` as 1.0 / 0.0."""
+    import torch
+    z = logits.reshape(-1).to(torch.float64)
+    y = labels.reshape(-1).to(torch.float64)
+    loss = torch.clamp(z, min=0.0) - y * z + torch.log1p(torch.exp(-torch.abs(z)))
+    brier = (torch.sigmoid(z) - y) ** 2
+    acc = ((z >= 0) == (y == 1.0)).to(torch.float64)
+    return torch.stack([loss, brier, acc], dim=1)
+
+
+def ctr_compare_pairs(n_models):
+    """The pairs ``(a, b)``, a < b, of compare_ctr in the order of its difference columns and of Holm's adjustment."""
+    return [(a, b) for a in range(int(n_models)) for b in range(a + 1, int(n_models))]
+
+
+def ctr_compare_table(tables):
+    """compare_ctr's resampling table from the models' ctr_row_table tensors: f64 [n, 3 K + 3 P], the K models' columns, then
+    for every pair of ctr_compare_pairs its three difference columns a - b."""
+    import torch
+    return torch.cat(list(tables) + [tables[a] - tables[b] for a, b in ctr_compare_pairs(len(tables))], dim=1).contiguous()
+
+
+def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288):
+    """CTR numbers of 2 to 8 models (``feeders``) on ONE split with their uncertainty, and every pair compared on the same rows.
+    Each model is scored once (logits and sigmoid scores of the same forward calls); its placements (ops.ctr_placements on the
+    sigmoid scores) go into one [K, n] buffer, ONE ops.placement_moments launch gives DeLong's covariance matrix of the K AUCs
+    (ops.delong_from_moments), and ops.resample_sums runs "observed", "bootstrap" and "signflip" over the per-row table
+    ctr_compare_table(ctr_row_table per model): every replicate resamples all models and differences with the same rows.  ONE
+    copy back.  Returns ``{"models": [...], "pairs": {(a, b): ...}, "n", "n_pos", "n_neg", "level", "n_rep"}``:
+      * per model: ``auc`` (ctr_eval_split's bits), ``auc_se``, ``auc_ci`` (DeLong, ops.delong_interval), and the means
+        ``logloss``, ``brier``, ``acc`` of the table's columns (in the kernel's summation order);
+      * per pair a < b: ``auc_diff`` = auc_a - auc_b with ``se``, ``lo``, ``hi`` (diff -+ z se), ``z``, ``p`` (ops.delong_test)
+        and ``p_holm`` (Holm over the pairs of the call); and for ``logloss``, ``brier``, ``acc`` a dict ``{"diff", "lo", "hi",
+        "p"}``: the paired mean difference, its percentile bootstrap interval at ``level`` (``n_rep`` replicates of ``seed``)
+        and the two-sided sign-flip p-value over rows.
+    What the numbers assume: the rows are independent draws.  A user's rows are correlated, so intervals are on the narrow
+    side and p-values on the small side; user-clustered variants, and intervals for f1 / ece / gauc, are not built.
+    ValueError: fewer than 2 or more than 8 feeders, a label other than 0 / 1, fewer than two rows of a class, a non-finite
+    score."""
+    import torch
+    from . import ops
+    feeders = list(feeders)
+    K = len(feeders)
+    if not 2 <= K <= 8:
+        raise ValueError(f"compare_ctr: {K} feeders: expected 2 to 8 models (mvin_placement_moments takes at most 8 per call)")
+    cols = np.asarray(data)
+    n = cols.shape[0]
+    lab = cols[:, 2] if n else np.zeros(0)
+    n_other = int(((lab != 0) & (lab != 1)).sum())
+    if n_other:
+        raise ValueError(f"compare_ctr: {n_other} row(s) of the split carry a label other than 0 / 1")
+    n_pos, n_neg = int((lab == 1).sum()), int((lab == 0).sum())
+    if n_pos < 2 or n_neg < 2:
+        raise ValueError(f"compare_ctr: {n_pos} positive and {n_neg} negative rows: DeLong's variance needs at least two rows of each class")
+    R = int(n_rep)
+    dev = feeders[0].model.device
+    place = torch.empty((K, n), dtype=torch.int64, device=dev)
+    pcounts = torch.empty((K, 4), dtype=torch.int64, device=dev)
+    tables, labels = [], None
+    for k, f in enumerate(feeders):
+        logits, scores, labels = _score_split_both(f, data, max_pairs)
+        ops.ctr_placements(scores, labels, out=(place[k], pcounts[k]))
+        tables.append(ctr_row_table(logits, labels))
+    cross, sums, counts = ops.placement_moments(place, labels)
+    t = ctr_compare_table(tables)
+    M = 3 * K
+    o_s, o_c = ops.resample_sums(t, 1, seed=seed, mode="observed")
+    b_s, b_c = ops.resample_sums(t, R, seed=seed, mode="bootstrap")
+    f_s, _ = ops.resample_sums(t[:, M:], R, seed=seed, mode="signflip")
+    as_f64 = lambda x: x.view(torch.float64)                     # noqa: E731  (int64 words through the one packed copy)
+    (o_s, b_s, f_s, cross, sums, counts, pcounts), (o_c, b_c) = _copy_back(
+        [o_s, b_s, f_s, as_f64(cross), as_f64(sums), as_f64(counts), as_f64(pcounts)], [o_c, b_c])
+    cross, sums, counts, pcounts = (x.view(np.int64) for x in (cross, sums, counts, pcounts))
+    if (pcounts[:, 3] > 0).any():
+        k = int(np.flatnonzero(pcounts[:, 3] > 0)[0])
+        raise ValueError(f"compare_ctr: model {k} gives {int(pcounts[k, 3])} non-finite score(s) on the split")
+    dl = ops.delong_from_moments(cross, sums, counts)
+    o_s, o_c = o_s.reshape(-1), o_c.reshape(-1)
+    summ = ops.resample_summary(o_s, o_c, b_s, b_c, level=level)
+    p_flip = ops.signflip_pvalue(o_s[M:], f_s)
+    models = []
+    for k in range(K):
+        se, lo, hi = ops.delong_interval(dl["auc"][k], dl["cov"][k, k], level)
+        row = {"auc": float(dl["auc"][k]), "auc_se": se, "auc_ci": (lo, hi)}
+        row.update({name: float(summ["mean"][3 * k + q]) for q, name in enumerate(CTR_ROW_METRICS)})
+        models.append(row)
+    from statistics import NormalDist
+    zq = NormalDist().inv_cdf(1.0 - (1.0 - float(level)) / 2.0)
+    pair_list = ctr_compare_pairs(K)
+    tests = [ops.delong_test(dl["auc"], dl["cov"], a, b) for a, b in pair_list]
+    holm = ops.holm_adjust(np.array([tt["p"] for tt in tests]))
+    pairs = {}
+    for j, ((a, b), tt) in enumerate(zip(pair_list, tests)):
+        row = {"auc_diff": tt["diff"], "se": tt["se"], "lo": tt["diff"] - zq * tt["se"], "hi": tt["diff"] + zq * tt["se"], "z": tt["z"],
+               "p": tt["p"], "p_holm": float(holm[j])}
+        for q, name in enumerate(CTR_ROW_METRICS):
+            c = M + 3 * j + q
+            row[name] = {"diff": float(summ["mean"][c]), "lo": float(summ["lo"][c]), "hi": float(summ["hi"][c]),
+                         "p": float(p_flip[c - M])}
+        pairs[(a, b)] = row
+    return {"models": models, "pairs": pairs, "n": n, "n_pos": dl["n_pos"], "n_neg": dl["n_neg"], "level": float(level), "n_rep": R}
 
 
 def topk_settings(train_data, eval_data, test_data, n_item, user_num=250, k_list=(1, 2, 5, 10, 25, 50, 100)):

@@ -563,6 +563,150 @@ def ctr_metrics_from_counts(counts):
     return auc, acc, f1
 
 
+PLACEMENT_COUNTS = ("n_pos", "n_neg", "u2", "bad")
+
+
+def ctr_placements(scores, labels, out=None):
+    """mvin_ctr_placements: every row's placement among the valid rows of the other class.  ``scores`` f32 [n] and ``labels``
+    int32 [n] (contiguous device tensors, ONE population).  Returns ``(place int64 [n], counts int64 [4])`` on the device
+    (``out``: the same two to write into): ``place[i] = 2 #{other class below} + #{other class equal}`` with ctr_counts' image
+    and tie rule, -1 for a row with a non-finite score or a label other than 0 / 1; ``counts`` = ``PLACEMENT_COUNTS``, with
+    ``u2`` the sum of the positives' placements -- ctr_counts' u2.  All integers, the same on every launch.  Enqueues only."""
+    lib = _lib.load()
+    for t, name in ((scores, "scores"), (labels, "labels")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    if scores.dtype != F32:
+        raise TypeError(f"scores: expected {F32}, got {scores.dtype}")
+    if labels.dtype != I32:
+        raise TypeError(f"labels: expected {I32}, got {labels.dtype}")
+    if scores.dim() != 1 or labels.dim() != 1 or scores.shape != labels.shape or not scores.is_contiguous() or not labels.is_contiguous():
+        raise ValueError(f"scores {tuple(scores.shape)} and labels {tuple(labels.shape)}: expected two contiguous [n] tensors")
+    n = scores.numel()
+    if not 1 <= n < 1 << 31:
+        raise ValueError(f"n={n}: mvin_ctr_placements takes 1 <= n < 2^31 rows")
+    dev = scores.device
+    if out is None:
+        out = (torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((4,), dtype=torch.int64, device=dev))
+    if len(out) != 2:
+        raise ValueError("out: expected (place, counts)")
+    place, counts = _chk(out[0], torch.int64, "out place"), _chk(out[1], torch.int64, "out counts")
+    if place is None or counts is None or tuple(place.shape) != (n,) or tuple(counts.shape) != (4,):
+        raise ValueError(f"out: expected place int64 [{n}] and counts int64 [4]")
+    nws = lib.mvin_ctr_placements_ws_bytes(n)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_ctr_placements_ws_bytes")
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    _lib.check(lib.mvin_ctr_placements(_p(scores), _p(labels), n, _p(ws), _p(place), _p(counts), _stream()), "mvin_ctr_placements")
+    return place, counts
+
+
+def placement_moments_max_models():
+    """mvin_placement_moments_max_models: the models one mvin_placement_moments call takes (8)."""
+    return int(_lib.load().mvin_placement_moments_max_models())
+
+
+def placement_moments(place, labels, max_groups=0):
+    """mvin_placement_moments: the exact sums and cross-products of K models' placements of the same rows.  ``place`` int64
+    [K, n] (ctr_placements rows, dense, possibly strided between models), ``labels`` int32 [n].  A row is used when its label is
+    0 / 1 and no model marked it -1.  Returns device tensors ``(cross int64 [2, K, K, 2], sums int64 [2, K], counts int64 [3])``:
+    per class (0 negatives, 1 positives) the 96-bit sums of place[a] * place[b] as two unsigned 64-bit words (value = [0] + [1]
+    * 2^32; each word is below 2^63, so its int64 reading is the word), the sums of place[a], and (used class 0, used class 1,
+    bad).  ``max_groups``: 0 automatic, else a cap on the workgroups per model; it changes no bit.  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(place, torch.Tensor) or place.dim() != 2:
+        raise ValueError("place: expected a [K, n] tensor")
+    for t, name, dt in ((place, "place", torch.int64), (labels, "labels", I32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected {dt}, got {t.dtype}")
+    K, n = place.shape
+    if not 1 <= K <= placement_moments_max_models():
+        raise ValueError(f"{K} models: mvin_placement_moments takes 1 .. {placement_moments_max_models()}")
+    if labels.dim() != 1 or labels.numel() != n or not labels.is_contiguous():
+        raise ValueError(f"labels {tuple(labels.shape)}: expected a contiguous [{n}] tensor")
+    ld = place.stride(0) if K > 1 else max(n, 1)
+    if n and ((n > 1 and place.stride(1) != 1) or ld < n):
+        raise ValueError("place: rows must be dense (stride 1 along the rows of the split, models at least n apart)")
+    max_groups = int(max_groups)
+    if max_groups < 0 or n >= 1 << 31:
+        raise ValueError(f"max_groups={max_groups} n={n}: expected max_groups >= 0 and n < 2^31")
+    dev = place.device
+    cross = torch.empty((2, K, K, 2), dtype=torch.int64, device=dev)
+    sums = torch.empty((2, K), dtype=torch.int64, device=dev)
+    counts = torch.empty((3,), dtype=torch.int64, device=dev)
+    _lib.check(lib.mvin_placement_moments(_p(place) if n else None, ld, K, _p(labels) if n else None, n, max_groups, _p(cross), _p(sums),
+                                          _p(counts), _stream()), "mvin_placement_moments")
+    return cross, sums, counts
+
+
+def delong_from_moments(cross, sums, counts):
+    """DeLong's AUCs and their covariance matrix from placement_moments' integers (host arrays [2, K, K, 2], [2, K], [3]), in
+    exact arithmetic until the last step.  With m positives, n negatives, T_c[a, b] the 96-bit value and s_c[a] the sums:
+      S10[a, b] = (m T_1 - s_1a s_1b) / (m (m - 1) 4 n^2),   S01[a, b] = (n T_0 - s_0a s_0b) / (n (n - 1) 4 m^2),
+      cov[a, b] = S10 / m + S01 / n  -- a fractions.Fraction, rounded to float64 once;
+      auc[a] = float64(s_1a) / (2.0 * float64(m) * float64(n)) -- ctr_metrics_from_counts' operations, so its bits.
+    Returns ``{"auc": f64 [K], "cov": f64 [K, K], "n_pos": m, "n_neg": n}``.  The variance treats the rows as independent draws.
+    ValueError when ``bad > 0`` (a row some model marked invalid) and when a class has fewer than two rows (the variance is
+    undefined)."""
+    from fractions import Fraction
+    cr = np.asarray(cross)
+    sm = np.asarray(sums)
+    ct = np.asarray(counts).reshape(-1)
+    if cr.ndim != 4 or cr.shape[0] != 2 or cr.shape[1] != cr.shape[2] or cr.shape[3] != 2 or sm.shape != (2, cr.shape[1]) or ct.size != 3:
+        raise ValueError(f"expected cross [2, K, K, 2], sums [2, K] and counts [3], got {cr.shape}, {sm.shape}, {ct.shape}")
+    K = cr.shape[1]
+    n, m, bad = int(ct[0]), int(ct[1]), int(ct[2])
+    if bad > 0:
+        raise ValueError(f"{bad} row(s) with a non-finite score (a placement of -1)")
+    if m < 2 or n < 2:
+        raise ValueError(f"{m} positive and {n} negative rows: DeLong's variance needs at least two of each class")
+    word = lambda v: int(v) & 0xFFFFFFFFFFFFFFFF               # noqa: E731  (an unsigned word read as int64)
+    T = [[[word(cr[c, a, b, 0]) + (word(cr[c, a, b, 1]) << 32) for b in range(K)] for a in range(K)] for c in range(2)]
+    s = [[int(sm[c, a]) for a in range(K)] for c in range(2)]
+    cov = np.empty((K, K), dtype=np.float64)
+    for a in range(K):
+        for b in range(K):
+            s10 = Fraction(m * T[1][a][b] - s[1][a] * s[1][b], m * (m - 1) * 4 * n * n)
+            s01 = Fraction(n * T[0][a][b] - s[0][a] * s[0][b], n * (n - 1) * 4 * m * m)
+            f = s10 / m + s01 / n
+            cov[a, b] = f.numerator / f.denominator            # int / int: correctly rounded
+    auc = np.array([np.float64(s[1][a]) / (2.0 * np.float64(m) * np.float64(n)) for a in range(K)], dtype=np.float64)
+    return {"auc": auc, "cov": cov, "n_pos": m, "n_neg": n}
+
+
+def delong_interval(auc, var, level=0.95):
+    """The Wald interval of an AUC from its DeLong variance: ``(se, lo, hi)`` with se = sqrt(var) and auc -+ z se clipped to
+    [0, 1], z the normal quantile of 1 - (1 - level) / 2 (statistics.NormalDist)."""
+    import math
+    from statistics import NormalDist
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level={level}: expected a value in (0, 1)")
+    se = math.sqrt(max(float(var), 0.0))
+    z = NormalDist().inv_cdf(1.0 - (1.0 - level) / 2.0)
+    return se, max(0.0, float(auc) - z * se), min(1.0, float(auc) + z * se)
+
+
+def delong_test(auc, cov, a, b):
+    """DeLong's paired test of ``auc[a] - auc[b]`` for two models scored on the same rows: ``{"diff", "se", "z", "p"}`` with
+    var = cov[a, a] + cov[b, b] - 2 cov[a, b] clamped at 0, z = diff / se and the two-sided p = erfc(|z| / sqrt 2).  With
+    var == 0: z = 0 and p = 1 when diff == 0, else z = +-inf and p = 0."""
+    import math
+    auc, cov = np.asarray(auc, dtype=np.float64), np.asarray(cov, dtype=np.float64)
+    diff = float(auc[a] - auc[b])
+    var = max(float(cov[a, a] + cov[b, b] - 2.0 * cov[a, b]), 0.0)
+    se = math.sqrt(var)
+    if se == 0.0:
+        z = 0.0 if diff == 0.0 else math.copysign(math.inf, diff)
+        p = 1.0 if diff == 0.0 else 0.0
+    else:
+        z = diff / se
+        p = math.erfc(abs(z) / math.sqrt(2.0))
+    return {"diff": diff, "se": se, "z": z, "p": p}
+
+
 CTR_CALIB_MAX_BINS = 64      # MVIN_CTR_CALIB_MAX_BINS
 CTR_CALIB_SUMS = ("loss", "r2", "r", "rz", "w", "wz", "wz2", "p")
 CTR_MASS_ONE = float(1 << 40)          # the confidence mass of p = 1 (mvin_ctr_calib: floor(p * 2^40) per pair)
