@@ -1075,6 +1075,53 @@ MVIN_API int mvin_placement_moments(const int64_t* place /* [K, n], rows ld apar
                                     const int32_t* labels, int64_t n, int max_groups, uint64_t* cross /* [2, K, K, 2] */,
                                     int64_t* sums /* [2, K] */, int64_t* counts /* [3] */, void* stream);
 
+/* ---- user-clustered CTR significance: what the clustered DeLong variance (Obuchowski 1997: the cluster, not the row, is the
+ * sampling unit) and the cluster bootstrap are made of (an opt-in extension) --
+ * Both calls take a grouping of the n rows into n_clusters clusters: seg_ptr [n_clusters + 1] int64 and `order` int32 [n] or NULL.
+ * Position j of the grouped order is row order[j] (row j when order is NULL), and it belongs to cluster i when
+ * seg_ptr[i] <= j < seg_ptr[i+1].  Clusters may be empty, one row or all n rows; there is no cap on a cluster's length.
+ * MALFORMED GROUPINGS do not fault: every seg_ptr value is clamped into [0, n] and an end below its begin is raised to the
+ * begin (such a cluster is empty; pointers that overlap count a position in several clusters), and a position whose order
+ * value lies outside [0, n) adds nothing (it keeps its number t in the rule of mvin_segment_sums_f64).  The result is then defined by these rules but means nothing.
+ *
+ * mvin_placement_cluster_moments: place [K, n] int64 (model a's row at place + a*ld) and labels [n] int32 are
+ * mvin_placement_moments' inputs, and a row is USED under its rule: label 0 or 1 and place[a][r] >= 0 for every model a.  A row
+ * with label 0 / 1 that some model marked -1 is BAD; other labels are skipped silently.  Per cluster i, over its used rows:
+ *   m_i, n_i = the positives, the negatives;  A_i^a, B_i^a = the sums of place[a] over its positives, its negatives.
+ *   csum [n_clusters, 2 + 2K] int64:  csum[i] = m_i, n_i, A_i^1 .. A_i^K, B_i^1 .. B_i^K;
+ *   totals [4 + 2K] int64 = I (the clusters with m_i + n_i > 0), m = sum m_i, n = sum n_i, s1^a = sum_i A_i^a (K values),
+ *     s0^a = sum_i B_i^a (K values), bad (the bad rows, counted once per cluster they sit in);
+ *   gram [K + 2, K + 2, 2, 4] uint64: with z_i = (m_i, n_i, D_i^1 .. D_i^K), D_i^a = A_i^a - B_i^a, entry [p][q] holds
+ *     G[p][q] = sum_i z_i[p] * z_i[q], exact and signed, as limb sums: |z_i[p] * z_i[q]| < 2^126 is cut into four 32-bit limbs
+ *     (limb k = bits 32k .. 32k + 31); [p][q][0][k] is the sum of limb k over the clusters whose product is >= 0, [p][q][1][k]
+ *     over those whose product is < 0:   G[p][q] = sum_k ([p][q][0][k] - [p][q][1][k]) * 2^(32 k).
+ *     The full symmetric matrix is written.  Every word stays below 2^63.
+ * gram and totals are zeroed by the call; csum is written for every cluster.  Integers only: the result depends on neither
+ * `max_groups` (0 = automatic, a positive value caps the workgroups of each launch), nor the launch shape, nor the order of an
+ * add.  No workspace.  place values outside [-1, 2^32) in a used row are NOT detected: the low 32 bits are taken.
+ * Errors (< 0, nothing launched): -2 for K outside 1 .. mvin_placement_moments_max_models() (8), n or n_clusters outside
+ * [0, 2^31), ld < n or max_groups < 0; -1 for null seg_ptr / gram / totals, null csum with n_clusters > 0, or null place /
+ * labels with n > 0.  n_clusters == 0 gives zeros.
+ *
+ * mvin_segment_sums_f64: vals f64 [n, n_cols], rows `ld` doubles apart, never written.  out [n_clusters, n_cols] f64, dense:
+ * THE RULE for cluster i and column c: 64 partial sums p_0 .. p_63 start at +0.0.  For t = 0, 1, .. over the cluster's
+ * positions j = seg_ptr[i] + t ascending, p_(t mod 64) = p_(t mod 64) + vals[order[j]*ld + c].  Then for h = 32, 16, 8, 4, 2, 1:
+ * p_l = p_l + p_(l+h) for l < h.  out[i*n_cols + c] = p_0.  So an empty cluster gives +0.0, NaN and infinities propagate by
+ * IEEE rules, and the bits of a cell depend on that cluster's rows and that column only -- not on the launch, the other
+ * clusters, n_cols or ld.  No floating-point atomics.  No workspace.
+ * Limits: 0 <= n, n_clusters < 2^31; 0 <= n_cols <= mvin_segment_sums_max_cols() (1024); n_cols <= ld < 2^31.
+ * Errors (< 0, nothing launched): -2 for sizes outside the limits or a pointer that is not 8-byte aligned; -1 for null seg_ptr,
+ * null out with something to write, or null vals with something to read. */
+MVIN_API int mvin_placement_cluster_moments(const int64_t* place /* [K, n], rows ld apart */, int64_t ld, int n_models,
+                                            const int32_t* labels, int64_t n, const int32_t* order /* [n] or NULL */,
+                                            const int64_t* seg_ptr /* [n_clusters + 1] */, int64_t n_clusters, int max_groups,
+                                            int64_t* csum /* [n_clusters, 2 + 2K] */, uint64_t* gram /* [K + 2, K + 2, 2, 4] */,
+                                            int64_t* totals /* [4 + 2K] */, void* stream);
+MVIN_API int mvin_segment_sums_max_cols(void);
+MVIN_API int mvin_segment_sums_f64(const double* vals, int64_t n, int n_cols, int64_t ld, const int32_t* order /* [n] or NULL */,
+                                   const int64_t* seg_ptr /* [n_clusters + 1] */, int64_t n_clusters,
+                                   double* out /* [n_clusters, n_cols] */, void* stream);
+
 /* ---- CTR report: probabilistic quality of the scores (logloss, Brier, reliability bins), one Newton iteration of a Platt
  * fit, and the CTR counts of segments of their own lengths (per-user AUC).  An extension: the reference reports none of these --
  * mvin_ctr_calib: mvin_ctr_counts' layout (segment s is logits[s*ld .. s*ld+seg_len) with labels[...]; the gaps between rows

@@ -127,6 +127,11 @@ SIGNATURES = {
     "mvin_ctr_placements": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "mvin_placement_moments_max_models": (C.c_int, []),
     "mvin_placement_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
+    "mvin_placement_cluster_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_int] + [C.c_void_p] * 4),
+    "mvin_segment_sums_max_cols": (C.c_int, []),
+    "mvin_segment_sums_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p]),
     "mvin_ctr_calib_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "mvin_ctr_calib": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_double] * 4
                        + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),

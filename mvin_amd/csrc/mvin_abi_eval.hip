@@ -325,6 +325,39 @@ int mvin_placement_moments(const int64_t* place, int64_t ld, int n_models, const
                       who);
 }
 
+int mvin_placement_cluster_moments(const int64_t* place, int64_t ld, int n_models, const int32_t* labels, int64_t n, const int32_t* order,
+                                   const int64_t* seg_ptr, int64_t n_clusters, int max_groups, int64_t* csum, uint64_t* gram,
+                                   int64_t* totals, void* stream) {
+    const char* who = "mvin_placement_cluster_moments";
+    const int64_t lim = int64_t(1) << 31;
+    if (n_models < 1 || n_models > mvin::placement_moments_max_models() || n < 0 || n >= lim || n_clusters < 0 || n_clusters >= lim ||
+        ld < n || max_groups < 0)
+        return fail(-2, "%s: n_models=%d n=%lld ld=%lld n_clusters=%lld max_groups=%d (1 <= n_models <= %d; 0 <= n, n_clusters < 2^31; "
+                    "ld >= n; max_groups >= 0)", who, n_models, (long long)n, (long long)ld, (long long)n_clusters, max_groups,
+                    mvin::placement_moments_max_models());
+    if (!gram || !totals || !seg_ptr || (n_clusters > 0 && !csum) || (n > 0 && (!place || !labels)))
+        return fail(-1, "%s: null place / labels / seg_ptr / csum / gram / totals", who);
+    return hip_result(mvin::launch_placement_cluster_moments(place, ld, n_models, labels, n, order, seg_ptr, n_clusters, max_groups, csum,
+                                                             gram, totals, (hipStream_t)stream), who);
+}
+
+int mvin_segment_sums_max_cols(void) { return mvin::segment_sums_max_cols(); }
+
+int mvin_segment_sums_f64(const double* vals, int64_t n, int n_cols, int64_t ld, const int32_t* order, const int64_t* seg_ptr,
+                          int64_t n_clusters, double* out, void* stream) {
+    const char* who = "mvin_segment_sums_f64";
+    const int64_t lim = int64_t(1) << 31;
+    if (n < 0 || n >= lim || n_clusters < 0 || n_clusters >= lim || n_cols < 0 || n_cols > mvin::segment_sums_max_cols() || ld < n_cols ||
+        ld >= lim)
+        return fail(-2, "%s: n=%lld n_cols=%d ld=%lld n_clusters=%lld (0 <= n, n_clusters < 2^31; 0 <= n_cols <= %d; n_cols <= ld < 2^31)",
+                    who, (long long)n, n_cols, (long long)ld, (long long)n_clusters, mvin::segment_sums_max_cols());
+    if (!seg_ptr || (n_clusters > 0 && n_cols > 0 && !out) || (n > 0 && n_cols > 0 && !vals))
+        return fail(-1, "%s: null vals / seg_ptr / out", who);
+    if ((reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(seg_ptr)) & 7)
+        return fail(-2, "%s: vals / seg_ptr / out must be 8-byte aligned", who);
+    return hip_result(mvin::launch_segment_sums_f64(vals, n, n_cols, ld, order, seg_ptr, n_clusters, out, (hipStream_t)stream), who);
+}
+
 int64_t mvin_ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len) {
     if (ctr_bad_sizes(n_seg, seg_len)) return fail(-2, "mvin_ctr_calib_ws_bytes: n_seg=%lld seg_len=%lld", (long long)n_seg, (long long)seg_len);
     return mvin::ctr_calib_ws_bytes(n_seg, seg_len);

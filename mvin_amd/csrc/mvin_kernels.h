@@ -504,6 +504,13 @@ hipError_t launch_ctr_placements(const float* scores, const int32_t* labels, int
 int placement_moments_max_models();
 hipError_t launch_placement_moments(const int64_t* place, int64_t ld, int K, const int32_t* labels, int64_t n, int max_groups,
                                     uint64_t* cross, int64_t* sums, int64_t* counts, hipStream_t st);
+int placement_cluster_gram_words(int K);                       // per-cluster placement sums, their Gram matrix, f64 cluster sums
+hipError_t launch_placement_cluster_moments(const int64_t* place, int64_t ld, int K, const int32_t* labels, int64_t n,   // (mvin_ctr_cluster.hip)
+                                            const int32_t* order, const int64_t* seg_ptr, int64_t n_clusters, int max_groups,
+                                            int64_t* csum, uint64_t* gram, int64_t* totals, hipStream_t st);
+int segment_sums_max_cols();
+hipError_t launch_segment_sums_f64(const double* vals, int64_t n, int M, int64_t ld, const int32_t* order, const int64_t* seg_ptr,
+                                   int64_t n_clusters, double* out, hipStream_t st);
 int64_t ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len);    // calibration sums and reliability bins (mvin_ctr_calib.hip)
 hipError_t launch_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b,
                             double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums,

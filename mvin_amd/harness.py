@@ -1224,7 +1224,86 @@ def fit_calibration(feeder, data, smooth=True, max_iter=50, tol=1e-10, max_pairs
     return Calibration(a, b, iterations, converged, float(before[0][0] / before[1]), float(after[0][0] / after[1]))
 
 
-def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288, ci=None):
+def _cluster_grouping(cluster, cols, who):
+    """The ``cluster=`` keyword of ctr_report / compare_ctr on the host, before anything is scored: None for None; else a dict
+    ``{"by", "order", "seg_ptr", "n_clusters", "max_rows", "users"}`` -- ops.cluster_csr of the split's user column
+    (``cluster="user"``) or of an integer array of one id per row, and whether the clusters ARE the users (the same ``order``
+    and ``seg_ptr`` as the user column's: GAUC, a statistic of users, is resampled only then).  ValueError for anything else and
+    for fewer than two clusters."""
+    from . import ops
+    if cluster is None:
+        return None
+    n = cols.shape[0]
+    users = np.ascontiguousarray(cols[:, 0], dtype=np.int64)
+    if isinstance(cluster, str):
+        if cluster != "user":
+            raise ValueError(f"{who}: cluster={cluster!r}: expected None, \"user\" or an integer array of one cluster id per row")
+        by, ids = "user", users
+    else:
+        ids = np.asarray(cluster)
+        if ids.ndim != 1 or ids.shape[0] != n or ids.dtype.kind not in "iu":
+            raise ValueError(f"{who}: cluster: expected None, \"user\" or an integer array [{n}] of cluster ids, got {ids.dtype} "
+                             f"{ids.shape}")
+        by = "ids"
+    order, seg_ptr, cids = ops.cluster_csr(ids)
+    if cids.size < 2:
+        raise ValueError(f"{who}: {cids.size} cluster(s): the clustered variance and the cluster bootstrap need at least two")
+    same = by == "user"
+    if not same:
+        uo, up, _ = ops.cluster_csr(users)
+        same = bool(np.array_equal(uo, order) and np.array_equal(up, seg_ptr))
+    return {"by": by, "order": order, "seg_ptr": seg_ptr, "n_clusters": int(cids.size), "max_rows": int(np.diff(seg_ptr).max()),
+            "users": same}
+
+
+def _gauc_columns(ucounts):
+    """Per-user columns of GAUC on the device from ops.ctr_counts_segments rows (int64 [U, 6]): f64 ``(w * auc, w, auc, one)``
+    with gauc_from_counts' operations (auc = u2 / (2 n_pos n_neg), w = n_pos + n_neg), every one NaN for a user without both
+    classes -- resample_sums skips NaN cells, so such a user takes part in no replicate's sums."""
+    import torch
+    n_pos, n_neg, u2 = (ucounts[:, c].to(torch.float64) for c in (0, 1, 4))
+    both = (ucounts[:, 0] > 0) & (ucounts[:, 1] > 0)
+    nan = torch.full_like(n_pos, float("nan"))
+    auc = torch.where(both, u2 / (2.0 * n_pos * n_neg), nan)
+    w = torch.where(both, n_pos + n_neg, nan)
+    return w * auc, w, auc, torch.where(both, torch.ones_like(n_pos), nan)
+
+
+def _cluster_launches(place, labels, grp, row_main, row_diff, user_main, user_diff, n_rep, seed):
+    """What ``cluster=`` adds on the device, enqueued only.  ``place`` int64 [K, n]; ``row_main`` / ``row_diff`` f64 [n, *]: per-row
+    columns (zero in rows that are not used) whose per-cluster sums are resampled, the difference columns apart (``row_diff``
+    may be None); ``user_main`` / ``user_diff`` f64 [I, *] or None: columns that are per cluster already (GAUC).  The resampling
+    table is [I, main | user_main | diff | user_diff]: ops.segment_sums (mvin_segment_sums_f64) of the row columns beside the
+    per-cluster ones; ops.resample_sums runs "observed" and "bootstrap" over all of it and "signflip" over the difference
+    columns, so every column shares one draw of clusters per replicate.  Returns ``(f64s, i32s, first_diff)``: the tensors of
+    _copy_back -- [observed sums, bootstrap sums, sign-flip sums, gram, totals] and [observed counts, bootstrap counts]."""
+    import torch
+    from . import ops
+    dev = place.device
+    order = torch.from_numpy(grp["order"]).to(dev)
+    seg_ptr = torch.from_numpy(grp["seg_ptr"]).to(dev)
+    _, gram, totals = ops.placement_cluster_moments(place, labels, seg_ptr, order=order)
+    a = row_main.shape[1]
+    rows = row_main if row_diff is None else torch.cat([row_main, row_diff], dim=1)
+    cs = ops.segment_sums(rows.contiguous(), seg_ptr, order=order)
+    parts = [cs[:, :a]] + ([user_main] if user_main is not None else [])
+    first_diff = sum(p.shape[1] for p in parts)
+    parts += [cs[:, a:]] + ([user_diff] if user_diff is not None else [])
+    tab = torch.cat(parts, dim=1).contiguous()
+    o_s, o_c = ops.resample_sums(tab, 1, seed=seed, mode="observed")
+    b_s, b_c = ops.resample_sums(tab, n_rep, seed=seed, mode="bootstrap")
+    if tab.shape[1] > first_diff:
+        f_s, _ = ops.resample_sums(tab[:, first_diff:], n_rep, seed=seed, mode="signflip")
+    else:
+        f_s = torch.empty((n_rep, 0), dtype=torch.float64, device=dev)
+    return [o_s, b_s, f_s, gram.view(torch.float64), totals.view(torch.float64)], [o_c, b_c], first_diff
+
+
+def _ratio_entry(summ, j):
+    return {"mean": float(summ["mean"][j]), "se": float(summ["se"][j]), "ci": (float(summ["lo"][j]), float(summ["hi"][j]))}
+
+
+def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288, ci=None, cluster=None, n_rep=2000, seed=1):
     """The CTR report of a split as ONE population (an extension: the reference reports none of these but the per-batch means
     of auc / acc / f1).  The split is scored once (logits and sigmoid scores of the same forward calls); everything else is
     reductions over the resident buffers and one copy back per result tensor.  Returns a dict:
@@ -1241,15 +1320,30 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     ``gauc`` do not change under an increasing map.
     ``ci`` (a level such as 0.95; None: the dict and the launches above, nothing more) adds ``"auc_se"`` and ``"auc_ci": (lo,
     hi)``: DeLong's standard error of ``auc`` and the Wald interval around it (ops.delong_interval), from ONE
-    mvin_ctr_placements launch and ONE mvin_placement_moments launch on the sigmoid scores ``auc`` is counted on.  The rows are
-    treated as independent draws; a user's rows are correlated, so the interval is on the narrow side.  A split with fewer than
-    two rows of a class raises ValueError.  (User-clustered variants and intervals for f1 / ece / gauc are not built.)"""
+    mvin_ctr_placements launch and ONE mvin_placement_moments launch on the sigmoid scores ``auc`` is counted on.  A split with
+    fewer than two rows of a class raises ValueError.
+    WHAT THE NUMBERS ASSUME: with ``cluster=None`` the rows are treated as independent draws; a user's rows are correlated, so
+    the interval is on the narrow side.  ``cluster="user"`` (the split's user column) or an integer array of one cluster id per
+    row (a session id, for instance) makes the cluster the sampling unit; it needs ``ci``.  Then ``auc_se`` / ``auc_ci`` are
+    Obuchowski's clustered DeLong numbers (ONE mvin_placement_cluster_moments call, ops.clustered_delong_from_gram) beside
+    ``auc_se_rows`` (the row-independent value) and ``design_effect`` = clustered variance / row variance; ``cluster`` = {"by",
+    "n_clusters", "max_rows"}; ``cluster_ci`` = {"logloss", "brier", "acc": {"mean", "se", "ci"}}: the ratio of the clusters'
+    sums of ctr_row_table's columns (of a z + b) over their rows and its percentile interval over ``n_rep`` bootstrap replicates
+    of ``seed`` that draw whole clusters (ops.segment_sums, ops.resample_sums); and, when the clusters are the users and
+    ``gauc=True``, ``gauc`` gains ``weighted_se``, ``weighted_ci``, ``mean_se``, ``mean_ci`` from the same replicates.  These
+    assume in turn that clusters are independent of one another and that there are enough of them for a normal approximation
+    (a percentile interval): tens of clusters give wide and shaky intervals, which is why ``n_clusters`` is reported.
+    ValueError: any other ``cluster`` value, ``cluster`` without ``ci``, fewer than two clusters (with a used row).  (Intervals for
+    f1 / ece / mce are not built.)"""
     import torch
     from . import ops
     cols = np.asarray(data)
     n = cols.shape[0]
     if n == 0:
         raise ValueError("ctr_report: empty split")
+    grp = _cluster_grouping(cluster, cols, "ctr_report")
+    if grp is not None and ci is None:
+        raise ValueError("ctr_report: cluster= changes the intervals of ci=; pass a level such as ci=0.95")
     a, b = (1.0, 0.0) if calibration is None else (float(calibration[0]), float(calibration[1]))
     edges = ops.calib_edges(n_bins, a, b)                       # refuses a <= 0
     seg_ptr = order = None
@@ -1284,6 +1378,13 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     if ci is not None:
         place, _ = ops.ctr_placements(scores, labels)
         moments = ops.placement_moments(place.view(1, n), labels)
+    cl = None
+    if grp is not None:
+        with_gauc = bool(gauc and grp["users"] and np.array_equal(order, grp["order"]))
+        t = ctr_row_table(logits.to(torch.float64) * a + b, labels)     # (a label other than 0 / 1 is refused below, as ever)
+        rows = torch.cat([t, torch.ones((n, 1), dtype=torch.float64, device=dev)], dim=1)
+        user_main = torch.stack(_gauc_columns(ucounts), dim=1) if with_gauc else None
+        cl = _cluster_launches(place.view(1, n), labels, grp, rows, None, user_main, None, int(n_rep), seed)
     counts = counts.cpu().numpy()
     auc, acc, f1 = ops.ctr_metrics_from_counts(counts)
     cal = ops.ctr_calibration_from_sums(sums.cpu().numpy(), valid.cpu().numpy(), bins.cpu().numpy())
@@ -1306,6 +1407,23 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
                    "conf": cal["bin_conf"][0].tolist()}
     if gauc:
         rep["gauc"] = ops.gauc_from_counts(ucounts.cpu().numpy())
+    if cl is not None:
+        (o_s, b_s, _, gram, totals), (o_c, b_c) = _copy_back(cl[0], cl[1])
+        cd = ops.clustered_delong_from_gram(gram.view(np.int64), totals.view(np.int64))
+        var = float(cd["cov"][0, 0])
+        se, lo, hi = ops.delong_interval(rep["auc"], var, ci)
+        rep["auc_se_rows"], rep["auc_se"], rep["auc_ci"] = rep["auc_se"], se, (lo, hi)
+        rep["design_effect"] = var / float(dl["cov"][0, 0]) if dl["cov"][0, 0] > 0 else float("nan")
+        rep["cluster"] = {"by": grp["by"], "n_clusters": cd["n_clusters"], "max_rows": grp["max_rows"]}
+        num, den = [0, 1, 2], [3, 3, 3]
+        if o_s.shape[-1] > 4:
+            num, den = num + [4, 6], den + [5, 7]
+        summ = ops.resample_summary(o_s.reshape(-1), o_c.reshape(-1), b_s, b_c, level=ci, num=num, den=den)
+        rep["cluster_ci"] = {name: _ratio_entry(summ, q) for q, name in enumerate(CTR_ROW_METRICS)}
+        if len(num) > 3:
+            for j, form in ((3, "weighted"), (4, "mean")):
+                rep["gauc"][form + "_se"] = float(summ["se"][j])
+                rep["gauc"][form + "_ci"] = (float(summ["lo"][j]), float(summ["hi"][j]))
     return rep
 
 
@@ -1339,7 +1457,100 @@ def ctr_compare_table(tables):
     return torch.cat(list(tables) + [tables[a] - tables[b] for a, b in ctr_compare_pairs(len(tables))], dim=1).contiguous()
 
 
-def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288):
+def ctr_cluster_columns(K, with_gauc):
+    """Where compare_ctr(cluster=...) keeps what in its per-cluster resampling table, as a dict of column numbers: ``metric[k][q]``
+    (model k, CTR_ROW_METRICS q), ``rows`` (the clusters' row counts), ``pair[j][q]`` (pair j of ctr_compare_pairs), ``first_diff``
+    (the difference columns, the ones the sign-flip call takes, start here) and, with GAUC, ``gauc[k]`` = (w auc, auc) columns,
+    ``w``, ``one`` and ``gauc_pair[j]`` = (w (auc_a - auc_b), auc_a - auc_b)."""
+    P = len(ctr_compare_pairs(K))
+    lay = {"metric": [[3 * k + q for q in range(3)] for k in range(K)], "rows": 3 * K}
+    at = 3 * K + 1
+    if with_gauc:
+        lay["gauc"] = [(at + 2 * k, at + 2 * k + 1) for k in range(K)]
+        lay["w"], lay["one"] = at + 2 * K, at + 2 * K + 1
+        at += 2 * K + 2
+    lay["first_diff"] = at
+    lay["pair"] = [[at + 3 * j + q for q in range(3)] for j in range(P)]
+    at += 3 * P
+    if with_gauc:
+        lay["gauc_pair"] = [(at + 2 * j, at + 2 * j + 1) for j in range(P)]
+        at += 2 * P
+    lay["width"] = at
+    return lay
+
+
+def _compare_ctr_clustered(grp, place, pcounts, labels, tables, ucounts, moments, n, level, R, seed):
+    """compare_ctr from the placements on: the clustered covariance, the per-cluster table (ctr_cluster_columns), ONE copy back."""
+    import torch
+    from . import ops
+    K = len(tables)
+    pair_list = ctr_compare_pairs(K)
+    with_gauc = len(ucounts) > 0
+    lay = ctr_cluster_columns(K, with_gauc)
+    ones = torch.ones((n, 1), dtype=torch.float64, device=place.device)
+    row_main = torch.cat(list(tables) + [ones], dim=1)
+    row_diff = torch.cat([tables[a] - tables[b] for a, b in pair_list], dim=1)
+    user_main = user_diff = None
+    if with_gauc:
+        g = [_gauc_columns(u) for u in ucounts]
+        user_main = torch.stack([c for wa, _, auc, _ in g for c in (wa, auc)] + [g[0][1], g[0][3]], dim=1)
+        user_diff = torch.stack([c for a, b in pair_list for c in (g[0][1] * (g[a][2] - g[b][2]), g[a][2] - g[b][2])], dim=1)
+    f64s, i32s, first_diff = _cluster_launches(place, labels, grp, row_main, row_diff, user_main, user_diff, R, seed)
+    assert first_diff == lay["first_diff"]
+    as_f64 = lambda x: x.view(torch.float64)                     # noqa: E731  (int64 words through the one packed copy)
+    extra = [as_f64(x) for x in moments] + [as_f64(pcounts)] + [as_f64(u) for u in ucounts]
+    host, (o_c, b_c) = _copy_back(f64s + extra, i32s)
+    o_s, b_s, f_s = host[0].reshape(-1), host[1], host[2]
+    gram, totals, cross, sums, counts, pcounts = (x.view(np.int64) for x in host[3:9])
+    ucounts = [x.view(np.int64) for x in host[9:]]
+    if (pcounts[:, 3] > 0).any():
+        k = int(np.flatnonzero(pcounts[:, 3] > 0)[0])
+        raise ValueError(f"compare_ctr: model {k} gives {int(pcounts[k, 3])} non-finite score(s) on the split")
+    dl = ops.delong_from_moments(cross, sums, counts)
+    cd = ops.clustered_delong_from_gram(gram, totals)
+    ratios = [(c, lay["rows"]) for k in range(K) for c in lay["metric"][k]] + [(c, lay["rows"]) for row in lay["pair"] for c in row]
+    if with_gauc:
+        ratios += [(c, d) for k in range(K) for c, d in zip(lay["gauc"][k], (lay["w"], lay["one"]))]
+        ratios += [(c, d) for j in range(len(pair_list)) for c, d in zip(lay["gauc_pair"][j], (lay["w"], lay["one"]))]
+    summ = ops.resample_summary(o_s, o_c.reshape(-1), b_s, b_c, level=level, num=[c for c, _ in ratios], den=[d for _, d in ratios])
+    at = {r: j for j, r in enumerate(ratios)}
+    p_flip = ops.signflip_pvalue(o_s[first_diff:], f_s)
+    ratio_var = lambda v, vr: float(v / vr) if vr > 0 else float("nan")      # noqa: E731
+    models = []
+    for k in range(K):
+        se, lo, hi = ops.delong_interval(cd["auc"][k], cd["cov"][k, k], level)
+        row = {"auc": float(cd["auc"][k]), "auc_se": se, "auc_ci": (lo, hi), "auc_se_rows": float(np.sqrt(max(dl["cov"][k, k], 0.0))),
+               "design_effect": ratio_var(cd["cov"][k, k], dl["cov"][k, k])}
+        row.update({name: float(summ["mean"][at[(lay["metric"][k][q], lay["rows"])]]) for q, name in enumerate(CTR_ROW_METRICS)})
+        if with_gauc:
+            row["gauc"] = ops.gauc_from_counts(ucounts[k])
+            for c, d, form in zip(lay["gauc"][k], (lay["w"], lay["one"]), ("weighted", "mean")):
+                j = at[(c, d)]
+                row["gauc"][form + "_se"] = float(summ["se"][j])
+                row["gauc"][form + "_ci"] = (float(summ["lo"][j]), float(summ["hi"][j]))
+        models.append(row)
+    from statistics import NormalDist
+    zq = NormalDist().inv_cdf(1.0 - (1.0 - float(level)) / 2.0)
+    tests = [ops.delong_test(cd["auc"], cd["cov"], a, b) for a, b in pair_list]
+    rows_tests = [ops.delong_test(dl["auc"], dl["cov"], a, b) for a, b in pair_list]
+    holm = ops.holm_adjust(np.array([tt["p"] for tt in tests]))
+    diff_entry = lambda c, d: {"diff": float(summ["mean"][at[(c, d)]]), "lo": float(summ["lo"][at[(c, d)]]),      # noqa: E731
+                               "hi": float(summ["hi"][at[(c, d)]]), "p": float(p_flip[c - first_diff])}
+    pairs = {}
+    for j, ((a, b), tt, rt) in enumerate(zip(pair_list, tests, rows_tests)):
+        row = {"auc_diff": tt["diff"], "se": tt["se"], "lo": tt["diff"] - zq * tt["se"], "hi": tt["diff"] + zq * tt["se"], "z": tt["z"],
+               "p": tt["p"], "p_holm": float(holm[j]), "se_rows": rt["se"], "design_effect": ratio_var(tt["se"] ** 2, rt["se"] ** 2)}
+        for q, name in enumerate(CTR_ROW_METRICS):
+            row[name] = diff_entry(lay["pair"][j][q], lay["rows"])
+        if with_gauc:
+            row["gauc_weighted"] = diff_entry(lay["gauc_pair"][j][0], lay["w"])
+            row["gauc_mean"] = diff_entry(lay["gauc_pair"][j][1], lay["one"])
+        pairs[(a, b)] = row
+    return {"models": models, "pairs": pairs, "n": n, "n_pos": cd["n_pos"], "n_neg": cd["n_neg"], "level": float(level), "n_rep": R,
+            "cluster": {"by": grp["by"], "n_clusters": cd["n_clusters"], "max_rows": grp["max_rows"]}}
+
+
+def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288, cluster=None):
     """CTR numbers of 2 to 8 models (``feeders``) on ONE split with their uncertainty, and every pair compared on the same rows.
     Each model is scored once (logits and sigmoid scores of the same forward calls); its placements (ops.ctr_placements on the
     sigmoid scores) go into one [K, n] buffer, ONE ops.placement_moments launch gives DeLong's covariance matrix of the K AUCs
@@ -1352,10 +1563,23 @@ def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288)
         and ``p_holm`` (Holm over the pairs of the call); and for ``logloss``, ``brier``, ``acc`` a dict ``{"diff", "lo", "hi",
         "p"}``: the paired mean difference, its percentile bootstrap interval at ``level`` (``n_rep`` replicates of ``seed``)
         and the two-sided sign-flip p-value over rows.
-    What the numbers assume: the rows are independent draws.  A user's rows are correlated, so intervals are on the narrow
-    side and p-values on the small side; user-clustered variants, and intervals for f1 / ece / gauc, are not built.
+    WHAT THE NUMBERS ASSUME: with ``cluster=None`` the rows are independent draws.  A user's rows are correlated, so intervals
+    are on the narrow side and p-values on the small side.  ``cluster="user"`` (the split's user column) or an integer array of
+    one cluster id per row makes the cluster the sampling unit:
+      * every AUC variance and covariance is Obuchowski's clustered DeLong (ONE mvin_placement_cluster_moments call,
+        ops.clustered_delong_from_gram); ``auc_se`` / ``se`` keep their names and gain ``auc_se_rows`` / ``se_rows`` (the
+        row-independent values of the launch above) and ``design_effect`` = clustered variance / row variance beside them;
+      * the table that is resampled has one row per cluster: the clusters' sums of the per-row columns (ops.segment_sums) and
+        their row counts; a mean becomes the ratio sum / rows, a replicate draws whole clusters, and the sign-flip test flips
+        a cluster's summed difference;
+      * when the clusters are the users (segments of at most ops.CTR_SEG_CAP rows), every model gets ``gauc`` (ctr_report's
+        dict with ``weighted_se``, ``weighted_ci``, ``mean_se``, ``mean_ci``) and every pair ``gauc_weighted`` / ``gauc_mean``
+        = {"diff", "lo", "hi", "p"} from the same replicates;
+      * the dict gains ``cluster`` = {"by", "n_clusters", "max_rows"}.
+    These assume in turn that clusters are independent of one another and numerous enough for a normal approximation: tens of
+    clusters give wide and shaky intervals, which is why ``n_clusters`` is reported.  Intervals for f1 / ece / mce are not built.
     ValueError: fewer than 2 or more than 8 feeders, a label other than 0 / 1, fewer than two rows of a class, a non-finite
-    score."""
+    score, a ``cluster`` that is none of the above or gives fewer than two clusters."""
     import torch
     from . import ops
     feeders = list(feeders)
@@ -1372,15 +1596,26 @@ def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288)
     if n_pos < 2 or n_neg < 2:
         raise ValueError(f"compare_ctr: {n_pos} positive and {n_neg} negative rows: DeLong's variance needs at least two rows of each class")
     R = int(n_rep)
+    grp = _cluster_grouping(cluster, cols, "compare_ctr")
+    with_gauc = grp is not None and grp["users"]
+    if with_gauc and grp["max_rows"] > ops.CTR_SEG_CAP:
+        raise ValueError(f"compare_ctr: a user has {grp['max_rows']} rows in the split; per-user AUC takes at most {ops.CTR_SEG_CAP}")
     dev = feeders[0].model.device
     place = torch.empty((K, n), dtype=torch.int64, device=dev)
     pcounts = torch.empty((K, 4), dtype=torch.int64, device=dev)
-    tables, labels = [], None
+    tables, labels, ucounts = [], None, []
+    if with_gauc:
+        od, ptr = torch.from_numpy(grp["order"].astype(np.int64)).to(dev), torch.from_numpy(grp["seg_ptr"]).to(dev)
     for k, f in enumerate(feeders):
         logits, scores, labels = _score_split_both(f, data, max_pairs)
         ops.ctr_placements(scores, labels, out=(place[k], pcounts[k]))
         tables.append(ctr_row_table(logits, labels))
+        if with_gauc:
+            ucounts.append(ops.ctr_counts_segments(logits.index_select(0, od), labels.index_select(0, od), ptr, threshold=0.0,
+                                                   max_len=grp["max_rows"])[0])
     cross, sums, counts = ops.placement_moments(place, labels)
+    if grp is not None:
+        return _compare_ctr_clustered(grp, place, pcounts, labels, tables, ucounts, (cross, sums, counts), n, level, R, seed)
     t = ctr_compare_table(tables)
     M = 3 * K
     o_s, o_c = ops.resample_sums(t, 1, seed=seed, mode="observed")

@@ -707,6 +707,175 @@ def delong_test(auc, cov, a, b):
     return {"diff": diff, "se": se, "z": z, "p": p}
 
 
+def cluster_csr(ids):
+    """The stable grouping of rows by an integer id on the host: ``(order int32 [n], seg_ptr int64 [I + 1], cluster_ids [I])`` with
+    ``ids[order]`` ascending, equal ids in row order, and cluster i = positions ``seg_ptr[i]:seg_ptr[i+1]`` of ``order`` -- what
+    placement_cluster_moments, segment_sums and (as user segments) ctr_counts_segments take.  ``ids``: a one-dimensional integer
+    array of fewer than 2^31 rows; anything else raises ValueError."""
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or ids.dtype.kind not in "iu":
+        raise ValueError(f"cluster ids: expected a one-dimensional integer array, got {ids.dtype} {ids.shape}")
+    n = ids.size
+    if n >= 1 << 31:
+        raise ValueError(f"n={n}: expected fewer than 2^31 rows")
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(1, np.int64), ids[:0].copy()
+    lo, hi = int(ids.min()), int(ids.max())
+    if hi - lo < (1 << 31):                                     # the stable argsort as ONE sort of (id, row) keys
+        order = np.sort((ids.astype(np.int64) - lo) * n + np.arange(n, dtype=np.int64)) % n
+    else:
+        order = np.argsort(ids, kind="stable")
+    s = ids[order]
+    first = np.flatnonzero(np.concatenate(([True], s[1:] != s[:-1])))
+    seg_ptr = np.concatenate((first, [n])).astype(np.int64)
+    return order.astype(np.int32), seg_ptr, s[first]
+
+
+def _cluster_grouping(seg_ptr, order, n, name):
+    """What placement_cluster_moments and segment_sums check alike: seg_ptr int64 [I + 1] and order int32 [n] or None."""
+    _chk(seg_ptr, torch.int64, "seg_ptr")
+    if seg_ptr is None or seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise ValueError(f"{name}: seg_ptr: expected a contiguous int64 [I + 1] tensor")
+    if order is not None:
+        _chk(order, I32, "order")
+        if order.dim() != 1 or order.numel() != n:
+            raise ValueError(f"{name}: order {tuple(order.shape)}: expected a contiguous int32 [{n}] tensor or None")
+    I = seg_ptr.numel() - 1
+    if I >= 1 << 31 or n >= 1 << 31:
+        raise ValueError(f"{name}: n={n} clusters={I}: expected fewer than 2^31 of each")
+    return I
+
+
+def placement_cluster_moments(place, labels, seg_ptr, order=None, max_groups=0, out=None):
+    """mvin_placement_cluster_moments: per-cluster sums of K models' placements and their Gram matrix, exact.  ``place`` int64
+    [K, n] and ``labels`` int32 [n] as placement_moments takes them (and a row is used under its rule); ``seg_ptr`` int64
+    [I + 1] and ``order`` int32 [n] or None group the rows (cluster_csr; a malformed grouping is clamped, include/mvin_hip.h).
+    Returns device tensors ``(csum int64 [I, 2 + 2K], gram int64 [K + 2, K + 2, 2, 4], totals int64 [4 + 2K])``: per cluster
+    (m_i, n_i, A_i^1..K, B_i^1..K); the limb sums of G = sum_i z_i z_i^T, z_i = (m_i, n_i, A_i - B_i) (each word below 2^63, so
+    its int64 reading is the word; clustered_delong_from_gram joins them); and (I with a used row, m, n, s1^1..K, s0^1..K, bad).
+    ``max_groups``: 0 automatic, else a cap on the workgroups per launch; it changes no bit.  ``out``: the same three to write
+    into.  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(place, torch.Tensor) or place.dim() != 2:
+        raise ValueError("place: expected a [K, n] tensor")
+    for t, name, dt in ((place, "place", torch.int64), (labels, "labels", I32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.MvinHipError(f"{name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected {dt}, got {t.dtype}")
+    K, n = place.shape
+    if not 1 <= K <= placement_moments_max_models():
+        raise ValueError(f"{K} models: mvin_placement_cluster_moments takes 1 .. {placement_moments_max_models()}")
+    if labels.dim() != 1 or labels.numel() != n or not labels.is_contiguous():
+        raise ValueError(f"labels {tuple(labels.shape)}: expected a contiguous [{n}] tensor")
+    ld = place.stride(0) if K > 1 else max(n, 1)
+    if n and ((n > 1 and place.stride(1) != 1) or ld < n):
+        raise ValueError("place: rows must be dense (stride 1 along the rows of the split, models at least n apart)")
+    max_groups = int(max_groups)
+    if max_groups < 0:
+        raise ValueError(f"max_groups={max_groups}: expected a value >= 0")
+    I = _cluster_grouping(seg_ptr, order, n, "placement_cluster_moments")
+    dev = place.device
+    if out is None:
+        out = (torch.empty((I, 2 + 2 * K), dtype=torch.int64, device=dev), torch.empty((K + 2, K + 2, 2, 4), dtype=torch.int64, device=dev),
+               torch.empty((4 + 2 * K,), dtype=torch.int64, device=dev))
+    if len(out) != 3:
+        raise ValueError("out: expected (csum, gram, totals)")
+    csum, gram, totals = (_chk(t, torch.int64, "out " + name) for t, name in zip(out, ("csum", "gram", "totals")))
+    if (csum is None or gram is None or totals is None or tuple(csum.shape) != (I, 2 + 2 * K) or tuple(gram.shape) != (K + 2, K + 2, 2, 4)
+            or tuple(totals.shape) != (4 + 2 * K,)):
+        raise ValueError(f"out: expected int64 csum [{I}, {2 + 2 * K}], gram [{K + 2}, {K + 2}, 2, 4] and totals [{4 + 2 * K}]")
+    _lib.check(lib.mvin_placement_cluster_moments(_p(place) if n else None, ld, K, _p(labels) if n else None, n, _p(order) if n else None,
+                                                  _p(seg_ptr), I, max_groups, _p(csum) if I else None, _p(gram), _p(totals), _stream()),
+               "mvin_placement_cluster_moments")
+    return csum, gram, totals
+
+
+def clustered_delong_from_gram(gram, totals):
+    """The AUCs and their cluster-robust covariance matrix (Obuchowski 1997) from placement_cluster_moments' integers (host arrays
+    [K + 2, K + 2, 2, 4] and [4 + 2K]), in exact arithmetic until the last step.  With I clusters, m positives, n negatives,
+    G the joined Gram matrix and c_a = (-n s1^a, m s0^a, m n unit_a):
+      sum_i e_i^a e_i^b = c_a^T G c_b,   cov[a, b] = I c_a^T G c_b / ((I - 1) 4 m^4 n^4)  -- a Fraction, rounded to float64 once;
+      auc[a] = float64(s1^a) / (2.0 * float64(m) * float64(n)) -- ctr_metrics_from_counts' operations, so its bits.
+    e_i^a = m n D_i^a - n m_i s1^a + m n_i s0^a is cluster i's share of model a's AUC deviation (sum_i e_i = 0): the cluster, not
+    the row, is the unit.  Returns ``{"auc", "cov", "n_pos", "n_neg", "n_clusters"}``.  ValueError when ``bad > 0``, when a class
+    has no row, and with fewer than two clusters."""
+    from fractions import Fraction
+    g = np.asarray(gram)
+    t = np.asarray(totals).reshape(-1)
+    if g.ndim != 4 or g.shape[0] != g.shape[1] or g.shape[0] < 3 or g.shape[2:] != (2, 4) or t.size != 2 * g.shape[0]:
+        raise ValueError(f"expected gram [K + 2, K + 2, 2, 4] and totals [4 + 2K], got {g.shape} and {t.shape}")
+    K = g.shape[0] - 2
+    I, m, n, bad = int(t[0]), int(t[1]), int(t[2]), int(t[3 + 2 * K])
+    if bad > 0:
+        raise ValueError(f"{bad} row(s) with a non-finite score (a placement of -1)")
+    if m < 1 or n < 1:
+        raise ValueError(f"{m} positive and {n} negative rows: the AUC needs a row of each class")
+    if I < 2:
+        raise ValueError(f"{I} cluster(s) with a used row: the clustered variance needs at least two")
+    word = lambda v: int(v) & 0xFFFFFFFFFFFFFFFF               # noqa: E731  (an unsigned word read as int64)
+    G = [[sum((word(g[p, q, 0, k]) - word(g[p, q, 1, k])) << (32 * k) for k in range(4)) for q in range(K + 2)] for p in range(K + 2)]
+    s1 = [int(v) for v in t[3:3 + K]]
+    s0 = [int(v) for v in t[3 + K:3 + 2 * K]]
+    c = [[-n * s1[a], m * s0[a]] + [m * n if b == a else 0 for b in range(K)] for a in range(K)]
+    Gc = [[sum(G[p][q] * c[b][q] for q in range(K + 2)) for p in range(K + 2)] for b in range(K)]
+    den = (I - 1) * 4 * m ** 4 * n ** 4
+    cov = np.empty((K, K), dtype=np.float64)
+    for a in range(K):
+        for b in range(K):
+            f = Fraction(I * sum(c[a][p] * Gc[b][p] for p in range(K + 2)), den)
+            cov[a, b] = f.numerator / f.denominator            # int / int: correctly rounded
+    auc = np.array([np.float64(s1[a]) / (2.0 * np.float64(m) * np.float64(n)) for a in range(K)], dtype=np.float64)
+    return {"auc": auc, "cov": cov, "n_pos": m, "n_neg": n, "n_clusters": I}
+
+
+def segment_sums_max_cols():
+    """mvin_segment_sums_max_cols: the columns one mvin_segment_sums_f64 call takes (1024)."""
+    return int(_lib.load().mvin_segment_sums_max_cols())
+
+
+def segment_sums(vals, seg_ptr, order=None, out=None):
+    """mvin_segment_sums_f64: per-cluster column sums of ``vals`` (f64 [n, M] on the device, dense rows that may be strided) for
+    the grouping ``seg_ptr`` int64 [I + 1] / ``order`` int32 [n] or None (cluster_csr).  Returns f64 [I, M].  One fixed summation
+    order per cell (include/mvin_hip.h: 64 interleaved partial sums in row order, folded 32 .. 1), so a cell's bits depend on its
+    cluster's rows and its column only; an empty cluster gives +0.0; NaN and infinities propagate.  A table wider than
+    segment_sums_max_cols() goes through one launch per block of columns, which changes no bit.  ``out``: f64 [I, M] to write into.
+    Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(vals, torch.Tensor) or vals.dim() != 2:
+        raise ValueError("vals: expected a [n, M] tensor")
+    if vals.dtype != torch.float64:
+        raise TypeError(f"vals: expected torch.float64, got {vals.dtype}")
+    if not vals.is_cuda:
+        raise _lib.MvinHipError("vals: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+    n, M = vals.shape
+    ld = vals.stride(0) if n > 1 else max(M, 1)
+    if n and ((M > 1 and vals.stride(1) != 1) or ld < M):
+        raise ValueError("vals: rows must be dense (stride 1 along the columns, rows at least M doubles apart)")
+    I = _cluster_grouping(seg_ptr, order, n, "segment_sums")
+    cap = segment_sums_max_cols()
+    if out is None:
+        out = torch.empty((I, M), dtype=torch.float64, device=vals.device)
+    if _chk(out, torch.float64, "out") is None or tuple(out.shape) != (I, M):
+        raise ValueError(f"out: expected f64 [{I}, {M}]")
+    if I == 0 or M == 0:
+        return out
+
+    def launch(c0, w, dst):
+        _lib.check(lib.mvin_segment_sums_f64(_p(vals, c0) if n else None, n, w, ld, _p(order) if n else None, _p(seg_ptr), I, _p(dst),
+                                             _stream()), "mvin_segment_sums_f64")
+
+    if M <= cap:
+        launch(0, M, out)
+        return out
+    for c0 in range(0, M, cap):
+        w = min(cap, M - c0)
+        part = torch.empty((I, w), dtype=torch.float64, device=vals.device)
+        launch(c0, w, part)
+        out[:, c0:c0 + w].copy_(part)
+    return out
+
+
 CTR_CALIB_MAX_BINS = 64      # MVIN_CTR_CALIB_MAX_BINS
 CTR_CALIB_SUMS = ("loss", "r2", "r", "rz", "w", "wz", "wz2", "p")
 CTR_MASS_ONE = float(1 << 40)          # the confidence mass of p = 1 (mvin_ctr_calib: floor(p * 2^40) per pair)
