@@ -1075,6 +1075,62 @@ MVIN_API int mvin_placement_moments(const int64_t* place /* [K, n], rows ld apar
                                     const int32_t* labels, int64_t n, int max_groups, uint64_t* cross /* [2, K, K, 2] */,
                                     int64_t* sums /* [2, K] */, int64_t* counts /* [3] */, void* stream);
 
+/* ---- CTR operating points: what the precision-recall summary, the ROC / PR curves and a threshold tuned on one split are made
+ * of, as integers (an opt-in extension; the reference reports acc and F1 at the fixed cut 0.5 only) --
+ * All three calls share mvin_ctr_placements' definitions: a row is VALID when its score is finite and its label is 0 or 1;
+ * image = the order-preserving image of the score (-0.0 equals +0.0, denormals are distinct numbers); m / n0 = the valid
+ * positives / negatives.  scores [n] f32 and labels [n] int32 are never written.
+ *
+ * mvin_ctr_tails: tails [n, 2] int32.  For a valid row i,
+ *     tails[i][0] = #{valid j: label_j == 1, image_j >= image_i}   (tp at the cut "row i's own score"; counts row i itself),
+ *     tails[i][1] = #{valid j: label_j == 0, image_j >= image_i}   (fp at that cut);
+ *   an invalid row gets (-1, -1).  counts [3] = m, n0, bad (the invalid rows).  Every number is an integer, independent of the
+ *   launch shape and the same on every launch.  n <= MVIN_CTR_SEG_CAP: one workgroup, no workspace; longer n take
+ *   mvin_ctr_placements' tile sorts and merges on `stream` through `ws` (mvin_ctr_tails_ws_bytes bytes, may be NULL when that
+ *   is 0) and one search launch.  Limit: 1 <= n < 2^31.
+ *
+ * mvin_ctr_operating_points: tails as mvin_ctr_tails wrote them for the same scores and labels (validity is decided from the
+ * scores and labels again; a valid row's pair is taken as it stands).  THE CANDIDATES are every valid row's cut (its score, tp,
+ * fp) and the empty cut (+inf, 0, 0).  Three criteria, each maximised by exact integer comparison:
+ *     [0] F1:       a beats b iff tp_a * (tp_b + fp_b + m) > tp_b * (tp_a + fp_a + m), in unsigned 64-bit (both < 2^31 * 2^33);
+ *     [1] accuracy: tp - fp;
+ *     [2] Youden:   tp * n0 - fp * m, signed 64-bit.
+ *   Equal values: the larger image wins, so the empty cut wins a tie with anything (and is the answer when m == 0).
+ *   thr [3] f32 = the winning cuts (a zero score comes back as +0.0, the empty cut as +inf); cells [3, 2] int64 = their (tp, fp).
+ *   The comparisons are on integers and the order is total, so no order of the reduction changes a bit: the same bytes for every
+ *   `max_groups` (0 = automatic, a positive value caps the workgroups of the row launches).  The workgroups' bests go through
+ *   `ws` into a one-workgroup last launch; no atomics on records.
+ *   ap_sum [1] f64 = the sum over the valid positives i of (double)tp_i / (double)(tp_i + fp_i), in ONE order that is a function
+ *   of n alone.  THE RULE: the rows are cut into chunks of MVIN_CTR_SEG_CAP consecutive rows.  For a chunk, 64 partial sums p_0
+ *   .. p_63 start at +0.0; for its rows r = 0, 1, .. ascending (r counted from the chunk's first row), a valid positive adds its
+ *   term to p_(r mod 64) and any other row adds nothing; then for h = 32, 16, 8, 4, 2, 1: p_l = p_l + p_(l+h) for l < h, and the
+ *   chunk's sum is p_0 (mvin_segment_sums_f64's fold).  The chunk sums are combined by the same rule over the chunk index: q_0
+ *   .. q_63 start at +0.0, chunk c adds its sum to q_(c mod 64) in ascending c, the same fold, ap_sum = q_0.  Each term is one IEEE
+ *   division and everything else is an add, so there is nothing to contract; no floating-point atomics.  The average precision
+ *   (sklearn's average_precision_score: sum (R_k - R_(k-1)) P_k over the distinct thresholds) is ap_sum / m.
+ *   `ws`: mvin_ctr_operating_points_ws_bytes(n) bytes, never NULL.  Limit: 1 <= n < 2^31.
+ *
+ * mvin_ctr_threshold_counts: out [n_thresholds, 2] int64, out[t] = (tp, fp) = the valid positives / negatives with
+ *   score >= thresholds[t] compared in f32 (so -0.0 equals +0.0).  The thresholds come in any order, duplicates allowed; -inf
+ *   gives (m, n0), +inf gives (0, 0) as no valid score is infinite, and a NaN threshold gives (0, 0).  counts [3] = m, n0, bad.
+ *   out and counts are zeroed by the call; integers only, merged by 64-bit integer atomics: the same bits for every
+ *   `max_groups` (0 = automatic, a positive value caps the workgroups over the rows).  No workspace.
+ *   Limits: 0 <= n < 2^31 (n == 0 gives zeros); 1 <= n_thresholds <= mvin_ctr_threshold_counts_max() (4096).
+ *
+ * Errors (< 0, nothing launched): -2 for sizes outside the limits, max_groups < 0, or tails / counts / cells / ap_sum / out /
+ * ws not 8-byte aligned; -1 for a null required pointer or a null ws that is needed. */
+MVIN_API int64_t mvin_ctr_tails_ws_bytes(int64_t n);                            /* < 0: invalid n */
+MVIN_API int mvin_ctr_tails(const float* scores, const int32_t* labels, int64_t n, void* ws, int32_t* tails /* [n, 2] */,
+                            int64_t* counts /* [3] */, void* stream);
+MVIN_API int64_t mvin_ctr_operating_points_ws_bytes(int64_t n);                 /* < 0: invalid n */
+MVIN_API int mvin_ctr_operating_points(const int32_t* tails /* [n, 2] */, const float* scores, const int32_t* labels, int64_t n,
+                                       void* ws, int max_groups, float* thr /* [3] */, int64_t* cells /* [3, 2] */,
+                                       double* ap_sum /* [1] */, void* stream);
+MVIN_API int mvin_ctr_threshold_counts_max(void);
+MVIN_API int mvin_ctr_threshold_counts(const float* scores, const int32_t* labels, int64_t n, const float* thresholds,
+                                       int n_thresholds, int max_groups, int64_t* out /* [n_thresholds, 2] */,
+                                       int64_t* counts /* [3] */, void* stream);
+
 /* ---- user-clustered CTR significance: what the clustered DeLong variance (Obuchowski 1997: the cluster, not the row, is the
  * sampling unit) and the cluster bootstrap are made of (an opt-in extension) --
  * Both calls take a grouping of the n rows into n_clusters clusters: seg_ptr [n_clusters + 1] int64 and `order` int32 [n] or NULL.

@@ -311,6 +311,56 @@ int mvin_ctr_placements(const float* scores, const int32_t* labels, int64_t n, v
     return hip_result(mvin::launch_ctr_placements(scores, labels, n, ws, place, counts, (hipStream_t)stream), who);
 }
 
+static bool misaligned8(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 7) != 0;
+}
+
+int64_t mvin_ctr_tails_ws_bytes(int64_t n) {
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "mvin_ctr_tails_ws_bytes: n=%lld (1 <= n < 2^31)", (long long)n);
+    return mvin::ctr_tails_ws_bytes(n);
+}
+
+int mvin_ctr_tails(const float* scores, const int32_t* labels, int64_t n, void* ws, int32_t* tails, int64_t* counts, void* stream) {
+    const char* who = "mvin_ctr_tails";
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "%s: n=%lld (1 <= n < 2^31)", who, (long long)n);
+    if (!scores || !labels || !tails || !counts) return fail(-1, "%s: null scores / labels / tails / counts", who);
+    if (!ws && mvin::ctr_tails_ws_bytes(n) > 0) return fail(-1, "%s: null ws (n=%lld needs mvin_ctr_tails_ws_bytes)", who, (long long)n);
+    if (misaligned8(tails, counts, ws)) return fail(-2, "%s: tails / counts / ws must be 8-byte aligned", who);
+    return hip_result(mvin::launch_ctr_tails(scores, labels, n, ws, tails, counts, (hipStream_t)stream), who);
+}
+
+int64_t mvin_ctr_operating_points_ws_bytes(int64_t n) {
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "mvin_ctr_operating_points_ws_bytes: n=%lld (1 <= n < 2^31)", (long long)n);
+    return mvin::ctr_operating_points_ws_bytes(n);
+}
+
+int mvin_ctr_operating_points(const int32_t* tails, const float* scores, const int32_t* labels, int64_t n, void* ws, int max_groups,
+                              float* thr, int64_t* cells, double* ap_sum, void* stream) {
+    const char* who = "mvin_ctr_operating_points";
+    if (n < 1 || n >= (int64_t(1) << 31) || max_groups < 0)
+        return fail(-2, "%s: n=%lld max_groups=%d (1 <= n < 2^31; max_groups >= 0)", who, (long long)n, max_groups);
+    if (!tails || !scores || !labels || !ws || !thr || !cells || !ap_sum)
+        return fail(-1, "%s: null tails / scores / labels / ws / thr / cells / ap_sum", who);
+    if (misaligned8(tails, ws, cells, ap_sum)) return fail(-2, "%s: tails / ws / cells / ap_sum must be 8-byte aligned", who);
+    return hip_result(mvin::launch_ctr_operating_points(tails, scores, labels, n, ws, max_groups, thr, cells, ap_sum, (hipStream_t)stream),
+                      who);
+}
+
+int mvin_ctr_threshold_counts_max(void) { return mvin::ctr_threshold_counts_max(); }
+
+int mvin_ctr_threshold_counts(const float* scores, const int32_t* labels, int64_t n, const float* thresholds, int n_thresholds,
+                              int max_groups, int64_t* out, int64_t* counts, void* stream) {
+    const char* who = "mvin_ctr_threshold_counts";
+    if (n < 0 || n >= (int64_t(1) << 31) || n_thresholds < 1 || n_thresholds > mvin::ctr_threshold_counts_max() || max_groups < 0)
+        return fail(-2, "%s: n=%lld n_thresholds=%d max_groups=%d (0 <= n < 2^31; 1 <= n_thresholds <= %d; max_groups >= 0)", who,
+                    (long long)n, n_thresholds, max_groups, mvin::ctr_threshold_counts_max());
+    if (!thresholds || !out || !counts || (n > 0 && (!scores || !labels)))
+        return fail(-1, "%s: null scores / labels / thresholds / out / counts", who);
+    if (misaligned8(out, counts)) return fail(-2, "%s: out / counts must be 8-byte aligned", who);
+    return hip_result(mvin::launch_ctr_threshold_counts(scores, labels, n, thresholds, n_thresholds, max_groups, out, counts,
+                                                        (hipStream_t)stream), who);
+}
+
 int mvin_placement_moments_max_models(void) { return mvin::placement_moments_max_models(); }
 
 int mvin_placement_moments(const int64_t* place, int64_t ld, int n_models, const int32_t* labels, int64_t n, int max_groups,

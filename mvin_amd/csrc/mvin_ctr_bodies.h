@@ -47,15 +47,15 @@ __device__ __forceinline__ void ctr_load(const float* srow, const int32_t* lrow,
     }
 }
 
-// ascending bitonic sort of keys[0, P), P a power of two
-template <int NT>
-__device__ __forceinline__ void ctr_sort(unsigned* keys, int P) {
+// ascending bitonic sort of keys[0, P), P a power of two (K: unsigned, or the 64-bit (image, index) keys of mvin_ctr_curve.hip)
+template <int NT, typename K>
+__device__ __forceinline__ void ctr_sort(K* keys, int P) {
     __syncthreads();
     for (int size = 2; size <= P; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             for (int t = threadIdx.x; t < P / 2; t += NT) {
                 const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const unsigned x = keys[i], y = keys[j];
+                const K x = keys[i], y = keys[j];
                 const bool asc = (i & size) == 0;
                 if ((x > y) == asc) {
                     keys[i] = y;

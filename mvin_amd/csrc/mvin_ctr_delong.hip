@@ -35,6 +35,7 @@ struct PlaceArgs {
     int64_t ntiles;
     long long* place;
     unsigned long long* counts;   // n_pos, n_neg, u2, bad
+    int bad_slot;                 // where the tile sorts add the invalid rows: 3 here, 2 for mvin_ctr_tails' (m, n0, bad)
 };
 
 // n <= kCtrSegCap: everything in one workgroup
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(NT) void ctr_place_tile_kernel(PlaceArgs a) {
     for (int i = threadIdx.x; i < (int)kCtrSegCap; i += NT) dst[i] = keys[i];
     unsigned long long v[6] = {cls == 1 ? n_cls : 0u, cls == 0 ? n_cls : 0u, 0ull, cls == 0 ? n_bad : 0u, 0ull, 0ull};
     const unsigned long long s = ctr_block_sum<NT>(v, red);
-    if (threadIdx.x < 4 && s != 0) atomicAdd(&a.counts[threadIdx.x], s);
+    if (threadIdx.x < 4 && s != 0) atomicAdd(&a.counts[threadIdx.x == 3 ? a.bad_slot : threadIdx.x], s);
 }
 
 // long path, step 2: runs of w sorted keys merged pairwise over the T = ntiles * kCtrSegCap keys of class blockIdx.y, from its
@@ -143,6 +144,39 @@ static hipError_t place_launch(K kern, int64_t groups, int ny, int nt, size_t ld
     return hipSuccess;
 }
 
+// long path, steps 1 and 2, for mvin_ctr_placements and mvin_ctr_tails (mvin_ctr_curve.hip) alike: zeroes counts[0 .. bad_slot],
+// sorts the tiles of both classes into `ws` and merges them (1 + ceil(log2(ntiles)) launches).  Afterwards counts holds the
+// classes' valid rows in [0] (label 1) and [1] (label 0) and the invalid rows in [bad_slot], and class c's sorted images (then
+// sentinels) are the T = ntiles * kCtrSegCap keys at ws + (c * 2 + *cur) * T.
+hipError_t ctr_sort_classes(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* counts, int bad_slot, int* cur,
+                            hipStream_t st) {
+    PlaceArgs a;
+    a.scores = scores;
+    a.labels = labels;
+    a.n = n;
+    a.group0 = 0;
+    a.P = (int)kCtrSegCap;
+    a.ws = reinterpret_cast<unsigned*>(ws);
+    a.cur = 0;
+    a.ntiles = place_ntiles(n);
+    a.place = nullptr;
+    a.counts = reinterpret_cast<unsigned long long*>(counts);
+    a.bad_slot = bad_slot;
+    const int64_t T = a.ntiles * kCtrSegCap;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)(bad_slot + 1) * sizeof(int64_t), st);
+    if (e != hipSuccess) return e;
+    e = place_launch(ctr_place_tile_kernel<256>, a.ntiles, 2, 256, (size_t)kCtrSegCap * sizeof(unsigned), st, a);
+    if (e != hipSuccess) return e;
+    const unsigned grid = (unsigned)min((T + 255) / 256, (int64_t)65536);
+    for (int64_t w = kCtrSegCap; w < T; w *= 2, a.cur ^= 1) {
+        ctr_place_merge_kernel<<<dim3(grid, 2), dim3(256), 0, st>>>(a.ws, a.cur, T, w);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    *cur = a.cur;
+    return hipSuccess;
+}
+
 // 1 <= n < 2^31, non-null pointers, ws where ctr_placements_ws_bytes(n) > 0 (checked by the caller, mvin_abi_eval.hip)
 hipError_t launch_ctr_placements(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* place, int64_t* counts,
                                  hipStream_t st) {
@@ -156,6 +190,7 @@ hipError_t launch_ctr_placements(const float* scores, const int32_t* labels, int
     a.ntiles = 0;
     a.place = reinterpret_cast<long long*>(place);
     a.counts = reinterpret_cast<unsigned long long*>(counts);
+    a.bad_slot = 3;
     if (n <= kCtrSegCap) {
         int P = 1;
         while (P < n) P <<= 1;
@@ -164,19 +199,10 @@ hipError_t launch_ctr_placements(const float* scores, const int32_t* labels, int
         if (P <= 1024) return place_launch(ctr_place_seg_kernel<64>, 1, 1, 64, lds, st, a);
         return place_launch(ctr_place_seg_kernel<256>, 1, 1, 256, lds, st, a);
     }
-    const int64_t ntiles = place_ntiles(n), T = ntiles * kCtrSegCap;
     a.P = (int)kCtrSegCap;
-    a.ntiles = ntiles;
-    hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), st);
+    a.ntiles = place_ntiles(n);
+    const hipError_t e = ctr_sort_classes(scores, labels, n, ws, counts, 3, &a.cur, st);
     if (e != hipSuccess) return e;
-    e = place_launch(ctr_place_tile_kernel<256>, ntiles, 2, 256, (size_t)kCtrSegCap * sizeof(unsigned), st, a);
-    if (e != hipSuccess) return e;
-    const unsigned grid = (unsigned)min((T + 255) / 256, (int64_t)65536);
-    for (int64_t w = kCtrSegCap; w < T; w *= 2, a.cur ^= 1) {
-        ctr_place_merge_kernel<<<dim3(grid, 2), dim3(256), 0, st>>>(a.ws, a.cur, T, w);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
     const int64_t chunks = (n + kPlaceSearchPerThread * 256 - 1) / (kPlaceSearchPerThread * 256);
     return place_launch(ctr_place_search_kernel<256>, chunks, 1, 256, 0, st, a);
 }

@@ -501,6 +501,8 @@ hipError_t launch_ctr_counts_segments(const float* scores, const int32_t* labels
 int64_t ctr_placements_ws_bytes(int64_t n);                    // per-row placements and their exact moments (mvin_ctr_delong.hip)
 hipError_t launch_ctr_placements(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* place, int64_t* counts,
                                  hipStream_t st);
+hipError_t ctr_sort_classes(const float* scores, const int32_t* labels, int64_t n, void* ws, int64_t* counts, int bad_slot, int* cur,
+                            hipStream_t st);                   // the long path's tile sorts and merges, shared with mvin_ctr_tails
 int placement_moments_max_models();
 hipError_t launch_placement_moments(const int64_t* place, int64_t ld, int K, const int32_t* labels, int64_t n, int max_groups,
                                     uint64_t* cross, int64_t* sums, int64_t* counts, hipStream_t st);
@@ -511,6 +513,15 @@ hipError_t launch_placement_cluster_moments(const int64_t* place, int64_t ld, in
 int segment_sums_max_cols();
 hipError_t launch_segment_sums_f64(const double* vals, int64_t n, int M, int64_t ld, const int32_t* order, const int64_t* seg_ptr,
                                    int64_t n_clusters, double* out, hipStream_t st);
+int64_t ctr_tails_ws_bytes(int64_t n);                         // tail counts, operating points, threshold counts (mvin_ctr_curve.hip)
+hipError_t launch_ctr_tails(const float* scores, const int32_t* labels, int64_t n, void* ws, int32_t* tails, int64_t* counts,
+                            hipStream_t st);
+int64_t ctr_operating_points_ws_bytes(int64_t n);
+hipError_t launch_ctr_operating_points(const int32_t* tails, const float* scores, const int32_t* labels, int64_t n, void* ws,
+                                       int max_groups, float* thr, int64_t* cells, double* ap_sum, hipStream_t st);
+int ctr_threshold_counts_max();
+hipError_t launch_ctr_threshold_counts(const float* scores, const int32_t* labels, int64_t n, const float* thresholds, int T,
+                                       int max_groups, int64_t* out, int64_t* counts, hipStream_t st);
 int64_t ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len);    // calibration sums and reliability bins (mvin_ctr_calib.hip)
 hipError_t launch_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b,
                             double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums,

@@ -1303,7 +1303,128 @@ def _ratio_entry(summ, j):
     return {"mean": float(summ["mean"][j]), "se": float(summ["se"][j]), "ci": (float(summ["lo"][j]), float(summ["hi"][j]))}
 
 
-def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288, ci=None, cluster=None, n_rep=2000, seed=1):
+OperatingPoint = collections.namedtuple("OperatingPoint", "criterion threshold tp fp n_pos n_neg value")
+OperatingPoint.__doc__ = """A cut on the LOGIT of a split (pick_threshold): predict positive when ``z >= threshold`` compared in f32.
+``criterion`` ("f1" / "acc" / "youden") is what the cut maximises on that split, ``value`` its maximum, ``tp`` / ``fp`` the
+cut's confusion cells among the split's ``n_pos`` / ``n_neg`` valid rows.  ``threshold`` is +inf when predicting nothing wins."""
+
+
+def _check_criterion(criterion, who):
+    from . import ops
+    if not isinstance(criterion, str) or criterion not in ops.OPERATING_CRITERIA:
+        raise ValueError(f"{who}: criterion={criterion!r}: expected one of {ops.OPERATING_CRITERIA}")
+    return ops.OPERATING_CRITERIA.index(criterion)
+
+
+def _curve_thresholds(thresholds, points, who):
+    """The logit thresholds of a curve as float32 [T]: ``thresholds`` as given (a one-dimensional array of real numbers, no
+    NaN), or with None ``logit(j / points)``, j = 1 .. points - 1.  ValueError for anything else."""
+    if thresholds is None:
+        if isinstance(points, (bool, np.bool_)) or not isinstance(points, (int, np.integer)) or points < 2:
+            raise ValueError(f"{who}: points={points!r}: expected an integer >= 2")
+        p = np.arange(1, int(points), dtype=np.float64) / np.float64(points)
+        return np.log(p / (1.0 - p)).astype(np.float32)
+    thr = np.asarray(thresholds)
+    if thr.ndim != 1 or thr.size < 1 or thr.dtype.kind not in "fiu" or np.isnan(thr.astype(np.float64)).any():
+        raise ValueError(f"{who}: thresholds: expected a one-dimensional array of at least one logit threshold, none NaN")
+    return np.ascontiguousarray(thr, dtype=np.float32)
+
+
+def _operating_launches(logits, labels):
+    """ops.ctr_tails and ops.ctr_operating_points on the resident logits, enqueued only: ONE f64 device tensor [13] = thr (3),
+    cells (6), ap_sum, counts (3); every integer in it is below 2^31 and every cut an f32, so float64 holds them exactly."""
+    import torch
+    from . import ops
+    tails, counts = ops.ctr_tails(logits, labels)
+    thr, cells, ap_sum = ops.ctr_operating_points(tails, logits, labels)
+    return torch.cat([thr.to(torch.float64), cells.reshape(-1).to(torch.float64), ap_sum, counts.to(torch.float64)])
+
+
+def _cut_entry(threshold, tp, fp, m, n0):
+    from . import ops
+    q = ops.operating_point_metrics(tp, fp, m, n0)
+    return {"threshold": float(threshold), "acc": q["acc"], "f1": q["f1"], "precision": q["precision"], "recall": q["recall"],
+            "tp": int(tp), "fp": int(fp)}, q
+
+
+def _operating_result(packed, who):
+    """The dict of ctr_operating_points from _operating_launches' tensor copied back."""
+    from . import ops
+    m, n0, bad = (int(v) for v in packed[10:13])
+    if bad > 0:
+        raise ValueError(f"{who}: the split holds {bad} non-finite logit(s) or label(s) other than 0 / 1")
+    best = {}
+    for c, name in enumerate(ops.OPERATING_CRITERIA):
+        entry, q = _cut_entry(np.float32(packed[c]), int(packed[3 + 2 * c]), int(packed[4 + 2 * c]), m, n0)
+        best[name] = dict(entry, value=q[name])
+    j = best["youden"]["value"]
+    return {"ap": ops.average_precision_from_sum(packed[9], (m, n0, bad)), "n_pos": m, "n_neg": n0, "best": best,
+            "ks": max(j, 0.0) if j == j else float("nan")}
+
+
+def ctr_operating_points(feeder, data, max_pairs=524288):
+    """Where to cut a split's logits, and its average precision, as ONE population (an extension: the reference reports acc
+    and F1 at the fixed cut 0.5 only, which means little under the ranking objectives).  The split is scored once; then ONE
+    ops.ctr_tails launch sequence, ONE ops.ctr_operating_points and one copy back.  Returns ``{"ap", "n_pos", "n_neg", "best":
+    {"f1" | "acc" | "youden": {"threshold", "value", "acc", "f1", "precision", "recall", "tp", "fp"}}, "ks"}``: per criterion
+    the logit cut (predict positive when z >= threshold in f32; +inf = predict nothing) that maximises it over every row's own
+    score and the empty cut, chosen by exact integer comparison with ties to the higher cut, and the metrics there
+    (ops.operating_point_metrics); ``ks`` = max(Youden's J, 0), the Kolmogorov-Smirnov distance of the two classes' scores.
+    ``ap`` is sklearn's average_precision_score of the LOGITS.  Tail counts, AP and the curves do not change under an increasing
+    map, with one exception: the f32 sigmoid merges distinct large logits into equal scores, so ``ap`` can differ from an AP
+    computed on the sigmoid scores ``auc`` is counted on.  NaN for ``ap`` and +inf cuts when the split has no valid positive.
+    ValueError for an empty split or one with a non-finite logit or a label other than 0 / 1."""
+    if np.asarray(data).shape[0] == 0:
+        raise ValueError("ctr_operating_points: empty split")
+    logits, _, labels = _score_split_both(feeder, data, max_pairs)
+    return _operating_result(_operating_launches(logits, labels).cpu().numpy(), "ctr_operating_points")
+
+
+def pick_threshold(feeder, data, criterion="f1", max_pairs=524288):
+    """The logit cut that maximises ``criterion`` ("f1", "acc" or "youden") on ``data`` -- usually the eval split, to report
+    the test split at it (ctr_report(threshold=)) -- as an ``OperatingPoint``.  ctr_operating_points' launches and rules.
+    ValueError for another criterion, an empty split, or a split with no valid row of a class."""
+    _check_criterion(criterion, "pick_threshold")
+    res = ctr_operating_points(feeder, data, max_pairs)
+    if res["n_pos"] == 0 or res["n_neg"] == 0:
+        raise ValueError(f"pick_threshold: {res['n_pos']} positive and {res['n_neg']} negative rows: a cut needs both classes")
+    b = res["best"][criterion]
+    return OperatingPoint(criterion, b["threshold"], b["tp"], b["fp"], res["n_pos"], res["n_neg"], b["value"])
+
+
+def _curves_result(thr, out, counts, ap):
+    from . import ops
+    cv = ops.curves_from_counts(thr, out, counts)
+    return {"thresholds": thr, "roc": cv["roc"], "pr": cv["pr"], "ap": ap}
+
+
+def ctr_curves(feeder, data, thresholds=None, points=101, max_pairs=524288):
+    """The ROC and PR curves of a split's logits at explicit cuts.  ``thresholds``: logit thresholds (any order, duplicates
+    allowed); None: ``logit(j / points)``, j = 1 .. points - 1, as float32 -- a uniform grid in probability.  Returns
+    ``{"thresholds" f32 [T], "roc": {"fpr", "tpr"}, "pr": {"precision", "recall"}, "ap"}`` (float64 arrays in the thresholds'
+    order, ops.curves_from_counts) from ONE ops.ctr_threshold_counts call, plus ctr_operating_points' exact ``ap`` -- the area
+    the PR points only sample.  ValueError for bad thresholds / points, an empty split, or invalid rows."""
+    import torch
+    from . import ops
+    thr = _curve_thresholds(thresholds, points, "ctr_curves")
+    if np.asarray(data).shape[0] == 0:
+        raise ValueError("ctr_curves: empty split")
+    logits, _, labels = _score_split_both(feeder, data, max_pairs)
+    out, counts = ops.ctr_threshold_counts(logits, labels, torch.from_numpy(thr).to(logits.device))
+    res = _operating_result(_operating_launches(logits, labels).cpu().numpy(), "ctr_curves")
+    return _curves_result(thr, out.cpu().numpy(), counts.cpu().numpy(), res["ap"])
+
+
+def _report_threshold(threshold):
+    """ctr_report's ``threshold=`` as a float: an OperatingPoint's cut or a real number (NaN refused)."""
+    t = threshold.threshold if isinstance(threshold, OperatingPoint) else threshold
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)) or t != t:
+        raise ValueError(f"ctr_report: threshold={threshold!r}: expected an OperatingPoint or a logit cut (a number, not NaN)")
+    return float(np.float32(t))
+
+
+def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288, ci=None, cluster=None, n_rep=2000, seed=1,
+               threshold=None, curves=None):
     """The CTR report of a split as ONE population (an extension: the reference reports none of these but the per-batch means
     of auc / acc / f1).  The split is scored once (logits and sigmoid scores of the same forward calls); everything else is
     reductions over the resident buffers and one copy back per result tensor.  Returns a dict:
@@ -1334,13 +1455,30 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     assume in turn that clusters are independent of one another and that there are enough of them for a normal approximation
     (a percentile interval): tens of clusters give wide and shaky intervals, which is why ``n_clusters`` is reported.
     ValueError: any other ``cluster`` value, ``cluster`` without ``ci``, fewer than two clusters (with a used row).  (Intervals for
-    f1 / ece / mce are not built.)"""
+    f1 / ece / mce are not built.)
+    ``threshold`` (an OperatingPoint of pick_threshold, usually from the eval split, or a logit cut as a number; None: nothing
+    more) adds ``"at_threshold": {"threshold", "acc", "f1", "precision", "recall", "tp", "fp"}``: the split at the prediction
+    z >= threshold compared in f32, from ONE ops.ctr_threshold_counts launch with one threshold on the resident logits; with a
+    ``calibration`` also ``"prob"`` = sigmoid(a threshold + b), the calibrated probability the cut stands for.  ``curves``
+    (True: 100 cuts uniform in probability; an int: ctr_curves' ``points``; an array: logit thresholds; None: nothing more) adds
+    ``"ap"``, ``"operating_points"`` (ctr_operating_points' dict) and ``"curves"`` (ctr_curves' dict without "ap"), all on the
+    LOGITS: see ctr_operating_points for how ``ap`` relates to the sigmoid scores ``auc`` is counted on.  With both None the
+    dict and the launches are exactly those without the two keywords."""
     import torch
     from . import ops
     cols = np.asarray(data)
     n = cols.shape[0]
     if n == 0:
         raise ValueError("ctr_report: empty split")
+    cut_at = None if threshold is None else _report_threshold(threshold)
+    curve_thr = None
+    if curves is not None and curves is not False:
+        if curves is True:
+            curve_thr = _curve_thresholds(None, 101, "ctr_report")
+        elif isinstance(curves, (int, np.integer)) and not isinstance(curves, (bool, np.bool_)):
+            curve_thr = _curve_thresholds(None, curves, "ctr_report")
+        else:
+            curve_thr = _curve_thresholds(curves, None, "ctr_report")
     grp = _cluster_grouping(cluster, cols, "ctr_report")
     if grp is not None and ci is None:
         raise ValueError("ctr_report: cluster= changes the intervals of ci=; pass a level such as ci=0.95")
@@ -1385,6 +1523,11 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
         rows = torch.cat([t, torch.ones((n, 1), dtype=torch.float64, device=dev)], dim=1)
         user_main = torch.stack(_gauc_columns(ucounts), dim=1) if with_gauc else None
         cl = _cluster_launches(place.view(1, n), labels, grp, rows, None, user_main, None, int(n_rep), seed)
+    at = cv = None
+    if cut_at is not None:
+        at = ops.ctr_threshold_counts(logits, labels, torch.tensor([cut_at], dtype=torch.float32, device=dev))
+    if curve_thr is not None:
+        cv = ops.ctr_threshold_counts(logits, labels, torch.from_numpy(curve_thr).to(dev)), _operating_launches(logits, labels)
     counts = counts.cpu().numpy()
     auc, acc, f1 = ops.ctr_metrics_from_counts(counts)
     cal = ops.ctr_calibration_from_sums(sums.cpu().numpy(), valid.cpu().numpy(), bins.cpu().numpy())
@@ -1424,6 +1567,17 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
             for j, form in ((3, "weighted"), (4, "mean")):
                 rep["gauc"][form + "_se"] = float(summ["se"][j])
                 rep["gauc"][form + "_ci"] = (float(summ["lo"][j]), float(summ["hi"][j]))
+    if at is not None:
+        cells, tc = at[0].cpu().numpy()[0], at[1].cpu().numpy()
+        rep["at_threshold"] = _cut_entry(cut_at, cells[0], cells[1], tc[0], tc[1])[0]
+        if calibration is not None:
+            t = a * cut_at + b
+            rep["at_threshold"]["prob"] = float(1.0 / (1.0 + np.exp(-t)) if t >= 0 else np.exp(t) / (1.0 + np.exp(t)))
+    if cv is not None:
+        op = _operating_result(cv[1].cpu().numpy(), "ctr_report")
+        curve = _curves_result(curve_thr, cv[0][0].cpu().numpy(), cv[0][1].cpu().numpy(), op["ap"])
+        rep["ap"] = curve.pop("ap")
+        rep["operating_points"], rep["curves"] = op, curve
     return rep
 
 
@@ -2213,7 +2367,7 @@ class EarlyStop(object):
 def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=None, topk_batch=65536, hoist=True,
           topk_early_stop=False, graph="auto", topk_impl="host", ctr_impl="host", negatives="fixed", on_best=None,
           objective="bce", n_neg=1, pool=16, shortlist=None, rescore=1, neg_dist="uniform", neg_alpha=0.75, neg_smooth=0.0,
-          clip_norm=None, skip_nonfinite=False, logq=False, eval_neg=None, ctr_report=False, calibrate=False):
+          clip_norm=None, skip_nonfinite=False, logq=False, eval_neg=None, ctr_report=False, calibrate=False, tune_threshold=None):
     """train.py:16-109 on the GPU path.  ``data`` = the 16-tuple of mvin_amd.data_io.load_data / the
     reference's ``load_data`` (read by position exactly as train.py:17-21 does; a 10-tuple prefix
     (..., user_triplet_set) is accepted for CTR runs).  Per epoch: shuffle, full minibatches only
@@ -2280,6 +2434,10 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
     map on the eval split every epoch (fit_calibration) and gives the test record "calibrated": {"a", "b", "logloss", "acc",
     "f1"} under that map.  An opt-in extension (the reference reports none of these): off, the records are exactly the ones
     without it.
+    ``tune_threshold``: "f1", "acc" or "youden" (needs ``ctr_report``; None: off, the records are unchanged) picks the logit cut
+    that maximises that criterion on the eval split every epoch (pick_threshold) and gives the test record "tuned":
+    {"criterion", "threshold", "acc", "f1", "precision", "recall"}: the test split at that cut (ctr_report(threshold=)) -- the
+    acc / F1 to read under the ranking objectives, whose logits are not centred on the fixed cut.
     ``on_best``: called as ``on_best(epoch, score, model)`` after every epoch whose evaluation score is above every earlier
     one's -- exactly where EarlyStop saves the stage-wise tables, whether or not ``args.path.emb`` is set.
     Returns (model, history): one dict per epoch."""
@@ -2301,6 +2459,12 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
         raise ValueError("ctr_report=True reports on the CTR evaluation, which show_topk=True replaces")
     if calibrate and not ctr_report:
         raise ValueError("calibrate=True reports the calibrated numbers in the CTR report: it needs ctr_report=True")
+    if tune_threshold is not None:
+        _check_criterion(tune_threshold, "train: tune_threshold")
+        if show_topk:
+            raise ValueError("tune_threshold tunes the cut of the CTR evaluation, which show_topk=True replaces")
+        if not ctr_report:
+            raise ValueError("tune_threshold reports the tuned numbers in the CTR report: it needs ctr_report=True")
     if negatives not in ("fixed", "resample", "hard"):
         raise ValueError(f"negatives={negatives!r}: expected 'fixed', 'resample' or 'hard'")
     if objective not in ("bce", "bpr", "softmax"):
@@ -2427,6 +2591,9 @@ def train(args, data, show_topk=False, model=None, device="cuda", rng=None, log=
                 cal = fit_calibration(feeder, eval_data, name="the eval split")
                 rep = _ctr_report(feeder, test_data, calibration=cal, gauc=False)
                 rec["test"]["calibrated"] = {"a": cal.a, "b": cal.b, "logloss": rep["logloss"], "acc": rep["acc"], "f1": rep["f1"]}
+            if tune_threshold is not None:
+                at = _ctr_report(feeder, test_data, threshold=pick_threshold(feeder, eval_data, tune_threshold), gauc=False)["at_threshold"]
+                rec["test"]["tuned"] = dict({"criterion": tune_threshold}, **{k: at[k] for k in ("threshold", "acc", "f1", "precision", "recall")})
             score = rec["eval"]["auc"]                                          # Eval_score_info.eval_st_score
         history.append(rec)
         if log:

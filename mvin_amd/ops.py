@@ -601,6 +601,161 @@ def ctr_placements(scores, labels, out=None):
     return place, counts
 
 
+TAIL_COUNTS = ("n_pos", "n_neg", "bad")
+OPERATING_CRITERIA = ("f1", "acc", "youden")          # the rows of ctr_operating_points' thr and cells
+
+
+def _curve_rows(scores, labels, who, allow_empty=False):
+    """The checks ctr_tails, ctr_operating_points and ctr_threshold_counts share: ValueError for anything but two contiguous device
+    tensors f32 [n] / int32 [n] of one population within the row limit; returns n."""
+    for t, name, dt in ((scores, "scores", F32), (labels, "labels", I32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: {name}: expected a CUDA/ROCm tensor (mvin_amd has no CPU path)")
+        if t.dtype != dt:
+            raise ValueError(f"{who}: {name}: expected {dt}, got {t.dtype}")
+    if scores.dim() != 1 or labels.dim() != 1 or scores.shape != labels.shape or not scores.is_contiguous() or not labels.is_contiguous():
+        raise ValueError(f"{who}: scores {tuple(scores.shape)} and labels {tuple(labels.shape)}: expected two contiguous [n] tensors")
+    if labels.device != scores.device:
+        raise ValueError(f"{who}: scores on {scores.device}, labels on {labels.device}")
+    n = scores.numel()
+    if not (0 if allow_empty else 1) <= n < 1 << 31:
+        raise ValueError(f"n={n}: {who} takes {'0' if allow_empty else '1'} <= n < 2^31 rows")
+    return n
+
+
+def _curve_out(t, name, dtype, shape, dev, who):
+    if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"{who}: {name}: expected a contiguous {dtype} {list(shape)} tensor on {dev}")
+    return t
+
+
+def ctr_tails(scores, labels, out=None):
+    """mvin_ctr_tails: every row's tail counts.  ``scores`` f32 [n] and ``labels`` int32 [n] (contiguous device tensors, ONE
+    population).  Returns ``(tails int32 [n, 2], counts int64 [3])`` on the device (``out``: the same two to write into):
+    ``tails[i] = (tp, fp)`` = the valid positives / negatives whose score is >= row i's own (ctr_counts' image: -0.0 equals +0.0),
+    i.e. the confusion cells at the cut "row i's score"; (-1, -1) for a row with a non-finite score or a label other than 0 / 1;
+    ``counts`` = ``TAIL_COUNTS``.  All integers, the same on every launch.  Enqueues only.  ValueError for anything but such
+    tensors."""
+    lib = _lib.load()
+    n = _curve_rows(scores, labels, "ctr_tails")
+    dev = scores.device
+    if out is None:
+        out = (torch.empty((n, 2), dtype=I32, device=dev), torch.empty((3,), dtype=torch.int64, device=dev))
+    if len(out) != 2:
+        raise ValueError("ctr_tails: out: expected (tails, counts)")
+    tails = _curve_out(out[0], "out tails", I32, (n, 2), dev, "ctr_tails")
+    counts = _curve_out(out[1], "out counts", torch.int64, (3,), dev, "ctr_tails")
+    nws = lib.mvin_ctr_tails_ws_bytes(n)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_ctr_tails_ws_bytes")
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if nws > 0 else None
+    _lib.check(lib.mvin_ctr_tails(_p(scores), _p(labels), n, _p(ws), _p(tails), _p(counts), _stream()), "mvin_ctr_tails")
+    return tails, counts
+
+
+def ctr_operating_points(tails, scores, labels, max_groups=0):
+    """mvin_ctr_operating_points: the best cuts of a split and its average-precision sum, from ctr_tails' ``tails`` of the same
+    ``scores`` and ``labels``.  Returns device tensors ``(thr f32 [3], cells int64 [3, 2], ap_sum f64 [1])``: per criterion of
+    ``OPERATING_CRITERIA`` the cut that maximises it over every valid row's own score and the empty cut (+inf), compared as
+    exact integers, ties to the higher cut; its (tp, fp); and the sum of tp / (tp + fp) over the valid positives in one fixed
+    order (average_precision_from_sum divides it by n_pos).  The same bits for every ``max_groups`` (0 automatic, else a cap on
+    the workgroups).  Enqueues only.  ValueError for anything but matching device tensors."""
+    lib = _lib.load()
+    n = _curve_rows(scores, labels, "ctr_operating_points")
+    dev = scores.device
+    _curve_out(tails, "tails", I32, (n, 2), dev, "ctr_operating_points")
+    max_groups = int(max_groups)
+    if max_groups < 0:
+        raise ValueError(f"max_groups={max_groups}: expected >= 0")
+    thr = torch.empty((3,), dtype=F32, device=dev)
+    cells = torch.empty((3, 2), dtype=torch.int64, device=dev)
+    ap_sum = torch.empty((1,), dtype=torch.float64, device=dev)
+    nws = lib.mvin_ctr_operating_points_ws_bytes(n)
+    if nws < 0:
+        _lib.check(int(nws), "mvin_ctr_operating_points_ws_bytes")
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mvin_ctr_operating_points(_p(tails), _p(scores), _p(labels), n, _p(ws), max_groups, _p(thr), _p(cells), _p(ap_sum),
+                                             _stream()), "mvin_ctr_operating_points")
+    return thr, cells, ap_sum
+
+
+def ctr_threshold_counts_max():
+    """mvin_ctr_threshold_counts_max: the thresholds one mvin_ctr_threshold_counts call takes (4096)."""
+    return int(_lib.load().mvin_ctr_threshold_counts_max())
+
+
+def ctr_threshold_counts(scores, labels, thresholds, max_groups=0):
+    """mvin_ctr_threshold_counts: the confusion cells of a split at many cuts at once.  ``thresholds`` f32 [T] on the device, in
+    any order, duplicates allowed.  Returns device tensors ``(out int64 [T, 2], counts int64 [3])``: ``out[t] = (tp, fp)`` = the
+    valid positives / negatives with ``score >= thresholds[t]`` compared in f32 (a NaN threshold: (0, 0)), ``counts`` =
+    ``TAIL_COUNTS``.  More than ctr_threshold_counts_max() thresholds are cut into calls.  Integers only, the same bits for
+    every ``max_groups``.  Enqueues only.  ValueError for wrong dtypes, devices or shapes."""
+    lib = _lib.load()
+    who = "ctr_threshold_counts"
+    n = _curve_rows(scores, labels, who, allow_empty=True)
+    dev = scores.device
+    if not isinstance(thresholds, torch.Tensor) or thresholds.device != dev or thresholds.dtype != F32 or thresholds.dim() != 1 \
+            or thresholds.numel() < 1 or not thresholds.is_contiguous():
+        raise ValueError(f"{who}: thresholds: expected a contiguous {F32} [T] tensor on {dev}, T >= 1")
+    max_groups = int(max_groups)
+    if max_groups < 0:
+        raise ValueError(f"max_groups={max_groups}: expected >= 0")
+    T, step = thresholds.numel(), ctr_threshold_counts_max()
+    out = torch.empty((T, 2), dtype=torch.int64, device=dev)
+    counts = torch.empty((3,), dtype=torch.int64, device=dev)
+    for t0 in range(0, T, step):
+        t1 = min(T, t0 + step)
+        _lib.check(lib.mvin_ctr_threshold_counts(_p(scores) if n else None, _p(labels) if n else None, n, _p(thresholds[t0:t1]), t1 - t0,
+                                                 max_groups, _p(out[t0:t1]), _p(counts), _stream()), "mvin_ctr_threshold_counts")
+    return out, counts
+
+
+def average_precision_from_sum(ap_sum, counts):
+    """The average precision ``ap_sum / n_pos`` in float64 from ctr_operating_points' sum and ctr_tails' counts (host values);
+    NaN when there is no valid positive.  sklearn's average_precision_score on the valid rows: the sum of the positives'
+    precisions at their own scores equals its sum of (R_k - R_(k-1)) P_k over the distinct thresholds."""
+    m = int(np.asarray(counts).reshape(-1)[0])
+    s = np.float64(np.asarray(ap_sum, dtype=np.float64).reshape(-1)[0])
+    return float(s / np.float64(m)) if m > 0 else float("nan")
+
+
+def operating_point_metrics(tp, fp, m, n0):
+    """The metrics of the cut with confusion cells ``tp``, ``fp`` on ``m`` positives and ``n0`` negatives (Python ints), in
+    float64 by ctr_metrics_from_counts' conventions: ``acc = (tp + n0 - fp) / n`` (NaN for no rows), ``f1 = 2 tp / (2 tp + fp +
+    fn)`` and ``precision = tp / (tp + fp)`` -- 0.0 where that denominator is 0 -- ``recall = tp / m`` and ``fpr = fp / n0`` --
+    NaN for an empty class -- and ``youden = recall - fpr``."""
+    tp, fp, m, n0 = int(tp), int(fp), int(m), int(n0)
+    f = np.float64
+    nan = float("nan")
+    den = 2 * tp + fp + (m - tp)
+    recall = float(f(tp) / f(m)) if m > 0 else nan
+    fpr = float(f(fp) / f(n0)) if n0 > 0 else nan
+    return {"acc": float(f(tp + n0 - fp) / f(m + n0)) if m + n0 > 0 else nan,
+            "f1": float(f(2 * tp) / f(den)) if den > 0 else 0.0,
+            "precision": float(f(tp) / f(tp + fp)) if tp + fp > 0 else 0.0,
+            "recall": recall, "fpr": fpr, "youden": recall - fpr}
+
+
+def curves_from_counts(thresholds, out, counts):
+    """The ROC and PR points at ctr_threshold_counts' thresholds (host arrays [T], [T, 2], [3]), float64, in the thresholds' own
+    order: ``{"roc": {"fpr", "tpr"}, "pr": {"precision", "recall"}}`` with tpr = recall = tp / n_pos and fpr = fp / n_neg (NaN
+    for an empty class) and precision = tp / (tp + fp), 1.0 where nothing is predicted positive (precision_recall_curve's last
+    point)."""
+    thr = np.asarray(thresholds).reshape(-1)
+    c = np.asarray(out).astype(np.int64)
+    ct = np.asarray(counts).reshape(-1)
+    if c.ndim != 2 or c.shape != (thr.size, 2) or ct.size != 3:
+        raise ValueError(f"expected thresholds [T], out [T, 2] and counts [3], got {thr.shape}, {c.shape}, {ct.shape}")
+    m, n0 = int(ct[0]), int(ct[1])
+    tp, fp = c[:, 0].astype(np.float64), c[:, 1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tpr = tp / np.float64(m) if m > 0 else np.full(thr.size, np.nan)
+        fpr = fp / np.float64(n0) if n0 > 0 else np.full(thr.size, np.nan)
+        pred = tp + fp
+        precision = np.where(pred > 0, tp / np.where(pred > 0, pred, 1.0), 1.0)
+    return {"roc": {"fpr": fpr, "tpr": tpr}, "pr": {"precision": precision, "recall": tpr.copy()}}
+
+
 def placement_moments_max_models():
     """mvin_placement_moments_max_models: the models one mvin_placement_moments call takes (8)."""
     return int(_lib.load().mvin_placement_moments_max_models())
