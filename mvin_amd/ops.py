@@ -862,11 +862,11 @@ def delong_test(auc, cov, a, b):
     return {"diff": diff, "se": se, "z": z, "p": p}
 
 
-def cluster_csr(ids):
+def cluster_csr(ids, order_dtype=np.int32):
     """The stable grouping of rows by an integer id on the host: ``(order int32 [n], seg_ptr int64 [I + 1], cluster_ids [I])`` with
     ``ids[order]`` ascending, equal ids in row order, and cluster i = positions ``seg_ptr[i]:seg_ptr[i+1]`` of ``order`` -- what
     placement_cluster_moments, segment_sums and (as user segments) ctr_counts_segments take.  ``ids``: a one-dimensional integer
-    array of fewer than 2^31 rows; anything else raises ValueError."""
+    array of fewer than 2^31 rows; anything else raises ValueError.  ``order_dtype``: np.int64 for an order index_select takes."""
     ids = np.asarray(ids)
     if ids.ndim != 1 or ids.dtype.kind not in "iu":
         raise ValueError(f"cluster ids: expected a one-dimensional integer array, got {ids.dtype} {ids.shape}")
@@ -874,16 +874,16 @@ def cluster_csr(ids):
     if n >= 1 << 31:
         raise ValueError(f"n={n}: expected fewer than 2^31 rows")
     if n == 0:
-        return np.zeros(0, np.int32), np.zeros(1, np.int64), ids[:0].copy()
+        return np.zeros(0, order_dtype), np.zeros(1, np.int64), ids[:0].copy()
     lo, hi = int(ids.min()), int(ids.max())
     if hi - lo < (1 << 31):                                     # the stable argsort as ONE sort of (id, row) keys
-        order = np.sort((ids.astype(np.int64) - lo) * n + np.arange(n, dtype=np.int64)) % n
+        order = np.sort((ids.astype(np.int64, copy=False) - lo) * n + np.arange(n, dtype=np.int64)) % n
     else:
         order = np.argsort(ids, kind="stable")
     s = ids[order]
     first = np.flatnonzero(np.concatenate(([True], s[1:] != s[:-1])))
     seg_ptr = np.concatenate((first, [n])).astype(np.int64)
-    return order.astype(np.int32), seg_ptr, s[first]
+    return order.astype(order_dtype, copy=False), seg_ptr, s[first]
 
 
 def _cluster_grouping(seg_ptr, order, n, name):

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mvin_amd import harness, ops, synth  # noqa: E402
+from mvin_amd import ctr_eval, harness, ops, synth  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--kernel-only", action="store_true")
@@ -146,7 +146,7 @@ def wall(fn):
     return times, res
 
 
-t_s, _ = wall(lambda: [harness._score_split_both(f, data, 524288) for f in feeders])
+t_s, _ = wall(lambda: [ctr_eval._score_split(f, data, None, 524288, logits=True) for f in feeders])
 t_c, res = wall(lambda: harness.compare_ctr(feeders, data, n_rep=a.replicates))
 emit(leg="compare", pairs=n, models=2, replicates=a.replicates, compare_ctr_s=spread(t_c, 4), scoring_alone_s=spread(t_s, 4),
      auc=[m["auc"] for m in res["models"]], auc_se=[m["auc_se"] for m in res["models"]], p=res["pairs"][(0, 1)]["p"])

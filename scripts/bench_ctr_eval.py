@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mvin_amd import harness, ops, synth  # noqa: E402
+from mvin_amd import ctr_eval, harness, ops, synth  # noqa: E402
 from mvin_amd.config import make_args  # noqa: E402
 from mvin_amd.model import MVIN  # noqa: E402
 from mvin_amd.params import init_params  # noqa: E402
@@ -107,7 +107,7 @@ emit(leg="eval", pairs=a.pairs, batch=B, batches=a.pairs // B, ctr_eval_device_s
 # sklearn on the very same scores, already on the host
 from sklearn.metrics import f1_score, roc_auc_score  # noqa: E402
 m = a.pairs // B * B
-scores = harness._score_split(feeder, split, m, B)[0].cpu().numpy().reshape(-1, B)
+scores = ctr_eval._score_split(feeder, split, m, B)[0].cpu().numpy().reshape(-1, B)
 labels = split[:m, 2].astype(np.float32).reshape(-1, B)
 t0 = time.perf_counter()
 with warnings.catch_warnings():

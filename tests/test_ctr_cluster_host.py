@@ -246,7 +246,7 @@ def test_harness_refusals_and_the_default_path(monkeypatch):
         with pytest.raises(Touched):
             harness.compare_ctr([StubFeeder()] * 2, data, cluster=ok)
     # cluster=None: nothing of the feature is called on the way to the feeder
-    for name in ("cluster_csr", "placement_cluster_moments", "segment_sums", "clustered_delong_from_gram"):
+    for name in ("placement_cluster_moments", "segment_sums", "clustered_delong_from_gram"):
         monkeypatch.setattr(ops, name, lambda *a, **k: pytest.fail("the clustered path ran with cluster=None"))
     with pytest.raises(Touched):
         harness.ctr_report(StubFeeder(), data, ci=0.95, cluster=None)

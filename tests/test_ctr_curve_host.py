@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import ctr_curve_oracle as co
-from mvin_amd import harness, ops
+from mvin_amd import ctr_eval, harness, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("mvin_ctr_tails_ws_bytes", "mvin_ctr_tails", "mvin_ctr_operating_points_ws_bytes", "mvin_ctr_operating_points",
@@ -231,7 +231,7 @@ def test_harness_refusals_and_the_default_path(monkeypatch):
                {"thresholds": [0.0, float("nan")]}, {"thresholds": ["a"]}):
         with pytest.raises(ValueError, match="points|thresholds"):
             harness.ctr_curves(StubFeeder(), data, **kw)
-    grid = harness._curve_thresholds(None, 101, "t")
+    grid = ctr_eval._curve_thresholds(None, 101, "t")
     assert grid.dtype == np.float32 and grid.size == 100 and grid[49] < 0.0 < grid[50] and np.all(np.diff(grid) > 0)
     assert abs(float(grid[0]) - math.log(1 / 100)) < 1e-6
     for bad in (float("nan"), "0.5", True, [0.0]):
@@ -249,7 +249,7 @@ def test_harness_refusals_and_the_default_path(monkeypatch):
     for name in ("ctr_tails", "ctr_operating_points", "ctr_threshold_counts", "average_precision_from_sum", "operating_point_metrics",
                  "curves_from_counts"):
         monkeypatch.setattr(ops, name, lambda *a, **k: pytest.fail("the operating-point path ran with threshold=None, curves=None"))
-    monkeypatch.setattr(harness, "_curve_thresholds", lambda *a, **k: pytest.fail("curve thresholds built with curves=None"))
+    monkeypatch.setattr(ctr_eval, "_curve_thresholds", lambda *a, **k: pytest.fail("curve thresholds built with curves=None"))
     with pytest.raises(Touched):
         harness.ctr_report(StubFeeder(), data)
     with pytest.raises(Touched):

@@ -17,7 +17,7 @@ from test_gpu_ctr_compare import N_REP, REPORT_KEYS, build
 pytestmark = pytest.mark.gpu
 
 CLUSTER_KEYS = {"auc_se", "auc_ci", "auc_se_rows", "design_effect", "cluster", "cluster_ci"}
-FEATURE_OPS = ("cluster_csr", "placement_cluster_moments", "segment_sums", "clustered_delong_from_gram")
+FEATURE_OPS = ("placement_cluster_moments", "segment_sums", "clustered_delong_from_gram")
 
 
 @pytest.fixture(scope="module")

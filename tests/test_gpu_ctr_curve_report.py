@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import ctr_curve_oracle as co
-from mvin_amd import harness, ops
+from mvin_amd import ctr_eval, harness, ops
 from test_gpu_ctr_report import N_ENTITY, N_ITEM, N_REL, N_USER, build
 
 pytestmark = pytest.mark.gpu
@@ -55,7 +55,7 @@ def test_operating_points_and_pick_threshold(case):
 def test_curves(case):
     feeder, data, z, lab, tails, counts = case
     ap = ops.average_precision_from_sum(co.ap_sum(tails, z, lab), counts)
-    for kw, thr in (({}, harness._curve_thresholds(None, 101, "t")), ({"points": 7}, harness._curve_thresholds(None, 7, "t")),
+    for kw, thr in (({}, ctr_eval._curve_thresholds(None, 101, "t")), ({"points": 7}, ctr_eval._curve_thresholds(None, 7, "t")),
                     ({"thresholds": [1.0, -1.0, 1.0, float(z[3])]}, np.array([1.0, -1.0, 1.0, z[3]], np.float32))):
         got = harness.ctr_curves(feeder, data, **kw)
         out, tc = co.threshold_counts(z, lab, thr)

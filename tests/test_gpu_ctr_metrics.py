@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from ctr_oracle import ctr_counts_oracle, families, sklearn_metrics
-from mvin_amd import harness, ops, synth
+from mvin_amd import ctr_eval, harness, ops, synth
 from mvin_amd.config import make_args
 from mvin_amd.params import init_params
 
@@ -134,7 +134,7 @@ def test_batched_eval_default_slices(hip_lib):
     a = harness.ctr_eval_device(feeder, data, 32)
     b = harness.ctr_eval_batched(feeder, data, 32)
     assert abs(a[3] - b[3]) <= 1e-5
-    scores, _ = harness._score_split(feeder, data, 700 // 32 * 32, 524288)
+    scores, _ = ctr_eval._score_split(feeder, data, 700 // 32 * 32, 524288)
     if not (np.abs(scores.cpu().numpy().astype(np.float64) - 0.5) < 1e-6).any():
         np.testing.assert_allclose(b[1], a[1], rtol=0, atol=1e-12)
         np.testing.assert_allclose(b[2], a[2], rtol=0, atol=1e-12)
@@ -144,7 +144,7 @@ def test_whole_split_metric_matches_sklearn(hip_lib):
     args, model, uts, data, _ = build()
     feeder = harness.DeviceFeeder(model, uts)
     auc, acc, f1 = harness.ctr_eval_split(feeder, data)
-    scores, _ = harness._score_split(feeder, data, data.shape[0], 524288)
+    scores, _ = ctr_eval._score_split(feeder, data, data.shape[0], 524288)
     ra, rc, rf = sklearn_metrics(scores.cpu().numpy(), data[:, 2])
     assert abs(auc - ra) <= 1e-12 and abs(acc - rc) <= 1e-12 and abs(f1 - rf) <= 1e-12
 
