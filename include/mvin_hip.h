@@ -1131,6 +1131,76 @@ MVIN_API int mvin_ctr_threshold_counts(const float* scores, const int32_t* label
                                        int n_thresholds, int max_groups, int64_t* out /* [n_thresholds, 2] */,
                                        int64_t* counts /* [3] */, void* stream);
 
+/* ---- resampled order statistics of a CTR split: what bootstrap intervals and paired tests of the average precision, of a
+ * tuned cut's value and of the metrics at a fixed cut are made of (an opt-in extension) --
+ * A replicate gives every sampling unit (a row, or a cluster of rows) an integer multiplicity; the AP, the AUC, the best cuts and
+ * the cells at a cut of the replicate are weighted prefix sums over the rows in descending score order.  The sort is done once
+ * per split (mvin_ctr_tails); the replicates only scan.
+ *
+ * mvin_resample_multiplicities: mult int32 [n_rep, ld].  THE RULE: mult[(r - first)*ld + i], for i < n_units, = the number of
+ *   positions j in [0, n_units) with (rnd32(seed, 7, r, 0, j) * n_units) >> 32 == i: the histogram of the draws of
+ *   mvin_resample_sums' bootstrap mode with n_rows = n_units, so replicate r here resamples the units replicate r there does.
+ *   Every row sums to n_units.  The call writes the first n_units words of each row (words n_units .. ld - 1 are left alone);
+ *   32-bit integer atomics in LDS (n_units <= 16384) or in global memory, the same integers either way.
+ *   Limits: 0 <= n_units < 2^31; n_units <= ld < 2^31; 0 <= first < 2^62; 0 <= n_rep < 2^40; n_rep * ld < 2^62.  n_units == 0
+ *   or n_rep == 0 launches nothing.  No workspace.
+ *
+ * mvin_ctr_rank_image: tails int32 [n, 2] as mvin_ctr_tails wrote them, labels int32 [n], units int32 [n] or NULL (NULL: row i is
+ *   its own unit i); none is written.  A row is VALID here when its pair is not negative and g = tp + fp is in 1 .. n (mvin_ctr_tails
+ *   marks the invalid rows (-1, -1)); g is the number of valid rows whose score is >= its own.  THE RULE: the valid rows with
+ *   one g are a tie group of t rows and occupy the positions [g - t, g) of the descending score order; WHICH row of the group
+ *   sits at which of its positions is not specified and may differ from launch to launch (one integer atomic counter per group,
+ *   mvin_order_by_key's precedent).  pos_row int32 [n]: the row at position p.  image int32 [n, 2]: (the unit of that row as it
+ *   stands in `units`, in range or not; info) with info bit 0 = the row's label is 1 and bit 1 = the position is the last of its
+ *   tie group (g - 1).  The positions n_valid .. n - 1 hold pos_row -1 and image (-1, 0).  Tails that are not a split's (more
+ *   rows claiming a group than it has positions) do not fault: the surplus rows are dropped.
+ *   `ws`: mvin_ctr_rank_image_ws_bytes(n) bytes, never NULL.  Limit: 1 <= n < 2^31.
+ *
+ * mvin_ctr_rank_resample: image [n, 2] as above (never written), mult int32 [n_rep, ld] or NULL, cut_pos int64 [n_cuts].  For
+ *   replicate r the weight of position p is w_p = mult[r*ld + unit_p], 0 for a unit outside [0, n_units); mult == NULL: w_p = 1
+ *   for p < n_valid, else 0 (the observed split; n_rep must be 1).  n_valid = 1 + the last position whose info has bit 1.
+ *   TP(p) / FP(p) = the sums of w over the positions <= p with label 1 / label 0; M, N their totals.  A TIE-GROUP END is a
+ *   position with bit 1; at the end p of group g, dTP / dFP = TP / FP at p minus TP / FP at the previous end (0 before the first).
+ *   out int64 [n_rep, 12 + 2 n_cuts], per replicate:
+ *     [0] M, [1] N;
+ *     [2] u2 = the sum over the ends of dFP * (2 * TP_before + dTP): twice the weighted Mann-Whitney U (AUC = u2 / (2 M N));
+ *         with unit weights mvin_ctr_counts' u2;
+ *     [3 .. 11] the best cut by F1, accuracy and Youden, in that order, as (tp, fp, pos): THE CANDIDATES are every end
+ *         (TP, FP, pos = p + 1) and the empty cut (0, 0, 0), compared by mvin_ctr_operating_points' three exact integer
+ *         comparisons with M and N in place of m and n0; equal values: the smaller pos (the higher cut).  The order is total,
+ *         so no order of the reduction changes a bit;
+ *     [12 + 2c], [13 + 2c] (TP, FP) over the positions < clamp(cut_pos[c], 0, n_valid).
+ *   ap_sum f64 [n_rep]: an end p with dTP > 0 has the term (double)dTP * ((double)TP / (double)(TP + FP)): one IEEE division and
+ *   one IEEE multiplication, each rounded on its own, and the product is NOT contracted into the add that follows (the kernel is
+ *   written with explicit round-to-nearest operations); every other position has no term.  THE ORDER is
+ *   mvin_ctr_operating_points' over the POSITIONS: chunks of MVIN_CTR_SEG_CAP consecutive positions; in a chunk 64 partial sums
+ *   start at +0.0, position p adds its term to p_(p mod 64) in ascending p, then for h = 32 .. 1: p_l = p_l + p_(l+h) for l < h;
+ *   the chunk sums are combined by the same rule over the chunk index.  AP = ap_sum / M (sklearn's average_precision_score with
+ *   sample_weight = w).  Terms sit at ends and depend on group totals only, so the twelve words, the cells of every cut that
+ *   falls between two tie groups (a threshold's cut does: tp + fp of mvin_ctr_threshold_counts) and every bit of ap_sum are the
+ *   same for any admissible order inside the tie groups; a cut inside a tie group splits it in the image's order.  The same
+ *   bits for every `max_groups` (0 = automatic, a positive value caps the workgroups of each launch) and for any split of the
+ *   replicates into calls.  No floating-point atomics.
+ *   OVERFLOW: a replicate with M + N >= 2^31 (where the 64-bit comparisons would no longer be exact) comes back with M and N as
+ *   computed, -1 in every other word of out and NaN in ap_sum.
+ *   `ws`: mvin_ctr_rank_resample_ws_bytes(n, n_rep) bytes, never NULL.
+ *   Limits: 1 <= n < 2^31; 0 <= n_rep < 2^31 and n_rep * ceil(n / MVIN_CTR_SEG_CAP) < 2^40 (n_rep == 0 launches nothing);
+ *   0 <= n_cuts <= mvin_ctr_rank_resample_max_cuts() (64); with mult: 0 <= n_units < 2^31, n_units <= ld < 2^31.
+ *
+ * Errors (< 0, nothing launched): -2 for sizes outside the limits, max_groups < 0, n_rep > 1 without mult, or a misaligned
+ * pointer (tails / image / ws / out / ap_sum / cut_pos: 8 bytes; mult: 4); -1 for a null required pointer. */
+MVIN_API int mvin_resample_multiplicities(int64_t n_units, uint64_t seed, int64_t first, int64_t n_rep,
+                                          int32_t* mult /* [n_rep, ld] */, int64_t ld, void* stream);
+MVIN_API int64_t mvin_ctr_rank_image_ws_bytes(int64_t n);                       /* < 0: invalid n */
+MVIN_API int mvin_ctr_rank_image(const int32_t* tails /* [n, 2] */, const int32_t* labels, const int32_t* units /* [n] or NULL */,
+                                 int64_t n, void* ws, int32_t* pos_row /* [n] */, int32_t* image /* [n, 2] */, void* stream);
+MVIN_API int mvin_ctr_rank_resample_max_cuts(void);
+MVIN_API int64_t mvin_ctr_rank_resample_ws_bytes(int64_t n, int64_t n_rep);     /* < 0: invalid sizes */
+MVIN_API int mvin_ctr_rank_resample(const int32_t* image /* [n, 2] */, int64_t n, const int32_t* mult /* [n_rep, ld] or NULL */,
+                                    int64_t ld, int64_t n_units, int64_t n_rep, const int64_t* cut_pos /* [n_cuts] */, int n_cuts,
+                                    int max_groups, void* ws, int64_t* out /* [n_rep, 12 + 2 n_cuts] */,
+                                    double* ap_sum /* [n_rep] */, void* stream);
+
 /* ---- user-clustered CTR significance: what the clustered DeLong variance (Obuchowski 1997: the cluster, not the row, is the
  * sampling unit) and the cluster bootstrap are made of (an opt-in extension) --
  * Both calls take a grouping of the n rows into n_clusters clusters: seg_ptr [n_clusters + 1] int64 and `order` int32 [n] or NULL.

@@ -131,6 +131,13 @@ SIGNATURES = {
     "mvin_ctr_operating_points": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "mvin_ctr_threshold_counts_max": (C.c_int, []),
     "mvin_ctr_threshold_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "mvin_resample_multiplicities": (C.c_int, [C.c_int64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvin_ctr_rank_image_ws_bytes": (C.c_int64, [C.c_int64]),
+    "mvin_ctr_rank_image": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4),
+    "mvin_ctr_rank_resample_max_cuts": (C.c_int, []),
+    "mvin_ctr_rank_resample_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "mvin_ctr_rank_resample": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int]
+                               + [C.c_void_p] * 4),
     "mvin_placement_moments_max_models": (C.c_int, []),
     "mvin_placement_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 4),
     "mvin_placement_cluster_moments": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,

@@ -361,6 +361,67 @@ int mvin_ctr_threshold_counts(const float* scores, const int32_t* labels, int64_
                                                         (hipStream_t)stream), who);
 }
 
+int mvin_resample_multiplicities(int64_t n_units, uint64_t seed, int64_t first, int64_t n_rep, int32_t* mult, int64_t ld, void* stream) {
+    const char* who = "mvin_resample_multiplicities";
+    if (n_units < 0 || n_units >= (int64_t(1) << 31) || ld < n_units || ld >= (int64_t(1) << 31))
+        return fail(-2, "%s: n_units=%lld ld=%lld (0 <= n_units < 2^31; n_units <= ld < 2^31)", who, (long long)n_units, (long long)ld);
+    if (first < 0 || n_rep < 0 || first >= (int64_t(1) << 62) || n_rep >= (int64_t(1) << 40) ||
+        (ld > 0 && n_rep > ((int64_t(1) << 62) - 1) / ld))
+        return fail(-2, "%s: first=%lld n_rep=%lld (0 <= first < 2^62, 0 <= n_rep < 2^40, n_rep * ld < 2^62)", who, (long long)first,
+                    (long long)n_rep);
+    if (n_rep > 0 && n_units > 0 && !mult) return fail(-1, "%s: null mult", who);
+    if (reinterpret_cast<uintptr_t>(mult) & 3) return fail(-2, "%s: mult is not 4-byte aligned", who);
+    if (n_rep == 0 || n_units == 0) return 0;
+    return hip_result(mvin::launch_resample_multiplicities(n_units, seed, first, n_rep, mult, ld, (hipStream_t)stream), who);
+}
+
+int64_t mvin_ctr_rank_image_ws_bytes(int64_t n) {
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "mvin_ctr_rank_image_ws_bytes: n=%lld (1 <= n < 2^31)", (long long)n);
+    return mvin::ctr_rank_image_ws_bytes(n);
+}
+
+int mvin_ctr_rank_image(const int32_t* tails, const int32_t* labels, const int32_t* units, int64_t n, void* ws, int32_t* pos_row,
+                        int32_t* image, void* stream) {
+    const char* who = "mvin_ctr_rank_image";
+    if (n < 1 || n >= (int64_t(1) << 31)) return fail(-2, "%s: n=%lld (1 <= n < 2^31)", who, (long long)n);
+    if (!tails || !labels || !ws || !pos_row || !image) return fail(-1, "%s: null tails / labels / ws / pos_row / image", who);
+    if (misaligned8(tails, ws, image)) return fail(-2, "%s: tails / ws / image must be 8-byte aligned", who);
+    return hip_result(mvin::launch_ctr_rank_image(tails, labels, units, n, ws, pos_row, image, (hipStream_t)stream), who);
+}
+
+int mvin_ctr_rank_resample_max_cuts(void) { return mvin::ctr_rank_resample_max_cuts(); }
+
+static bool rank_resample_bad_sizes(int64_t n, int64_t n_rep) {
+    if (n < 1 || n >= (int64_t(1) << 31) || n_rep < 0 || n_rep >= (int64_t(1) << 31)) return true;
+    return n_rep * ((n + MVIN_CTR_SEG_CAP - 1) / MVIN_CTR_SEG_CAP) >= (int64_t(1) << 40);
+}
+
+int64_t mvin_ctr_rank_resample_ws_bytes(int64_t n, int64_t n_rep) {
+    if (rank_resample_bad_sizes(n, n_rep))
+        return fail(-2, "mvin_ctr_rank_resample_ws_bytes: n=%lld n_rep=%lld (1 <= n < 2^31; 0 <= n_rep < 2^31; n_rep * chunks < 2^40)",
+                    (long long)n, (long long)n_rep);
+    return mvin::ctr_rank_resample_ws_bytes(n, n_rep);
+}
+
+int mvin_ctr_rank_resample(const int32_t* image, int64_t n, const int32_t* mult, int64_t ld, int64_t n_units, int64_t n_rep,
+                           const int64_t* cut_pos, int n_cuts, int max_groups, void* ws, int64_t* out, double* ap_sum, void* stream) {
+    const char* who = "mvin_ctr_rank_resample";
+    if (rank_resample_bad_sizes(n, n_rep) || n_cuts < 0 || n_cuts > mvin::ctr_rank_resample_max_cuts() || max_groups < 0)
+        return fail(-2, "%s: n=%lld n_rep=%lld n_cuts=%d max_groups=%d (1 <= n < 2^31; 0 <= n_rep < 2^31; n_rep * chunks < 2^40; "
+                    "0 <= n_cuts <= %d; max_groups >= 0)", who, (long long)n, (long long)n_rep, n_cuts, max_groups,
+                    mvin::ctr_rank_resample_max_cuts());
+    if (mult && (n_units < 0 || n_units >= (int64_t(1) << 31) || ld < n_units || ld >= (int64_t(1) << 31)))
+        return fail(-2, "%s: n_units=%lld ld=%lld (0 <= n_units < 2^31; n_units <= ld < 2^31)", who, (long long)n_units, (long long)ld);
+    if (!mult && n_rep > 1) return fail(-2, "%s: n_rep=%lld without mult (the observed call is one replicate)", who, (long long)n_rep);
+    if (!image || !ws || (n_rep > 0 && (!out || !ap_sum)) || (n_cuts > 0 && !cut_pos))
+        return fail(-1, "%s: null image / ws / out / ap_sum / cut_pos", who);
+    if (misaligned8(image, ws, out, ap_sum) || misaligned8(cut_pos) || (reinterpret_cast<uintptr_t>(mult) & 3))
+        return fail(-2, "%s: image / ws / out / ap_sum / cut_pos must be 8-byte aligned, mult 4-byte aligned", who);
+    if (n_rep == 0) return 0;
+    return hip_result(mvin::launch_ctr_rank_resample(image, n, mult, ld, n_units, n_rep, cut_pos, n_cuts, max_groups, ws, out, ap_sum,
+                                                     (hipStream_t)stream), who);
+}
+
 int mvin_placement_moments_max_models(void) { return mvin::placement_moments_max_models(); }
 
 int mvin_placement_moments(const int64_t* place, int64_t ld, int n_models, const int32_t* labels, int64_t n, int max_groups,

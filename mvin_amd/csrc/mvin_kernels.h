@@ -522,6 +522,16 @@ hipError_t launch_ctr_operating_points(const int32_t* tails, const float* scores
 int ctr_threshold_counts_max();
 hipError_t launch_ctr_threshold_counts(const float* scores, const int32_t* labels, int64_t n, const float* thresholds, int T,
                                        int max_groups, int64_t* out, int64_t* counts, hipStream_t st);
+hipError_t launch_resample_multiplicities(int64_t n_units, uint64_t seed, int64_t first, int64_t n_rep, int32_t* mult, int64_t ld,
+                                          hipStream_t st);     // resampled order statistics of a split (mvin_ctr_rank_resample.hip)
+int64_t ctr_rank_image_ws_bytes(int64_t n);
+hipError_t launch_ctr_rank_image(const int32_t* tails, const int32_t* labels, const int32_t* units, int64_t n, void* ws,
+                                 int32_t* pos_row, int32_t* image, hipStream_t st);
+int ctr_rank_resample_max_cuts();
+int64_t ctr_rank_resample_ws_bytes(int64_t n, int64_t n_rep);
+hipError_t launch_ctr_rank_resample(const int32_t* image, int64_t n, const int32_t* mult, int64_t ld, int64_t n_units, int64_t n_rep,
+                                    const int64_t* cut_pos, int n_cuts, int max_groups, void* ws, int64_t* out, double* ap_sum,
+                                    hipStream_t st);
 int64_t ctr_calib_ws_bytes(int64_t n_seg, int64_t seg_len);    // calibration sums and reliability bins (mvin_ctr_calib.hip)
 hipError_t launch_ctr_calib(const float* logits, const int32_t* labels, int64_t n_seg, int64_t seg_len, int64_t ld, double a, double b,
                             double y0, double y1, const float* edges, int n_bins, int max_groups, void* ws, double* out_sums,

@@ -261,11 +261,14 @@ def _curve_thresholds(thresholds, points, who):
     return np.ascontiguousarray(thr, dtype=np.float32)
 
 
-def _operating_part(logits, labels, who):
+def _operating_part(logits, labels, who, keep=None):
     """ops.ctr_tails and ops.ctr_operating_points on the resident logits, enqueued only, into ONE f64 device tensor [13] = thr
     (3), cells (6), ap_sum, counts (3); every integer in it is below 2^31 and every cut an f32, so float64 holds them exactly.
-    Returns the function that copies it back and gives ctr_operating_points' dict."""
+    Returns the function that copies it back and gives ctr_operating_points' dict.  ``keep`` (a dict) receives the device
+    ``tails`` for the rank resampling that follows."""
     tails, counts = ops.ctr_tails(logits, labels)
+    if keep is not None:
+        keep["tails"] = tails
     thr, cells, ap_sum = ops.ctr_operating_points(tails, logits, labels)
     packed = torch.cat([thr.to(torch.float64), cells.reshape(-1).to(torch.float64), ap_sum, counts.to(torch.float64)])
     return lambda: _operating_result(packed.cpu().numpy(), who)
@@ -291,7 +294,81 @@ def _operating_result(packed, who):
             "ks": max(j, 0.0) if j == j else float("nan")}
 
 
-def ctr_operating_points(feeder, data, max_pairs=524288):
+def _rank_level(ci, n_rep, who):
+    """``ci`` of the rank resampling as a level in (0, 1) and ``n_rep`` as an int >= 2; ValueError otherwise."""
+    if isinstance(ci, (bool, np.bool_)) or not isinstance(ci, (int, float, np.integer, np.floating)) or not 0.0 < float(ci) < 1.0:
+        raise ValueError(f"{who}: ci={ci!r}: expected a level in (0, 1) such as 0.95")
+    if int(n_rep) < 2:
+        raise ValueError(f"{who}: n_rep={n_rep}: an interval needs at least two replicates")
+    return float(ci), int(n_rep)
+
+
+def _rank_units(grp, n, who):
+    """The sampling units of the rank resampling: ``(units int32 [n] or None, n_units, by)`` -- the rows themselves (``grp``
+    None), or every row's cluster number in _cluster_grouping's order, which is the order of the per-cluster table
+    ops.resample_sums draws from.  ValueError for fewer than two units."""
+    if grp is None:
+        if n < 2:
+            raise ValueError(f"{who}: {n} row(s): the bootstrap needs at least two units")
+        return None, n, "rows"
+    n_units = int(grp["ids"].size)
+    units = np.empty(n, dtype=np.int32)
+    units[grp["order"]] = np.repeat(np.arange(n_units, dtype=np.int32), np.diff(grp["seg_ptr"]))
+    return units, n_units, grp["by"]
+
+
+def _order_interval(x, level):
+    """The percentile interval of ``x`` by order statistics (numpy.quantile's "lower" / "higher"), which +inf cuts pass through."""
+    x = np.asarray(x, dtype=np.float64)
+    x = x[~np.isnan(x)]
+    if not x.size:
+        return float("nan"), float("nan")
+    a = (1.0 - level) / 2.0
+    return float(np.quantile(x, a, method="lower")), float(np.quantile(x, 1.0 - a, method="higher"))
+
+
+def _rank_note(st, level, n_rep, seed, by, n_units):
+    return {"level": level, "n_rep": n_rep, "seed": int(seed), "by": by, "n_units": n_units, "degenerate": int((~st["ok"]).sum())}
+
+
+def _operating_ci_part(logits, labels, tails, units, n_units, n_rep, seed):
+    """``ci`` of ctr_operating_points, enqueued only: ops.ctr_rank_image, ops.ctr_rank_resample over ``n_rep`` replicates, and
+    per replicate and criterion the OBSERVED tails and logit at the replicate's own best cut (the row at position pos - 1),
+    gathered on the device.  Returns the finisher ``(res, level, by)`` that copies back and writes the keys."""
+    dev = logits.device
+    pos_row, image = ops.ctr_rank_image(tails, labels, None if units is None else torch.from_numpy(units).to(dev))
+    out, ap = ops.ctr_rank_resample(image, n_units=n_units, n_rep=n_rep, seed=seed)
+    pos = out[:, 5:12:3]                                                 # [R, 3]; -1 in an overflowed replicate
+    live = pos > 0
+    row = pos_row.to(torch.int64)[(pos - 1).clamp(min=0)].clamp(min=0)
+    seen = tails.to(torch.int64)[row]                                    # [R, 3, 2]
+    seen = torch.where(live.unsqueeze(-1), seen, torch.zeros_like(seen)) # the empty cut: (0, 0)
+    z = logits[row].to(torch.float64)
+    cut = torch.where(live, z, torch.full_like(z, float("inf")))
+    def finish(res, level, by):
+        o, seen_h, cut_h = out.cpu().numpy(), seen.cpu().numpy(), cut.cpu().numpy()
+        st = ops.rank_resample_stats(o, ap.cpu().numpy())
+        ok = st["ok"]
+        m, n0 = res["n_pos"], res["n_neg"]
+        se, lo, hi = ops.percentile_interval(st["ap"], level)
+        res["ap_se"], res["ap_ci"] = se, (lo, hi)
+        for c, name in enumerate(ops.OPERATING_CRITERIA):
+            own = st[name + "_max"]
+            same = np.array([ops.operating_point_metrics(seen_h[r, c, 0], seen_h[r, c, 1], m, n0)[name] if ok[r] else np.nan
+                             for r in range(o.shape[0])])
+            gap = (own - same)[ok]
+            gap = gap[np.isfinite(gap)]
+            b = res["best"][name]
+            _, vlo, vhi = ops.percentile_interval(own, level)
+            b["value_ci"] = (vlo, vhi)
+            b["threshold_ci"] = _order_interval(cut_h[ok, c], level)
+            b["optimism"] = float(gap.mean()) if gap.size else float("nan")
+            b["value_corrected"] = b["value"] - b["optimism"]
+        res["rank_ci"] = _rank_note(st, level, o.shape[0], seed, by, n_units)
+    return finish
+
+
+def ctr_operating_points(feeder, data, max_pairs=524288, ci=None, cluster=None, n_rep=2000, seed=1):
     """Where to cut a split's logits, and its average precision, as ONE population (an extension: the reference reports acc
     and F1 at the fixed cut 0.5 only, which means little under the ranking objectives).  The split is scored once; then ONE
     ops.ctr_tails launch sequence, ONE ops.ctr_operating_points and one copy back.  Returns ``{"ap", "n_pos", "n_neg", "best":
@@ -302,11 +379,36 @@ def ctr_operating_points(feeder, data, max_pairs=524288):
     ``ap`` is sklearn's average_precision_score of the LOGITS.  Tail counts, AP and the curves do not change under an increasing
     map, with one exception: the f32 sigmoid merges distinct large logits into equal scores, so ``ap`` can differ from an AP
     computed on the sigmoid scores ``auc`` is counted on.  NaN for ``ap`` and +inf cuts when the split has no valid positive.
-    ValueError for an empty split or one with a non-finite logit or a label other than 0 / 1."""
-    if np.asarray(data).shape[0] == 0:
+    ValueError for an empty split or one with a non-finite logit or a label other than 0 / 1.
+    ``ci`` (a level such as 0.95; None: the dict and the launches above, nothing more) adds bootstrap numbers from ``n_rep``
+    replicates of ``seed`` (ops.ctr_rank_image once, then ops.resample_multiplicities and ops.ctr_rank_resample, which only
+    scan): ``ap_se`` and ``ap_ci``; per criterion ``value_ci`` (the criterion at each replicate's OWN best cut), ``threshold_ci``
+    (that cut's logit; +inf for the empty cut; order statistics), ``optimism`` = the mean over the replicates of (the criterion
+    at the replicate's best cut on the replicate - the criterion at that same cut on the split as observed) -- how much a
+    maximum flatters itself -- and ``value_corrected`` = value - optimism; and ``rank_ci`` = {"level", "n_rep", "seed", "by",
+    "n_units", "degenerate"} (degenerate: the replicates left out for an empty class).  WHAT THE NUMBERS ASSUME: percentile
+    intervals; the units are independent draws.  With ``cluster=None`` the units are the rows, which is on the narrow side
+    when a user's rows are correlated; ``cluster="user"`` or an integer array of one id per row draws whole clusters -- the
+    clusters ctr_report(cluster=) draws, replicate for replicate.  ValueError: ``cluster`` without ``ci``, a level outside
+    (0, 1), fewer than two replicates or fewer than two units."""
+    who = "ctr_operating_points"
+    cols = np.asarray(data)
+    if cols.shape[0] == 0:
         raise ValueError("ctr_operating_points: empty split")
+    if ci is None:
+        if cluster is not None:
+            raise ValueError(f"{who}: cluster= changes the intervals of ci=; pass a level such as ci=0.95")
+        logits, _, labels = _score_split(feeder, data, None, max_pairs, logits=True)
+        return _operating_part(logits, labels, who)()
+    level, R = _rank_level(ci, n_rep, who)
+    units, n_units, by = _rank_units(_cluster_grouping(cluster, cols, who), cols.shape[0], who)
     logits, _, labels = _score_split(feeder, data, None, max_pairs, logits=True)
-    return _operating_part(logits, labels, "ctr_operating_points")()
+    keep = {}
+    operating = _operating_part(logits, labels, who, keep)
+    boot = _operating_ci_part(logits, labels, keep["tails"], units, n_units, R, seed)
+    res = operating()                                           # refuses a split with invalid rows
+    boot(res, level, by)
+    return res
 
 
 def pick_threshold(feeder, data, criterion="f1", max_pairs=524288):
@@ -321,11 +423,11 @@ def pick_threshold(feeder, data, criterion="f1", max_pairs=524288):
     return OperatingPoint(criterion, b["threshold"], b["tp"], b["fp"], res["n_pos"], res["n_neg"], b["value"])
 
 
-def _curves_part(logits, labels, thr, who):
+def _curves_part(logits, labels, thr, who, keep=None):
     """The ``curves`` option of ctr_report, and ctr_curves: ONE ops.ctr_threshold_counts call at the f32 thresholds ``thr``, then
     _operating_part.  The finisher writes ``ap``, ``operating_points`` and ``curves``."""
     out, counts = ops.ctr_threshold_counts(logits, labels, torch.from_numpy(thr).to(logits.device))
-    operating = _operating_part(logits, labels, who)
+    operating = _operating_part(logits, labels, who, keep)
     def finish(rep):
         op = operating()
         cv = ops.curves_from_counts(thr, out.cpu().numpy(), counts.cpu().numpy())
@@ -358,7 +460,7 @@ def _report_threshold(threshold):
 
 
 def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=524288, ci=None, cluster=None, n_rep=2000, seed=1,
-               threshold=None, curves=None):
+               threshold=None, curves=None, rank_ci=False):
     """The CTR report of a split as ONE population (an extension: the reference reports none of these but the per-batch means
     of auc / acc / f1).  The split is scored once (logits and sigmoid scores of the same forward calls); everything else is
     reductions over the resident buffers and one copy back per result tensor.  Returns a dict:
@@ -397,7 +499,13 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     (True: 100 cuts uniform in probability; an int: ctr_curves' ``points``; an array: logit thresholds; None: nothing more) adds
     ``"ap"``, ``"operating_points"`` (ctr_operating_points' dict) and ``"curves"`` (ctr_curves' dict without "ap"), all on the
     LOGITS: see ctr_operating_points for how ``ap`` relates to the sigmoid scores ``auc`` is counted on.  With both None the
-    dict and the launches are exactly those without the two keywords."""
+    dict and the launches are exactly those without the two keywords.
+    ``rank_ci=True`` (it needs ``ci``; False: nothing more) adds percentile bootstrap intervals of the order statistics the two
+    options above report, from ``n_rep`` replicates of ``seed`` whose units follow ``cluster`` (the rows, or the clusters
+    ``cluster_ci`` draws, replicate for replicate; ops.ctr_rank_image once, then ops.ctr_rank_resample): ``at_threshold``
+    gains ``acc_ci``, ``f1_ci``, ``precision_ci``, ``recall_ci`` with the cut HELD FIXED (the positions above it: tp + fp of
+    the launch above), and with ``curves`` the report gains ``ap_se`` / ``ap_ci``; ``rank_ci`` = ctr_operating_points' note.
+    With ``cluster=None`` the rows are taken as independent, which is on the narrow side."""
     cols = np.asarray(data)
     n = cols.shape[0]
     if n == 0:
@@ -405,9 +513,15 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     # 1. the options, on the host alone
     cut_at = None if threshold is None else _report_threshold(threshold)
     curve_thr = _report_curve_thresholds(curves)
+    if rank_ci and ci is None:
+        raise ValueError("ctr_report: rank_ci=True adds intervals at the level of ci=; pass a level such as ci=0.95")
     grp = _cluster_grouping(cluster, cols, "ctr_report")
     if grp is not None and ci is None:
         raise ValueError("ctr_report: cluster= changes the intervals of ci=; pass a level such as ci=0.95")
+    rank_units = rank_level = rank_rep = None
+    if rank_ci:
+        rank_level, rank_rep = _rank_level(ci, n_rep, "ctr_report")
+        rank_units = _rank_units(grp, n, "ctr_report")
     a, b = (1.0, 0.0) if calibration is None else (float(calibration[0]), float(calibration[1]))
     edges = ops.calib_edges(n_bins, a, b)                       # refuses a <= 0
     ug = None
@@ -427,8 +541,10 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     fin_ci, place = _report_ci(scores, labels, ci) if ci is not None else (skip, None)
     fin_cluster = skip if grp is None else _report_cluster(place, logits, labels, a, b, grp, ucounts if grp["users"] else None, ci,
                                                            int(n_rep), seed)
-    fin_at = _report_at_threshold(logits, labels, cut_at, calibration is not None, a, b) if cut_at is not None else skip
-    fin_curves = _curves_part(logits, labels, curve_thr, "ctr_report") if curve_thr is not None else skip
+    keep = {} if rank_units is not None else None
+    fin_at = _report_at_threshold(logits, labels, cut_at, calibration is not None, a, b, keep) if cut_at is not None else skip
+    fin_curves = _curves_part(logits, labels, curve_thr, "ctr_report", keep) if curve_thr is not None else skip
+    fin_rank = _report_rank_ci(logits, labels, keep, rank_units, rank_level, rank_rep, seed) if keep else skip
     # ... then their finishers, in the order of the report's keys
     rep = {}
     counts = head(rep)
@@ -439,7 +555,29 @@ def ctr_report(feeder, data, calibration=None, n_bins=10, gauc=True, max_pairs=5
     fin_cluster(rep, var_rows)
     fin_at(rep)
     fin_curves(rep)
+    fin_rank(rep)
     return rep
+
+
+def _report_rank_ci(logits, labels, keep, rank_units, level, n_rep, seed):
+    """``rank_ci``: ops.ctr_rank_image of the tails (_curves_part's, or one ops.ctr_tails of its own) and ops.ctr_rank_resample
+    with the threshold's cut held at the position tp + fp of _report_at_threshold's cells, which stays on the device."""
+    units, n_units, by = rank_units
+    tails = keep["tails"] if "tails" in keep else ops.ctr_tails(logits, labels)[0]
+    _, image = ops.ctr_rank_image(tails, labels, None if units is None else torch.from_numpy(units).to(logits.device))
+    cut_pos = keep["cells"].sum(dim=1) if "cells" in keep else None       # int64 [1]
+    out, ap = ops.ctr_rank_resample(image, n_units=n_units, n_rep=n_rep, seed=seed, cut_pos=cut_pos)
+    def finish(rep):
+        o, s = out.cpu().numpy(), ap.cpu().numpy()
+        summ = ops.rank_resample_summary(o, s, level)
+        if cut_pos is not None:
+            for k in ("acc", "f1", "precision", "recall"):
+                rep["at_threshold"][k + "_ci"] = (summ["cuts"][0][k]["lo"], summ["cuts"][0][k]["hi"])
+        if "tails" in keep:
+            rep["ap_se"], rep["ap_ci"] = summ["ap"]["se"], (summ["ap"]["lo"], summ["ap"]["hi"])
+        rep["rank_ci"] = {"level": level, "n_rep": n_rep, "seed": int(seed), "by": by, "n_units": n_units,
+                          "degenerate": summ["degenerate"]}
+    return finish
 
 
 def _report_curve_thresholds(curves):
@@ -535,9 +673,12 @@ def _report_cluster(place, logits, labels, a, b, grp, ucounts, level, n_rep, see
     return finish
 
 
-def _report_at_threshold(logits, labels, cut_at, calibrated, a, b):
-    """``threshold``: the split at the prediction z >= ``cut_at``, ONE ops.ctr_threshold_counts with one threshold."""
+def _report_at_threshold(logits, labels, cut_at, calibrated, a, b, keep=None):
+    """``threshold``: the split at the prediction z >= ``cut_at``, ONE ops.ctr_threshold_counts with one threshold.  ``keep`` (a
+    dict) receives the device ``cells`` [1, 2] for the rank resampling that follows."""
     cells, totals = ops.ctr_threshold_counts(logits, labels, torch.tensor([cut_at], dtype=torch.float32, device=logits.device))
+    if keep is not None:
+        keep["cells"] = cells
     def finish(rep):
         c, tc = cells.cpu().numpy()[0], totals.cpu().numpy()
         rep["at_threshold"] = _cut_entry(cut_at, c[0], c[1], tc[0], tc[1])[0]
@@ -595,7 +736,7 @@ def ctr_cluster_columns(K, with_gauc):
     return lay
 
 
-def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288, cluster=None):
+def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288, cluster=None, ap=False):
     """CTR numbers of 2 to 8 models (``feeders``) on ONE split with their uncertainty, and every pair compared on the same rows.
     Each model is scored once (logits and sigmoid scores of the same forward calls); its placements (ops.ctr_placements on the
     sigmoid scores) go into one [K, n] buffer, ONE ops.placement_moments launch gives DeLong's covariance matrix of the K AUCs
@@ -623,8 +764,16 @@ def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288,
       * the dict gains ``cluster`` = {"by", "n_clusters", "max_rows"}.
     These assume in turn that clusters are independent of one another and numerous enough for a normal approximation: tens of
     clusters give wide and shaky intervals, which is why ``n_clusters`` is reported.  Intervals for f1 / ece / mce are not built.
+    ``ap=True`` (False: nothing more) compares the order statistics of the LOGITS under ONE shared table of bootstrap
+    multiplicities per replicate (ops.ctr_tails and ops.ctr_rank_image per model, then ops.ctr_rank_resample over all models;
+    the units are the rows or, with ``cluster``, the clusters above, replicate for replicate): every model gains ``ap`` (its
+    average precision), ``ap_se``, ``ap_ci`` (percentile) and ``auc_se_boot``, the bootstrap counterpart of ``auc_se`` as a
+    cross-check; every pair gains ``"ap"`` and ``"f1_max"`` (the best F1 over all cuts) = {"diff", "lo", "hi", "p", "p_holm"}:
+    the observed difference a - b, the percentile interval of the replicates' paired differences d_r, p = min(1, 2 (1 +
+    min(#{d_r <= 0}, #{d_r >= 0})) / (R + 1)) and Holm over the pairs of the call.  The same assumptions as above: percentile
+    intervals, independent units, rows on the narrow side.
     ValueError: fewer than 2 or more than 8 feeders, a label other than 0 / 1, fewer than two rows of a class, a non-finite
-    score, a ``cluster`` that is none of the above or gives fewer than two clusters."""
+    score, a ``cluster`` that is none of the above or gives fewer than two clusters, fewer than two replicates with ``ap``."""
     feeders = list(feeders)
     K = len(feeders)
     if not 2 <= K <= 8:
@@ -643,7 +792,11 @@ def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288,
     with_gauc = grp is not None and grp["users"]
     if with_gauc and grp["max_rows"] > ops.CTR_SEG_CAP:
         raise ValueError(f"compare_ctr: a user has {grp['max_rows']} rows in the split; per-user AUC takes at most {ops.CTR_SEG_CAP}")
+    rank_units = _rank_units(grp, n, "compare_ctr") if ap else None
+    if ap and R < 2:
+        raise ValueError(f"compare_ctr: n_rep={n_rep}: an interval needs at least two replicates")
     dev = feeders[0].model.device
+    images = []
     place = torch.empty((K, n), dtype=torch.int64, device=dev)
     pcounts = torch.empty((K, 4), dtype=torch.int64, device=dev)
     tables, labels, ucounts = [], None, []
@@ -655,6 +808,9 @@ def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288,
         tables.append(ctr_row_table(logits, labels))
         if with_gauc:
             ucounts.append(_user_counts(logits, labels, od, ptr, grp["max_rows"]))
+        if ap:
+            units = None if rank_units[0] is None else torch.from_numpy(rank_units[0]).to(dev)
+            images.append(ops.ctr_rank_image(ops.ctr_tails(logits, labels)[0], labels, units)[1])
     moments = ops.placement_moments(place, labels)
     if grp is None:
         lay = _row_columns(K)
@@ -668,7 +824,37 @@ def compare_ctr(feeders, data, level=0.95, n_rep=2000, seed=1, max_pairs=524288,
         f64s, i32s = _compare_cluster_launches(grp, place, labels, tables, ucounts, lay, R, seed)
     as_f64 = lambda x: x.view(torch.float64)                     # noqa: E731  (int64 words through the one packed copy)
     host, (o_c, b_c) = _copy_back(f64s + [as_f64(x) for x in (*moments, pcounts, *ucounts)], i32s)
-    return _compare_result(host, o_c, b_c, lay, grp, K, n, level, R)
+    if not ap:
+        return _compare_result(host, o_c, b_c, lay, grp, K, n, level, R)
+    observed = [ops.ctr_rank_resample(im) for im in images]
+    boots = ops.ctr_rank_resample(images, n_units=rank_units[1], n_rep=R, seed=seed)
+    res = _compare_result(host, o_c, b_c, lay, grp, K, n, level, R)
+    _compare_rank(res, observed, boots, K, float(level), R, seed, rank_units)
+    return res
+
+
+def _compare_rank(res, observed, boots, K, level, R, seed, rank_units):
+    """``ap=True`` of compare_ctr: the models' and pairs' keys from the observed and the resampled ops.ctr_rank_resample outputs
+    (device tensor pairs per model), all replicates under one table of multiplicities."""
+    host = lambda pair: ops.rank_resample_stats(pair[0].cpu().numpy(), pair[1].cpu().numpy())      # noqa: E731
+    obs, st = [host(p) for p in observed], [host(p) for p in boots]
+    for k, row in enumerate(res["models"]):
+        se, lo, hi = ops.percentile_interval(st[k]["ap"], level)
+        row["ap"], row["ap_se"], row["ap_ci"] = float(obs[k]["ap"][0]), se, (lo, hi)
+        row["auc_se_boot"] = ops.percentile_interval(st[k]["auc"], level)[0]
+    pair_list = ctr_compare_pairs(K)
+    for key in ("ap", "f1_max"):
+        entries = []
+        for a, b in pair_list:
+            d = st[a][key] - st[b][key]                         # NaN where either replicate is degenerate
+            _, lo, hi = ops.percentile_interval(d, level)
+            entries.append({"diff": float(obs[a][key][0] - obs[b][key][0]), "lo": lo, "hi": hi, "p": ops.paired_bootstrap_pvalue(d)})
+        holm = ops.holm_adjust(np.array([e["p"] for e in entries]))
+        for j, (pair, e) in enumerate(zip(pair_list, entries)):
+            res["pairs"][pair][key] = dict(e, p_holm=float(holm[j]))
+    degenerate = int((~np.logical_and.reduce([s["ok"] for s in st])).sum())
+    res["rank_ci"] = {"level": level, "n_rep": R, "seed": int(seed), "by": rank_units[2], "n_units": rank_units[1],
+                      "degenerate": degenerate}
 
 
 def _row_columns(K):

@@ -756,6 +756,239 @@ def curves_from_counts(thresholds, out, counts):
     return {"roc": {"fpr": fpr, "tpr": tpr}, "pr": {"precision": precision, "recall": tpr.copy()}}
 
 
+RANK_RESAMPLE_WORDS = 12                              # out's words before the fixed cuts: M, N, u2, 3 x (tp, fp, pos)
+RANK_RESAMPLE_MULT_BYTES = 256 << 20                  # ctr_rank_resample's default budget for one call's multiplicities and workspace
+
+
+def resample_multiplicities(n_units, n_rep, seed=1, first=0, device=None, out=None):
+    """mvin_resample_multiplicities: ``mult`` int32 [n_rep, n_units] on the device, ``mult[r - first][i]`` = how often replicate r
+    of ``seed`` draws unit i -- the histogram of resample_sums' bootstrap draws over ``n_units`` rows, so replicate r here
+    resamples the units replicate r of a resample_sums call over a table of ``n_units`` rows does.  Every row sums to n_units.
+    ``out``: an int32 [n_rep, >= n_units] tensor with dense rows to write into (columns beyond n_units are left alone).
+    Enqueues only."""
+    lib = _lib.load()
+    n_units, n_rep, seed, first = int(n_units), int(n_rep), int(seed), int(first)
+    if not 0 <= n_units < 1 << 31 or n_rep < 0 or first < 0:
+        raise ValueError(f"n_units={n_units} n_rep={n_rep} first={first}: expected 0 <= n_units < 2^31 and n_rep, first >= 0")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed={seed}: expected an unsigned 64-bit value")
+    if out is None:
+        out = torch.empty((n_rep, n_units), dtype=I32, device=device if device is not None else "cuda")
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != I32 or out.dim() != 2 or out.shape[0] != n_rep \
+            or out.shape[1] < n_units or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"resample_multiplicities: out: expected a device int32 [{n_rep}, >= {n_units}] tensor with dense rows")
+    ld = out.stride(0) if n_rep > 1 else max(out.shape[1], 1)
+    if ld < out.shape[1]:
+        raise ValueError("resample_multiplicities: out: rows overlap")
+    if n_rep and n_units:
+        _lib.check(lib.mvin_resample_multiplicities(n_units, C.c_uint64(seed), first, n_rep, _p(out), ld, _stream()),
+                   "mvin_resample_multiplicities")
+    return out[:, :n_units]
+
+
+def ctr_rank_image(tails, labels, units=None):
+    """mvin_ctr_rank_image: the split in descending score order, from ctr_tails' ``tails`` int32 [n, 2] and ``labels`` int32 [n].
+    ``units`` int32 [n] names every row's sampling unit (its cluster); None: the row is its own unit.  Returns device tensors
+    ``(pos_row int32 [n], image int32 [n, 2])``: the row at every position and (its unit, info) with info bit 0 = the label and
+    bit 1 = the last position of a tie group; the positions behind the valid rows hold -1 and (-1, 0).  Which row of a tie group
+    sits where inside it is not specified (nothing downstream depends on it).  Enqueues only.  ValueError for anything but
+    matching contiguous device tensors."""
+    lib = _lib.load()
+    who = "ctr_rank_image"
+    if not isinstance(tails, torch.Tensor) or not tails.is_cuda or tails.dtype != I32 or tails.dim() != 2 or tails.shape[1] != 2 \
+            or not tails.is_contiguous():
+        raise ValueError(f"{who}: tails: expected a contiguous device int32 [n, 2] tensor")
+    n, dev = tails.shape[0], tails.device
+    if not 1 <= n < 1 << 31:
+        raise ValueError(f"n={n}: {who} takes 1 <= n < 2^31 rows")
+    _curve_out(labels, "labels", I32, (n,), dev, who)
+    if units is not None:
+        _curve_out(units, "units", I32, (n,), dev, who)
+    pos_row = torch.empty((n,), dtype=I32, device=dev)
+    image = torch.empty((n, 2), dtype=I32, device=dev)
+    ws = torch.empty((int(lib.mvin_ctr_rank_image_ws_bytes(n)),), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mvin_ctr_rank_image(_p(tails), _p(labels), _p(units), n, _p(ws), _p(pos_row), _p(image), _stream()),
+               "mvin_ctr_rank_image")
+    return pos_row, image
+
+
+def ctr_rank_resample_max_cuts():
+    """mvin_ctr_rank_resample_max_cuts: the fixed cuts one mvin_ctr_rank_resample call takes (64)."""
+    return int(_lib.load().mvin_ctr_rank_resample_max_cuts())
+
+
+def ctr_rank_resample(image, n_units=None, n_rep=0, seed=1, first=0, cut_pos=None, mult=None, max_groups=0, budget_bytes=None):
+    """mvin_ctr_rank_resample over ctr_rank_image's ``image``: per replicate the weighted class totals, twice the weighted
+    Mann-Whitney U, the best cut by F1 / accuracy / Youden as (tp, fp, pos) and the cells (TP, FP) above the fixed cuts
+    ``cut_pos`` (positions, a list of ints or an int64 tensor), plus the average-precision sum.  Three forms:
+      * ``n_units=None``: the observed split (every weight 1), one replicate;
+      * ``mult`` int32 [R, n_units] on the device: these multiplicities;
+      * otherwise the replicates ``first .. first + n_rep - 1`` of ``seed`` (resample_multiplicities), cut into calls so that one
+        call's multiplicities and workspace stay within ``budget_bytes`` (RANK_RESAMPLE_MULT_BYTES) -- the rule makes that
+        bit-neutral.
+    Returns device tensors ``(out int64 [R, 12 + 2 n_cuts], ap_sum f64 [R])``; a replicate whose weights sum to 2^31 or more has
+    -1 behind its totals and NaN.  The same bits for every ``max_groups``.  Enqueues only."""
+    lib = _lib.load()
+    who = "ctr_rank_resample"
+    if isinstance(image, (list, tuple)):                    # several splits' images of the SAME units: one multiplicity table
+        if n_units is None or mult is not None or not image:
+            raise ValueError(f"{who}: a list of images takes n_units and the seeded form")
+        if any(not isinstance(t, torch.Tensor) or t.shape != image[0].shape or t.device != image[0].device for t in image):
+            raise ValueError(f"{who}: the images of a list must have one shape and one device")
+        n_rep, first = int(n_rep), int(first)
+        if n_rep < 0 or first < 0:
+            raise ValueError(f"n_rep={n_rep} first={first}: expected values >= 0")
+        budget = RANK_RESAMPLE_MULT_BYTES if budget_bytes is None else int(budget_bytes)
+        n0 = image[0].shape[0]
+        per_rep = 4 * max(int(n_units), 1) + max(int(lib.mvin_ctr_rank_resample_ws_bytes(n0, 1)), 0)
+        step = max(1, budget // per_rep)
+        parts = [[] for _ in image]
+        buf = torch.empty((min(step, n_rep), max(int(n_units), 1)), dtype=I32, device=image[0].device) if n_rep else None
+        for r0 in range(0, n_rep, step):
+            R = min(step, n_rep - r0)
+            resample_multiplicities(n_units, R, seed=seed, first=first + r0, out=buf[:R])
+            for k, im in enumerate(image):
+                parts[k].append(ctr_rank_resample(im, n_units=n_units, cut_pos=cut_pos, mult=buf[:R], max_groups=max_groups))
+        if not n_rep:
+            return [ctr_rank_resample(im, n_units=n_units, n_rep=0, cut_pos=cut_pos) for im in image]
+        return [(torch.cat([o for o, _ in p]), torch.cat([a for _, a in p])) for p in parts]
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dtype != I32 or image.dim() != 2 or image.shape[1] != 2 \
+            or not image.is_contiguous():
+        raise ValueError(f"{who}: image: expected a contiguous device int32 [n, 2] tensor")
+    n, dev = image.shape[0], image.device
+    if not 1 <= n < 1 << 31:
+        raise ValueError(f"n={n}: {who} takes 1 <= n < 2^31 positions")
+    max_groups = int(max_groups)
+    if max_groups < 0:
+        raise ValueError(f"max_groups={max_groups}: expected >= 0")
+    if cut_pos is None:
+        cut_pos = []
+    if not isinstance(cut_pos, torch.Tensor):
+        cut_pos = torch.tensor([int(q) for q in cut_pos], dtype=torch.int64, device=dev)
+    if cut_pos.device != dev or cut_pos.dtype != torch.int64 or cut_pos.dim() != 1 or not cut_pos.is_contiguous():
+        raise ValueError(f"{who}: cut_pos: expected ints or a contiguous int64 [n_cuts] tensor on {dev}")
+    n_cuts = cut_pos.numel()
+    if n_cuts > ctr_rank_resample_max_cuts():
+        raise ValueError(f"{who}: {n_cuts} cuts: one call takes at most {ctr_rank_resample_max_cuts()}")
+    W = RANK_RESAMPLE_WORDS + 2 * n_cuts
+
+    def launch(m, ld, nu, R, out, ap):
+        nws = lib.mvin_ctr_rank_resample_ws_bytes(n, R)
+        if nws < 0:
+            _lib.check(int(nws), "mvin_ctr_rank_resample_ws_bytes")
+        ws = torch.empty((int(nws),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.mvin_ctr_rank_resample(_p(image), n, _p(m), ld, nu, R, _p(cut_pos) if n_cuts else None, n_cuts, max_groups,
+                                              _p(ws), _p(out), _p(ap), _stream()), "mvin_ctr_rank_resample")
+
+    if n_units is None:
+        if mult is not None:
+            raise ValueError(f"{who}: mult needs n_units")
+        out = torch.empty((1, W), dtype=torch.int64, device=dev)
+        ap = torch.empty((1,), dtype=torch.float64, device=dev)
+        launch(None, 0, 0, 1, out, ap)
+        return out, ap
+    n_units = int(n_units)
+    if not 0 <= n_units < 1 << 31:
+        raise ValueError(f"n_units={n_units}: expected 0 <= n_units < 2^31")
+    if mult is not None:
+        if not isinstance(mult, torch.Tensor) or mult.device != dev or mult.dtype != I32 or mult.dim() != 2 or mult.shape[1] < n_units \
+                or not mult.is_contiguous():
+            raise ValueError(f"{who}: mult: expected a contiguous int32 [R, >= {n_units}] tensor on {dev}")
+        R = mult.shape[0]
+        out = torch.empty((R, W), dtype=torch.int64, device=dev)
+        ap = torch.empty((R,), dtype=torch.float64, device=dev)
+        if R:
+            launch(mult, max(mult.shape[1], 1), n_units, R, out, ap)
+        return out, ap
+    n_rep, first = int(n_rep), int(first)
+    if n_rep < 0 or first < 0:
+        raise ValueError(f"n_rep={n_rep} first={first}: expected values >= 0")
+    budget = RANK_RESAMPLE_MULT_BYTES if budget_bytes is None else int(budget_bytes)
+    per_rep = 4 * max(n_units, 1) + int(lib.mvin_ctr_rank_resample_ws_bytes(n, 1))
+    step = max(1, budget // per_rep)
+    out = torch.empty((n_rep, W), dtype=torch.int64, device=dev)
+    ap = torch.empty((n_rep,), dtype=torch.float64, device=dev)
+    buf = torch.empty((min(step, n_rep), max(n_units, 1)), dtype=I32, device=dev) if n_rep else None
+    for r0 in range(0, n_rep, step):
+        R = min(step, n_rep - r0)
+        m = buf[:R]
+        resample_multiplicities(n_units, R, seed=seed, first=first + r0, out=m)
+        launch(m, max(n_units, 1), n_units, R, out[r0:r0 + R], ap[r0:r0 + R])
+    return out, ap
+
+
+def rank_resample_stats(out, ap_sum):
+    """Per replicate, in float64 on the host, from ctr_rank_resample's ``out`` [R, 12 + 2 n_cuts] and ``ap_sum`` [R]: a dict of
+    arrays [R] -- ``ap`` = ap_sum / M, ``auc`` = u2 / (2 M N), per criterion of OPERATING_CRITERIA its value at the replicate's
+    best cut (``f1_max``, ``acc_max``, ``youden_max``, by operating_point_metrics' conventions) and its position (``f1_pos``,
+    ...), ``ok`` = the replicate has both classes and did not overflow (the rest is NaN where it is False) -- and ``cuts``: per
+    fixed cut a dict of ``acc`` / ``f1`` / ``precision`` / ``recall`` arrays [R]."""
+    o = np.asarray(out).astype(np.int64)
+    s = np.asarray(ap_sum, dtype=np.float64).reshape(-1)
+    if o.ndim != 2 or o.shape[1] < RANK_RESAMPLE_WORDS or (o.shape[1] - RANK_RESAMPLE_WORDS) % 2 or o.shape[0] != s.size:
+        raise ValueError(f"expected out [R, 12 + 2 n_cuts] and ap_sum [R], got {o.shape} and {s.shape}")
+    R, n_cuts = o.shape[0], (o.shape[1] - RANK_RESAMPLE_WORDS) // 2
+    ok = (o[:, 0] > 0) & (o[:, 1] > 0) & (o[:, 2] >= 0) & np.isfinite(s)
+    nan = np.full(R, np.nan)
+    res = {"ok": ok, "ap": nan.copy(), "auc": nan.copy(), "cuts": [{k: nan.copy() for k in ("acc", "f1", "precision", "recall")}
+                                                                   for _ in range(n_cuts)]}
+    for name in OPERATING_CRITERIA:
+        res[name + "_max"] = nan.copy()
+        res[name + "_pos"] = np.full(R, -1, dtype=np.int64)
+    for r in np.flatnonzero(ok):
+        M, N = int(o[r, 0]), int(o[r, 1])
+        res["ap"][r] = s[r] / np.float64(M)
+        res["auc"][r] = np.float64(int(o[r, 2])) / (2.0 * np.float64(M) * np.float64(N))
+        for c, name in enumerate(OPERATING_CRITERIA):
+            tp, fp, pos = (int(v) for v in o[r, 3 + 3 * c:6 + 3 * c])
+            res[name + "_max"][r] = operating_point_metrics(tp, fp, M, N)[name]
+            res[name + "_pos"][r] = pos
+        for k in range(n_cuts):
+            met = operating_point_metrics(int(o[r, 12 + 2 * k]), int(o[r, 13 + 2 * k]), M, N)
+            for key in ("acc", "f1", "precision", "recall"):
+                res["cuts"][k][key][r] = met[key]
+    return res
+
+
+def percentile_interval(x, level):
+    """se (ddof 1) and the percentile interval of the finite values of x: (se, lo, hi), NaN where undefined."""
+    x = np.asarray(x, dtype=np.float64)
+    x = x[np.isfinite(x)]
+    a = (1.0 - float(level)) / 2.0
+    lo, hi = (float(np.quantile(x, a)), float(np.quantile(x, 1.0 - a))) if x.size else (float("nan"), float("nan"))
+    return (float(np.std(x, ddof=1)) if x.size > 1 else float("nan")), lo, hi
+
+
+def rank_resample_summary(out, ap_sum, level=0.95):
+    """Intervals from ctr_rank_resample's replicates, on the host in float64 (rank_resample_stats per replicate): ``{"ap", "auc",
+    "f1_max", "acc_max", "youden_max": {"se", "lo", "hi"}, "cuts": [{"acc", "f1", "precision", "recall": {"se", "lo", "hi"}}],
+    "degenerate"}`` -- ``se`` the sample standard deviation (ddof 1) of the replicate values, ``lo`` / ``hi`` their percentiles
+    at (1 - level) / 2 and 1 - (1 - level) / 2, ``degenerate`` the replicates left out because a class was empty (M == 0 or
+    N == 0) or the weights overflowed."""
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level={level}: expected a value in (0, 1)")
+    st = rank_resample_stats(out, ap_sum)
+
+    def box(x):
+        se, lo, hi = percentile_interval(x, level)
+        return {"se": se, "lo": lo, "hi": hi}
+
+    res = {k: box(st[k]) for k in ("ap", "auc") + tuple(c + "_max" for c in OPERATING_CRITERIA)}
+    res["cuts"] = [{k: box(v) for k, v in cut.items()} for cut in st["cuts"]]
+    res["degenerate"] = int((~st["ok"]).sum())
+    return res
+
+
+def paired_bootstrap_pvalue(d):
+    """The two-sided bootstrap p-value of paired replicate differences ``d`` [R] (NaNs left out): ``min(1, 2 (1 + min(#{d <= 0},
+    #{d >= 0})) / (R + 1))`` -- never 0.  NaN with no replicate."""
+    d = np.asarray(d, dtype=np.float64).reshape(-1)
+    d = d[np.isfinite(d)]
+    if not d.size:
+        return float("nan")
+    return float(min(1.0, 2.0 * (1.0 + min((d <= 0).sum(), (d >= 0).sum())) / (d.size + 1.0)))
+
+
 def placement_moments_max_models():
     """mvin_placement_moments_max_models: the models one mvin_placement_moments call takes (8)."""
     return int(_lib.load().mvin_placement_moments_max_models())
