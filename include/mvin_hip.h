@@ -1422,6 +1422,62 @@ MVIN_API int mvin_rank_head_offset(const float* user_o, const float* item_emb, c
                                    int64_t n_groups, int G, int D, int mode, float scale, float* scores, float* dscore, float* du,
                                    float* di, float* loss_accum, int64_t* counts /* [2] or NULL */, void* stream);
 
+/* ---- matrix factorisation (MF): the baseline the paper's tables compare against (the reference's KGAT/BPRMF.py) and a learned
+ * retrieval tower, score(u, i) = <U[u], V[i]> -- the quantity mvin_mips_topk ranks.  An opt-in extension; no other call changes.
+ * mvin_mf_head: mvin_rank_head reading its rows by id from the tables instead of from gathered buffers.  U f32 [n_user, D] and
+ * V f32 [n_item, D] contiguous; users int64 [n_groups]; items int64 [B], B = n_groups * G, group-major, slot 0 the positive (the
+ * layout of data_prep.rank_groups); valid f32 [B] or NULL; labels f32 [B] or NULL.  Every id is clamped into its table for
+ * every read.  Row g*G + j pairs U[users[g]] with V[items[g*G + j]].
+ * mode MVIN_RANK_SOFTMAX / MVIN_RANK_BPR (G in 2..64): mvin_rank_head's loss, dscore and counts; slot 0 is valid whatever valid
+ *     says.
+ * mode MVIN_MF_BCE (G = 1, labels required; the objective BPRMF.py is trained with): with s the row's score and y its label
+ *     l = max(s, 0) - s*y + log1p(exp(-|s|)),  dscore = scale * (sigmoid(s) - y), sigmoid(s) = (s >= 0 ? 1 : e) / (1 + e) with
+ *     e = exp(-|s|).  A row is its own group and has no negatives, so here valid masks ANY row (a padded batch); the label of a
+ *     masked row is never read.  counts is not written.
+ * OUTPUTS: scores [B], dscore [B] (0 on a masked row); loss_accum [2]: [0] += scale * sum of the losses, [1] += the regulariser
+ * reg/2 * (sum_g |U[u_g]|^2 + sum over valid rows |V[i]|^2), every occurrence counted (BPRMF.py's l2_loss of the batch rows;
+ * in BCE mode a valid row is a group); both with float atomics, the only order-dependent outputs; counts int64 [2] or NULL as
+ * mvin_rank_head defines them.  Gradient rows of a valid row of group g, every product and sum rounded on its own (never
+ * contracted):
+ *     di[row] = dscore[row] * U[u_g] + reg * V[i_row];   du[row] = dscore[row] * V[i_row] (+ reg * U[u_g] on slot 0 only).
+ * With reg == 0 the regulariser's terms are not added at all (not even as +0): du and di are mvin_rank_head's own products.
+ * With reg != 0 a masked row is all +0.
+ * BITS: the dot product is mvin_rank_head's (float4 chunks, its fmaf chain, the sum over the row's lanes) and so is the group
+ * phase -- one piece of source (csrc/mvin_rank_head_body.h).  On the gathered rows scores and dscore equal mvin_rank_head's bit
+ * for bit, and with reg == 0 so do du and di.  scores, dscore, du and di of a group are a pure function of that group: not of
+ * n_groups, of the other groups or of the grid (grid_cap > 0 caps the workgroups launched; 0 = no cap).
+ * Errors (< 0, nothing launched): -1 for a null U / V / users / items / scores / dscore / du / di / loss_accum, or null labels in
+ * BCE mode; -2 for D not a multiple of 4 or outside [4, 128], G outside 2..64 (ranking) or != 1 (BCE), an unknown mode,
+ * n_groups < 0, grid_cap < 0 or an empty table.  n_groups == 0 launches nothing. */
+#define MVIN_MF_BCE 2
+MVIN_API int mvin_mf_head(const float* U, int64_t n_user, const float* V, int64_t n_item, int D, const int64_t* users /* [n_groups] */,
+                          const int64_t* items /* [B] */, const float* valid /* [B] or NULL */, const float* labels /* [B] or NULL */,
+                          int64_t n_groups, int G, int mode, float scale, float reg, float* scores, float* dscore, float* du,
+                          float* di, float* loss_accum /* [2] */, int64_t* counts /* [2] or NULL */, int grid_cap, void* stream);
+/* mvin_mf_scores: the forward only.  users int64 [B], items int64 [B], clamped as above; logits [B] = <U[u], V[i]> with the
+ * head's dot-product bits, probs [B] = the f32 sigmoid of the logit evaluated as above; either may be NULL, not both.
+ * Errors: -1 for a null U / V / users / items or both outputs null; -2 for D as above, B < 0 or an empty table. */
+MVIN_API int mvin_mf_scores(const float* U, int64_t n_user, const float* V, int64_t n_item, int D, const int64_t* users,
+                            const int64_t* items, int64_t B, float* logits, float* probs, void* stream);
+/* mvin_sparse_adam_rows: row-sparse ("lazy") Adam over the rows a batch touched.  x, m, v f32 [n_rows, D]; keys int64 [n] the
+ * row each gradient row belongs to; order int32 [n] a permutation that sorts keys ascending with ties by ascending index (a
+ * STABLE sort); grads f32 [n, D]; valid f32 [n] or NULL.  An entry whose order word is outside [0, n) is dropped as if it were
+ * not in the list; an entry whose key is outside [0, n_rows) is dropped too; status[1] += the number of dropped entries, and
+ * none is dereferenced.  For every run of equal keys among the remaining entries, in order, that holds at least one valid one:
+ *     g  = the run's valid gradient rows added left to right, plain f32 adds starting from the first valid row;
+ *     c1 = 1.f - b1, c2 = 1.f - b2 (f32);
+ *     m' = b1*m + c1*g;   v' = b2*v + c2*(g*g);   x' = x - lr_t * (m' / (sqrt(v') + eps))
+ * with every operation individually and correctly rounded in f32 (no contraction), so numpy float32 restates it exactly.  Rows
+ * outside every such run are neither read nor written: their m and v do NOT decay (the SparseAdam convention; TF1's dense
+ * AdamOptimizer decays every row at every step).  status int64 [2], accumulated with integer atomics: [0] += rows updated.
+ * An order that does not sort keys gives unspecified values in the rows named, no out-of-bounds access.  The bits depend on
+ * (x, m, v, keys, grads, valid) alone: not on the grid (grid_cap as above) nor on how order was produced.
+ * Errors: -1 for a null x / m / v / status, or null keys / order / grads with n > 0; -2 for D as above, n outside [0, 2^31),
+ * n_rows < 0 or grid_cap < 0.  n == 0 launches nothing. */
+MVIN_API int mvin_sparse_adam_rows(float* x, float* m, float* v, int64_t n_rows, int D, const int64_t* keys, const int32_t* order,
+                                   const float* grads, const float* valid /* [n] or NULL */, int64_t n, float lr_t, float b1,
+                                   float b2, float eps, int64_t* status /* [2] */, int grid_cap, void* stream);
+
 /* ---- hard negatives for the ranking objectives: pick the negatives a step trains on out of a scored pool (dynamic negative
  * sampling; an opt-in extension, the reference trains on the fixed negatives of its ratings file) --
  * mvin_select_negatives: n_groups pool groups of Gp slots, row-major.  Slot 0 of a group is the positive, slots 1 .. Gp-1 are

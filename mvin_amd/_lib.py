@@ -241,6 +241,12 @@ SIGNATURES = {
                        + [C.c_void_p, C.c_void_p]),
     "mvin_rank_head_offset": (C.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]
                               + [_c_f32p] * 5 + [C.c_void_p, C.c_void_p]),
+    "mvin_mf_head": (C.c_int, [_c_f32p, C.c_int64, _c_f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _c_f32p, _c_f32p, C.c_int64,
+                              C.c_int, C.c_int, C.c_float, C.c_float] + [_c_f32p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "mvin_mf_scores": (C.c_int, [_c_f32p, C.c_int64, _c_f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _c_f32p, _c_f32p,
+                                C.c_void_p]),
+    "mvin_sparse_adam_rows": (C.c_int, [_c_f32p] * 3 + [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, _c_f32p, _c_f32p, C.c_int64]
+                              + [C.c_float] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
     "mvin_select_negatives": (C.c_int, [_c_f32p, C.c_void_p, _c_f32p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                         C.c_uint64, C.c_void_p, _c_f32p, _c_f32p, C.c_void_p, C.c_void_p]),
     "mvin_explain_paths_max_k": (C.c_int, []),

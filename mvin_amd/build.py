@@ -18,10 +18,10 @@ INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_PATH = os.path.join(PKG_DIR, "libmvin_hip.so")
 STAMP_PATH = LIB_PATH + ".stamp"
 OBJ_DIR = os.path.join(PKG_DIR, "_build")
-SOURCES = ["mvin_kernels.hip", "mvin_fused.hip", "mvin_fused_split.hip", "mvin_fused_packed.hip", "mvin_fused_wpp.hip", "mvin_fused_agg.hip", "mvin_fused_agg32.hip", "mvin_fused_wpp_fold.hip", "mvin_fused_d16.hip", "mvin_fused_d32.hip", "mvin_tail.hip", "mvin_tail_flash.hip", "mvin_score_small.hip", "mvin_keyaddr.hip", "mvin_keyaddr_stream.hip", "mvin_keyaddr_grouped.hip", "mvin_keyaddr_dense.hip", "mvin_keyaddr_static.hip", "mvin_keyaddr_flash.hip", "mvin_keyaddr_wave.hip", "mvin_hoist.hip", "mvin_probe.hip", "mvin_group.hip", "mvin_order.hip", "mvin_topk.hip", "mvin_rank.hip", "mvin_segments.hip", "mvin_mmr.hip", "mvin_mips.hip", "mvin_resample.hip", "mvin_explore.hip", "mvin_ctr_metrics.hip", "mvin_ctr_delong.hip", "mvin_ctr_curve.hip", "mvin_ctr_rank_resample.hip","mvin_ctr_cluster.hip", "mvin_ctr_segments.hip", "mvin_ctr_calib.hip", "mvin_rank_head.hip", "mvin_select_negatives.hip", "mvin_explain.hip", "mvin_explain_mem.hip", "mvin_prep.hip", "mvin_negatives.hip", "mvin_linear_mfma.hip", "mvin_entity_tables.hip", "mvin_bwd.hip", "mvin_grad_guard.hip",
+SOURCES = ["mvin_kernels.hip", "mvin_fused.hip", "mvin_fused_split.hip", "mvin_fused_packed.hip", "mvin_fused_wpp.hip", "mvin_fused_agg.hip", "mvin_fused_agg32.hip", "mvin_fused_wpp_fold.hip", "mvin_fused_d16.hip", "mvin_fused_d32.hip", "mvin_tail.hip", "mvin_tail_flash.hip", "mvin_score_small.hip", "mvin_keyaddr.hip", "mvin_keyaddr_stream.hip", "mvin_keyaddr_grouped.hip", "mvin_keyaddr_dense.hip", "mvin_keyaddr_static.hip", "mvin_keyaddr_flash.hip", "mvin_keyaddr_wave.hip", "mvin_hoist.hip", "mvin_probe.hip", "mvin_group.hip", "mvin_order.hip", "mvin_topk.hip", "mvin_rank.hip", "mvin_segments.hip", "mvin_mmr.hip", "mvin_mips.hip", "mvin_resample.hip", "mvin_explore.hip", "mvin_ctr_metrics.hip", "mvin_ctr_delong.hip", "mvin_ctr_curve.hip", "mvin_ctr_rank_resample.hip","mvin_ctr_cluster.hip", "mvin_ctr_segments.hip", "mvin_ctr_calib.hip", "mvin_rank_head.hip", "mvin_mf.hip", "mvin_select_negatives.hip", "mvin_explain.hip", "mvin_explain_mem.hip", "mvin_prep.hip", "mvin_negatives.hip", "mvin_linear_mfma.hip", "mvin_entity_tables.hip", "mvin_bwd.hip", "mvin_grad_guard.hip",
            # the extern "C" boundary, one translation unit per section of include/mvin_hip.h
            "mvin_abi_basic.hip", "mvin_abi_levels.hip", "mvin_abi_keyaddr.hip", "mvin_abi_score.hip", "mvin_abi_eval.hip", "mvin_abi_train.hip"]
-HEADERS = ["mvin_common.h", "mvin_kernels.h", "mvin_launch.h", "mvin_fused_agg.h", "mvin_score_image.h", "mvin_ctr_bodies.h", "mvin_row_select.h", "mvin_rnd.h", "mvin_explain_mass.h",
+HEADERS = ["mvin_common.h", "mvin_kernels.h", "mvin_launch.h", "mvin_fused_agg.h", "mvin_score_image.h", "mvin_ctr_bodies.h", "mvin_row_select.h", "mvin_rnd.h", "mvin_explain_mass.h", "mvin_rank_head_body.h",
            "mvin_workspaces.h", "mvin_score_plan.h", "mvin_abi_util.h", "mvin_entity_tables_plan.h", "mvin_l2_kernel_plan.h"]
 VERSION_SCRIPT = os.path.join(CSRC, "libmvin_hip.map")
 ARCH = "gfx950"

@@ -142,6 +142,17 @@ int mvin_mmr_segments(const float* scores, int64_t total, const int64_t* seg_ptr
                       who);
 }
 
+int mvin_mf_scores(const float* U, int64_t n_user, const float* V, int64_t n_item, int D, const int64_t* users, const int64_t* items,
+                   int64_t B, float* logits, float* probs, void* stream) {
+    const char* who = "mvin_mf_scores";
+    if (!U || !V || (B > 0 && (!users || !items))) return fail(-1, "%s: null pointer (U / V / users / items)", who);
+    if (!logits && !probs) return fail(-1, "%s: logits and probs are both null", who);
+    if (D < 4 || D > 128 || (D & 3) != 0) return fail(-2, "%s: D=%d (a multiple of 4, 4..128)", who, D);
+    if (B < 0) return fail(-2, "%s: B=%lld", who, (long long)B);
+    if (n_user < 1 || n_item < 1) return fail(-2, "%s: empty table (n_user=%lld n_item=%lld)", who, (long long)n_user, (long long)n_item);
+    return hip_result(mvin::launch_mf_scores(U, V, n_user, n_item, users, items, B, D, logits, probs, (hipStream_t)stream), who);
+}
+
 int mvin_mips_topk_max_k(void) { return mvin::mips_topk_max_k(); }
 
 int mvin_mips_topk_supported(int k, int D) { return mvin::mips_topk_supported(k, D) ? 1 : 0; }

@@ -80,6 +80,40 @@ int mvin_rank_head_offset(const float* user_o, const float* item_emb, const floa
                           di, loss_accum, counts, stream);
 }
 
+// the MF head: mvin_rank_head's kernel body over rows read by id from U and V
+int mvin_mf_head(const float* U, int64_t n_user, const float* V, int64_t n_item, int D, const int64_t* users, const int64_t* items,
+                 const float* valid, const float* labels, int64_t n_groups, int G, int mode, float scale, float reg, float* scores,
+                 float* dscore, float* du, float* di, float* loss_accum, int64_t* counts, int grid_cap, void* stream) {
+    const char* who = "mvin_mf_head";
+    if (!U || !V || !users || !items || !scores || !dscore || !du || !di || !loss_accum)
+        return fail(-1, "%s: null pointer (U / V / users / items / scores / dscore / du / di / loss_accum)", who);
+    if (mode != MVIN_RANK_SOFTMAX && mode != MVIN_RANK_BPR && mode != MVIN_MF_BCE) return fail(-2, "%s: unknown mode=%d", who, mode);
+    if (mode == MVIN_MF_BCE) {
+        if (G != 1) return fail(-2, "%s: G=%d (MVIN_MF_BCE takes G = 1)", who, G);
+        if (!labels) return fail(-1, "%s: null labels (MVIN_MF_BCE)", who);
+    } else if (G < 2 || G > 64) {
+        return fail(-2, "%s: G=%d (2..64)", who, G);
+    }
+    if (D < 4 || D > 128 || (D & 3) != 0) return fail(-2, "%s: D=%d (a multiple of 4, 4..128)", who, D);
+    if (n_groups < 0 || grid_cap < 0) return fail(-2, "%s: n_groups=%lld grid_cap=%d", who, (long long)n_groups, grid_cap);
+    if (n_user < 1 || n_item < 1) return fail(-2, "%s: empty table (n_user=%lld n_item=%lld)", who, (long long)n_user, (long long)n_item);
+    return hip_result(mvin::launch_mf_head(U, V, n_user, n_item, users, items, valid, labels, n_groups, G, D, mode, scale, reg, scores,
+                                           dscore, du, di, loss_accum, counts, grid_cap, (hipStream_t)stream), who);
+}
+
+int mvin_sparse_adam_rows(float* x, float* m, float* v, int64_t n_rows, int D, const int64_t* keys, const int32_t* order,
+                          const float* grads, const float* valid, int64_t n, float lr_t, float b1, float b2, float eps,
+                          int64_t* status, int grid_cap, void* stream) {
+    const char* who = "mvin_sparse_adam_rows";
+    if (!x || !m || !v || !status) return fail(-1, "%s: null pointer (x / m / v / status)", who);
+    if (n > 0 && (!keys || !order || !grads)) return fail(-1, "%s: null pointer (keys / order / grads)", who);
+    if (D < 4 || D > 128 || (D & 3) != 0) return fail(-2, "%s: D=%d (a multiple of 4, 4..128)", who, D);
+    if (n < 0 || n > INT32_MAX || n_rows < 0 || grid_cap < 0)
+        return fail(-2, "%s: n=%lld (0..2^31-1: order is int32) n_rows=%lld grid_cap=%d", who, (long long)n, (long long)n_rows, grid_cap);
+    return hip_result(mvin::launch_sparse_adam_rows(x, m, v, n_rows, D, keys, order, grads, valid, n, lr_t, b1, b2, eps, status, grid_cap,
+                                                    (hipStream_t)stream), who);
+}
+
 int mvin_count_ids(const int32_t* ids, int64_t n, int nbins, float* out, void* stream) {
     if (n < 0 || nbins < 1 || nbins > 4096) return fail(-2, "mvin_count_ids: n=%lld nbins=%d (1..4096)", (long long)n, nbins);
     if (n == 0) return 0;

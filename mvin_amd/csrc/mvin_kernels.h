@@ -546,6 +546,15 @@ hipError_t launch_rank_head(const float* user_o, const float* item_emb, const fl
                             float* loss_accum, int64_t* counts,
                             hipStream_t st);                  // grouped BPR / sampled-softmax head of the step (mvin_rank_head.hip);
                                                               // offset NULL: mvin_rank_head, else mvin_rank_head_offset
+hipError_t launch_mf_head(const float* U, const float* V, int64_t n_user, int64_t n_item, const int64_t* users, const int64_t* items,
+                          const float* valid, const float* labels, int64_t n_groups, int G, int D, int mode, float scale, float reg,
+                          float* scores, float* dscore, float* du, float* di, float* loss_accum, int64_t* counts, int grid_cap,
+                          hipStream_t st);                    // the ranking head over rows read by id from two tables (mvin_mf.hip)
+hipError_t launch_mf_scores(const float* U, const float* V, int64_t n_user, int64_t n_item, const int64_t* users, const int64_t* items,
+                            int64_t B, int D, float* logits, float* probs, hipStream_t st);
+hipError_t launch_sparse_adam_rows(float* x, float* m, float* v, int64_t n_rows, int D, const int64_t* keys, const int32_t* order,
+                                   const float* grads, const float* valid, int64_t n, float lr_t, float b1, float b2, float eps,
+                                   int64_t* status, int grid_cap, hipStream_t st);   // row-sparse (lazy) Adam (mvin_mf.hip)
 int explain_paths_max_k();                                      // merged, ranked KG attention paths per pair (mvin_explain.hip)
 hipError_t launch_explain_paths(const float* imp0, const float* imp1, const int32_t* rel0, const int32_t* ent1, const int32_t* rel1,
                                 const int32_t* ent2, int64_t B, int K, int top, int n_relation, int32_t* out_paths,

@@ -408,14 +408,19 @@ class DeviceFeeder(object):
         return ids.long(), sims
 
     def recommend_two_stage(self, users, k, n_cand, candidates, queries=None, history=None, cosine=False, exclude=None,
-                            max_pairs=524288):
+                            max_pairs=524288, retriever=None):
         """``retrieve`` followed by ``recommend_lists`` on the retrieved lists: the model scores ``n_cand`` items per user, not
         the catalogue.  Arguments as in ``retrieve`` (``max_pairs`` is ``recommend_lists``'); the -1 padding of a short
         retrieved list is ``recommend_lists``' padding.  Returns what ``recommend_lists`` returns, ``positions`` being places
         in the user's retrieved list.  With ``n_cand`` at least the user's eligible candidates the item set is ``recommend``'s.
-        Nothing is copied back."""
+        Nothing is copied back.  ``retriever`` (None: this feeder's own ``retrieve``, as above): any object with a
+        ``retrieve(users, n_cand, candidates, exclude=...)`` method returning ``(items int64 [U, n_cand], sims)`` -- a learned
+        tower such as ``mf.MFFeeder`` -- runs the first stage instead; ``queries`` / ``history`` / ``cosine`` are then not used."""
         k, n_cand = int(k), int(n_cand)
-        items, _ = self.retrieve(users, n_cand, candidates, queries=queries, history=history, cosine=cosine, exclude=exclude)
+        if retriever is not None:
+            items, _ = retriever.retrieve(users, n_cand, candidates, exclude=exclude)
+        else:
+            items, _ = self.retrieve(users, n_cand, candidates, queries=queries, history=history, cosine=cosine, exclude=exclude)
         U = items.shape[0]
         ptr = np.arange(U + 1, dtype=np.int64) * n_cand
         return self.recommend_lists(users, (ptr, items.reshape(-1)), k, max_pairs=max_pairs)
@@ -1226,7 +1231,7 @@ def diversity_eval(feeder, users, lists, truth_record, k, lams=(1.0, 0.7, 0.5, 0
 
 
 def retrieval_eval(feeder, users, train_record, truth_record, candidates, n_cand_list, k, history, full_users=0, cosine=False,
-                   max_pairs=524288):
+                   max_pairs=524288, retriever=None):
     """What first-stage retrieval with the history-mean query (DeviceFeeder.user_queries, a PROXY for MVIN's item-dependent
     user vector) keeps of the model's ranking: for every ``n_cand`` of ``n_cand_list`` ONE ``retrieve`` (the user's
     ``train_record`` items excluded), ONE ``recommend_lists`` over the retrieved lists and ONE copy back (both id matrices
@@ -1236,7 +1241,10 @@ def retrieval_eval(feeder, users, train_record, truth_record, candidates, n_cand
       recall, ndcg -- recall_at_k and ndcg_at_k (hits in the returned order) at ``k`` of the two-stage result, means over users;
       overlap -- with ``full_users`` > 0: |two-stage top-k intersect ``recommend``'s top-k| / |``recommend``'s top-k| over
       the first ``full_users`` users (``recommend`` over all candidates runs once, one more copy back), else None;
-      n_users; items -- the two-stage lists, int64 [U, k] on the host (-1 = padding)."""
+      n_users; items -- the two-stage lists, int64 [U, k] on the host (-1 = padding).
+    ``retriever`` (None: the proxy above): an object with ``retrieve(users, n_cand, candidates, exclude=...)``, e.g. an
+    ``mf.MFFeeder``; its lists are the first stage (``history`` and ``cosine`` are then not used) and the report is the same, so
+    the proxy and a learned tower are compared on candidate recall and overlap."""
     import torch
     k = int(k)
     if k < 1:
@@ -1258,7 +1266,10 @@ def retrieval_eval(feeder, users, train_record, truth_record, candidates, n_cand
         full = full_ids.to(torch.int32).cpu().numpy().reshape(F, k)
     rows = []
     for n_cand in n_cand_list:
-        cand, _ = feeder.retrieve(users, n_cand, candidates, history=history, cosine=cosine, exclude=excl)
+        if retriever is not None:
+            cand, _ = retriever.retrieve(users, n_cand, candidates, exclude=excl)
+        else:
+            cand, _ = feeder.retrieve(users, n_cand, candidates, history=history, cosine=cosine, exclude=excl)
         ptr = np.arange(U + 1, dtype=np.int64) * n_cand
         top, _, _ = feeder.recommend_lists(users, (ptr, cand.reshape(-1)), k, max_pairs=max_pairs)
         packed = torch.cat([cand.to(torch.int32).reshape(-1), top.to(torch.int32).reshape(-1)]).cpu().numpy()
@@ -2189,3 +2200,14 @@ def memory_relation_profile(feeder, data, batch_size):
     tot = mass.sum(axis=1, keepdims=True)
     share = np.divide(mass.astype(np.float64), tot, out=np.zeros(mass.shape, np.float64), where=tot > 0)
     return dict(mass=mass, share=share, n_pairs=int(data.shape[0]))
+
+
+# the matrix-factorisation baseline and retrieval tower (mf.py, which builds on DeviceFeeder above): re-exported on first use
+_MF_NAMES = ("MFModel", "MFTrainer", "MFFeeder", "train_mf")
+
+
+def __getattr__(name):
+    if name in _MF_NAMES:
+        from . import mf
+        return getattr(mf, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

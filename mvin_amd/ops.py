@@ -2843,6 +2843,135 @@ def rank_head(user_o, item_emb, group_size, mode, scale, loss_accum, valid=None,
     return scores, dscore, du, di
 
 
+MF_MODES = {"softmax": 0, "bpr": 1, "bce": 2}   # MVIN_RANK_SOFTMAX / MVIN_RANK_BPR / MVIN_MF_BCE
+
+
+def _mf_tables(U, V, who):
+    for t, nm in ((U, "U"), (V, "V")):
+        if not torch.is_tensor(t) or t.dtype != F32 or t.dim() != 2:
+            raise ValueError(f"{who}: {nm} must be a float32 [rows, D] tensor, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    D = U.shape[1]
+    if V.shape[1] != D or D < 4 or D > 128 or D % 4:
+        raise ValueError(f"{who}: U {tuple(U.shape)} and V {tuple(V.shape)}: one D, a multiple of 4 in 4..128")
+    if U.shape[0] < 1 or V.shape[0] < 1:
+        raise ValueError(f"{who}: empty table (U {tuple(U.shape)}, V {tuple(V.shape)})")
+    return D
+
+
+def _mf_vec(t, name, dtype, n, dev, who):
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError(f"{who}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 1 or (n is not None and t.numel() != n) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{who}: {name}: expected {'' if n is None else n} contiguous values [n] on {dev}, got "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def mf_head(U, V, users, items, mode, scale, reg, loss_accum, group_size=None, valid=None, labels=None, counts=None, out=None,
+            grid_cap=0):
+    """mvin_mf_head: the head of a matrix-factorisation step in one launch, rows read by id from the tables.  ``U`` f32
+    [n_user, D], ``V`` f32 [n_item, D]; ``users`` int64 [n_groups]; ``items`` int64 [B], B = n_groups * ``group_size``
+    group-major (slot 0 the positive: the layout of data_prep.rank_groups); ``mode`` "softmax" / "bpr" (group_size 2..64) or "bce"
+    (group_size 1, the default there; ``labels`` f32 [B] required, and ``valid`` masks any row).  Adds the loss and the regulariser
+    to ``loss_accum`` (f32 [2]) and the pairwise-accuracy integers to ``counts`` (int64 [2], ranking modes).  Returns
+    (scores [B], dscore [B], du [B, D], di [B, D]); ``out`` may pass those four in.  include/mvin_hip.h states the rule and the
+    bits.  Enqueues only."""
+    who = "mf_head"
+    if mode not in MF_MODES:
+        raise ValueError(f"mode={mode!r}: expected 'softmax', 'bpr' or 'bce'")
+    D = _mf_tables(U, V, who)
+    dev = U.device
+    G = 1 if group_size is None and mode == "bce" else group_size
+    if G is None or int(G) != G or not ((G == 1) if mode == "bce" else (2 <= G <= 64)):
+        raise ValueError(f"{who}: group_size={group_size!r} (1 for 'bce', 2..64 for the ranking modes)")
+    G = int(G)
+    users = _mf_vec(users, "users", torch.int64, None, dev, who)
+    items = _mf_vec(items, "items", torch.int64, users.numel() * G, dev, who)
+    B = items.numel()
+    if valid is not None:
+        _mf_vec(valid, "valid", F32, B, dev, who)
+    if mode == "bce" and labels is None:
+        raise ValueError(f"{who}: mode 'bce' needs labels")
+    if labels is not None:
+        _mf_vec(labels, "labels", F32, B, dev, who)
+    _mf_vec(loss_accum, "loss_accum", F32, 2, dev, who)
+    if counts is not None:
+        _mf_vec(counts, "counts", torch.int64, 2, dev, who)
+    _chk(U, F32, "U"), _chk(V, F32, "V")           # the shapes are right: now they must be on the device
+    if out is None:
+        out = (torch.empty(B, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev),
+               torch.empty((B, D), dtype=F32, device=dev), torch.empty((B, D), dtype=F32, device=dev))
+    scores, dscore, du, di = out
+    for t, nm, n in ((scores, "scores", B), (dscore, "dscore", B), (du, "du", B * D), (di, "di", B * D)):
+        _chk(t, F32, nm)
+        if t.numel() != n:
+            raise ValueError(f"{who}: {nm}: {t.numel()} elements, expected {n}")
+    if B == 0:
+        return scores, dscore, du, di
+    _lib.check(_lib.load().mvin_mf_head(_p(U), U.shape[0], _p(V), V.shape[0], D, _p(users), _p(items), _p(valid), _p(labels),
+                                        B // G, G, MF_MODES[mode], float(scale), float(reg), _p(scores), _p(dscore), _p(du), _p(di),
+                                        _p(loss_accum), _p(counts), int(grid_cap), _stream()), "mvin_mf_head")
+    return scores, dscore, du, di
+
+
+def mf_scores(U, V, users, items, want_logits=True, want_probs=True):
+    """mvin_mf_scores: logits [B] = <U[users], V[items]> with mf_head's bits and probs [B] = their f32 sigmoid, in one launch.
+    Returns (logits, probs); one of them is None when not wanted.  Enqueues only."""
+    who = "mf_scores"
+    D = _mf_tables(U, V, who)
+    dev = U.device
+    users = _mf_vec(users, "users", torch.int64, None, dev, who)
+    items = _mf_vec(items, "items", torch.int64, users.numel(), dev, who)
+    if not (want_logits or want_probs):
+        raise ValueError(f"{who}: nothing asked for (want_logits and want_probs are both false)")
+    _chk(U, F32, "U"), _chk(V, F32, "V")
+    B = users.numel()
+    logits = torch.empty(B, dtype=F32, device=dev) if want_logits else None
+    probs = torch.empty(B, dtype=F32, device=dev) if want_probs else None
+    if B:
+        _lib.check(_lib.load().mvin_mf_scores(_p(U), U.shape[0], _p(V), V.shape[0], D, _p(users), _p(items), B, _p(logits),
+                                              _p(probs), _stream()), "mvin_mf_scores")
+    return logits, probs
+
+
+def sparse_adam_rows(x, m, v, keys, grads, lr_t, beta1, beta2, eps, status, valid=None, order=None, grid_cap=0):
+    """mvin_sparse_adam_rows: the lazy Adam over the rows ``keys`` (int64 [n]) name, ``grads`` f32 [n, D] their gradient rows
+    (duplicates are summed in ascending index order; include/mvin_hip.h states the rule, exact in numpy float32).  ``x`` / ``m`` /
+    ``v`` f32 [n_rows, D] are updated in place; rows no valid key names are not touched.  ``order`` (int32 [n]) defaults to the
+    stable ascending sort of ``keys`` (torch.sort: plumbing); ``status`` int64 [2] accumulates (rows updated, entries dropped).
+    Enqueues only."""
+    who = "sparse_adam_rows"
+    for t, nm in ((x, "x"), (m, "m"), (v, "v")):
+        if not torch.is_tensor(t) or t.dtype != F32 or t.dim() != 2 or tuple(t.shape) != tuple(x.shape):
+            raise ValueError(f"{who}: {nm} must be float32 [n_rows, D] like x, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    n_rows, D = x.shape
+    if D < 4 or D > 128 or D % 4:
+        raise ValueError(f"{who}: D={D} (a multiple of 4 in 4..128)")
+    dev = x.device
+    keys = _mf_vec(keys, "keys", torch.int64, None, dev, who)
+    n = keys.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"{who}: {n} keys (order is int32: below 2^31)")
+    if not torch.is_tensor(grads) or grads.dtype != F32 or tuple(grads.shape) != (n, D) or grads.device != dev:
+        raise ValueError(f"{who}: grads must be float32 [{n}, {D}] on {dev}, got {getattr(grads, 'dtype', type(grads))} "
+                         f"{tuple(getattr(grads, 'shape', ()))}")
+    if valid is not None:
+        _mf_vec(valid, "valid", F32, n, dev, who)
+    _mf_vec(status, "status", torch.int64, 2, dev, who)
+    _chk(x, F32, "x"), _chk(m, F32, "m"), _chk(v, F32, "v"), _chk(grads, F32, "grads")
+    if order is None:
+        order = torch.sort(keys, stable=True)[1].to(I32)
+    else:
+        _mf_vec(order, "order", I32, n, dev, who)
+    if n:
+        _lib.check(_lib.load().mvin_sparse_adam_rows(_p(x), _p(m), _p(v), n_rows, D, _p(keys), _p(order), _p(grads), _p(valid), n,
+                                                     float(lr_t), float(beta1), float(beta2), float(eps), _p(status), int(grid_cap),
+                                                     _stream()), "mvin_sparse_adam_rows")
+    return order
+
+
 EXPLAIN_SCALE = float(1 << 40)                 # a mass is floor(w0 * w1 * 2^40); weight = mass / EXPLAIN_SCALE
 EXPLAIN_PROFILE_SLOTS = 1 << 22                # B * K * K of one call with rel_mass (mvin_explain_paths' bound)
 
