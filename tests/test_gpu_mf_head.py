@@ -3,6 +3,18 @@
 Cases: D in {4, 16, 64, 128} x G in {1 (BCE), 2, 5, 64} x n_groups in {1, 3, 257, 1000}, over tables of 7 users x 11 items
 (every row shared many times) and of 1000 x 2000, both ranking modes at G >= 2; validity random at 80 %.
 
+mf_head_kernel is compiled once per (L2, NP) -- 2^L2 lanes per row, NP passes over a group's rows (tests/rank_head_shapes.py
+restates the rule) -- and that product reaches six of the twelve instances, with D / 4 always a power of two, so that no lane of
+a row's lane group is ever without a chunk.  EXTRA (G, D), through the same checks, tables and n_groups, holds the rest:
+  (3, 1)  (3, 20), (8, 24), (32, 32)    (3, 2)  (33, 32), (64, 24)    (4, 2)  (17, 36), (32, 64)
+  (5, 2)  (9, 68), (16, 128)            (5, 4)  (17, 100), (32, 128)  -- D = 20, 24, 36, 68, 100: idle lanes (id loads, s_ok, the
+          regulariser's sum); D = 32, 64, 128: none;
+  (1, 1)  (4, 8), and (16, 64) at (4, 1): with 8 and 32 above, G a power of two in 4..32 (the segment of phase 2 is G lanes);
+  BCE     (1, 20), (1, 32), (1, 100) at (3, 1), (3, 1), (5, 1).
+G = 5 at D = 4, in the product, is the shape whose 408 slots take phase 2 through a second trip.  mvin_mf_scores runs at SCORES_DS: every
+L2 of mf_scores_kernel, idle lanes at 12, 20 and 100.  Clamped ids and the integer tables run at (3, 20) and (17, 100) too: idle
+lanes AND ids outside the tables.  tests/test_rank_head_shapes_host.py holds the lists to all that without a GPU.
+
 Exact checks: scores and dscore equal mvin_gather_rows + mvin_rank_head bit for bit, du / di too at reg = 0, counts too; du / di
 at reg != 0 equal the numpy float32 rule (mf_oracle.grad_rows32) applied to the device's OWN dscore; integer tables give exact
 scores and an exact regulariser; masked slots are exactly 0 and a NaN label there reaches nothing; ids outside the tables are
@@ -21,6 +33,12 @@ Bounds against float64 (mf_oracle.head64), derived, with u = 2^-24:
            group's loss (no term cancels: log Z >= 0 and m - z_0 >= 0; softplus >= 0), then a sum of n_groups terms in any
            order.
   BCE against mvin_eltwise mode 1 on the device's own scores: the dscore bound above.
+
+Measured on the MI355X, worst error / bound:   score   dscore   loss
+  the product GS x DS                          0.585   0.086    0.059
+  the EXTRA shapes                             0.275   0.059    0.019
+(the bounds are worst-case summation bounds, so a ratio well below 1 is what a correct kernel gives; the bit equalities are the
+sharp checks, and they hold at every shape).
 """
 import functools
 
@@ -36,6 +54,17 @@ U32 = 2.0 ** -24
 DS = (4, 16, 64, 128)
 GS = (1, 2, 5, 64)
 NGROUPS = (1, 3, 257, 1000)
+# (G, D) beside the product GS x DS: the smallest that reach what the product misses (tests/rank_head_shapes.py has the rule,
+# tests/test_rank_head_shapes_host.py holds this list to it)
+EXTRA = [(3, 20), (8, 24), (32, 32),          # (3, 1): idle lanes (5, 6 of 8 chunks) and full lanes; G a power of two
+         (33, 32), (64, 24),                  # (3, 2)
+         (17, 36), (32, 64),                  # (4, 2)
+         (9, 68), (16, 128),                  # (5, 2)
+         (17, 100), (32, 128),                # (5, 4)
+         (4, 8), (16, 64),                    # (1, 1), which GS x DS has not; G a power of two at (1, 1) and (4, 1)
+         (1, 20), (1, 32), (1, 100)]          # BCE at (3, 1) and (5, 1), with idle lanes and without
+SHAPES = [(G, D) for G in GS for D in DS] + EXTRA
+SCORES_DS = DS + (8, 12, 20, 32, 100)         # mvin_mf_scores: every L2, idle lanes at 12, 20 and 100
 TABLES = ((7, 11), (1000, 2000))
 
 
@@ -151,10 +180,7 @@ def group_losses(ref, G, mode, scale):
     return out
 
 
-@pytest.mark.parametrize("table", TABLES, ids=lambda t: f"{t[0]}x{t[1]}")
-@pytest.mark.parametrize("G", GS)
-@pytest.mark.parametrize("D", DS)
-def test_head_every_shape(D, G, table):
+def check_head_shape(D, G, table):
     n_user, n_item = table
     U, V = make_tables(n_user, n_item, D)
     for n_groups in NGROUPS:
@@ -207,9 +233,35 @@ def test_head_every_shape(D, G, table):
             assert abs(gr["reg_loss"] - refr["reg_loss"]) <= gamma(D * len(items) * 2 + 8) * refr["reg_loss"] + 1e-30
 
 
+@pytest.mark.parametrize("table", TABLES, ids=lambda t: f"{t[0]}x{t[1]}")
+@pytest.mark.parametrize("G", GS)
+@pytest.mark.parametrize("D", DS)
+def test_head_every_shape(D, G, table):
+    check_head_shape(D, G, table)
+
+
+@pytest.mark.parametrize("table", TABLES, ids=lambda t: f"{t[0]}x{t[1]}")
+@pytest.mark.parametrize("G,D", EXTRA)
+def test_head_extra_shapes(G, D, table):
+    """The instances, idle lanes and power-of-two groups that GS x DS does not reach, through every check of the product."""
+    check_head_shape(D, G, table)
+
+
+IDLE_AND_CLAMPED = [(3, 20), (17, 100)]       # a lane group wider than the row AND ids outside the tables
+
+
 @pytest.mark.parametrize("G", GS)
 def test_integer_tables_are_exact(G):
-    U, V = make_tables(7, 11, 16, integer=True)
+    check_integer_tables(G, 16)
+
+
+@pytest.mark.parametrize("G,D", IDLE_AND_CLAMPED)
+def test_integer_tables_are_exact_with_idle_lanes(G, D):
+    check_integer_tables(G, D)
+
+
+def check_integer_tables(G, D):
+    U, V = make_tables(7, 11, D, integer=True)
     users, items, valid, labels = make_batch(7, 11, 257, G)
     for mode in modes_of(G):
         got = run_head(U, V, users, items, mode, 1.0, 0.5, G, valid, labels)
@@ -236,7 +288,16 @@ def test_bce_against_eltwise(D):
 
 @pytest.mark.parametrize("G", GS)
 def test_ids_are_clamped(G):
-    n_user, n_item, D = 7, 11, 16
+    check_clamped_ids(G, 16)
+
+
+@pytest.mark.parametrize("G,D", IDLE_AND_CLAMPED)
+def test_ids_are_clamped_with_idle_lanes(G, D):
+    check_clamped_ids(G, D)
+
+
+def check_clamped_ids(G, D):
+    n_user, n_item = 7, 11
     U, V = make_tables(n_user, n_item, D)
     users, items, valid, labels = make_batch(n_user, n_item, 257, G)
     users, items = users.copy(), items.copy()
@@ -277,7 +338,7 @@ def test_group_bits_do_not_depend_on_the_launch(G, D):
                 same(alone[k], full[k][rows], f"{k} of group {g} alone")
 
 
-@pytest.mark.parametrize("D", DS)
+@pytest.mark.parametrize("D", SCORES_DS)
 def test_mf_scores_gives_the_head_bits(D):
     from mvin_amd import ops
     n_user, n_item = 1000, 2000

@@ -2,7 +2,9 @@
 
 Lazy steps are held to BITS: three steps of each objective on the 7 x 11 tables (every row shared many times) equal the numpy
 float32 rules of tests/mf_oracle.py -- grad_rows32 on the device's own dscore, then adam_rows32 -- in both tables and both
-moments after every step; the same run twice gives the same bits.
+moments after every step; the same run twice gives the same bits.  The module's D = 8 selects 2 lanes per row, all of them busy;
+BCE and softmax run the same three steps at D = 20 as well (8 lanes per row, 5 of them with a chunk: the (3, 1) instance of
+mf_head_kernel and sparse_adam_rows_kernel<3>, tests/rank_head_shapes.py), and hold to the same bits on the MI355X.
 
 The dense form depends on atomic order, so its tolerance is MEASURED (``dense_yardstick``): the same three steps restated in
 numpy float32 (head formulas in float32, the scatter-add in a random order, the dense Adam in float32) deviate from the float64
@@ -44,10 +46,10 @@ def dev(a, dtype=None):
     return (t if dtype is None else t.to(dtype)).cuda()
 
 
-def device_steps(mode, G, adam, seed=0):
+def device_steps(mode, G, adam, seed=0, dim=D):
     """Three steps on the device.  Yields (trainer, model, batch) after each."""
     from mvin_amd import mf
-    model = mf.MFModel(N_USER, N_ITEM, D, seed=seed)
+    model = mf.MFModel(N_USER, N_ITEM, dim, seed=seed)
     tr = mf.MFTrainer(model, LR, reg=REG, objective=mode, group_size=None if G == 1 else G, adam=adam)
     for users, items, valid, labels in batches(mode, G):
         loss, reg_loss = tr.step(dev(users, torch.int64), dev(items, torch.int64), valid=dev(valid),
@@ -63,10 +65,21 @@ def bits(t):
 
 @pytest.mark.parametrize("mode,G", OBJECTIVES)
 def test_lazy_steps_equal_the_float32_rule_bit_for_bit(mode, G):
-    U, V = mo.xavier64(N_USER, N_ITEM, D, 0)
+    check_lazy_steps(mode, G, D)
+
+
+@pytest.mark.parametrize("mode,G", (("bce", 1), ("softmax", 5)))
+def test_lazy_steps_equal_the_float32_rule_at_dim_20(mode, G):
+    """D = 20: 8 lanes per row of which 5 hold a chunk, in the head, in the lazy Adam and between them (the (3, 1) instance of
+    mf_head_kernel and sparse_adam_rows_kernel<3>, which D = 8 does not select)."""
+    check_lazy_steps(mode, G, 20)
+
+
+def check_lazy_steps(mode, G, dim):
+    U, V = mo.xavier64(N_USER, N_ITEM, dim, 0)
     mu, vu, mi, vi = np.zeros_like(U), np.zeros_like(U), np.zeros_like(V), np.zeros_like(V)
     t = 0
-    for tr, model, (users, items, valid, labels), loss, reg_loss in device_steps(mode, G, "lazy"):
+    for tr, model, (users, items, valid, labels), loss, reg_loss in device_steps(mode, G, "lazy", dim=dim):
         t += 1
         val = mo.effective_valid(valid, len(items), G, mode)
         h = mo.head64(U, V, users, items, mode, 1.0 / len(users), REG, G, valid, labels)

@@ -1,10 +1,16 @@
 """-m gpu: mvin_sparse_adam_rows (ops.sparse_adam_rows) alone, BIT FOR BIT against the numpy float32 restatement of its rule
 (tests/mf_oracle.py: adam_rows32 -- stable run order, left-to-right sums, every operation rounded on its own).
 
-n in {1, 2, 63, 64, 65, 4097} x D in {4, 64, 128} x n_rows in {1, 5, 1000}; keys distinct / all equal (one run of 4097) /
+n in {1, 2, 63, 64, 65, 4097} x D in {4, 8, 32, 64, 128} x n_rows in {1, 5, 1000}, and D in {12, 20, 100} -- where 1, 3 and 7
+lanes of a row's lane group hold no chunk of the row -- at n in {1, 65, 4097} only (a reduction, to keep the module's time down:
+the run structure does not depend on D, and those three n are one lane group, more than one workgroup (64, 32 and 8 lane groups each), and
+the long launch).  D covers every instance of the kernel: sparse_adam_rows_kernel<L2>, L2 = 0, 1, 2, 3, 3, 4, 5, 5 for the eight dims
+(tests/rank_head_shapes.py; tests/test_rank_head_shapes_host.py holds DS to it).  The one run of 4097 and the grid caps run at
+D = 20 and 32 too (L2 = 3, with idle lanes and without).  Keys distinct / all equal (one run of 4097) /
 geometric run lengths / random; runs masked whole, a masked first entry, valid absent; keys below 0 and at n_rows, order words
 outside [0, n); zero, huge, denormal and NaN gradients; every grid cap; a second launch and a second stream.  All three tables
 sit between guard rows, and every byte of tables and guards is compared, so a row outside the runs that moved shows.
+On the MI355X every case of every dim equals the rule bit for bit (the check has no tolerance, so there is no ratio to record).
 """
 import numpy as np
 import pytest
@@ -15,8 +21,11 @@ import mf_oracle as mo
 pytestmark = pytest.mark.gpu
 
 NS = (1, 2, 63, 64, 65, 4097)
-DS = (4, 64, 128)
+DS = (4, 8, 12, 20, 32, 64, 100, 128)        # every L2 of the kernel (0, 1, 2, 3, 3, 4, 5, 5); idle lanes at 12, 20 and 100
+IDLE_DS = (12, 20, 100)                      # a lane group wider than the row: 3 of 4, 5 of 8, 25 of 32 lanes hold a chunk
+IDLE_NS = (1, 65, 4097)
 ROWS = (1, 5, 1000)
+CASES = [(n, D, n_rows) for n_rows in ROWS for D in DS for n in (IDLE_NS if D in IDLE_DS else NS)]
 HP = (np.float32(0.0123), np.float32(0.9), np.float32(0.999), np.float32(1e-8))
 GUARD = np.float32(-7.25)
 
@@ -92,11 +101,9 @@ def check(x, m, v, keys, grads, valid, **kw):
     return got
 
 
-@pytest.mark.parametrize("n_rows", ROWS)
-@pytest.mark.parametrize("D", DS)
-@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("n,D,n_rows", CASES)
 def test_bits_every_shape(n, D, n_rows):
-    """Every (n, D, n_rows): random keys with a random mask, then the same keys without a mask; distinct keys where they fit."""
+    """Every (n, D, n_rows) of CASES: random keys with a random mask, then the same keys without a mask; distinct keys where they fit."""
     rng = np.random.default_rng(1000 * n + 10 * D + n_rows)
     x, m, v = tables(n_rows, D, n + D)
     grads = rng.normal(size=(n, D)).astype(np.float32)
@@ -110,7 +117,7 @@ def test_bits_every_shape(n, D, n_rows):
         assert got[3] == (n, 0)
 
 
-@pytest.mark.parametrize("D", DS)
+@pytest.mark.parametrize("D", (4, 20, 32, 64, 128))
 def test_one_run_of_4097_and_geometric_runs(D):
     rng = np.random.default_rng(D)
     n, n_rows = 4097, 1000
@@ -186,13 +193,14 @@ def test_special_values():
 
 @pytest.mark.parametrize("cap", (1, 2, 3, 7, 64))
 def test_bits_do_not_depend_on_the_grid(cap):
-    rng = np.random.default_rng(13)
-    n, n_rows, D = 4097, 1000, 64
-    x, m, v = tables(n_rows, D, 9)
-    grads = rng.normal(size=(n, D)).astype(np.float32)
-    keys = make_keys("geometric", n, n_rows, rng)
-    valid = (rng.random(n) < 0.9).astype(np.float32)
-    check(x, m, v, keys, grads, valid, grid_cap=cap)
+    for D in (64, 20, 32):                                # L2 = 4; L2 = 3 with idle lanes and without
+        rng = np.random.default_rng(13)
+        n, n_rows = 4097, 1000
+        x, m, v = tables(n_rows, D, 9)
+        grads = rng.normal(size=(n, D)).astype(np.float32)
+        keys = make_keys("geometric", n, n_rows, rng)
+        valid = (rng.random(n) < 0.9).astype(np.float32)
+        check(x, m, v, keys, grads, valid, grid_cap=cap)
 
 
 def test_second_launch_and_second_stream():

@@ -1,7 +1,10 @@
 """-m gpu: the training step under the ranking objectives (Trainer.set_objective "bpr" / "softmax": the fused head
 mvin_rank_head in place of the four launches of the cross-entropy head, the tape behind it unchanged) against
 tests/rank_loss_ref.ranked_loss_and_grads -- oracle/train_ref.py with the grouped head in place of its cross-entropy term.
-The small shapes, the setup and every tolerance are those of tests/test_gpu_train.py."""
+The small shapes, the setup and every tolerance are those of tests/test_gpu_train.py, plus one shape at dim 32 -- the dimension
+of BASELINE config C2, where the head runs 8 lanes per row, the (3, 1) instance of tests/rank_head_shapes.py -- under both
+objectives with groups of 2 and 5 and, once, of 17 (test_dim_32_with_groups_of_17).  On the MI355X the dim-32 cases pass under
+the module's tolerance as the others do (loss within 1e-5 relative, every gradient within 2e-4 of its largest entry)."""
 import types
 
 import numpy as np
@@ -21,9 +24,12 @@ SHAPES = {
     "d16k4h2m2p1": dict(dim=16, neighbor_sample_size=4, h_hop=2, n_mix_hop=2, p_hop=1, n_memory=8),
     "d64k8h2m1p2": dict(dim=64, neighbor_sample_size=8, h_hop=2, n_mix_hop=1, p_hop=2, n_memory=16),
     "d12k5h3m1p0": dict(dim=12, neighbor_sample_size=5, h_hop=3, n_mix_hop=1, p_hop=0, n_memory=4),
+    # the dimension of BASELINE config C2: the head's 8-lanes-per-row instances, which no other dim of this module selects
+    "d32k4h2m1p1": dict(dim=32, neighbor_sample_size=4, h_hop=2, n_mix_hop=1, p_hop=1, n_memory=8),
 }
 CASES = [("d8k3h2m1p2", "all"), ("d16k4h2m2p1", "all"), ("d64k8h2m1p2", "all"), ("d12k5h3m1p0", "all"),
-         ("d8k3h2m1p2", "ho_only")]          # ho_only: no consumer of the key-addressing output
+         ("d8k3h2m1p2", "ho_only"),          # ho_only: no consumer of the key-addressing output
+         ("d32k4h2m1p1", "all")]
 
 
 def build(shape, G, n_groups, ablation="all", seed=70):
@@ -92,6 +98,20 @@ def test_loss_and_every_gradient(shape, ablation, mode, G, n_groups, hip_lib):
     s = out.scores.numpy().reshape(-1, G)
     if np.abs(s[:, 1:] - s[:, :1]).min() > 1e-4 * np.abs(s).max():
         assert tuple(tr.rank_counts.cpu().tolist()) == rl.pair_counts(s.reshape(-1), valid, G)
+
+
+def test_dim_32_with_groups_of_17(hip_lib):
+    """C2's dimension under sampled softmax with 16 negatives (and BPR): still one pass of 8 lanes per row, but a segment of 32
+    lanes per group in phase 2, of which 17 hold a slot.  The reference and the tolerance of test_loss_and_every_gradient."""
+    from mvin_amd.training import Trainer
+    G, n_groups = 17, 2
+    for mode in ("bpr", "softmax"):
+        args, case, params, valid, model = build("d32k4h2m1p1", G, n_groups)
+        tr = Trainer(model, objective=mode, group_size=G)
+        loss = tr.step(*dev_feed(model, case, valid), apply=False)
+        torch.cuda.synchronize()
+        ref_loss, ref_grads = ref_step(args, params, case, valid, G, mode)
+        check_grads(tr.grads_by_reference_name(), ref_grads, loss, ref_loss)
 
 
 def test_a_batch_of_partial_groups_is_refused(hip_lib):
